@@ -3,6 +3,11 @@
 
     python bench.py --gpus 1 --steps 50 --warmup 10
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus 1 --steps 50 --warmup 10 --full        (+ roofline leg, C4 / C5 / c2-wgan-gp steps, CPU baseline)
+    python bench.py --gpus 1 --steps 50 --warmup 10 --dump-outputs DIR   (the last timed step's outputs as DIR/*.npy)
+
+A plain run sets up, warms up, times exactly --steps steps and prints one JSON line (ms_per_step = milliseconds per timed
+step); everything else it can measure runs only with --full, behind the headline's timed region.
 
 Workload (config C2 of BASELINE.json / SURVEY 8): CIFAR-shaped 3x32x32, patch 4 (64+1 tokens), E=384,
 4 heads, 6 blocks discriminator (src/v2) + SLN/SIREN generator (src/v1), per-GPU batch 256, bf16 MFMA
@@ -232,6 +237,30 @@ def step_roofline(torch, B, reps=30):
     return out
 
 
+DUMP_MAX_VALUES = 4 << 20  # per dumped array: 16 MB of float32, so the four arrays stay under 64 MB
+
+
+def dump_outputs(torch, out_dir, eng, losses):
+    """--dump-outputs: what the timed path computed in its last step, as float32 DIR/<name>.npy, so that two builds can be compared
+    output for output - the losses step() returned, the generated images of that step and both networks' fp32 master weights after
+    its AdamW updates (what D.state_dict() / G.state_dict() hold).  An array of more than DUMP_MAX_VALUES values is replaced by the
+    values at a fixed, seeded set of DUMP_MAX_VALUES flat indices (ascending), the same on every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"losses": losses, "fake_images": eng.imgs[eng.B:], "d_params": eng.vit._flat.flat, "g_params": eng.gen._flat.flat}
+    meta = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        rec = {"shape": list(t.shape)}
+        if t.numel() > DUMP_MAX_VALUES:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_VALUES].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+            rec["sampled_values"] = DUMP_MAX_VALUES
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+        meta[name] = rec
+    return {"dir": out_dir, "arrays": meta}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -269,11 +298,19 @@ def main():
     ap.add_argument("--dense-top-block", type=int, default=0,
                     help="1: compute every row of the top encoder block (the reference's operator graph row for row); default 0: only the CLS rows "
                          "the classifier reads behind that block's attention - same logits and gradients (DESIGN.md s3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what follows the headline's timed region: the dominant-kernel roofline leg, the C4 / C5 / c2-wgan-gp "
+                         "steps (extra_workloads, one GPU) and the CPU baseline - each still skipped by its --no-* option; without --full "
+                         "a run sets up, warms up, times the --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32, rank 0): losses, "
+                         "fake_images, d_params and g_params (the fp32 master weights); an array above 4 M values is replaced by a "
+                         "fixed seeded sample of 4 M of them")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extra-workloads", action="store_true",
-                    help="skip the C4 / C5 measurements that follow the headline's timed region on one GPU (JSON field extra_workloads)")
+                    help="with --full: skip the C4 / C5 measurements that follow the headline's timed region on one GPU (JSON field extra_workloads)")
     ap.add_argument("--no-roofline", action="store_true",
-                    help="profiling aid: skip the dominant-kernel timing leg, so a rocprofv3 run of this command contains the step's launches only")
+                    help="with --full: skip the dominant-kernel timing leg (profiling aid: a rocprofv3 run then contains the step's launches only)")
     ap.add_argument("--single-stream", action="store_true", help="(default since round 2; kept for the profiling scripts) weight gradients on the main stream")
     ap.add_argument("--concurrent-wgrad", type=int, default=0,
                     help="1: the discriminator's weight gradients on a side stream beside its input gradients (the default until the "
@@ -288,6 +325,8 @@ def main():
                     help="nccl (= RCCL, the default and the measured path); gloo only to rehearse the multi-rank code path on a box "
                          "with fewer GPUs than ranks (ranks then share devices: local_rank %% device_count)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     if args.roofline_only:
         import torch
         import vit_gan_amd  # noqa: F401
@@ -403,13 +442,17 @@ def main():
     win = sorted(marks[k].elapsed_time(marks[k + 1]) / (bounds[k + 1] - bounds[k]) for k in range(nwin))
     lv = losses.cpu().tolist()
     ok = all(x == x and abs(x) < 1e4 for x in lv)
+    dumped = dump_outputs(torch, args.dump_outputs, eng, losses) if (args.dump_outputs and rank == 0) else None
 
     if rank == 0:
         f_step, f_exec = step_flops(geo, G, fp8_attn)
         ips = args.steps * B * world / elapsed
         step_tf = ips * f_step / 1e12 / world
         # the roofline leg always times the C2 shape
-        roof = {"skipped": "--no-roofline"} if args.no_roofline else step_roofline(torch, 256 if args.workload != "c2" else B)
+        if not args.full or args.no_roofline:
+            roof = {"skipped": "--no-roofline" if args.full else "needs --full"}
+        else:
+            roof = step_roofline(torch, 256 if args.workload != "c2" else B)
         roof["step_tflops_per_gpu"] = round(step_tf, 1)
         roof["step_frac_of_peak"] = round(step_tf / PEAK_BF16_TFLOPS, 4)
         # BASELINE.md's definition (images/s x F_step of the reference's graph / peak) above; the MFMA pipe itself did less:
@@ -438,9 +481,11 @@ def main():
                        "losses_finite": ok, "last_losses": [round(x, 4) for x in lv]},
             "roofline": roof,
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         # The other single-GPU configurations of BASELINE.json (configs[3], configs[4]: C4 and C5 at B = 128 per GPU, C5 with fp8 attention),
-        # timed by the SAME driver-run command: behind the headline's timed region, so the C2 number is untouched.
-        if world == 1 and not dp and args.workload == "c2" and not args.no_extra_workloads and args.gp == 0.0:
+        # timed by the same --full command: behind the headline's timed region, so the C2 number is untouched.
+        if args.full and world == 1 and not dp and args.workload == "c2" and not args.no_extra_workloads and args.gp == 0.0:
             eng.close()
             del eng
             extras = []
@@ -487,7 +532,7 @@ def main():
                 except Exception as exc:  # noqa: BLE001
                     extras.append({"workload": wl, "error": f"{type(exc).__name__}: {exc}"})
             out["extra_workloads"] = extras
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out))
     if dp:

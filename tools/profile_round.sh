@@ -36,5 +36,5 @@ python3 tools/step_timeline.py $OUT/ks_gp > $OUT/${TAG}_gp_step_timeline.txt 2>&
 python3 -m pytest tests/test_blocks_gpu.py -m gpu -q -s 2>&1 | grep -E "tensors checked|SLN scalars|^ +(sln|transformer_layers|layer_norm)" > $OUT/stage_raw.txt
 # the bench line quotes the two PMC summaries from profiles/ (when their tree hash is this tree's): put this run's there first
 cp $OUT/${TAG}_gemm_pmc_traffic.json $OUT/${TAG}_step_pmc_summary.json $R/profiles/ 2>/dev/null
-python3 bench.py 2>/dev/null | tail -1 > $OUT/${TAG}_bench_line.json
+python3 bench.py --full 2>/dev/null | tail -1 > $OUT/${TAG}_bench_line.json
 tail -4 $OUT/traffic.txt; tail -12 $OUT/summary.txt; grep -v amdgpu.ids $OUT/${TAG}_gemm_bench.txt; cut -c1-400 $OUT/${TAG}_bench_line.json
