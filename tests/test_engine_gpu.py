@@ -295,7 +295,7 @@ def _dp_worker(rank, world, port, out):
         from vit_gan_amd.modules import ViTDiscriminator
         B = 4
 
-        def run(dp_chunks, compress, shard=False):
+        def run(dp_chunks, compress, shard=False, ref_master=None):
             torch.manual_seed(0)  # identical init on every rank (and for every exchange variant)
             D = ViTDiscriminator(Config(embeddings_dimension=128, classes_count=1, dropout_rate=0.1, batch_size=B,
                                         transformer_blocks_count=4)).cuda().train()
@@ -308,16 +308,16 @@ def _dp_worker(rank, world, port, out):
                 real = torch.rand(B, 3, 32, 32, device="cuda") * 2 - 1
                 losses = eng.step(real)
             torch.cuda.synchronize()
-            stale = G._flat.flat.detach().cpu().clone()
-            eng.gather_master()  # (sharded update: every rank's fp32 master of the mapping layer current again; a no-op otherwise)
+            before = G._flat.flat.detach().cpu().clone()
             if shard:
                 w0, w1 = eng._map_range()
                 a_, b_ = eng.sync.share(w0, w1)
                 own = torch.zeros(w1 - w0, dtype=torch.bool)
                 own[a_ - w0:b_ - w0] = True
-                fresh = G._flat.flat.detach().cpu()
-                # the shares this rank does not own had NOT been updated (that is the point), its own share had
-                assert torch.equal(stale[w0:w1][own], fresh[w0:w1][own]) and not torch.equal(stale[w0:w1][~own], fresh[w0:w1][~own])
+                # the shares this rank does not own are already current - equal to the replicated update's - with no gather_master() call
+                assert torch.equal(before[w0:w1][~own], ref_master[w0:w1][~own]) and torch.equal(before[w0:w1][own], ref_master[w0:w1][own])
+            eng.gather_master()  # a no-op kept for callers: it must change nothing
+            assert torch.equal(before, G._flat.flat.detach().cpu())
             return (D.vit._flat.flat.detach().cpu(), G._flat.flat.detach().cpu(), D.vit._flat.grad.detach().cpu(), losses.cpu(),
                     G._flat.grad.detach().cpu(), G._flat.shadow.detach().cpu())
         # hipGraph replay cannot capture a gloo exchange: the engine must say so and run eager, never silently
@@ -335,7 +335,7 @@ def _dp_worker(rank, world, port, out):
         w, gw, gsum, losses, ggrad, gsh = run(3, False)    # D and G backward in 3 pieces, exchange overlapped
         w1, gw1, _, _, ggrad1, _ = run(1, False)           # one all-reduce per network after its whole backward
         w2, gw2, _, _, ggrad2, _ = run(3, True)            # + mapping-layer gradient exchanged as bf16
-        w3, gw3, _, _, _, gsh3 = run(3, False, shard=True)  # mapping layer: reduce-scatter, AdamW on this rank's share, all-gather of the shadow
+        w3, gw3, _, _, _, gsh3 = run(3, False, shard=True, ref_master=gw)  # mapping layer: reduce-scatter, AdamW on this rank's share, all-gather of the master
         gather = [None] * world
         dist.all_gather_object(gather, (w, gw, gsum, losses, gw2, gsh3, gw3))
         if rank == 0:
@@ -360,12 +360,13 @@ def _dp_worker(rank, world, port, out):
 
 
 @pytest.mark.timeout(600)
-def test_two_rank_data_parallel_engine_on_one_gpu():
+def test_two_rank_data_parallel_engine_with_current_sharded_master_on_one_gpu():
     """world_size 2 through the real engine path (staged D and G backward + overlapped ranged all-reduce on a side
     stream + 1/world folded into AdamW): replicas must stay bit-identical, gradients must be the all-reduced sum; the
     staged exchange must equal one all-reduce per network bitwise; the bf16-compressed mapping gradient stays within
     2^-7 of the fp32 exchange; the sharded update of the mapping layer (reduce-scatter, AdamW on each rank's share, all-gather of the
-    bf16 shadow) leaves bit-identical replicas and the replicated update's weights."""
+    fp32 master) leaves bit-identical replicas and the replicated update's weights, and every rank's master of the
+    shares it does not own is already current after the step, with no gather_master() call."""
     import socket
     import torch.multiprocessing as mp
     with socket.socket() as s:
@@ -386,6 +387,88 @@ def test_two_rank_data_parallel_engine_on_one_gpu():
     assert staged_equal, "staged (overlapped) D / G exchange must equal the single all-reduce bit for bit"
     assert compressed_close, f"bf16 exchange of the mapping gradient: relative deviation {rel}"
     assert sharded_ok, "sharded update of the mapping layer: replicas / the replicated update differ"
+
+
+def _dp_coherence_worker(rank, world, port, out):
+    import os, sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    import torch.distributed as dist
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        import vit_gan_amd  # noqa: F401
+        from vit_gan_amd.config import Config
+        from vit_gan_amd.engine import GanEngine
+        from vit_gan_amd.generator import SirenGenerator
+        from vit_gan_amd.modules import ViTDiscriminator
+        B = 4
+        gen = torch.Generator().manual_seed(60 + rank)  # different data per rank
+        reals = [(torch.rand(B, 3, 32, 32, generator=gen) * 2 - 1).cuda() for _ in range(3)]
+        z = torch.randn(B, 1024, generator=torch.Generator().manual_seed(7)).cuda()
+
+        def run(shard):
+            torch.manual_seed(0)  # identical init on every rank
+            D = ViTDiscriminator(Config(embeddings_dimension=128, classes_count=1, dropout_rate=0.0, batch_size=B,
+                                        transformer_blocks_count=2)).cuda().train()
+            G = SirenGenerator(embed=128, layers=3, siren_hidden=256, dropout=0.0).cuda().train()
+            eng = GanEngine(D, G, batch=B, seed=100 + rank, shard_mapping_update=shard)
+            assert eng.world == world and eng.shard_map == shard
+            eng.step(reals[0])
+            with torch.no_grad():
+                G(z)                    # a module forward (sampling, FID): refresh_shadow() recasts the whole shadow from the master
+            eng.step(reals[1])
+            eng.sync_from_modules()     # the same recast, as after an in-place edit or a load_state_dict
+            eng.step(reals[2])
+            torch.cuda.synchronize()    # no gather_master() anywhere
+            fd, fg = D.vit._flat, G._flat
+            got = tuple(t.detach().cpu().clone() for t in (fd.flat, fd.shadow, fg.flat, fg.shadow))
+            eng.close()
+            return got
+
+        rep, sh = run(False), run(True)
+        gather = [None] * world
+        dist.all_gather_object(gather, (rep, sh))
+        if rank == 0:
+            bits = lambda t: t.view(torch.int16)  # noqa: E731
+            res = {
+                "ranks_equal": all(torch.equal(gather[0][k][i], g[k][i]) for g in gather[1:] for k in (0, 1) for i in range(4)),
+                "shard_equals_replicated": all(torch.equal(g[0][i], g[1][i]) for g in gather for i in range(4)),
+                "shadow_is_rne": all(torch.equal(bits(g[k][i + 1]), bits(g[k][i].to(torch.bfloat16))) for g in gather for k in (0, 1)
+                                     for i in (0, 2)),
+                "finite": all(bool(torch.isfinite(g[k][i]).all()) for g in gather for k in (0, 1) for i in (0, 2)),
+            }
+            out.put(("ok", res))
+    except Exception as e:
+        import traceback
+        out.put(("err", f"rank {rank}: {type(e).__name__}: {e}\n{traceback.format_exc()[-1500:]}"))
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.timeout(600)
+def test_two_rank_sharded_mapping_update_keeps_masters_coherent():
+    """shard_mapping_update on two gloo ranks (one GPU): step, a module forward of G (which recasts the whole bf16 shadow from the fp32
+    master), step, sync_from_modules(), step.  The replicas' D and G masters and shadows must be bit-identical across the ranks with no
+    gather_master() call, bit-equal to the replicated update's, and every shadow the round-to-nearest-even of its master: a rank whose
+    master of the mapping shares it does not own were stale would recast stale weights over the gathered ones and diverge."""
+    import socket
+    import torch.multiprocessing as mp
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    ctx = mp.get_context("spawn")
+    out = ctx.Queue()
+    procs = [ctx.Process(target=_dp_coherence_worker, args=(r, 2, port, out)) for r in range(2)]
+    for p in procs:
+        p.start()
+    status, val = out.get(timeout=500)
+    for p in procs:
+        p.join(timeout=120)
+    assert status == "ok", val
+    assert val["finite"], val
+    assert val["shadow_is_rne"], val
+    assert val["ranks_equal"], val
+    assert val["shard_equals_replicated"], val
 
 
 def test_engine_step_with_patch_grid_generator_at_c4_shape():

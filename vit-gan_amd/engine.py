@@ -75,11 +75,14 @@ class GanEngine:
         then formed in bf16 inside the collective (8 mantissa bits, error growing with the world size), so the default step is
         the exact fp32 all-reduce and a caller that wants the halved link traffic opts in (bench.py does and says so in its line).
         shard_mapping_update (data parallel only, default OFF): the same layer's gradient is reduce-SCATTERED in fp32 (each rank receives
-        the exact sum of one 1/world share), every rank runs AdamW on its share alone, and the updated bf16 shadow shares - what the
-        GEMMs read - are all-gathered (GradSync.reduce_scatter_range / all_gather_range): exact sums like the default, 3/4 of its bytes
-        on the links, 1/world of AdamW's traffic on the layer.  The fp32 master (and AdamW's moments) of the shares a rank does not
-        own go stale on that rank: ``gather_master()`` brings the master up to date before a ``state_dict()`` is taken.  Not with
-        ``clip_g`` (the clipping norm is taken over the whole gradient) nor together with ``compress_mapping_grad``.
+        the exact sum of one 1/world share), every rank runs AdamW on its share alone, the updated fp32 master shares are all-gathered
+        (GradSync.reduce_scatter_range / all_gather_range) and every rank casts the layer's bf16 shadow from the gathered master: exact
+        sums like the default, 1/world of AdamW's traffic on the layer, and on every rank the master equals the replicated update's and
+        the shadow is its round-to-nearest-even - so a later ``refresh_shadow()`` (a module forward, ``sync_from_modules``, the
+        load_state_dict hook) recasts current weights.  The links carry the reduce-scatter plus a 4 B/parameter gather: the bytes of
+        the all-reduce, not fewer (the cost on more than one real GPU is unmeasured).  AdamW's moments of the shares a rank does not
+        own stay unused on that rank.  Not with ``clip_g`` (the clipping norm is taken over the whole gradient) nor together with
+        ``compress_mapping_grad``.
         exchange_single_rank: run the staged backward and its all-reduces on a one-rank group as well (tests: the RCCL
         collectives inside a captured step, on a box with one GPU).
         dense_top_block: compute EVERY row of the top encoder block like the reference's operator graph does.  Default off: behind
@@ -286,7 +289,8 @@ class GanEngine:
 
     def _adamw_g_sharded(self, st) -> None:
         """The generator's AdamW with the mapping Linear sharded: the whole buffer but that layer as usual, of the layer this rank's
-        share only; then the updated bf16 shadow shares to every rank (the GEMMs of every rank read the whole shadow)."""
+        share only; then the updated fp32 master shares to every rank and the layer's bf16 shadow cast from them there (the GEMMs of
+        every rank read the whole shadow; gathering the master, not the shadow, keeps every rank's master current)."""
         fg, h, L = self.gen._flat, self.hyp, _lib.lib()
         w0, w1 = self._map_range()
         a, b = self.sync.share(w0, w1)
@@ -300,18 +304,14 @@ class GanEngine:
         upd(0, w0)
         upd(a, b)
         upd(w1, fg.total)
-        self.sync.all_gather_range(fg.shadow, w0, w1)
+        self.sync.all_gather_range(fg.flat, w0, w1)
         self.sync.wait()
+        _lib.check(L.vg_cast_f32_bf16(C.c_void_p(fg.flat.data_ptr() + 4 * w0), C.c_void_p(fg.shadow.data_ptr() + 2 * w0), w1 - w0, st),
+                   "vg_cast_f32_bf16")
 
     def gather_master(self) -> None:
-        """shard_mapping_update: bring the fp32 master of the mapping Linear up to date on every rank (each rank updates its share
-        only); call it before ``state_dict()`` / a checkpoint.  A no-op otherwise."""
-        if not self.shard_map:
-            return
-        w0, w1 = self._map_range()
-        self.sync.all_gather_range(self.gen._flat.flat, w0, w1)
-        self.sync.wait()
-        torch.cuda.current_stream().synchronize()
+        """A no-op, kept for callers: the sharded update of the mapping Linear all-gathers its fp32 master inside the step, so every
+        rank's master is current after every step.  (It issues no collective, so it is safe on a branch that differs by rank.)"""
 
     def _adamw(self, fp, m, v, lr, st, clip=None, slot=0):
         h = self.hyp
