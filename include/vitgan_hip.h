@@ -385,6 +385,41 @@ int vg_vit_backward_stages(const VgVitNet* net, int B, void* ws, const float* dl
 long long vg_vit_penalty_ws_bytes(const VgVitDims* d, int B);
 int vg_vit_penalty(const VgVitNet* net, int B, const void* real, const void* fake, const float* eps, float weight, void* ws, void* ws_pen,
                    float* penalty_out, void* stream);
+
+/* fp32 mode of the same network (opt-in; the bf16 entry points above are unchanged): activations, saved tensors, gradients and GEMM
+ * operands are fp32, the GEMMs run on the exact f32-input MFMA (v_mfma_f32_16x16x4_f32).  Reads net->P (fp32 master), accumulates
+ * G += dL/dP into net->G (same flat layout); dropout_p / dropout_seed / dropout_step give the same masks as the bf16 engine
+ * (vg_dropout_apply).  net->Pb, net->ctx and net->dense_top are ignored (every row of every block; one stream); net->attn_fp8 = 1
+ * returns -4.  img / d_img: fp32 [B,C,IH,IH] (d_img may be NULL); logits / dlogits fp32 [B,Kc].  ws: vg_vit_ws_bytes_f32(d, B)
+ * bytes, written by the forward and read by the backward of that forward.  -1 null pointer / B < 1, -3 a shape vg_vit_layout
+ * refuses. */
+long long vg_vit_ws_bytes_f32(const VgVitDims* d, int B); /* host only */
+int vg_vit_forward_f32(const VgVitNet* net, int B, const float* img, void* ws, float* logits, void* stream);
+int vg_vit_backward_f32(const VgVitNet* net, int B, void* ws, const float* dlogits, float* d_img, int want_wgrad, void* stream);
+
+/* Single operators of the fp32 mode (all tensors fp32, row-major):
+ * vg_linear_f32_fwd:   Y[M,N] = act(X[M,K] W[N,K]^T + bias) * mask(site) + res; act 0 none, 1 exact-erf GELU (Z = pre-activation,
+ *                      nullable), 2 tanh; drop_p = 0: no dropout, else the mask of vg_dropout_apply over the [M,N] output.
+ * vg_linear_f32_dgrad: dX[M,K] = (dY[M,N] W[N,K]) * f(aux); act 0: f = 1, 1: gelu'(aux) (aux = pre-activation), 2: 1 - aux^2 (aux = tanh out).
+ * vg_linear_f32_wgrad: dW[N,K] += dY^T X, db[N] += column sums of dY (db nullable); split-K slices folded in a fixed order
+ *                      (bitwise deterministic); slab: vg_linear_f32_wgrad_slab_floats(M, N, K) floats of scratch (-2 if smaller).
+ * vg_attention_f32_fwd / _bwd: as vg_attention_fwd / _bwd in fp32 (HE in {32,64,96}, S <= 80; lse fp32 [B,H,S]).
+ * vg_layernorm_f32_fwd / _bwd: nn.LayerNorm over E (a multiple of 128, <= 1024); bwd: dx = gres + LN'(dy) (gres nullable),
+ *                      dgamma / dbeta += column sums (both NULL: skipped), part: vg_layernorm_f32_bwd_part_floats(R, E) floats. */
+int vg_linear_f32_fwd(const float* X, const float* W, const float* bias, const float* res, float* Y, float* Z, int M, int N, int K, int act,
+                      float drop_p, unsigned long long seed, int site, const unsigned* step_dev, void* stream);
+int vg_linear_f32_dgrad(const float* dY, const float* W, const float* aux, float* dX, int M, int N, int K, int act, void* stream);
+long long vg_linear_f32_wgrad_slab_floats(int M, int N, int K);
+int vg_linear_f32_wgrad(const float* dY, const float* X, float* dW, float* db, float* slab, long long slab_floats, int M, int N, int K,
+                        void* stream);
+int vg_attention_f32_fwd(const float* qkv, float* out, float* lse, int B, int H, int S, int HE, float scale, void* stream);
+int vg_attention_f32_bwd(const float* qkv, const float* out, const float* d_out, const float* lse, float* d_qkv, int B, int H, int S, int HE,
+                         float scale, void* stream);
+int vg_layernorm_f32_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int R, int E, float eps,
+                         void* stream);
+long long vg_layernorm_f32_bwd_part_floats(int R, int E);
+int vg_layernorm_f32_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* gres, float* dx,
+                         float* dgamma, float* dbeta, float* part, int R, int E, void* stream);
 /* v1 generator: mapping Linear -> L x TransformerSLN -> SLN -> SIREN x2 (src/v1/generator.py:58-69). */
 typedef struct VgGenDims {
   int Z, T, E, H, L, O, CW; /* latent, tokens, embed, heads, layers, siren hidden, output features per token */

@@ -134,6 +134,18 @@ _SIGNATURES = {
     "vg_vit_backward_stages": (c_int, [C.POINTER(VgVitNet), c_int, P, P, P, c_int, c_int, c_int, P]),
     "vg_vit_penalty_ws_bytes": (c_ll, [C.POINTER(VgVitDims), c_int]),
     "vg_vit_penalty": (c_int, [C.POINTER(VgVitNet), c_int, P, P, P, c_float, P, P, P, P]),
+    "vg_vit_ws_bytes_f32": (c_ll, [C.POINTER(VgVitDims), c_int]),
+    "vg_vit_forward_f32": (c_int, [C.POINTER(VgVitNet), c_int, P, P, P, P]),
+    "vg_vit_backward_f32": (c_int, [C.POINTER(VgVitNet), c_int, P, P, P, c_int, P]),
+    "vg_linear_f32_fwd": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, C.c_ulonglong, c_int, P, P]),
+    "vg_linear_f32_dgrad": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
+    "vg_linear_f32_wgrad_slab_floats": (c_ll, [c_int, c_int, c_int]),
+    "vg_linear_f32_wgrad": (c_int, [P, P, P, P, P, c_ll, c_int, c_int, c_int, P]),
+    "vg_attention_f32_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
+    "vg_attention_f32_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
+    "vg_layernorm_f32_fwd": (c_int, [P, P, P, P, P, P, c_int, c_int, c_float, P]),
+    "vg_layernorm_f32_bwd_part_floats": (c_ll, [c_int, c_int]),
+    "vg_layernorm_f32_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, c_int, c_int, P]),
     "vg_gen_layout": (c_int, [C.POINTER(VgGenDims), C.POINTER(VgGenLayout)]),
     "vg_gen_ws_bytes": (c_ll, [C.POINTER(VgGenDims), c_int]),
     "vg_gen_forward": (c_int, [C.POINTER(VgGenNet), c_int, P, P, P, P]),

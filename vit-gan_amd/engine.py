@@ -98,6 +98,8 @@ class GanEngine:
         vit = discriminator.vit if isinstance(discriminator, ViTDiscriminator) else discriminator
         if not isinstance(vit, VisionTransformer) or not isinstance(generator, SirenGenerator):
             raise TypeError("GanEngine needs a ViTDiscriminator/VisionTransformer and a SirenGenerator")
+        if getattr(vit, "precision", "bf16") != "bf16":
+            raise ValueError("GanEngine: the fused step is bf16; it does not take a discriminator in precision='fp32'")
         self.vit, self.gen = vit, generator
         self.dev = vit._flat.flat.device
         if self.dev.type != "cuda" or generator._flat.flat.device != self.dev:

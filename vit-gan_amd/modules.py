@@ -158,6 +158,44 @@ def _fresh_seed() -> int:
     return int(torch.randint(0, 2 ** 62, (1,)).item())
 
 
+class _VitF32Fn(torch.autograd.Function):
+    """The fp32 mode (``VisionTransformer.precision = "fp32"``): vg_vit_forward_f32 / vg_vit_backward_f32 on the fp32 master
+    parameters; the weight gradients land in the same flat gradient buffer."""
+
+    @staticmethod
+    def forward(ctx, mod: "VisionTransformer", x, anchor, drop_p):
+        ctx.drop = (float(drop_p), _fresh_seed() if drop_p > 0 else 0)
+        B = x.shape[0]
+        xin = x.detach().float().contiguous()
+        ws = torch.empty(mod._ws_bytes_f32(B), dtype=torch.uint8, device=x.device)
+        logits = torch.empty(B, mod._dims.Kc, dtype=torch.float32, device=x.device)
+        net = mod._net(need_grad=False, drop=ctx.drop)
+        _lib.check(_lib.lib().vg_vit_forward_f32(C.byref(net), B, xin.data_ptr(), ws.data_ptr(), logits.data_ptr(), _stream()),
+                   "vg_vit_forward_f32")
+        ctx.mod, ctx.ws, ctx.B, ctx.xdtype = mod, ws, B, x.dtype
+        ctx.need_dx = x.requires_grad
+        ctx.xshape = x.shape
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        mod = ctx.mod
+        want_w = any(p.requires_grad for p in mod.parameters())
+        if want_w:
+            mod._flat.attach_grads()
+        dl = dlogits.detach().float().contiguous()
+        dimg = torch.empty(ctx.xshape, dtype=torch.float32, device=dl.device) if ctx.need_dx else None
+        net = mod._net(need_grad=want_w, drop=ctx.drop)
+        _lib.check(_lib.lib().vg_vit_backward_f32(C.byref(net), ctx.B, ctx.ws.data_ptr(), dl.data_ptr(),
+                                                  None if dimg is None else dimg.data_ptr(), int(want_w), _stream()),
+                   "vg_vit_backward_f32")
+        ctx.ws = None
+        return None, (None if dimg is None else dimg.to(ctx.xdtype)), None, None
+
+
+PRECISIONS = ("bf16", "fp32")
+
+
 class _VitFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mod: "VisionTransformer", x, anchor, drop_p):
@@ -215,6 +253,10 @@ class VisionTransformer(nn.Module):
         # - the reference's arithmetic is fp32 and the parity tiers are stated for bf16 storage.  Not a Config field: set
         # ``model.vit.attention_fp8 = True`` (GanEngine picks it up too).
         self.attention_fp8 = False
+        # "bf16" (default): the engine above.  "fp32": fp32 activations, gradients and GEMM operands on the exact f32-input MFMA -
+        # the reference's own arithmetic, for checking a run against the fp32 model or reproducing its numbers.  Not a Config field
+        # either: set ``model.vit.precision = "fp32"``.  GanEngine and the gradient penalty stay bf16 and refuse it.
+        self._precision = "bf16"
         self._dims = flat.vit_dims_struct(n_channels, image_size, patch_size, embed_dim, n_attention_heads, n_layers,
                                           forward_mul, n_classes)
         lay = flat.vit_layout(self._dims)  # raises for shapes the kernels do not cover
@@ -237,6 +279,22 @@ class VisionTransformer(nn.Module):
             raise RuntimeError("vg_vit_ws_bytes failed")
         return n
 
+    @property
+    def precision(self) -> str:
+        return self._precision
+
+    @precision.setter
+    def precision(self, value: str) -> None:
+        if value not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}, got {value!r}")
+        self._precision = value
+
+    def _ws_bytes_f32(self, B: int) -> int:
+        n = _lib.lib().vg_vit_ws_bytes_f32(C.byref(self._dims), B)
+        if n <= 0:
+            raise RuntimeError("vg_vit_ws_bytes_f32 failed")
+        return n
+
     def _net(self, need_grad: bool, drop=(0.0, 0)) -> _lib.VgVitNet:
         fp = self._flat
         return _lib.VgVitNet(self._dims, fp.flat.data_ptr(), fp.shadow.data_ptr(), fp.grad.data_ptr() if need_grad else None,
@@ -250,6 +308,10 @@ class VisionTransformer(nn.Module):
             self._flat.named = dict(self.named_parameters())
             self._flat.rebuild()
         p = self._dropout_p if self.training else 0.0
+        if self._precision == "fp32":
+            if self.attention_fp8:
+                raise ValueError("precision='fp32' and attention_fp8=True exclude each other: the fp32 mode has no fp8 attention")
+            return _VitF32Fn.apply(self, x, self.norm.weight, p)
         return _VitFn.apply(self, x, self.norm.weight, p)
 
     def composed_forward(self, x):
@@ -266,6 +328,8 @@ class VisionTransformer(nn.Module):
         """The same network through the twice-differentiable operator set (ops2.py): what ``gradient_penalty`` runs, since
         it differentiates the input gradient (``torch.autograd.grad(..., create_graph=True)``, src/v2/utils.py:132-139).
         Dropout, as in ``composed_forward``, is torch's own on the modules' nn.Dropout layers."""
+        if self._precision != "bf16":
+            raise ValueError("twice_differentiable_forward is built on the bf16 operator set; set precision = 'bf16' for it")
         if not x.is_cuda:
             raise RuntimeError("VisionTransformer: the HIP engine needs cuda tensors; there is no CPU fallback")
         emb = self.embedding

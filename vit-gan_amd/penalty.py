@@ -17,12 +17,14 @@ def gradient_penalty(discriminator, real_images: torch.Tensor, fake_images: torc
                      epsilon: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Same signature and arithmetic as src/v2/utils.py:124-144; ``epsilon`` [B,1,1,1] may be supplied (tests), else it
     is drawn with ``torch.rand`` like the reference does."""
+    vit = discriminator.vit if hasattr(discriminator, "vit") else discriminator
+    if getattr(vit, "precision", "bf16") != "bf16":
+        raise ValueError("gradient_penalty runs the bf16 operator set; it does not take a discriminator in precision='fp32'")
     batch_size = real_images.size(0)
     if epsilon is None:
         epsilon = torch.rand(batch_size, 1, 1, 1, device=real_images.device if device is None else device)
     interpolated = (epsilon * real_images.float() + (1 - epsilon) * fake_images.float()).detach().requires_grad_(True)
-    vit = discriminator.vit if hasattr(discriminator, "vit") else discriminator
-    out = vit.twice_differentiable_forward(interpolated)
+    out =vit.twice_differentiable_forward(interpolated)
     from . import ops2
     with ops2.input_grad_only():  # this backward is for d out / d interpolated alone: no parameter gradients
         (gradients,) = torch.autograd.grad(outputs=out, inputs=interpolated, grad_outputs=torch.ones_like(out), create_graph=True,
