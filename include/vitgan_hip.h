@@ -196,7 +196,8 @@ int vg_dropout_apply(const void* x, void* y, long long n, float p, unsigned long
 
 /* Fused multi-head self-attention (src/v2/modules.py:128-159 after the projections; src/v1/attention.py
  * :43-52,:97-101).  qkv bf16 [B*S, 3*H*HE] (Q | K | V thirds, head-major inside each third);
- * out bf16 [B*S, H*HE]; lse fp32 [B,H,S].  softmax(scale * q.k).  HE in {32,64,96}, S <= 80. */
+ * out bf16 [B*S, H*HE]; lse fp32 [B,H,S].  softmax(scale * q.k).  HE in {32,64,96}, S <= 256
+ * (S <= 80: csrc/attention.hip; 80 < S <= 256: csrc/attention_long.hip).  The fp8 and L2-distance forms are S <= 80. */
 int vg_attention_fwd(const void* qkv, void* out, float* lse, int B, int H, int S, int HE,
                      float scale, void* stream);
 int vg_attention_bwd(const void* qkv, const void* out, const void* d_out, const float* lse,
@@ -204,7 +205,7 @@ int vg_attention_bwd(const void* qkv, const void* out, const void* d_out, const 
 /* The same attention for ONE query per image, row 0 (ABI v7): what the classifier sees of the top encoder block
  * (src/v2/modules.py:195 reads the CLS row only).  out_cls / d_out_cls bf16 [B, H*HE] (the CLS rows, compact), lse_cls fp32
  * [B, H]; d_qkv is the full [B*S, 3*H*HE] gradient (dK, dV of every key, dQ zero off row 0) - exactly what vg_attention_bwd
- * writes when d_out is zero on every other row.  S <= 128. */
+ * writes when d_out is zero on every other row.  S <= 256. */
 int vg_attention_cls_fwd(const void* qkv, void* out_cls, float* lse_cls, int B, int H, int S, int HE, float scale, void* stream);
 int vg_attention_cls_bwd(const void* qkv, const void* out_cls, const void* d_out_cls, const float* lse_cls, void* d_qkv, int B, int H,
                          int S, int HE, float scale, void* stream);

@@ -13,92 +13,9 @@
 //
 // qkv layout: [B*S, 3E] bf16 row-major, columns [0,E) = Q, [E,2E) = K, [2E,3E) = V, head h at
 // columns h*HE .. (h+1)*HE of each third.  o / d_o: [B*S, E].  lse: [B, H, S] fp32 (natural log).
-#include "vg_common.h"
+#include "vg_attn.h"
+#include "vg_kernels.h"
 
-// LDS image of one head: row-major [rows][HE] bf16 whose 16-B chunks are XOR-swizzled by the row so that BOTH
-// access patterns are bank-conflict free:
-//   row form   (ds_read_b128, 16 lanes = 16 consecutive rows, same chunk)   and
-//   transposed (ds_read_b64_tr_b16, 32 lanes = 8 consecutive rows x one 32-B chunk pair).
-// HE = 96 / 32 (row pitch 48 / 16 banks: rows r and r+4 share a bank quadrant): position inside each 64-B window
-//   is XORed with F[(r>>2)&3], F = {0,2,1,3} - rows r+4 move to the other pair, rows r+8 / r+12 swap halves.
-// HE = 64 (pitch 32 banks: rows r and r+2 collide): pair index ^ (r>>1)&3, half ^ (r>>3)&1.
-// The map is an involution on the chunk index, so the DMA applies the same function to its SOURCE chunk.
-template <int HE>
-__device__ __forceinline__ int swz_chunk(int r, int c) {
-  if (HE == 64) return (((c >> 1) ^ ((r >> 1) & 3)) << 1) | ((c & 1) ^ ((r >> 3) & 1));
-  const int x = (r >> 2) & 3;
-  return (c & ~3) | ((c & 3) ^ (((x & 1) << 1) | (x >> 1)));
-}
-template <int HE>
-__device__ __forceinline__ int lds_off(int r, int d) {
-  return r * (HE * 2) + (swz_chunk<HE>(r, d >> 3) << 4) + ((d & 7) << 1);
-}
-
-// Stage rows [0, rows_alloc) x HE of one head into an LDS image by LDS-DMA (global_load_lds_dwordx4: no trip
-// through registers, every request a whole 16-B chunk of a 64..192-B row segment).  One instruction fills
-// 1 KiB lane-linearly, so LDS chunk (row r, position c') = linear chunk 64*piece + lane and the XOR swizzle
-// (swz_chunk) is applied to the SOURCE chunk index.  Rows >= S come from a 16-byte zero page (the padded keys'
-// V rows multiply p = 0 and must be finite).  rows_alloc * HE / 8 must be a multiple of 64.
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-template <int HE, int NW>
-__device__ __forceinline__ void dma_head(unsigned char* img, const bf16* __restrict__ src, size_t ld, int S, int rows_alloc,
-                                         const void* zeros, int wave, int lane) {
-  constexpr int CPR = HE / 8;  // 16-B chunks per row
-  const int pieces = rows_alloc * CPR / 64;
-  for (int pc = wave; pc < pieces; pc += NW) {
-    const int ci = 64 * pc + lane;
-    const int r = ci / CPR, cp = ci - r * CPR;
-    const int c = swz_chunk<HE>(r, cp);
-    const void* p = (r < S) ? (const void*)(src + (size_t)r * ld + 8 * c) : zeros;
-    __builtin_amdgcn_global_load_lds((gptr_t)p, (lptr_t)(img + 1024 * pc), 16, 0, 0);
-  }
-}
-
-// Accumulator tiles [dt] (lane = row li, 4 consecutive head-dim columns 16*dt + 4*g ..) -> bf16 row segments.
-// v_permlane16_swap between the even and the odd tile of a pair hands every lane 8 CONSECUTIVE columns, so a lane
-// stores 16 B and a wave-instruction covers 16 rows x 64 B (same exchange as the GEMM epilogue).
-template <int DT>
-__device__ __forceinline__ void store_tiles(bf16* __restrict__ rowp, const f32x4 (&acc)[DT], float mul, int g, bool ok) {
-#pragma unroll
-  for (int pr = 0; pr < DT / 2; ++pr) {
-    const f32x4 te = acc[2 * pr], to = acc[2 * pr + 1];
-    bf16x8 w;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(te[r] * mul), __float_as_uint(to[r] * mul), false, false);
-      w[r] = vg_f2bf(__uint_as_float(sw[0]));
-      w[r + 4] = vg_f2bf(__uint_as_float(sw[1]));
-    }
-    if (ok) *(bf16x8*)(rowp + 32 * pr + ((g & 1) << 4) + ((g & 2) << 2)) = w;
-  }
-}
-
-// row-form fragment straight from global: rows r0+li, head-dim slice 32*ks + 8*g
-__device__ __forceinline__ bf16x8 gfrag(const bf16* __restrict__ src, size_t ld, int r0, int ks, int S, int lane) {
-  const int row = r0 + (lane & 15), d = 32 * ks + 8 * (lane >> 4);
-  bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (row < S) z = *(const bf16x8*)(src + (size_t)row * ld + d);
-  return z;
-}
-template <int HE>
-__device__ __forceinline__ bf16x8 lfrag_row(const unsigned char* lds, int r0, int ks, int lane) {
-  return *(const bf16x8*)(lds + lds_off<HE>(r0 + (lane & 15), 32 * ks + 8 * (lane >> 4)));
-}
-// transposed fragment: non-k index = head-dim columns d0..d0+15 (on the lane), k = rows
-// (keys or queries) in the accumulator order {32u + 4g + j (j<4), 32u + 16 + 4g + (j-4)}.
-template <int HE>
-__device__ __forceinline__ bf16x8 lfrag_tr(const unsigned char* lds, int u, int d0, int lane) {
-  const int g = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3;
-  typedef bf16x4 __attribute__((address_space(3))) * lds4;
-  const int r = 32 * u + 4 * g + q;
-  bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4)(lds + lds_off<HE>(r, d0 + 4 * p)));
-  bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds4)(lds + lds_off<HE>(r + 16, d0 + 4 * p)));
-  bf16x8 o;
-  o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = lo[3];
-  o[4] = hi[0]; o[5] = hi[1]; o[6] = hi[2]; o[7] = hi[3];
-  return o;
-}
 // ---- fp8 (OCP e4m3) operands for the activation-side products (config C5: "fp8 MFMA attention") ------------------------
 // An fp8 16x16x32 fragment is 8 bytes per lane, element j of lane group g pairing with element j of the other operand's
 // lane group g exactly like the bf16 fragment's 8 elements - so a bf16 fragment converts element by element.
@@ -126,23 +43,6 @@ __device__ __forceinline__ f32x4 score_mfma(bf16x8 a, bf16x8 b, f32x4 c) {
 }
 #define VG_P_FP8_SCALE 256.0f  // softmax numerators in (0, 1] are scaled into e4m3's normal range before the P.V product
 
-__device__ __forceinline__ bf16x8 pack_pair(f32x4 a, f32x4 b) {
-  bf16x8 o;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { o[j] = vg_f2bf(a[j]); o[j + 4] = vg_f2bf(b[j]); }
-  return o;
-}
-__device__ __forceinline__ float group_sum(float v) {  // over the 4 lane groups (lane>>4)
-  v += __shfl_xor(v, 16, 64);
-  v += __shfl_xor(v, 32, 64);
-  return v;
-}
-__device__ __forceinline__ float group_max(float v) {
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  v = fmaxf(v, __shfl_xor(v, 32, 64));
-  return v;
-}
-
 // squared L2 norm of every row of an LDS head image -> out[rows] (rows >= S are zero rows).  One thread per row.
 template <int HE>
 __device__ __forceinline__ void row_sqnorms(const unsigned char* img, float* out, int rows, int tid, int nthreads) {
@@ -159,21 +59,6 @@ __device__ __forceinline__ void row_sqnorms(const unsigned char* img, float* out
 }
 // v1 attention score (src/v1/attention.py:66-67): the Euclidean distance |q - k| from q.k and the squared norms
 __device__ __forceinline__ float l2_dist(float qk, float qn, float kn) { return sqrtf(fmaxf(qn + kn - 2.f * qk, 0.f)); }
-
-// workgroup -> (image, head).  The heads of one image read interleaved 2 HE-byte slices of the same rows of qkv / o / d_o
-// (HE = 96: 192-byte segments, 1.5 cache lines - neighbouring heads share a line), and consecutive workgroup ids go round-robin
-// over the 8 XCDs, each with its own L2: the heads of an image therefore sit on ONE XCD, as consecutive workgroups of it
-// (id = 8 i + x: image 8 (i / H) + x, head i % H), so a shared line is fetched from HBM once.
-__device__ __forceinline__ bool attn_block(int B, int H, int& b, int& h) {
-#ifdef VG_ATTN_LINEAR_MAP  // A/B builds: the plain mapping
-  b = blockIdx.x / H; h = blockIdx.x - b * H;
-#else
-  const int x = blockIdx.x & 7, i = blockIdx.x >> 3;
-  b = (i / H) * 8 + x; h = i % H;
-#endif
-  return b < B;
-}
-static inline int attn_grid(int B, int H) { return ((B + 7) / 8) * 8 * H; }
 
 template <int HE, int NT, bool L2, bool FP8>
 __global__ __launch_bounds__(64 * NT) void vg_attn_fwd_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ o,
@@ -850,7 +735,7 @@ static int launch_bwd(const bf16* qkv, const bf16* o, const bf16* d_o, const flo
   return (int)hipGetLastError();
 }
 
-// Supported shapes: head dim 32, 64 or 96; S <= 32 (2 tiles) or S <= 80 (5 tiles).
+// Supported shapes: head dim 32, 64 or 96; S <= 32 (2 tiles) or S <= 80 (5 tiles).  (80 < S <= 256, mode 0: attention_long.hip.)
 // mode = 0: dot-product scores (src/v2/modules.py:142-155, v1 lp = 1); 1: Euclidean-distance scores (v1 lp = 2);
 // 2: dot-product scores with fp8 (e4m3) operands for Q.K^T (forward and recompute) and P.V (config C5).
 #define VG_ATTN_BY_NT(FN, HE_, MODE_, ...) return small ? FN<HE_, 2, MODE_>(__VA_ARGS__) : FN<HE_, 5, MODE_>(__VA_ARGS__)
@@ -870,11 +755,14 @@ static int launch_bwd(const bf16* qkv, const bf16* o, const bf16* d_o, const flo
     if (HE == 32) VG_ATTN_BY_MODE(FN, 32, __VA_ARGS__);                \
     return -3;                                                         \
   } while (0)
+// 80 < S <= VG_ATTN_LONG_MAX_S with dot-product scores (mode 0): the streaming kernels of attention_long.hip; modes 1 and 2 stay S <= 80.
 int vg_attn_fwd_launch(const bf16* qkv, bf16* o, float* lse, int B, int H, int S, int HE, float scale, int mode, hipStream_t st) {
+  if (mode == 0 && S > VG_SHORT_MAX_S && S <= VG_ATTN_LONG_MAX_S) return vg_attn_long_fwd_launch(qkv, o, lse, B, H, S, HE, scale, st);
   VG_ATTN_DISPATCH(launch_fwd, qkv, o, lse, B, H, S, scale, st);
 }
 int vg_attn_bwd_launch(const bf16* qkv, const bf16* o, const bf16* d_o, const float* lse, bf16* dqkv, int B, int H,
                        int S, int HE, float scale, int mode, hipStream_t st) {
+  if (mode == 0 && S > VG_SHORT_MAX_S && S <= VG_ATTN_LONG_MAX_S) return vg_attn_long_bwd_launch(qkv, o, d_o, lse, dqkv, B, H, S, HE, scale, st);
   VG_ATTN_DISPATCH(launch_bwd, qkv, o, d_o, lse, dqkv, B, H, S, scale, st);
 }
 
@@ -889,13 +777,14 @@ int vg_attn_bwd_launch(const bf16* qkv, const bf16* o, const bf16* d_o, const fl
 // ---------------------------------------------------------------------------------------------------------------------
 // Work layout of both kernels: a wave walks the head's K / V rows RPI at a time, lane = (row rr = lane / CPR, 16-byte chunk c = lane % CPR),
 // so every load and store of a wave-instruction covers RPI whole 2 HE-byte row segments (HE = 96: 60 of the 64 lanes, 5 rows).
-template <int HE>
+template <int HE, int KMAX>  // KMAX: key capacity (128 or 256) of the LDS score arrays
 __global__ __launch_bounds__(64) void vg_attn_cls_fwd_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ o_cls, float* __restrict__ lse_cls,
                                                              int B, int S, int H, float scale) {
   constexpr int CPR = HE / 8, RPI = 64 / CPR;
   __shared__ float q0l[HE];
-  __shared__ float part[128 * CPR];  // per (key, chunk) partial dot products; then the per-lane partial outputs
-  __shared__ float pl[128];
+  constexpr int NR = KMAX / 64;  // keys per lane in the softmax
+  __shared__ float part[KMAX * CPR];  // per (key, chunk) partial dot products; then the per-lane partial outputs
+  __shared__ float pl[KMAX];
   int b, h;
   if (!attn_block(B, H, b, h)) return;
   const int lane = threadIdx.x;
@@ -922,9 +811,9 @@ __global__ __launch_bounds__(64) void vg_attn_cls_fwd_kernel(const bf16* __restr
     }
   }
   __syncthreads();
-  float sv[2];
+  float sv[NR];
 #pragma unroll
-  for (int rnd = 0; rnd < 2; ++rnd) {
+  for (int rnd = 0; rnd < NR; ++rnd) {
     const int j = lane + 64 * rnd;
     float a = 0.f;
     if (j < S) {
@@ -933,11 +822,16 @@ __global__ __launch_bounds__(64) void vg_attn_cls_fwd_kernel(const bf16* __restr
     }
     sv[rnd] = (j < S) ? a * scale : -INFINITY;
   }
-  const float m = vg_wave_max(fmaxf(sv[0], sv[1]));
-  const float p0 = __expf(sv[0] - m), p1 = __expf(sv[1] - m);  // exp(-inf) = 0 for the padded keys
-  const float l = vg_wave_sum(p0 + p1);
-  pl[lane] = vg_bf2f(vg_f2bf(p0));       // the full kernel multiplies V by bf16(p) (an MFMA operand) and divides the fp32 sum by l
-  pl[lane + 64] = vg_bf2f(vg_f2bf(p1));
+  float mx = sv[0];
+#pragma unroll
+  for (int rnd = 1; rnd < NR; ++rnd) mx = fmaxf(mx, sv[rnd]);
+  const float m = vg_wave_max(mx);
+  float pv[NR], ps = 0.f;
+#pragma unroll
+  for (int rnd = 0; rnd < NR; ++rnd) { pv[rnd] = __expf(sv[rnd] - m); ps = rnd ? ps + pv[rnd] : pv[rnd]; }  // exp(-inf) = 0 for the padded keys
+  const float l = vg_wave_sum(ps);
+#pragma unroll
+  for (int rnd = 0; rnd < NR; ++rnd) pl[lane + 64 * rnd] = vg_bf2f(vg_f2bf(pv[rnd]));  // the full kernel multiplies V by bf16(p) (an MFMA operand) and divides the fp32 sum by l
   if (lane == 0) lse_cls[(size_t)b * H + h] = m + __logf(l);
   __syncthreads();
   // o[d] = sum_j p_j V[j][d] / l: every lane sums its chunk over its rows, then the RPI row slots are added up through LDS
@@ -965,14 +859,14 @@ __global__ __launch_bounds__(64) void vg_attn_cls_fwd_kernel(const bf16* __restr
   }
 }
 
-template <int HE>
+template <int HE, int KMAX>
 __global__ __launch_bounds__(64) void vg_attn_cls_bwd_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ o_cls, const bf16* __restrict__ do_cls,
                                                              const float* __restrict__ lse_cls, bf16* __restrict__ dqkv, int B, int S, int H,
                                                              float scale) {
   constexpr int CPR = HE / 8, RPI = 64 / CPR;
   __shared__ float q0l[HE], d0l[HE];
-  __shared__ float ps[128 * CPR], pd[128 * CPR];  // per (key, chunk) partial dot products q0.K and dO0.V; ps then holds the partial dQ
-  __shared__ float dsl[128], pbl[128];
+  __shared__ float ps[KMAX * CPR], pd[KMAX * CPR];  // per (key, chunk) partial dot products q0.K and dO0.V; ps then holds the partial dQ
+  __shared__ float dsl[KMAX], pbl[KMAX];
   int b, h;
   if (!attn_block(B, H, b, h)) return;
   const int lane = threadIdx.x;
@@ -1011,7 +905,7 @@ __global__ __launch_bounds__(64) void vg_attn_cls_bwd_kernel(const bf16* __restr
   }
   __syncthreads();
 #pragma unroll
-  for (int rnd = 0; rnd < 2; ++rnd) {
+  for (int rnd = 0; rnd < KMAX / 64; ++rnd) {
     const int j = lane + 64 * rnd;
     float dsv = 0.f, pb = 0.f;
     if (j < S) {
@@ -1060,19 +954,24 @@ __global__ __launch_bounds__(64) void vg_attn_cls_bwd_kernel(const bf16* __restr
 }
 
 // o_cls / do_cls: [B, E] (the CLS rows, compact); lse_cls: [B, H]; dqkv: the full [B*S, 3E] gradient.  Dot-product scores only
-// (the engine keeps the full kernels for the top block when the fp8 mode is on); -3: head dim not 32 / 64 / 96.
+// (the engine keeps the full kernels for the top block when the fp8 mode is on); -3: head dim not 32 / 64 / 96.  S <= 128 runs the
+// 128-key instance (half the LDS of the 256-key one: twice the workgroups per CU), 128 < S <= VG_ATTN_LONG_MAX_S the 256-key one.
 int vg_attn_cls_fwd_launch(const bf16* qkv, bf16* o_cls, float* lse_cls, int B, int H, int S, int HE, float scale, hipStream_t st) {
-  if (S < 1 || S > 128 || B < 1 || H < 1) return -2;
-#define VG_ACLS(HE_) hipLaunchKernelGGL((vg_attn_cls_fwd_kernel<HE_>), dim3(attn_grid(B, H)), dim3(64), 0, st, qkv, o_cls, lse_cls, B, S, H, scale)
-  if (HE == 96) VG_ACLS(96); else if (HE == 64) VG_ACLS(64); else if (HE == 32) VG_ACLS(32); else return -3;
+  if (S < 1 || S > VG_ATTN_LONG_MAX_S || B < 1 || H < 1) return -2;
+#define VG_ACLS(HE_, K_) hipLaunchKernelGGL((vg_attn_cls_fwd_kernel<HE_, K_>), dim3(attn_grid(B, H)), dim3(64), 0, st, qkv, o_cls, lse_cls, B, S, H, scale)
+#define VG_ACLS_K(K_) if (HE == 96) VG_ACLS(96, K_); else if (HE == 64) VG_ACLS(64, K_); else if (HE == 32) VG_ACLS(32, K_); else return -3
+  if (S <= 128) { VG_ACLS_K(128); } else { VG_ACLS_K(256); }
+#undef VG_ACLS_K
 #undef VG_ACLS
   return (int)hipGetLastError();
 }
 int vg_attn_cls_bwd_launch(const bf16* qkv, const bf16* o_cls, const bf16* do_cls, const float* lse_cls, bf16* dqkv, int B, int H, int S, int HE,
                            float scale, hipStream_t st) {
-  if (S < 1 || S > 128 || B < 1 || H < 1) return -2;
-#define VG_ACLS(HE_) hipLaunchKernelGGL((vg_attn_cls_bwd_kernel<HE_>), dim3(attn_grid(B, H)), dim3(64), 0, st, qkv, o_cls, do_cls, lse_cls, dqkv, B, S, H, scale)
-  if (HE == 96) VG_ACLS(96); else if (HE == 64) VG_ACLS(64); else if (HE == 32) VG_ACLS(32); else return -3;
+  if (S < 1 || S > VG_ATTN_LONG_MAX_S || B < 1 || H < 1) return -2;
+#define VG_ACLS(HE_, K_) hipLaunchKernelGGL((vg_attn_cls_bwd_kernel<HE_, K_>), dim3(attn_grid(B, H)), dim3(64), 0, st, qkv, o_cls, do_cls, lse_cls, dqkv, B, S, H, scale)
+#define VG_ACLS_K(K_) if (HE == 96) VG_ACLS(96, K_); else if (HE == 64) VG_ACLS(64, K_); else if (HE == 32) VG_ACLS(32, K_); else return -3
+  if (S <= 128) { VG_ACLS_K(128); } else { VG_ACLS_K(256); }
+#undef VG_ACLS_K
 #undef VG_ACLS
   return (int)hipGetLastError();
 }

@@ -52,7 +52,7 @@ extern "C" int vg_vit_layout(const VgVitDims* d, VgVitLayout* o) {
   if (d->E % 128 || d->E % d->H || d->IH % d->P || (K & 7) || d->L < 1 || d->Kc < 1 || d->R < 1) return -3;
   const int HE = d->E / d->H;
   if (HE != 32 && HE != 64 && HE != 96) return -3;
-  if (NP + 1 > 80) return -3;
+  if (NP + 1 > VG_ATTN_LONG_MAX_S) return -3;  // attention: S <= 80 on every path, 80 < S <= 256 on the dot-product bf16 one
   // depth: the backward queues 3 deferred folds per block + 3 more (classifier head, final LayerNorm, the pruned top block's CLS-summed
   // bias row) and uses one event pair per block (+1 for the join)
   if (3 * d->L + 3 > VG_MAX_FOLD_JOBS || d->L >= VG_CTX_EVENTS - 1) return -3;
@@ -91,7 +91,7 @@ extern "C" int vg_vit_layout(const VgVitDims* d, VgVitLayout* o) {
 extern "C" int vg_gen_layout(const VgGenDims* d, VgGenLayout* o) {
   if (!d || !o) return -1;
   const long long E = d->E, T = d->T;
-  if (d->E % 128 || d->E % d->H || (d->Z & 7) || (d->O & 7) || (d->CW & 7) || d->T > 80 || d->L < 1) return -3;
+  if (d->E % 128 || d->E % d->H || (d->Z & 7) || (d->O & 7) || (d->CW & 7) || d->T > VG_ATTN_LONG_MAX_S || d->L < 1) return -3;
   const int HE = d->E / d->H;
   if (HE != 32 && HE != 64 && HE != 96) return -3;
   if (d->patch < 0) return -3;
@@ -320,6 +320,7 @@ static int vit_forward_impl(const VgVitNet* net, int B, const void* img, int img
   hipStream_t st = (hipStream_t)stream;
   const int E = d.E, NP = (d.IH / d.P) * (d.IH / d.P), S = NP + 1, M = B * S, Kp = d.C * d.P * d.P, rE = d.R * E;
   const int HE = E / d.H;
+  if (net->attn_fp8 && S > VG_SHORT_MAX_S) return -3;  // the fp8 attention kernels are S <= 80
   VitWs w; carve_vit(d, B, ws, w);
   const float* P = net->P; const bf16* Pb = (const bf16*)net->Pb;
   const size_t ME = (size_t)M * E;
@@ -468,6 +469,7 @@ static int vit_backward_impl(const VgVitNet* net, int B, void* ws, const float* 
   hipStream_t st = (hipStream_t)stream;
   const int E = d.E, NP = (d.IH / d.P) * (d.IH / d.P), S = NP + 1, M = B * S, Kp = d.C * d.P * d.P, rE = d.R * E;
   const int HE = E / d.H;
+  if (net->attn_fp8 && S > VG_SHORT_MAX_S) return -3;  // the fp8 attention kernels are S <= 80
   VitWs w; carve_vit(d, B, ws, w);
   const float* P = net->P; const bf16* Pb = (const bf16*)net->Pb; float* G = net->G;
   const size_t ME = (size_t)M * E;
@@ -811,10 +813,12 @@ static long long carve_pen(const VgVitDims& d, int B, void* base, PenWs& q) {
 }
 // Every network the plain step trains in bf16 (E a multiple of 128: the alignment of the elementwise kernels follows); where the full-row
 // kernels take the shape (E = 384 / 512, rows in whole units of 16) the input gradients and LayerNorm backwards of passes 2 and 5 are fused,
-// elsewhere they are the GEMM + LayerNorm pairs.  -3: fp8 attention (the second-order attention kernel differentiates the bf16 one).
+// elsewhere they are the GEMM + LayerNorm pairs.  -3: fp8 attention (the second-order attention kernel differentiates the bf16 one), or
+// more than 80 tokens (the second-order attention kernel is S <= 80).
 static int pen_shape_ok(const VgVitNet* net, int B) {
   const VgVitDims& d = net->d;
-  return !net->attn_fp8 && ((long long)B * d.E) % 8 == 0 && ((long long)d.C * d.IH * d.IH) % 4 == 0 && ((long long)d.C * d.P * d.P) % 4 == 0;
+  const long long S = (long long)(d.IH / d.P) * (d.IH / d.P) + 1;
+  return !net->attn_fp8 && S <= VG_SHORT_MAX_S && ((long long)B * d.E) % 8 == 0 && ((long long)d.C * d.IH * d.IH) % 4 == 0 && ((long long)d.C * d.P * d.P) % 4 == 0;
 }
 extern "C" long long vg_vit_penalty_ws_bytes(const VgVitDims* d, int B) {
   VgVitLayout lay;

@@ -61,9 +61,12 @@ F32Drop f32_drop(float p, unsigned long long seed, const unsigned* step) {
   d.thr = (unsigned)t; d.scale = t ? 256.f / (256.f - (float)t) : 1.f; d.seed = seed; d.step = step; return d;
 }
 
+int f32_tokens(const VgVitDims& d) { return (d.IH / d.P) * (d.IH / d.P) + 1; }
+
 int check_net(const VgVitNet* net, int B, VgVitLayout& lay) {
   if (!net || !net->P || B < 1) return -1;
   VG_TRY(vg_vit_layout(&net->d, &lay));
+  if (f32_tokens(net->d) > VG_SHORT_MAX_S) return -3;  // the fp32 attention kernels are S <= 80
   if (net->attn_fp8) return -4;
   return 0;
 }
@@ -72,7 +75,7 @@ int check_net(const VgVitNet* net, int B, VgVitLayout& lay) {
 
 extern "C" long long vg_vit_ws_bytes_f32(const VgVitDims* d, int B) {
   VgVitLayout lay;
-  if (!d || B < 1 || vg_vit_layout(d, &lay)) return -1;
+  if (!d || B < 1 || vg_vit_layout(d, &lay) || f32_tokens(*d) > VG_SHORT_MAX_S) return -1;
   F32Ws w;
   return carve_f32(*d, B, nullptr, w);
 }

@@ -100,6 +100,8 @@ class GanEngine:
             raise TypeError("GanEngine needs a ViTDiscriminator/VisionTransformer and a SirenGenerator")
         if getattr(vit, "precision", "bf16") != "bf16":
             raise ValueError("GanEngine: the fused step is bf16; it does not take a discriminator in precision='fp32'")
+        if float(gp_weight) != 0.0:
+            vit.require_short_attention("gp_weight > 0 (the gradient penalty)")
         self.vit, self.gen = vit, generator
         self.dev = vit._flat.flat.device
         if self.dev.type != "cuda" or generator._flat.flat.device != self.dev:

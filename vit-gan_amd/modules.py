@@ -194,6 +194,7 @@ class _VitF32Fn(torch.autograd.Function):
 
 
 PRECISIONS = ("bf16", "fp32")
+SHORT_ATTENTION_MAX_TOKENS = 80  # fp32 mode, fp8 attention, gradient penalty; bf16 dot-product attention runs up to 256
 
 
 class _VitFn(torch.autograd.Function):
@@ -251,8 +252,9 @@ class VisionTransformer(nn.Module):
         self._dropout_p = float(dropout)
         # fp8 (e4m3) MFMA operands for the attention's Q.K^T and P.V (BASELINE.json's 128x128 configuration); off by default
         # - the reference's arithmetic is fp32 and the parity tiers are stated for bf16 storage.  Not a Config field: set
-        # ``model.vit.attention_fp8 = True`` (GanEngine picks it up too).
-        self.attention_fp8 = False
+        # ``model.vit.attention_fp8 = True`` (GanEngine picks it up too).  S <= 80 tokens only.
+        self.tokens = (image_size // patch_size) ** 2 + 1
+        self._attention_fp8 = False
         # "bf16" (default): the engine above.  "fp32": fp32 activations, gradients and GEMM operands on the exact f32-input MFMA -
         # the reference's own arithmetic, for checking a run against the fp32 model or reproducing its numbers.  Not a Config field
         # either: set ``model.vit.precision = "fp32"``.  GanEngine and the gradient penalty stay bf16 and refuse it.
@@ -287,7 +289,26 @@ class VisionTransformer(nn.Module):
     def precision(self, value: str) -> None:
         if value not in PRECISIONS:
             raise ValueError(f"precision must be one of {PRECISIONS}, got {value!r}")
+        if value == "fp32":
+            self.require_short_attention("precision='fp32'")
         self._precision = value
+
+    @property
+    def attention_fp8(self) -> bool:
+        return self._attention_fp8
+
+    @attention_fp8.setter
+    def attention_fp8(self, value: bool) -> None:
+        if value:
+            self.require_short_attention("attention_fp8=True")
+        self._attention_fp8 = bool(value)
+
+    def require_short_attention(self, what: str) -> None:
+        """The attention kernels cover 80 < S <= 256 tokens for bf16 dot-product attention only: the fp32 mode, the fp8
+        attention and the gradient penalty's second-order attention stay at S <= 80."""
+        if self.tokens > SHORT_ATTENTION_MAX_TOKENS:
+            raise ValueError(f"{what} runs attention kernels for at most {SHORT_ATTENTION_MAX_TOKENS} tokens; this network has "
+                             f"{self.tokens} ((image_size / patch_size)^2 + 1)")
 
     def _ws_bytes_f32(self, B: int) -> int:
         n = _lib.lib().vg_vit_ws_bytes_f32(C.byref(self._dims), B)
@@ -330,6 +351,7 @@ class VisionTransformer(nn.Module):
         Dropout, as in ``composed_forward``, is torch's own on the modules' nn.Dropout layers."""
         if self._precision != "bf16":
             raise ValueError("twice_differentiable_forward is built on the bf16 operator set; set precision = 'bf16' for it")
+        self.require_short_attention("twice_differentiable_forward")
         if not x.is_cuda:
             raise RuntimeError("VisionTransformer: the HIP engine needs cuda tensors; there is no CPU fallback")
         emb = self.embedding

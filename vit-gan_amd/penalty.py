@@ -20,6 +20,7 @@ def gradient_penalty(discriminator, real_images: torch.Tensor, fake_images: torc
     vit = discriminator.vit if hasattr(discriminator, "vit") else discriminator
     if getattr(vit, "precision", "bf16") != "bf16":
         raise ValueError("gradient_penalty runs the bf16 operator set; it does not take a discriminator in precision='fp32'")
+    vit.require_short_attention("gradient_penalty")
     batch_size = real_images.size(0)
     if epsilon is None:
         epsilon = torch.rand(batch_size, 1, 1, 1, device=real_images.device if device is None else device)
