@@ -1,0 +1,356 @@
+"""Exact-input probes for the GEMM and attention kernels (a plain helper module, imported like gpu_util).
+
+The inputs are chosen so that the exact result is known and representable: small integers (the counting regime) or
+dyadic fractions i/8, j/16 (the dyadic regime) for the GEMMs, saturated softmax rows for attention.  fp32 accumulation of
+such inputs is exact in any order, so a kernel must reproduce the fp64 result, cast once with round-to-nearest-even,
+bit for bit; one dropped, doubled or misplaced product changes an integer by at least 1.  Everything here is plain torch
+on whatever device the tensors live on: tests/test_exact_probes_cpu.py checks the generators and the checkers themselves.
+"""
+import itertools
+
+import torch
+
+BF = torch.bfloat16
+GUARD_ROWS = 256      # rows of sentinel behind every output: a 256-row tile that overruns M lands in them
+BF_SENTINEL = 0x7FC1  # quiet NaNs with a payload no kernel produces: an unwritten element can never pass
+F32_SENTINEL = 0x7FC00ABC
+EXACT_LIMIT = 2.0 ** 24
+
+
+def gpu():
+    """gpu_util (raw C-ABI calls), imported only by the GPU tests that call it"""
+    import gpu_util
+    return gpu_util
+
+
+def collect(cases, fn, label=""):
+    """run fn(case) for every case and report every failing one in one message"""
+    fails = []
+    for c in cases:
+        try:
+            fn(c)
+        except AssertionError as e:
+            fails.append(f"{label}{c}: {e}")
+    assert not fails, f"{len(fails)} of {len(cases)} cases failed:\n" + "\n".join(fails[:12])
+
+
+def gen(seed, device="cpu"):
+    return torch.Generator(device=device).manual_seed(seed)
+
+
+# ------------------------------------------------------------------------------------------------------------- inputs
+def counting(shape, g, lo=-1, hi=1, density=1.0):
+    """integers uniform in [lo, hi] (fp64, on the generator's device); each kept with probability `density` (else 0)"""
+    x = torch.randint(lo, hi + 1, shape, generator=g, device=g.device).double()
+    if density < 1.0:
+        x = x * (torch.rand(shape, generator=g, device=g.device) < density).double()
+    return x
+
+
+def dyadic(shape, g, den, lim, density=1.0):
+    """i / den with i uniform in [-lim, lim]"""
+    return counting(shape, g, -lim, lim, density) / den
+
+
+def check_exact_gemm(A, B, extra=(), out_dtype=BF, what="gemm"):
+    """preconditions of a bitwise GEMM check, C = A @ B + sum(extra):
+    every partial sum, in any order, stays below 2^24 in magnitude (so fp32 accumulation is exact), and for a bf16
+    output every result is exactly representable (|y| <= 256 for integers).  Returns the fp64 result."""
+    A, B = A.double(), B.double()
+    bound = A.abs() @ B.abs()
+    for e in extra:
+        bound = bound + e.double().abs()
+    assert float(bound.max()) < EXACT_LIMIT, f"{what}: a partial sum can reach {float(bound.max())} >= 2^24"
+    y = A @ B
+    for e in extra:
+        y = y + e.double()
+    assert torch.equal(y, y.float().double()), f"{what}: result not exact in fp32"
+    if out_dtype == BF:
+        assert torch.equal(y, y.to(BF).double()), f"{what}: result not exactly representable in bf16 (max |y| {float(y.abs().max())})"
+    return y
+
+
+# ------------------------------------------------------------------------------------------------------- expectations
+def rne(x64, dtype):
+    """fp64 -> dtype with ONE round-to-nearest-even.  bf16 goes through fp32, which is exact for every value it is given here
+    (asserted): a double rounding would otherwise hide in it."""
+    x64 = x64.double()
+    x32 = x64.float()
+    if dtype == torch.float32:
+        return x32
+    assert torch.equal(x32.double(), x64), "rne: value not exact in fp32 (double rounding)"
+    return x32.to(dtype)
+
+
+def bits(t):
+    """integer bit patterns; -0 folded onto +0 (the sign of an exact zero sum depends on the accumulator's start value)"""
+    t = t.detach().contiguous()
+    if t.dtype == BF:
+        b = t.view(torch.int16).int() & 0xFFFF
+        return torch.where(b == 0x8000, torch.zeros_like(b), b)
+    if t.dtype == torch.float32:
+        b = t.view(torch.int32).long() & 0xFFFFFFFF
+        return torch.where(b == 0x80000000, torch.zeros_like(b), b)
+    if t.dtype == torch.uint8:
+        return t.int()
+    raise TypeError(t.dtype)
+
+
+def assert_bitwise(got, want, what):
+    """got == want bit for bit (want already in got's dtype)"""
+    assert got.dtype == want.dtype, (what, got.dtype, want.dtype)
+    assert got.shape == want.shape, (what, tuple(got.shape), tuple(want.shape))
+    bad = bits(got) != bits(want.to(got.device))
+    n = int(bad.sum())
+    if n:
+        idx = tuple(int(i) for i in bad.nonzero()[0])
+        raise AssertionError(f"{what}: {n} of {bad.numel()} elements differ; first at {idx}: got {float(got[idx])!r} "
+                             f"want {float(want[idx])!r}")
+
+
+def bf16_ulp(x64):
+    """spacing of bf16 at |x| (normal range; the subnormal spacing below 2^-126)"""
+    e = torch.floor(torch.log2(x64.abs().clamp_min(2.0 ** -126)))
+    return torch.pow(2.0, e - 7)
+
+
+def assert_ulps(got, ref64, what, ulps=1.0, floor=0.0):
+    """|got - ref| <= ulps * ulp_bf16(ref) + floor, elementwise, ref in fp64"""
+    got64 = got.detach().double().to(ref64.device)
+    assert got64.shape == ref64.shape, (what, tuple(got64.shape), tuple(ref64.shape))
+    err = (got64 - ref64).abs()
+    lim = ulps * bf16_ulp(ref64) + floor
+    bad = ~(err <= lim)
+    n = int(bad.sum())
+    if n:
+        idx = tuple(int(i) for i in bad.nonzero()[0])
+        raise AssertionError(f"{what}: {n} of {bad.numel()} elements off by more than {ulps} bf16 ulp; first at {idx}: "
+                             f"got {float(got64[idx])!r} want {float(ref64[idx])!r}")
+
+
+# ------------------------------------------------------------------------------------------------------------ canaries
+def guarded(rows, cols, dtype, device, guard=GUARD_ROWS):
+    """[rows + guard, cols] filled with the sentinel; the kernel gets buf[:rows]"""
+    if dtype == BF:
+        return torch.full((rows + guard, cols), BF_SENTINEL, dtype=torch.int16, device=device).view(BF)
+    if dtype == torch.float32:
+        return torch.full((rows + guard, cols), F32_SENTINEL, dtype=torch.int32, device=device).view(torch.float32)
+    if dtype == torch.uint8:
+        return torch.full((rows + guard, cols), 0xA5, dtype=torch.uint8, device=device)
+    raise TypeError(dtype)
+
+
+def sentinel_bits(dtype):
+    return {BF: BF_SENTINEL, torch.float32: F32_SENTINEL, torch.uint8: 0xA5}[dtype]
+
+
+def assert_guard(buf, rows, what):
+    """the guard rows behind `rows` still hold the sentinel"""
+    g = bits(buf[rows:]) != sentinel_bits(buf.dtype)
+    n = int(g.sum())
+    if n:
+        idx = tuple(int(i) for i in g.nonzero()[0])
+        raise AssertionError(f"{what}: {n} guard elements overwritten; first at row {rows + idx[0]} col {idx[1]}")
+
+
+def assert_written(buf, rows, what):
+    """no in-range element still holds the sentinel"""
+    s = bits(buf[:rows]) == sentinel_bits(buf.dtype)
+    n = int(s.sum())
+    if n:
+        idx = tuple(int(i) for i in s.nonzero()[0])
+        raise AssertionError(f"{what}: {n} elements never written; first at {idx}")
+
+
+# ---------------------------------------------------------------------------------------- saturated-softmax attention
+CODE = 64.0  # the key code c (e_a + e_b): target score 2 c^2, every other score <= c^2
+MIN_GAP = 110.0  # c^2 * scale >= 110: exp(-gap) underflows to 0 in fp32 even with denormals (e^-103.3 is the last one)
+
+
+class AttnProbe:
+    """one saturated-softmax probe of B images x H heads x S tokens (head dim HE), with its exact consequences.
+
+    kind: 'perm'   query q carries the code of key pi(q): O[q] = V[pi(q)], dQ = dK = 0
+          'tie2'   key `ties[1]` duplicates the code of key `ties[0]`: the queries on that code see a 2-way tie
+          'tie4'   four keys share one code (4-way tie); with either tie, query 0 carries the tied code
+          'sum'    some queries carry the sum of two keys' codes (4 distinct dims, no third key inside them): nonzero dQ
+    P is the exact softmax (1/t on the t tied maxima, 0 elsewhere); everything else follows from it in fp64."""
+
+    def __init__(self, B, H, S, HE, kind="perm", ties=None, seed=0, vlim=3, dolim=1):
+        assert S >= 1 and HE >= 4
+        self.B, self.H, self.S, self.HE, self.kind = B, H, S, HE, kind
+        g = gen(seed * 7919 + S * 131 + HE)
+        pairs = torch.tensor(list(itertools.combinations(range(HE), 2)))
+        assert len(pairs) >= S, "not enough codes"
+        Q = torch.zeros(B, H, S, HE, dtype=torch.float64)
+        K = torch.zeros(B, H, S, HE, dtype=torch.float64)
+        keys = torch.arange(S)
+        self.designed = torch.zeros(B, H, S, S, dtype=torch.bool)  # [b, h, q, k]: key k is one of query q's maxima by design
+        tied = kind in ("tie2", "tie4") and S >= len(ties)
+        for b in range(B):
+            for h in range(H):
+                sel = torch.randperm(len(pairs), generator=g)[:S]
+                if tied:
+                    sel[list(ties[1:])] = sel[ties[0]].clone()
+                kp = pairs[sel]  # key k's two dims
+                K[b, h, keys, kp[:, 0]] = CODE
+                K[b, h, keys, kp[:, 1]] = CODE
+                pi = torch.randperm(S, generator=g)
+                Q[b, h] = K[b, h, pi]
+                self.designed[b, h, keys, pi] = True
+                if tied:
+                    Q[b, h, 0] = K[b, h, ties[0]]  # query 0 (the CLS row) is always on the tie
+                    on_tie = [q for q in range(S) if q == 0 or int(pi[q]) in ties]
+                    self.designed[b, h, on_tie] = False
+                    for q in on_tie:
+                        self.designed[b, h, q, list(ties)] = True
+                if kind == "sum":
+                    for q, a, c in self._sum_queries(Q[b, h], [tuple(p) for p in kp.tolist()], g):
+                        self.designed[b, h, q] = False
+                        self.designed[b, h, q, [a, c]] = True
+        self.V = counting((B, H, S, HE), g, -vlim, vlim)
+        self.dO = counting((B, H, S, HE), g, -dolim, dolim)
+        self.Q, self.K = Q, K
+        self.qkv = torch.cat([self.flat(t) for t in (Q, K, self.V)], 1)
+
+    @staticmethod
+    def _sum_queries(Qh, kp, g):
+        """replace up to S/4 queries by code_a + code_b for key pairs (a, b) on 4 distinct dims whose 4 cross pairs are
+        nobody's code (so only a and b reach 2 c^2); returns the (query, a, b) triples"""
+        S = len(kp)
+        used = set(kp)
+        order = torch.randperm(S, generator=g).tolist()
+        nq, made = 0, []
+        for a, b in itertools.combinations(order, 2):
+            if nq >= max(1, S // 4):
+                break
+            (i, j), (k, l) = kp[a], kp[b]
+            if len({i, j, k, l}) < 4:
+                continue
+            if any(tuple(sorted(p)) in used for p in ((i, k), (i, l), (j, k), (j, l))):
+                continue
+            Qh[nq].zero_()
+            Qh[nq, [i, j, k, l]] = CODE
+            made.append((nq, a, b))
+            nq += 1
+        return made
+
+    # ---- exact consequences
+    def scores(self):
+        return self.Q @ self.K.transpose(-1, -2)  # exact integers (fp64)
+
+    def P(self):
+        s = self.scores()
+        top = s == s.amax(-1, keepdim=True)
+        return top.double() / top.sum(-1, keepdim=True)
+
+    def ties_per_query(self):
+        s = self.scores()
+        return (s == s.amax(-1, keepdim=True)).sum(-1)
+
+    def forward(self):
+        P = self.P()
+        return P @ self.V
+
+    def backward(self, scale, dO=None):
+        dO = self.dO if dO is None else dO
+        P = self.P()
+        O = P @ self.V
+        dV = P.transpose(-1, -2) @ dO
+        dP = dO @ self.V.transpose(-1, -2)
+        D = (dO * O).sum(-1, keepdim=True)
+        dS = P * (dP - D)
+        dQ = scale * dS @ self.K
+        dK = scale * dS.transpose(-1, -2) @ self.Q
+        return dQ, dK, dV, dS
+
+    def lse_exact(self, scale, queries=slice(None)):
+        """fp32 m (the kernels' scale * score in fp32) and log t of each query's t-way tie, [B, H, len(queries)]"""
+        m = torch.tensor(2 * CODE * CODE, dtype=torch.float32) * torch.tensor(scale, dtype=torch.float32)
+        s = self.scores()[:, :, queries]
+        top = s.amax(-1)
+        assert bool((top == 2 * CODE * CODE).all()), "every query's maximum is 2 c^2"
+        return m.double(), torch.log((s == top.unsqueeze(-1)).sum(-1).double())
+
+    def flat(self, t):
+        """[B, H, S, HE] -> [B*S, H*HE] (the kernels' row layout)"""
+        return t.permute(0, 2, 1, 3).reshape(self.B * self.S, self.H * self.HE)
+
+    def check_preconditions(self, scales):
+        """every query's maximum is 2 c^2 and its maxima are exactly the designed keys (its target, the designed tie or the
+        pair it is the sum of: no unintended tie anywhere), every other score is far enough below
+        it that its exp underflows to 0 in fp32 at each scale, and the backward's dS is exact in bf16"""
+        s = self.scores()
+        top = s.amax(-1, keepdim=True)
+        assert bool((top == 2 * CODE * CODE).all()), "a query's maximum is not 2 c^2"
+        rest = torch.where(s == top, torch.full_like(s, -1.0), s).amax(-1)  # scores are >= 0: -1 marks "no other key"
+        for scale in scales:
+            gap = (top.squeeze(-1) - rest) * scale
+            if bool((rest >= 0).any()):
+                assert float(gap[rest >= 0].min()) >= MIN_GAP, f"score gap {float(gap[rest >= 0].min())} < {MIN_GAP} at scale {scale}"
+        wrong = (s == top) != self.designed
+        if bool(wrong.any()):
+            b, h, q, k = (int(v) for v in wrong.nonzero()[0])
+            raise AssertionError(f"query {q} of head ({b}, {h}): key {k} is {'not ' if self.designed[b, h, q, k] else ''}"
+                                 f"a maximum, against the design")
+        dP = self.dO @ self.V.transpose(-1, -2)
+        spread = float((dP.amax(-1) - dP.amin(-1)).max())
+        assert spread <= 256, f"|dO.(V_a - V_b)| reaches {spread} > 256: dS would not survive its bf16 packing"
+        dS = self.backward(1.0)[3]
+        assert torch.equal(dS, dS.to(BF).double()), "dS not exact in bf16"
+
+
+# ---------------------------------------------------------------------------------- which GEMM kernel a shape reaches
+# A mirror of the dispatch in csrc/gemm.hip (vg_gemm_launch), gemm_wr.hip (vg_gemm_wr_try) and gemm_tn.hip (vg_gemm_tn384_try),
+# for naming the kernel in a failure message and for checking (tests/test_exact_probes_cpu.py) that the shape tables below
+# reach every one of them.
+def fwd_target(M, N, K, act=0, pre=None, res=False):
+    """vg_linear_fwd (pre: None / 'f32' / 'bf16' pre-activation output) and vg_linear_gelu_fwd (act 1, pre 'bf16': its byte
+    codes take the second-output slot)"""
+    c2 = pre == "bf16"
+    wr_epilogue = (act == 0 and not c2) or (act == 1 and c2 and not res) or (act == 3 and not c2 and not res)
+    if K == 384 and N % 128 == 0 and M >= 256 and M % 32 == 0 and pre != "f32" and N // 128 <= 64 and wr_epilogue:
+        return "wr"
+    light = act in (0, 1)
+    return "tiled256" if light and -(-M // 256) * -(-N // 128) >= 96 else "tiled128"
+
+
+def dgrad_target(M, N, K):
+    """vg_linear_dgrad: dX[M,K] = dY[M,N] W[N,K] (NN, contraction N)"""
+    if N == 384 and K % 128 == 0 and M >= 256 and M % 32 == 0 and K // 128 <= 64:
+        return "wr"
+    return "tiled256" if -(-M // 256) * -(-K // 128) >= 96 else "tiled128"
+
+
+def wgrad_target(M, N, K):
+    """vg_linear_wgrad: dW[N,K] = dY[M,N]^T X[M,K] (TN, contraction M)"""
+    if N % 128 == 0 and M % 32 == 0 and M >= 64 and (K % 384 == 0 or K % 512 == 0):
+        return "tn384" if K % 384 == 0 else "tn512"
+    return "tiled_tn"
+
+
+def wr_runs(M, N):
+    """(nfull, rem) of every run of the weights-in-registers kernel: units of 32 rows dealt to 8 * (64 / (N / 128)) runs"""
+    units, nruns = M // 32, 8 * (64 // (N // 128))
+    out = set()
+    for r in range(nruns):
+        n = (r + 1) * units // nruns - r * units // nruns
+        if n:
+            out.add((n >> 2, n & 3))
+    return out
+
+
+M_RESIDUES = [1, 2, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 288, 383, 384, 385, 511, 512, 513, 1040]
+# (M list, N, K) for vg_linear_fwd in the counting regime
+FWD_SHAPES = (
+    [(M_RESIDUES, N, K) for K in (48, 96, 384, 768, 1536) for N in (136, 256)]  # tiled128 (N % 128 != 0) and, at K = 384, wr
+    + [(M_RESIDUES, 136, 40), (M_RESIDUES, 256, 56)]                             # tiled128 with K tails of 8 and 24 (BK = 32)
+    + [([4100], 768, 96), ([3073], 1032, 48), ([8192], 384, 768)]                # tiled256: >= 96 tiles of 256 x 128
+    + [([256, 512, 768, 1024, 1280, 2560, 2816, 3328, 1120], 8192, 384)]         # wr with 8 runs: nfull 0 / 1 / many, rem 0..3
+    + [([16640], 1152, 384), ([16640], 384, 384), ([16640], 1536, 384)]          # wr at the step's shapes (QKV, out-proj, fc1)
+)
+# (M list, N, K) for vg_linear_dgrad (dX[M,K] = dY[M,N] W[N,K]); wr needs N = 384 (the contraction) and K % 128 == 0
+DGRAD_SHAPES = (
+    [(M_RESIDUES, 136, 200), (M_RESIDUES, 384, 256), (M_RESIDUES, 1536, 384)]
+    + [([4100], 96, 768), ([256, 1024, 2816], 384, 8192), ([16640], 384, 384), ([16640], 1536, 384)]
+)
