@@ -251,7 +251,8 @@ int vg_layernorm_bwd_bwd_parts(int R);
 int vg_layernorm_bwd_bwd(const void* u, const void* dy, const void* x, const float* mean, const float* rstd,
                          const float* gamma, void* d_dy, void* d_x, float* part, int R, int E, void* stream);
 /* backward of vg_attention_bwd: given u_qkv = dL/d(d_qkv) ([B*S, 3E], same layout as qkv), writes d_d_out = dL/d(d_out)
- * [B*S, E] and d_qkv2 = dL/d(qkv) [B*S, 3E].  lse from the forward.  S <= 80 and 14 S HE + 16 S^2 + 8 S <= 160 KiB. */
+ * [B*S, E] and d_qkv2 = dL/d(qkv) [B*S, 3E].  lse from the forward ([B, H, S]).  Every 1 <= S <= 80 at HE = 32, 64 or 96 (one
+ * five-tile MFMA instance, rows padded to 96, a fixed 74 KiB of LDS); -2: S outside that range, -3: another HE. */
 int vg_attention_bwd_bwd(const void* qkv, const void* d_out, const float* lse, const void* u_qkv, void* d_d_out,
                          void* d_qkv2, int B, int H, int S, int HE, float scale, void* stream);
 

@@ -20,7 +20,10 @@ __device__ __forceinline__ void act_derivs(int mode, float h, float& f, float& d
     float Phi, e;
     vg_phi_e(h, Phi, e);
     const float phi = 0.39894228040143268f * e;
-    f = h * Phi; d1 = Phi + h * phi; d2 = phi * (2.0f - h * h);
+    // a finite bf16 |h| >= 1.85e19 squares to +inf in fp32 while phi is exactly 0: 0 * -inf would be NaN where the derivative is 0.
+    // Where phi has underflowed any finite h gives the same -0, so take one whose square is finite (every other h: unchanged bits).
+    const float hs = (phi == 0.0f) ? 2.0f : h;
+    f = h * Phi; d1 = Phi + h * phi; d2 = phi * (2.0f - hs * hs);
   } else {
     const float t = vg_tanh(h);
     f = t; d1 = 1.0f - t * t; d2 = -2.0f * t * d1;
