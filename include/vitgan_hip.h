@@ -266,6 +266,34 @@ int vg_zero_tick(float* g, long long n, int* step_dev, void* stream);
 int vg_step_inputs(const float* real, void* imgs_bf16, long long n_img, float* z, long long n_z,
                    unsigned long long seed, const int* step_dev, void* stream);
 
+/* Differentiable augmentation of the discriminator's input (DiffAugment: color, translation, cutout; the reference has none, so this
+ * header is its definition) and its adjoint.  x, y, dy, dx bf16 [B, C, IH, IH] (x and y, dy and dx must not overlap); fp32 arithmetic.
+ * Per image n:  T = cutout o translation o contrast o saturation o brightness,  members switched by `policy` (bit 0 the three color
+ * members together, bit 1 translation, bit 2 cutout; 0 = a plain copy) with parameters (b, s, k, tx, ty, cx, cy):
+ *   brightness   x + b                                                          b = u0 - 0.5
+ *   saturation   m + s (x - m),  m = mean over the C channels of the pixel      s = 2 u1
+ *   contrast     M + k (x - M),  M = mean over the C*IH*IH elements of the image k = u2 + 0.5
+ *   translation  y[i, j] = x[i - ty, j - tx], zero outside                      tx = I3(2r + 1) - r, ty = I4(2r + 1) - r, r = IH / 8
+ *   cutout       zero for rows [cy - IH/4, cy - IH/4 + IH/2) x columns [cx - IH/4, cx - IH/4 + IH/2), clipped;  cx = I5(IH + 1), cy = I6(IH + 1)
+ * (integer divisions round down).  The parameters are a pure function of (seed, site, step_dev[0], n, p), in 32-bit arithmetic modulo 2^32
+ * behind the host key:
+ *   key  = fold(splitmix64(seed + 0x9E3779B97F4A7C15 (site + 1)))   the key of vg_dropout_apply's (seed, site): z = that sum mod 2^64;
+ *          z = (z ^ z >> 30) 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) 0x94D049BB133111EB;  z ^= z >> 31;  key = low 32 bits of (z ^ z >> 32)
+ *   h(k, i) = the counter hash of the dropout masks: x = i 0x9E3779B1 + k;  x ^= x >> 16;  x *= 0x7FEB352D;  x ^= x >> 15;
+ *          x *= 0x846CA68B;  x ^= x >> 16
+ *   ks   = h(step_dev ? key ^ (step_dev[0] 0x9E3779B1 + 0x7F4A7C15) : key, 0);   kn = h(ks, n);   k_p = h(kn, p) >> 8   (24 bits)
+ *   u_p  = k_p 2^-24 (exact in fp32, and so are b and s; k = u2 + 0.5 is that ONE fp32 addition, round to nearest even);   I_p(m) = (k_p m) >> 24
+ * A member that is off takes its identity: b = 0, s = k = 1, tx = ty = 0, cx = cy = -IH (a square that misses the image).
+ * params_out (nullable): fp32 [B, 8] = (b, s, k, tx, ty, cx, cy, policy) as the kernel used them.
+ * T is affine in x, so the adjoint takes dy and the same (policy, seed, site, step) only: with g[i, j] = dy[i + ty, j + tx] where that
+ * pixel is inside the frame and outside the cutout, else 0:  dx = k (s g + (1 - s) mean_channels(g)) + (1 - k) mean_image(g);
+ * accumulate = 1 adds into dx.  One launch each, one workgroup per image, fixed-order sums (bitwise reproducible), no scratch.
+ * Returns -1: null x / y or B < 1;  -2: policy outside [0, 7], C < 1, IH < 8 or IH > 255;  -3: C*IH*IH % 8 != 0 - all before any launch. */
+int vg_diffaug_fwd(const void* x, void* y, float* params_out, int B, int C, int IH, int policy, unsigned long long seed,
+                   int site, const unsigned* step_dev, void* stream);
+int vg_diffaug_bwd(const void* dy, void* dx, int accumulate, int B, int C, int IH, int policy, unsigned long long seed,
+                   int site, const unsigned* step_dev, void* stream);
+
 /* GAN losses on logits (src/v1/gan.py:16-20,227,238,250 for kind 0; hinge for kind 1;
  * kind 2 = the Wasserstein critic losses of src/v2/training.py:72,97).
  * role 0 D-real, 1 D-fake, 2 G.  loss_out[0] = mean loss, dlogits = d loss / d logits * grad_scale. */

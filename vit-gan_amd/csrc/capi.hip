@@ -384,3 +384,20 @@ extern "C" int vg_cast_f32_bf16(const float* src, void* dst_bf16, long long n, v
   if (!src || !dst_bf16 || n < 1) return -1;
   return vg_cast_f32_bf16_launch(src, (bf16*)dst_bf16, n, (hipStream_t)stream);
 }
+// ---- differentiable augmentation (augment.hip) ----
+static int vg_diffaug_args(const void* a, const void* b, int B, int C, int IH, int policy) {
+  if (!a || !b || B < 1) return -1;
+  if (policy < 0 || policy > 7 || C < 1 || IH < 8 || IH > 255) return -2;
+  if (((long long)C * IH * IH) & 7) return -3;
+  return 0;
+}
+extern "C" int vg_diffaug_fwd(const void* x, void* y, float* params_out, int B, int C, int IH, int policy, unsigned long long seed, int site,
+                              const unsigned* step_dev, void* stream) {
+  VG_TRY(vg_diffaug_args(x, y, B, C, IH, policy));
+  return vg_diffaug_fwd_launch((const bf16*)x, (bf16*)y, params_out, B, C, IH, policy, vg_site_key(seed, site), step_dev, (hipStream_t)stream);
+}
+extern "C" int vg_diffaug_bwd(const void* dy, void* dx, int accumulate, int B, int C, int IH, int policy, unsigned long long seed, int site,
+                              const unsigned* step_dev, void* stream) {
+  VG_TRY(vg_diffaug_args(dy, dx, B, C, IH, policy));
+  return vg_diffaug_bwd_launch((const bf16*)dy, (bf16*)dx, accumulate, B, C, IH, policy, vg_site_key(seed, site), step_dev, (hipStream_t)stream);
+}

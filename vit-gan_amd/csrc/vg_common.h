@@ -118,3 +118,40 @@ __device__ __forceinline__ uint32_t vg_drop_key(uint32_t key, const unsigned* __
 __device__ __forceinline__ float vg_drop_factor(uint32_t word, int e, uint32_t thresh, float scale) {
   return (((word >> (8 * (e & 3))) & 0xFFu) >= thresh) ? scale : 0.f;
 }
+
+// Differentiable augmentation (augment.hip): the per-image parameters, a pure function of (key, step counter, image, parameter).
+//   ks = vg_drop_word(vg_drop_key(key, dstep), 0)      the launch's key: host key of (seed, site) mixed with the device step counter
+//   kn = vg_drop_word(ks, n)                           image n of the launch
+//   k_p = vg_drop_word(kn, p) >> 8                     a 24-bit value for parameter p = 0..6 (b, s, k, tx, ty, cx, cy)
+// A uniform float is u = k_p * 2^-24 (exact in fp32); a uniform integer over m values is (k_p * m) >> 24 plus its lower end
+// (m <= 256, so the product stays inside 32 bits).  Members the policy switches off get their identity.
+struct VgAug {
+  float b, s, k;       // brightness u - 0.5, saturation 2u, contrast u + 0.5
+  int tx, ty, cx, cy;  // translation in [-IH/8, IH/8]; cutout centre in [0, IH] (off: -IH, a square that misses the image)
+};
+__device__ __forceinline__ VgAug vg_aug_draw(uint32_t key, const unsigned* __restrict__ dstep, uint32_t n, int IH, int policy) {
+  const uint32_t kn = vg_drop_word(vg_drop_word(vg_drop_key(key, dstep), 0u), n);
+  auto k24 = [&](uint32_t p) { return vg_drop_word(kn, p) >> 8; };
+  VgAug a = {0.f, 1.f, 1.f, 0, 0, -IH, -IH};
+  if (policy & 1) {
+    a.b = (float)k24(0) * 0x1p-24f - 0.5f;
+    a.s = (float)k24(1) * 0x1p-23f;
+    a.k = (float)k24(2) * 0x1p-24f + 0.5f;
+  }
+  if (policy & 2) {
+    const int r = IH >> 3;
+    a.tx = (int)((k24(3) * (uint32_t)(2 * r + 1)) >> 24) - r;
+    a.ty = (int)((k24(4) * (uint32_t)(2 * r + 1)) >> 24) - r;
+  }
+  if (policy & 4) {
+    a.cx = (int)((k24(5) * (uint32_t)(IH + 1)) >> 24);
+    a.cy = (int)((k24(6) * (uint32_t)(IH + 1)) >> 24);
+  }
+  return a;
+}
+// workgroup size of the augmentation kernels: one thread per chunk of 8 pixels of the IH*IH plane, in whole waves, 64 to 1024
+__host__ __device__ inline int vg_aug_threads(int IH) {
+  const int nch = (IH * IH + 7) >> 3;
+  const int nt = ((nch + 63) >> 6) << 6;
+  return nt < 64 ? 64 : nt > 1024 ? 1024 : nt;
+}

@@ -109,3 +109,8 @@ int vg_pen_norm_launch(const bf16* g, bf16* u, float* pen_img, float* pen_out, i
 int vg_pen_head2_launch(const bf16* u, const bf16* t, const float* W2, bf16* u_gt, bf16* s_p, int B, int E, int Kc, hipStream_t st);
 int vg_add_bf16_launch(const bf16* a, const bf16* b, bf16* out, long long n, hipStream_t st);
 int vg_fill_f32_launch(float* p, long long n, float v, hipStream_t st);
+// differentiable augmentation of the discriminator's input and its adjoint (augment.hip); key = vg_site_key(seed, site)
+int vg_diffaug_fwd_launch(const bf16* x, bf16* y, float* params_out, int B, int C, int IH, int policy, unsigned key, const unsigned* dstep,
+                          hipStream_t st);
+int vg_diffaug_bwd_launch(const bf16* dy, bf16* dx, int accumulate, int B, int C, int IH, int policy, unsigned key, const unsigned* dstep,
+                          hipStream_t st);

@@ -24,7 +24,7 @@ from typing import Optional
 import torch
 import torch.distributed as dist
 
-from . import _lib, flat
+from . import _lib, flat, ops
 from .dist import GradSync, backward_pieces
 from .generator import SirenGenerator
 from .modules import ViTDiscriminator, VisionTransformer
@@ -45,7 +45,7 @@ class GanEngine:
                  diversity_weight: float = 0.0, instance_noise: float = 0.0,
                  process_group: Optional["dist.ProcessGroup"] = None, external_noise: bool = False,
                  two_stream: bool = False, compress_mapping_grad: bool = False, shard_mapping_update: bool = False, gp_weight: float = 0.0,
-                 exchange_single_rank: bool = False, dense_top_block: bool = False, gp_autograd: bool = False):
+                 exchange_single_rank: bool = False, dense_top_block: bool = False, gp_autograd: bool = False, diffaug: str = ""):
         """concurrent_wgrad: the discriminator's weight gradients on a side stream beside its input gradients.  Off by default
         since the persistent GEMMs (csrc/gemm_wr.hip, gemm_tn.hip: their workgroups hold the CUs for a whole launch) - the
         side stream measured 6.70 against 6.67 ms/step.
@@ -94,7 +94,17 @@ class GanEngine:
         engine says so loudly (warning + ``graph_fallback_reason``) and runs eager - it never falls back silently.
         external_noise: the latent batch is supplied by the caller (``step(real, z)``) instead of being drawn on the
         device inside the step - what parity tests use to give their CPU checker and the engine the same noise, also under
-        hipGraph replay."""
+        hipGraph replay.
+        diffaug: differentiable augmentation of what the discriminator sees, a comma-separated subset of ``color,translation,cutout``
+        ("" = none: the step is launch for launch the plain one).  In its own step D sees T_1([real ; fake]) - after the instance
+        noise when both are on, real and fake rows drawing independently, the gradient penalty taken on the augmented pair; in the
+        generator's pass D sees T_2(fake) and ``dfake = T_2^T(dL/d T_2(fake))`` (vg_diffaug_fwd / vg_diffaug_bwd: one launch per
+        application, one for the adjoint).  The transforms are keyed on (seed, rank, site, device step counter), so data-parallel ranks
+        and every replay of the captured step draw their own; ``aug_params`` holds the last step's parameters of both sites.  Not
+        with ``two_stream``."""
+        self.aug = ops.parse_aug_policy(diffaug)  # ValueError names the three members; argument errors come before any device check
+        if self.aug and two_stream:
+            raise ValueError("diffaug: the augmented step is verified on the single-chain schedule only; switch two_stream off")
         vit = discriminator.vit if isinstance(discriminator, ViTDiscriminator) else discriminator
         if not isinstance(vit, VisionTransformer) or not isinstance(generator, SirenGenerator):
             raise TypeError("GanEngine needs a ViTDiscriminator/VisionTransformer and a SirenGenerator")
@@ -146,6 +156,8 @@ class GanEngine:
         self.shard_map = self._want_shard_map and self.sync.active and (g_.T * g_.E * g_.Z) % (4 * self.world) == 0
         # latent noise drawn on the device (vg_step_inputs): one stream per (seed, rank)
         self._noise_seed = (self.seed * 0x9E3779B97F4A7C15 + 0xD1B54A32D192ED03 * (self.sync.rank + 1)) & 0xFFFFFFFFFFFFFFFF
+        # differentiable augmentation (vg_diffaug_fwd): its own stream per (seed, rank), apart from the latent noise's
+        self._aug_seed = (self._noise_seed ^ 0xA0761D6478BD642F) & 0xFFFFFFFFFFFFFFFF
         d, g = vit._dims, generator._dims
         if g.T * g.CW != d.C * d.IH * d.IH:
             raise ValueError("generator output does not match the discriminator's image shape")
@@ -173,6 +185,11 @@ class GanEngine:
         if self.inst_sigma > 0.0:  # noisy copy of [real ; fake] for the D step, and the noise itself (kept for inspection / tests)
             self.inoise = torch.empty(2 * B, d.C, d.IH, d.IH, dtype=torch.float32, device=dev)
             self.imgs_noisy = torch.empty_like(self.imgs)
+        if self.aug:
+            # D step: imgs_aug = T_1(D's input pair).  Generator pass: imgs_aug[:B] = T_2(fake), imgs_aug[B:] = dL/d T_2(fake)
+            self.imgs_aug = torch.empty_like(self.imgs)
+            self.aug_params = {"d": torch.zeros(2 * B, 8, dtype=torch.float32, device=dev),  # (b, s, k, tx, ty, cx, cy, policy) per row
+                               "g": torch.zeros(B, 8, dtype=torch.float32, device=dev)}
         self.div_scratch = torch.zeros((d.C * d.IH * d.IH + 15) // 16, dtype=torch.float32, device=dev)
         self.logits = torch.empty(2 * B, d.Kc, dtype=torch.float32, device=dev)
         self.dlogits = torch.empty(2 * B, d.Kc, dtype=torch.float32, device=dev)
@@ -424,6 +441,7 @@ class GanEngine:
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         (nd, nd_b, nd_c), ng = self._nets()
         fd, fg = self.vit._flat, self.gen._flat
+        d_ = self.vit._dims
         img_bytes = self.imgs[0].numel() * 2
         fake_ptr = C.c_void_p(self.imgs.data_ptr() + B * img_bytes)
         # gan.discriminator.zero_grad() (training.py:177) and the device step counter += 1, one launch
@@ -435,6 +453,10 @@ class GanEngine:
             torch.add(self.imgs.float(), self.inoise, alpha=self.inst_sigma, out=self.inoise)
             self.imgs_noisy.copy_(self.inoise)
             d_in = self.imgs_noisy
+        if self.aug:  # D sees T_1([real ; fake]) (site 0), and so does the penalty below
+            _lib.check(L.vg_diffaug_fwd(_p(d_in), _p(self.imgs_aug), _p(self.aug_params["d"]), 2 * B, d_.C, d_.IH, self.aug, self._aug_seed, 0,
+                                        _p(self.step_t), st), "vg_diffaug_fwd")
+            d_in = self.imgs_aug
         if self.gp_c_call:  # gradient_penalty(D, noisy_real, noisy_fake) joins the D loss (training.py:101-106): one C call
             if self.gp_epsilon is not None:
                 torch.add(self.gp_epsilon.reshape(-1).float(), 0.0, out=self.gp_eps)  # (an elementwise kernel, not a D2D copy: no memcpy / memset nodes in the captured step)
@@ -474,9 +496,16 @@ class GanEngine:
         self.sync.wait()
         self._adamw(fd, self.m_d, self.v_d, self.hyp["lr_d"], st, self.clip_d, 0)
         fg.grad.zero_()            # gan.generator.zero_grad(), training.py:199
-        _lib.check(L.vg_vit_forward(C.byref(nd_c), B, fake_ptr, 1, _p(self.ws_d), _p(self.logits), st), "vg_vit_forward")
+        g_in, g_dimg = fake_ptr, _p(self.dfake)
+        if self.aug:  # D sees T_2(fake) (site 1); its input gradient goes back through the adjoint into dfake
+            g_in, g_dimg = _p(self.imgs_aug), C.c_void_p(self.imgs_aug.data_ptr() + B * img_bytes)
+            _lib.check(L.vg_diffaug_fwd(fake_ptr, g_in, _p(self.aug_params["g"]), B, d_.C, d_.IH, self.aug, self._aug_seed, 1, _p(self.step_t), st),
+                       "vg_diffaug_fwd")
+        _lib.check(L.vg_vit_forward(C.byref(nd_c), B, g_in, 1, _p(self.ws_d), _p(self.logits), st), "vg_vit_forward")
         self._loss(0, B, 2, 2, st)
-        _lib.check(L.vg_vit_backward(C.byref(nd_c), B, _p(self.ws_d), _p(self.dlogits), _p(self.dfake), 0, st), "vg_vit_backward")
+        _lib.check(L.vg_vit_backward(C.byref(nd_c), B, _p(self.ws_d), _p(self.dlogits), g_dimg, 0, st), "vg_vit_backward")
+        if self.aug:
+            _lib.check(L.vg_diffaug_bwd(g_dimg, _p(self.dfake), 0, B, d_.C, d_.IH, self.aug, self._aug_seed, 1, _p(self.step_t), st), "vg_diffaug_bwd")
         if self.div_w != 0.0:  # total_gen_loss = loss + w * diversity_loss(fake_images): its gradient joins dL/d fake
             Dn = self.dfake[0].numel()
             _lib.check(L.vg_diversity_loss(fake_ptr, _p(self.dfake), _p(self.div_loss), _p(self.div_scratch), B, Dn, self.div_w, st),

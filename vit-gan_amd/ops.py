@@ -272,3 +272,59 @@ def attention(qkv, heads: int, scale: Optional[float] = None, lp: int = 1):
     if scale is None:
         scale = 1.0 / math.sqrt(qkv.shape[-1] // 3 // heads)
     return AttentionFn.apply(qkv, heads, scale, lp)
+
+
+AUG_MEMBERS = {"color": 1, "translation": 2, "cutout": 4}  # policy bits of vg_diffaug_fwd
+
+
+def parse_aug_policy(policy) -> int:
+    """``"color,translation,cutout"`` (any comma-separated subset, "" = none) or the bit mask itself -> the policy bits."""
+    if isinstance(policy, int) and not isinstance(policy, bool):
+        if not 0 <= policy <= 7:
+            raise ValueError(f"augmentation policy bits must be in [0, 7], got {policy}")
+        return policy
+    if not isinstance(policy, str):
+        raise ValueError(f"augmentation policy must be a comma-separated subset of {', '.join(AUG_MEMBERS)}, got {policy!r}")
+    bits = 0
+    for name in (s.strip() for s in policy.split(",")):
+        if name == "" and policy.strip() == "":
+            continue
+        if name not in AUG_MEMBERS:
+            raise ValueError(f"unknown augmentation {name!r}: the policy is a comma-separated subset of {', '.join(AUG_MEMBERS)}")
+        bits |= AUG_MEMBERS[name]
+    return bits
+
+
+class DiffAugmentFn(torch.autograd.Function):
+    """T = cutout o translation o contrast o saturation o brightness per image (include/vitgan_hip.h, vg_diffaug_fwd); T is affine
+    in x, so the backward is the adjoint kernel on dy with the same (policy, seed, site, step) and nothing is saved."""
+
+    @staticmethod
+    def forward(ctx, x, policy, seed, site, step):
+        _need_cuda(x, "diff_augment")
+        B, Cc, IH, IW = x.shape
+        assert IH == IW, "The provided images are not square shaped"
+        if step is not None and (not step.is_cuda or step.dtype != torch.int32):
+            raise ValueError("diff_augment: step is the device step counter, a cuda int32 tensor")
+        xb = _bf(x)
+        y = torch.empty_like(xb)
+        _lib.check(_lib.lib().vg_diffaug_fwd(_p(xb), _p(y), None, B, Cc, IH, policy, seed, site, _p(step), _st()), "vg_diffaug_fwd")
+        # the adjoint must see the counter value of THIS forward, whatever the caller does to the counter before backward()
+        ctx.key = (policy, seed, site, None if step is None else step.clone(), x.dtype)
+        return y.to(x.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        policy, seed, site, step, dt = ctx.key
+        B, Cc, IH, _ = dy.shape
+        d = _bf(dy)
+        dx = torch.empty_like(d)
+        _lib.check(_lib.lib().vg_diffaug_bwd(_p(d), _p(dx), 0, B, Cc, IH, policy, seed, site, _p(step), _st()), "vg_diffaug_bwd")
+        return dx.to(dt), None, None, None, None
+
+
+def diff_augment(x, policy, seed: int, site: int, step: Optional[torch.Tensor] = None):
+    """Differentiable augmentation of images [B, C, IH, IH]: ``policy`` a comma-separated subset of color, translation, cutout (or
+    its bit mask); the transform of image n is a pure function of (seed, site, step[0], n) - ``step``: a cuda int32 counter, or None."""
+    return DiffAugmentFn.apply(x, parse_aug_policy(policy), int(seed) & 0xFFFFFFFFFFFFFFFF, int(site), step)

@@ -203,12 +203,16 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                 loss: str = "ns", device: str = "cuda:0", seed: int = 0, data_loader: Optional[Iterable] = None,
                 fid_fn: Optional[Callable[[nn.Module, int], float]] = None, output_base: Optional[str] = None,
                 save_artifacts: bool = True, clip_d: Optional[float] = None, clip_g: Optional[float] = None,
-                diversity_weight: float = 0.0, instance_noise: float = 0.0, gp_weight: float = 0.0):
+                diversity_weight: float = 0.0, instance_noise: float = 0.0, gp_weight: float = 0.0, diffaug: str = ""):
     """``loss``: "ns" (default: the executable v1 loss), "hinge", or "wasserstein" - the critic losses of the reference's
     unreached step (training.py:67-125); ``clip_d`` / ``clip_g``: its clip_grad_norm_ limits (5.0 / 0.5 there);
     ``diversity_weight``: its diversity term (0.1 there); ``instance_noise``: sigma of the noise on D's inputs (0.1
-    there); ``gp_weight``: the weight of its gradient penalty (``c.lambda_gp``, a field the reference's Config lacks)."""
+    there); ``gp_weight``: the weight of its gradient penalty (``c.lambda_gp``, a field the reference's Config lacks);
+    ``diffaug``: differentiable augmentation of the discriminator's inputs, a comma-separated subset of color, translation, cutout
+    (``GanEngine(diffaug=...)``; the reference has none)."""
     global _log_file
+    from .ops import parse_aug_policy
+    parse_aug_policy(diffaug)  # a bad policy string is the caller's error whatever the machine: before the device check
     c = Config() if not config else Config(**config)
     if not torch.cuda.is_available():
         raise RuntimeError("train_model needs an MI355X: the HIP engine has no CPU path")
@@ -222,7 +226,7 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     D, G = gan.discriminator, gan.generator
     eng = GanEngine(D, G, batch=c.batch_size, loss=loss, lr_d=c.discriminator_learning_rate, lr_g=c.generator_learning_rate,
                     weight_decay=1e-3, seed=seed, clip_d=clip_d, clip_g=clip_g, diversity_weight=diversity_weight,
-                    instance_noise=instance_noise, gp_weight=gp_weight)
+                    instance_noise=instance_noise, gp_weight=gp_weight, diffaug=diffaug)
     loader = data_loader if data_loader is not None else SyntheticLoader(c, steps_per_epoch, dev)
     epochs = c.epochs if max_epochs is None else min(c.epochs, max_epochs)
 
@@ -250,6 +254,8 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     try:
         log(f"Starting training at: {datetime.datetime.now()}")
         log("Parameters:\n" + str(c))
+        if diffaug:
+            log(f"Differentiable augmentation: {diffaug}")
         for epoch in range(epochs):
             noise = construct_noise()
             if save_artifacts:
