@@ -311,6 +311,21 @@ int vg_gan_loss_pair(const float* logits, float* dlogits, float* loss_out, int n
 int vg_adamw_step(float* p, const float* g, float* m, float* v, void* shadow_bf16, long long n,
                   float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                   const int* step_dev, float gscale, void* stream);
+/* vg_adamw_step plus an exponential moving average of the updated weights in the same pass (38 B per parameter against 30; the
+ * generator's sample / FID weights).  p, m, v and shadow_bf16 come out bit for bit as vg_adamw_step writes them.  With
+ * t = step_dev ? step_dev[0] : step (read, never written) and p1 the updated weight:
+ *   t <= max(1, ema_start):  ema = p1                    (the average follows the weights through the warm-up; the first step always
+ *                                                         copies, whatever ema held - a zeroed step counter restarts the average)
+ *   else:                    ema = fmaf(1 - d, p1 - ema, ema),  d = ema_decay.
+ * ema (fp32, n elements) must not overlap another buffer.  -1: a null pointer, -3: n % 4 != 0, -2: ema_decay outside [0, 1) or
+ * ema_start < 0 - all before any launch. */
+int vg_adamw_ema_step(float* p, const float* g, float* m, float* v, void* shadow_bf16, float* ema, long long n,
+                      float lr, float beta1, float beta2, float eps, float weight_decay, int step, const int* step_dev,
+                      float gscale, float ema_decay, int ema_start, void* stream);
+/* The same rule applied to given (already updated) weights p: bit-equal to vg_adamw_ema_step's ema.  For ranges whose AdamW ran
+ * elsewhere (the sharded update of the generator's mapping Linear). */
+int vg_ema_update(float* ema, const float* p, long long n, float ema_decay, int ema_start, int step, const int* step_dev,
+                  void* stream);
 /* diversity_loss of the reference's unreached generator step (src/v2/utils.py:147-152; training.py:73-74 adds 0.1 x it
  * to the generator loss): loss_out[0] = sum_{i,j} |x_i - x_j|_1 / (B (B-1)) over images bf16 [B, D]; when d_images is
  * not NULL, d_images (bf16 [B, D]) += weight * d loss / d images.  scratch: ceil(D/16) floats.  B <= 1024. */

@@ -371,6 +371,18 @@ extern "C" int vg_adamw_step(float* p, const float* g, float* m, float* v, void*
   return vg_adamw_launch(p, g, m, v, (bf16*)shadow_bf16, n, lr, beta1, beta2, eps, weight_decay, step, step_dev, gscale,
                          (hipStream_t)stream);
 }
+extern "C" int vg_adamw_ema_step(float* p, const float* g, float* m, float* v, void* shadow_bf16, float* ema, long long n, float lr,
+                                 float beta1, float beta2, float eps, float weight_decay, int step, const int* step_dev, float gscale,
+                                 float ema_decay, int ema_start, void* stream) {
+  if (!p || !g || !m || !v || !shadow_bf16 || !ema || n < 1 || (step < 1 && !step_dev)) return -1;
+  return vg_adamw_ema_launch(p, g, m, v, (bf16*)shadow_bf16, ema, n, lr, beta1, beta2, eps, weight_decay, step, step_dev, gscale, ema_decay,
+                             ema_start, (hipStream_t)stream);
+}
+extern "C" int vg_ema_update(float* ema, const float* p, long long n, float ema_decay, int ema_start, int step, const int* step_dev,
+                             void* stream) {
+  if (!ema || !p || n < 1 || (step < 1 && !step_dev)) return -1;
+  return vg_ema_launch(ema, p, n, ema_decay, ema_start, step, step_dev, (hipStream_t)stream);
+}
 extern "C" int vg_diversity_loss(const void* images, void* d_images, float* loss_out, float* scratch, int B, int D, float weight,
                                 void* stream) {
   if (!images || !loss_out || !scratch) return -1;

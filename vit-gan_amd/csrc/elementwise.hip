@@ -451,17 +451,21 @@ int vg_diversity_launch(const bf16* x, bf16* d_img, float* loss_out, float* scra
 // ---- fused AdamW over a flat parameter buffer (torch.optim.AdamW semantics) ----------------------
 // p *= 1 - lr*wd;  m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;
 // p -= (lr / bc1) * m / (sqrt(v)/sqrt(bc2) + eps);  shadow = bf16(p).   g is pre-scaled by gscale.
-__global__ __launch_bounds__(256) void vg_adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                       float* __restrict__ v, bf16* __restrict__ shadow, long long n, float lr,
-                                                       float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                                                       float gscale, const int* __restrict__ step_dev) {
-  const long long i4 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
-  if (i4 >= n) return;
-  if (step_dev) {  // step counter kept on the device so a captured hipGraph replays correctly
-    const float t = (float)step_dev[0];
-    bc1 = 1.f - __powf(b1, t);
-    bc2_sqrt = sqrtf(1.f - __powf(b2, t));
+struct VgAdamwArgs {
+  float lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale;
+  const int* step_dev;
+};
+// The update of four adjacent elements, the ONE copy of the arithmetic that vg_adamw_kernel and vg_adamw_ema_kernel share (their p, m, v
+// and shadow agree bit for bit).  Returns the updated weights; they, the moments and the shadow are stored here.
+__device__ __forceinline__ f32x4 vg_adamw_update4(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                  float* __restrict__ v, bf16* __restrict__ shadow, long long i4, const VgAdamwArgs& a) {
+  float bc1 = a.bc1, bc2_sqrt = a.bc2_sqrt;
+  if (a.step_dev) {  // step counter kept on the device so a captured hipGraph replays correctly
+    const float t = (float)a.step_dev[0];
+    bc1 = 1.f - __powf(a.b1, t);
+    bc2_sqrt = sqrtf(1.f - __powf(a.b2, t));
   }
+  const float lr = a.lr, b1 = a.b1, b2 = a.b2, eps = a.eps, wd = a.wd, gscale = a.gscale;
   f32x4 pv = *(f32x4*)(p + i4), gv = *(const f32x4*)(g + i4), mv = *(f32x4*)(m + i4), vv = *(f32x4*)(v + i4);
   bf16x4 sh;
 #pragma unroll
@@ -475,6 +479,43 @@ __global__ __launch_bounds__(256) void vg_adamw_kernel(float* __restrict__ p, co
   }
   *(f32x4*)(p + i4) = pv; *(f32x4*)(m + i4) = mv; *(f32x4*)(v + i4) = vv;
   *(bf16x4*)(shadow + i4) = sh;
+  return pv;
+}
+__global__ __launch_bounds__(256) void vg_adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                       float* __restrict__ v, bf16* __restrict__ shadow, long long n, VgAdamwArgs a) {
+  const long long i4 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i4 >= n) return;
+  vg_adamw_update4(p, g, m, v, shadow, i4, a);
+}
+// ---- exponential moving average of the weights (the generator's sample / FID weights) ------------
+// t <= max(1, start): e = p (the average follows the weights through the warm-up; the first step ALWAYS copies, so e's old content -
+// an uninitialised buffer, a NaN - never enters: it is not even read);  else e += (1 - d)(p - e) as ONE fma.  The counter is read only.
+__device__ __forceinline__ void vg_ema_update4(float* __restrict__ e, const f32x4 p1, long long i4, float decay, int start, int step,
+                                               const int* __restrict__ step_dev) {
+  const int t = step_dev ? step_dev[0] : step;
+  f32x4 ev = p1;
+  if (t > (start > 1 ? start : 1)) {  // (uniform over the launch)
+    const float omd = 1.f - decay;    // exact for d in [0.5, 1)
+    const f32x4 e0 = *(const f32x4*)(e + i4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ev[j] = fmaf(omd, p1[j] - e0[j], e0[j]);
+  }
+  *(f32x4*)(e + i4) = ev;
+}
+// AdamW and the average in one pass over the weights: 38 B per parameter (30 for AdamW alone; 42 as two launches, which read p again)
+__global__ __launch_bounds__(256) void vg_adamw_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, bf16* __restrict__ shadow, float* __restrict__ ema,
+                                                           long long n, VgAdamwArgs a, float decay, int start, int step) {
+  const long long i4 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i4 >= n) return;
+  const f32x4 p1 = vg_adamw_update4(p, g, m, v, shadow, i4, a);
+  vg_ema_update4(ema, p1, i4, decay, start, step, a.step_dev);
+}
+__global__ __launch_bounds__(256) void vg_ema_kernel(float* __restrict__ ema, const float* __restrict__ p, long long n, float decay, int start,
+                                                     int step, const int* __restrict__ step_dev) {
+  const long long i4 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i4 >= n) return;
+  vg_ema_update4(ema, *(const f32x4*)(p + i4), i4, decay, start, step, step_dev);
 }
 __global__ __launch_bounds__(256) void vg_cast_f32_bf16_kernel(const float* __restrict__ src, bf16* __restrict__ dst, long long n) {
   const long long i4 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
@@ -712,11 +753,28 @@ int vg_gan_loss_launch(const float* logit, float* dlog, float* loss_out, int n, 
   hipLaunchKernelGGL(vg_gan_loss_kernel, dim3(1), dim3(256), 0, st, logit, dlog, loss_out, n, kind, role, grad_scale);
   return (int)hipGetLastError();
 }
+static VgAdamwArgs vg_adamw_args(float lr, float b1, float b2, float eps, float wd, int step, const int* step_dev, float gscale) {
+  return VgAdamwArgs{lr, b1, b2, eps, wd, 1.f - powf(b1, (float)step), sqrtf(1.f - powf(b2, (float)step)), gscale, step_dev};
+}
 int vg_adamw_launch(float* p, const float* g, float* m, float* v, bf16* shadow, long long n, float lr, float b1, float b2,
                     float eps, float wd, int step, const int* step_dev, float gscale, hipStream_t st) {
   if (n & 3) return -3;
-  const float bc1 = 1.f - powf(b1, (float)step), bc2s = sqrtf(1.f - powf(b2, (float)step));
-  hipLaunchKernelGGL(vg_adamw_kernel, dim3(nblk(n / 4)), dim3(256), 0, st, p, g, m, v, shadow, n, lr, b1, b2, eps, wd, bc1, bc2s, gscale, step_dev);
+  hipLaunchKernelGGL(vg_adamw_kernel, dim3(nblk(n / 4)), dim3(256), 0, st, p, g, m, v, shadow, n,
+                     vg_adamw_args(lr, b1, b2, eps, wd, step, step_dev, gscale));
+  return (int)hipGetLastError();
+}
+int vg_adamw_ema_launch(float* p, const float* g, float* m, float* v, bf16* shadow, float* ema, long long n, float lr, float b1, float b2,
+                        float eps, float wd, int step, const int* step_dev, float gscale, float decay, int start, hipStream_t st) {
+  if (n & 3) return -3;
+  if (!(decay >= 0.f && decay < 1.f) || start < 0) return -2;
+  hipLaunchKernelGGL(vg_adamw_ema_kernel, dim3(nblk(n / 4)), dim3(256), 0, st, p, g, m, v, shadow, ema, n,
+                     vg_adamw_args(lr, b1, b2, eps, wd, step, step_dev, gscale), decay, start, step);
+  return (int)hipGetLastError();
+}
+int vg_ema_launch(float* ema, const float* p, long long n, float decay, int start, int step, const int* step_dev, hipStream_t st) {
+  if (n & 3) return -3;
+  if (!(decay >= 0.f && decay < 1.f) || start < 0) return -2;
+  hipLaunchKernelGGL(vg_ema_kernel, dim3(nblk(n / 4)), dim3(256), 0, st, ema, p, n, decay, start, step, step_dev);
   return (int)hipGetLastError();
 }
 int vg_cast_f32_bf16_launch(const float* src, bf16* dst, long long n, hipStream_t st) {

@@ -68,6 +68,9 @@ int vg_gan_loss_launch(const float* logit, float* dlog, float* loss_out, int n, 
                        hipStream_t st);
 int vg_adamw_launch(float* p, const float* g, float* m, float* v, bf16* shadow, long long n, float lr, float b1, float b2,
                     float eps, float wd, int step, const int* step_dev, float gscale, hipStream_t st);
+int vg_adamw_ema_launch(float* p, const float* g, float* m, float* v, bf16* shadow, float* ema, long long n, float lr, float b1, float b2,
+                        float eps, float wd, int step, const int* step_dev, float gscale, float decay, int start, hipStream_t st);
+int vg_ema_launch(float* ema, const float* p, long long n, float decay, int start, int step, const int* step_dev, hipStream_t st);
 int vg_cast_f32_bf16_launch(const float* src, bf16* dst, long long n, hipStream_t st);
 int vg_slab_reduce_launch(const float* slab, long long stride, int nslab, float* dst, long long n, int accumulate, hipStream_t st);
 // two folds of the same shape in one launch (the two blocks of a paired weight-gradient launch)

@@ -45,7 +45,8 @@ class GanEngine:
                  diversity_weight: float = 0.0, instance_noise: float = 0.0,
                  process_group: Optional["dist.ProcessGroup"] = None, external_noise: bool = False,
                  two_stream: bool = False, compress_mapping_grad: bool = False, shard_mapping_update: bool = False, gp_weight: float = 0.0,
-                 exchange_single_rank: bool = False, dense_top_block: bool = False, gp_autograd: bool = False, diffaug: str = ""):
+                 exchange_single_rank: bool = False, dense_top_block: bool = False, gp_autograd: bool = False, diffaug: str = "",
+                 ema_decay: float = 0.0, ema_start: int = 0):
         """concurrent_wgrad: the discriminator's weight gradients on a side stream beside its input gradients.  Off by default
         since the persistent GEMMs (csrc/gemm_wr.hip, gemm_tn.hip: their workgroups hold the CUs for a whole launch) - the
         side stream measured 6.70 against 6.67 ms/step.
@@ -101,8 +102,21 @@ class GanEngine:
         generator's pass D sees T_2(fake) and ``dfake = T_2^T(dL/d T_2(fake))`` (vg_diffaug_fwd / vg_diffaug_bwd: one launch per
         application, one for the adjoint).  The transforms are keyed on (seed, rank, site, device step counter), so data-parallel ranks
         and every replay of the captured step draw their own; ``aug_params`` holds the last step's parameters of both sites.  Not
-        with ``two_stream``."""
+        with ``two_stream``.
+        ema_decay: decay d of an exponential moving average of the GENERATOR's fp32 master weights, kept in ``ema_g`` by the generator's
+        optimizer kernel itself (vg_adamw_ema_step: one pass, 38 B per parameter against AdamW's 30; no extra launch, nothing a
+        replayed graph could miss).  With t the device step counter and p_t the weights after step t:  e_t = p_t while
+        t <= max(1, ema_start) (the average follows the weights through the warm-up), then e_t = e_{t-1} + (1 - d)(p_t - e_{t-1}).
+        0.0 (default) = no average: no buffer, and the step is launch for launch the plain one.  The discriminator is not averaged.
+        Under ``shard_mapping_update`` the mapping Linear's average is updated from the gathered master (vg_ema_update), so every
+        rank holds the average of a replicated run, bit for bit.  ``sample(z)`` draws from the average, ``ema_state_dict()`` exports
+        it under the generator's keys, ``state_dict()`` carries it across a restart."""
         self.aug = ops.parse_aug_policy(diffaug)  # ValueError names the three members; argument errors come before any device check
+        self.ema_decay, self.ema_start = float(ema_decay), int(ema_start)
+        if not 0.0 <= self.ema_decay < 1.0:
+            raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
+        if self.ema_start < 0 or self.ema_start != ema_start:
+            raise ValueError(f"ema_start must be a non-negative integer, got {ema_start!r}")
         if self.aug and two_stream:
             raise ValueError("diffaug: the augmented step is verified on the single-chain schedule only; switch two_stream off")
         vit = discriminator.vit if isinstance(discriminator, ViTDiscriminator) else discriminator
@@ -199,6 +213,13 @@ class GanEngine:
         fd, fg = vit._flat, generator._flat
         self.m_d, self.v_d = torch.zeros_like(fd.flat), torch.zeros_like(fd.flat)
         self.m_g, self.v_g = torch.zeros_like(fg.flat), torch.zeros_like(fg.flat)
+        # the generator's averaged weights (a copy of the master until the first step, which copies again: see ema_decay)
+        self.ema_g: Optional[torch.Tensor] = fg.flat.detach().clone() if self.ema_decay > 0.0 else None
+        self._ema_from = self.ema_start  # the kernels' ema_start (a non-strict load_state_dict without an average moves it)
+        self._ema_shadow: Optional[torch.Tensor] = None  # bf16 cast of ema_g for sample(): allocated on first use
+        self._ema_cast_key = None                        # (steps, loads) the cast was made at
+        self._ema_loads = 0
+        self._sample_ws: Optional[torch.Tensor] = None
         fd.refresh_shadow()
         fg.refresh_shadow()
         self.ctx = _lib.context() if concurrent_wgrad else None
@@ -316,31 +337,44 @@ class GanEngine:
         w0, w1 = self._map_range()
         a, b = self.sync.share(w0, w1)
 
-        def upd(lo, hi):
+        def upd(lo, hi, ema=None):
             if hi <= lo:
                 return
             off = lambda t, es: C.c_void_p(t.data_ptr() + es * lo)  # noqa: E731
-            _lib.check(L.vg_adamw_step(off(fg.flat, 4), off(fg.grad, 4), off(self.m_g, 4), off(self.v_g, 4), off(fg.shadow, 2), hi - lo,
-                                       self.hyp["lr_g"], h["b1"], h["b2"], h["eps"], h["wd"], 0, _p(self.step_t), 1.0 / self.world, st), "vg_adamw_step")
-        upd(0, w0)
+            if ema is None:
+                _lib.check(L.vg_adamw_step(off(fg.flat, 4), off(fg.grad, 4), off(self.m_g, 4), off(self.v_g, 4), off(fg.shadow, 2), hi - lo,
+                                           self.hyp["lr_g"], h["b1"], h["b2"], h["eps"], h["wd"], 0, _p(self.step_t), 1.0 / self.world, st), "vg_adamw_step")
+            else:
+                _lib.check(L.vg_adamw_ema_step(off(fg.flat, 4), off(fg.grad, 4), off(self.m_g, 4), off(self.v_g, 4), off(fg.shadow, 2), off(ema, 4),
+                                               hi - lo, self.hyp["lr_g"], h["b1"], h["b2"], h["eps"], h["wd"], 0, _p(self.step_t), 1.0 / self.world,
+                                               self.ema_decay, self._ema_from, st), "vg_adamw_ema_step")
+        upd(0, w0, self.ema_g)
         upd(a, b)
-        upd(w1, fg.total)
+        upd(w1, fg.total, self.ema_g)
         self.sync.all_gather_range(fg.flat, w0, w1)
         self.sync.wait()
         _lib.check(L.vg_cast_f32_bf16(C.c_void_p(fg.flat.data_ptr() + 4 * w0), C.c_void_p(fg.shadow.data_ptr() + 2 * w0), w1 - w0, st),
                    "vg_cast_f32_bf16")
+        if self.ema_g is not None:  # the layer's average from the gathered master: what the fused kernel of a replicated run writes
+            _lib.check(L.vg_ema_update(C.c_void_p(self.ema_g.data_ptr() + 4 * w0), C.c_void_p(fg.flat.data_ptr() + 4 * w0), w1 - w0,
+                                       self.ema_decay, self._ema_from, 0, _p(self.step_t), st), "vg_ema_update")
 
     def gather_master(self) -> None:
         """A no-op, kept for callers: the sharded update of the mapping Linear all-gathers its fp32 master inside the step, so every
         rank's master is current after every step.  (It issues no collective, so it is safe on a branch that differs by rank.)"""
 
-    def _adamw(self, fp, m, v, lr, st, clip=None, slot=0):
+    def _adamw(self, fp, m, v, lr, st, clip=None, slot=0, ema=None):
         h = self.hyp
         if clip is not None:  # on the exchanged (global) gradient, like clip_grad_norm_ before optimizer.step()
             _lib.check(_lib.lib().vg_grad_clip(_p(fp.grad), fp.total, 1.0 / self.world, float(clip), _p(self.clip_scratch[slot]), st),
                        "vg_grad_clip")
-        _lib.check(_lib.lib().vg_adamw_step(_p(fp.flat), _p(fp.grad), _p(m), _p(v), _p(fp.shadow), fp.total, lr, h["b1"], h["b2"],
-                                            h["eps"], h["wd"], 0, _p(self.step_t), 1.0 / self.world, st), "vg_adamw_step")
+        if ema is None:
+            _lib.check(_lib.lib().vg_adamw_step(_p(fp.flat), _p(fp.grad), _p(m), _p(v), _p(fp.shadow), fp.total, lr, h["b1"], h["b2"],
+                                                h["eps"], h["wd"], 0, _p(self.step_t), 1.0 / self.world, st), "vg_adamw_step")
+        else:  # the same update and the weights' moving average in one pass
+            _lib.check(_lib.lib().vg_adamw_ema_step(_p(fp.flat), _p(fp.grad), _p(m), _p(v), _p(fp.shadow), _p(ema), fp.total, lr, h["b1"],
+                                                    h["b2"], h["eps"], h["wd"], 0, _p(self.step_t), 1.0 / self.world, self.ema_decay,
+                                                    self._ema_from, st), "vg_adamw_ema_step")
 
     def _loss(self, lo, n, role, slot, st):
         L = _lib.lib()
@@ -408,7 +442,7 @@ class GanEngine:
             _lib.check(L.vg_diversity_loss(fake_ptr, _p(self.dfake), _p(self.div_loss), _p(self.div_scratch), B, Dn, self.div_w, st0),
                        "vg_diversity_loss")
         _lib.check(L.vg_gen_backward(C.byref(ng), B, _p(self.ws_g), _p(self.dfake), st0), "vg_gen_backward")
-        self._adamw(fg, self.m_g, self.v_g, self.hyp["lr_g"], st0, self.clip_g, 1)
+        self._adamw(fg, self.m_g, self.v_g, self.hyp["lr_g"], st0, self.clip_g, 1, self.ema_g)
 
     def _inputs(self, real: torch.Tensor) -> None:
         """The step's inputs, ONE launch in front of the step proper (and outside its hipGraph, so it reads the caller's tensor
@@ -515,19 +549,21 @@ class GanEngine:
         if self.shard_map:
             self._adamw_g_sharded(st)
         else:
-            self._adamw(fg, self.m_g, self.v_g, self.hyp["lr_g"], st, self.clip_g, 1)
+            self._adamw(fg, self.m_g, self.v_g, self.hyp["lr_g"], st, self.clip_g, 1, self.ema_g)
 
     # ------------------------------------------------------------------------------------------
     def _state_tensors(self):
         """Everything a step changes that the next step reads (the training state held on the device)."""
         fd, fg = self.vit._flat, self.gen._flat
-        return [fd.flat, fd.shadow, fg.flat, fg.shadow, self.m_d, self.v_d, self.m_g, self.v_g, self.step_t]
+        state = [fd.flat, fd.shadow, fg.flat, fg.shadow, self.m_d, self.v_d, self.m_g, self.v_g, self.step_t]
+        return state if self.ema_g is None else state + [self.ema_g]
 
     def sync_from_modules(self, reset_optimizer: bool = False) -> None:
         """Call after the modules' parameters were changed behind the engine's back (``load_state_dict``, an in-place
         edit): refreshes the bf16 shadows the GEMMs read; ``reset_optimizer`` also clears AdamW's moments and step count
         (a fresh optimizer, which is what the reference has after a restart: it saves no optimizer state,
-        training.py:218-226,262-263)."""
+        training.py:218-226,262-263).  The generator's moving average needs no code here: a plain refresh leaves it alone, and a
+        cleared step counter makes the next step's kernel copy the updated weights into it - the average restarts with the optimizer."""
         self.vit._flat.refresh_shadow()
         self.gen._flat.refresh_shadow()
         if reset_optimizer:
@@ -536,6 +572,112 @@ class GanEngine:
             # the latent noise is keyed on the device step counter just cleared: move to a fresh stream, keyed on the steps this
             # engine has really done, so a restarted run does not replay the first run's latent sequence
             self._noise_seed = (self._noise_seed * 0x9E3779B97F4A7C15 + 0xD1B54A32D192ED03 * (self.steps + 1)) & 0xFFFFFFFFFFFFFFFF
+
+    # ------------------------------------------------------------------------------------------ averaged generator, sampling
+    def _need_ema(self, what: str) -> torch.Tensor:
+        if self.ema_g is None:
+            raise RuntimeError(f"{what}: this engine keeps no averaged generator (built with ema_decay=0)")
+        return self.ema_g
+
+    def sample(self, z: torch.Tensor, ema: bool = True) -> torch.Tensor:
+        """Images [n, C, IH, IW] (``generator.out_dtype``) of the latent batch ``z`` [n, Z], n any batch size: one forward-only
+        vg_gen_forward without dropout on the current stream, from the averaged weights (``ema=True``: ``ema_g`` and a bf16 cast of
+        it, recast only after a step or a load) or from the live master and shadow (``ema=False``: what ``G.eval()(z)`` computes).
+        It has its own workspace - the step's belongs to the captured graph - and changes no training state."""
+        gen, fg = self.gen, self.gen._flat
+        if ema:
+            self._need_ema("sample(ema=True)")
+        if z.dim() != 2 or z.shape[1] != gen._dims.Z or z.shape[0] < 1 or z.device != self.dev:
+            raise ValueError(f"z must be a [n, {gen._dims.Z}] tensor on {self.dev}")
+        L, n = _lib.lib(), int(z.shape[0])
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if ema:
+            if self._ema_shadow is None:
+                self._ema_shadow = torch.empty(fg.total, dtype=torch.bfloat16, device=self.dev)
+            key = (self.steps, self._ema_loads)
+            if self._ema_cast_key != key:
+                _lib.check(L.vg_cast_f32_bf16(_p(self.ema_g), _p(self._ema_shadow), fg.total, st), "vg_cast_f32_bf16")
+                self._ema_cast_key = key
+            master, shadow = self.ema_g, self._ema_shadow
+        else:
+            fg.refresh_shadow()  # like a module forward: the same bits after a step, current weights after an in-place edit
+            master, shadow = fg.flat, fg.shadow
+        need = gen._ws_bytes(n)
+        if self._sample_ws is None or self._sample_ws.numel() < need:
+            self._sample_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        tab = gen.fourier_table
+        net = _lib.VgGenNet(gen._dims, master.data_ptr(), shadow.data_ptr(), fg.grad.data_ptr(), 0.0, 0, None, None if tab is None else tab.data_ptr())
+        zin = z.detach().float().contiguous()
+        img = torch.empty(n, gen.channels, gen.image_size, gen.image_size, dtype=torch.bfloat16, device=self.dev)
+        _lib.check(L.vg_gen_forward(C.byref(net), n, _p(zin), _p(self._sample_ws), _p(img), st), "vg_gen_forward")
+        return img.to(gen.out_dtype)
+
+    def ema_state_dict(self) -> dict:
+        """The averaged generator under the generator's own keys and shapes (fp32 clones): loads ``strict=True`` into a SirenGenerator."""
+        e = self._need_ema("ema_state_dict()")
+        return {k: e[off:off + flat.numel(shape)].view(shape).clone() for k, (off, shape) in self.gen._flat.slots.items()}
+
+    def load_ema_state_dict(self, sd) -> None:
+        """Copy an ``ema_state_dict()`` into the average in place (a captured graph stays valid)."""
+        e, slots = self._need_ema("load_ema_state_dict()"), self.gen._flat.slots
+        if set(sd) != set(slots):
+            odd = sorted(set(sd) ^ set(slots))
+            raise ValueError(f"load_ema_state_dict: keys differ from the generator's, e.g. {odd[:3]}")
+        for k, (off, shape) in slots.items():
+            if tuple(sd[k].shape) != tuple(shape):
+                raise ValueError(f"load_ema_state_dict: {k} has shape {tuple(sd[k].shape)}, the generator's is {tuple(shape)}")
+        with torch.no_grad():
+            for k, (off, shape) in slots.items():
+                e[off:off + flat.numel(shape)].view(shape).copy_(sd[k])
+        self._ema_loads += 1
+
+    # ------------------------------------------------------------------------------------------ training state across a restart
+    STATE_FORMAT = 1
+
+    def state_dict(self) -> dict:
+        """The engine's training state - what ``gan.state_dict()`` (the networks' weights) does not hold: AdamW's moments, the
+        device step counter (it keys the bias corrections, the dropout masks, the latent noise and the augmentation), the host's
+        step count, the current latent-noise stream and, when it is on, the generator's moving average."""
+        sd = {"format_version": self.STATE_FORMAT, "steps": int(self.steps), "noise_seed": int(self._noise_seed)}
+        for k in ("m_d", "v_d", "m_g", "v_g", "step_t"):
+            sd[k] = getattr(self, k).detach().clone()
+        if self.ema_g is not None:
+            sd["ema_g"] = self.ema_g.detach().clone()
+        return sd
+
+    def load_state_dict(self, sd, strict: bool = True) -> None:
+        """Restore ``state_dict()`` in place (a captured graph stays valid) and refresh the shadows from the modules' current
+        weights - so: load the ``gan`` state, then this, then go on stepping.  Wrong sizes, a missing entry or another format
+        version raise ValueError.  An engine with the moving average on that is given a state without ``ema_g`` raises under
+        ``strict``; with ``strict=False`` the average restarts as a copy of the weights at the next step (the step is captured again)."""
+        if sd.get("format_version") != self.STATE_FORMAT:
+            raise ValueError(f"engine state format {sd.get('format_version')!r}, this engine reads format {self.STATE_FORMAT}")
+        names = ("m_d", "v_d", "m_g", "v_g", "step_t")
+        missing = [k for k in names + ("steps", "noise_seed") if k not in sd]
+        if missing:
+            raise ValueError(f"engine state lacks {missing}")
+        has_ema = sd.get("ema_g") is not None
+        if strict and has_ema != (self.ema_g is not None):
+            raise ValueError("engine state has no ema_g but this engine keeps a moving average (strict=False restarts it)" if not has_ema
+                             else "engine state has an ema_g but this engine keeps no moving average")
+        pairs = [(getattr(self, k), sd[k], k) for k in names]
+        if has_ema and self.ema_g is not None:
+            pairs.append((self.ema_g, sd["ema_g"], "ema_g"))
+        for dst, src, k in pairs:
+            if not torch.is_tensor(src) or src.numel() != dst.numel():
+                raise ValueError(f"engine state {k}: {tuple(getattr(src, 'shape', ()))} does not fit this engine's {tuple(dst.shape)}")
+        with torch.no_grad():
+            for dst, src, _ in pairs:
+                dst.copy_(src.reshape(dst.shape))
+        self.steps, self._noise_seed = int(sd["steps"]), int(sd["noise_seed"]) & 0xFFFFFFFFFFFFFFFF
+        if self.ema_g is not None:
+            self._ema_loads += 1
+            # no average in the state: the step after the loaded counter copies.  ema_start is an argument of the captured kernel
+            # node, so that (rare) case drops the graph; the next step captures it again
+            start = self.ema_start if has_ema else max(self.ema_start, int(sd["step_t"].reshape(-1)[0]) + 1)
+            if start != self._ema_from:
+                self._ema_from, self._graph = start, None
+        self.sync_from_modules()
 
     def step(self, real: torch.Tensor, z: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Run one G/D step on ``real`` [B,C,IH,IW] (cuda).  Returns the device tensor

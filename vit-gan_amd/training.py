@@ -42,7 +42,7 @@ from torch import nn
 from . import _lib
 from .config import Config
 from .engine import GanEngine
-from .modules import ViTGAN
+from .modules import ViTGAN, generator_from_config
 
 START_TIME = datetime.datetime.now()
 
@@ -203,16 +203,27 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                 loss: str = "ns", device: str = "cuda:0", seed: int = 0, data_loader: Optional[Iterable] = None,
                 fid_fn: Optional[Callable[[nn.Module, int], float]] = None, output_base: Optional[str] = None,
                 save_artifacts: bool = True, clip_d: Optional[float] = None, clip_g: Optional[float] = None,
-                diversity_weight: float = 0.0, instance_noise: float = 0.0, gp_weight: float = 0.0, diffaug: str = ""):
+                diversity_weight: float = 0.0, instance_noise: float = 0.0, gp_weight: float = 0.0, diffaug: str = "",
+                ema_decay: float = 0.0, ema_start: int = 0):
     """``loss``: "ns" (default: the executable v1 loss), "hinge", or "wasserstein" - the critic losses of the reference's
     unreached step (training.py:67-125); ``clip_d`` / ``clip_g``: its clip_grad_norm_ limits (5.0 / 0.5 there);
     ``diversity_weight``: its diversity term (0.1 there); ``instance_noise``: sigma of the noise on D's inputs (0.1
     there); ``gp_weight``: the weight of its gradient penalty (``c.lambda_gp``, a field the reference's Config lacks);
     ``diffaug``: differentiable augmentation of the discriminator's inputs, a comma-separated subset of color, translation, cutout
-    (``GanEngine(diffaug=...)``; the reference has none)."""
+    (``GanEngine(diffaug=...)``; the reference has none);
+    ``ema_decay`` / ``ema_start``: an exponential moving average of the generator's weights, kept inside the step
+    (``GanEngine(ema_decay=...)``; the reference has none).  When it is on, the sample grids and ``fid_fn`` see the AVERAGED
+    generator - an eval-mode ``SirenGenerator`` refreshed from the engine before each use, returned as ``"generator_ema"`` -
+    and ``generator_ema.pth`` (its state_dict) is written beside ``final_model.ckpt`` and beside each best-FID checkpoint.
+    ``engine_state.pth`` (``GanEngine.state_dict()``: optimizer moments, step counter, the average) is written beside
+    ``final_model.ckpt`` in every run; the ``gan.state_dict()`` files keep the reference's keys."""
     global _log_file
     from .ops import parse_aug_policy
     parse_aug_policy(diffaug)  # a bad policy string is the caller's error whatever the machine: before the device check
+    if not 0.0 <= float(ema_decay) < 1.0:
+        raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
+    if int(ema_start) != ema_start or ema_start < 0:
+        raise ValueError(f"ema_start must be a non-negative integer, got {ema_start!r}")
     c = Config() if not config else Config(**config)
     if not torch.cuda.is_available():
         raise RuntimeError("train_model needs an MI355X: the HIP engine has no CPU path")
@@ -226,7 +237,17 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     D, G = gan.discriminator, gan.generator
     eng = GanEngine(D, G, batch=c.batch_size, loss=loss, lr_d=c.discriminator_learning_rate, lr_g=c.generator_learning_rate,
                     weight_decay=1e-3, seed=seed, clip_d=clip_d, clip_g=clip_g, diversity_weight=diversity_weight,
-                    instance_noise=instance_noise, gp_weight=gp_weight, diffaug=diffaug)
+                    instance_noise=instance_noise, gp_weight=gp_weight, diffaug=diffaug, ema_decay=ema_decay, ema_start=ema_start)
+    G_ema: Optional[nn.Module] = None
+    gan_ema: Optional[nn.Module] = None
+    if eng.ema_g is not None:  # the averaged generator as a module of its own: same constructor arguments, eval mode, never trained
+        G_ema = generator_from_config(trainable_config(c)).to(dev).eval()
+        gan_ema = nn.Module()  # what fid_fn receives: .generator = the averaged network, .discriminator = D
+        gan_ema.generator, gan_ema.discriminator = G_ema, D
+
+    def refresh_ema():
+        if G_ema is not None:
+            G_ema.load_state_dict(eng.ema_state_dict(), strict=True)
     loader = data_loader if data_loader is not None else SyntheticLoader(c, steps_per_epoch, dev)
     epochs = c.epochs if max_epochs is None else min(c.epochs, max_epochs)
 
@@ -236,11 +257,16 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     def save_samples(label: Union[str, int], noise: torch.Tensor):  # training.py:52-57
         if not save_artifacts:
             return
-        was = G.training
-        G.eval()
-        with torch.no_grad():
-            samples = G(noise).detach().float().cpu() * 0.5 + 0.5
-        G.train(was)
+        if G_ema is not None:  # from the averaged weights
+            refresh_ema()
+            with torch.no_grad():
+                samples = G_ema(noise).detach().float().cpu() * 0.5 + 0.5
+        else:
+            was = G.training
+            G.eval()
+            with torch.no_grad():
+                samples = G(noise).detach().float().cpu() * 0.5 + 0.5
+            G.train(was)
         save_images(os.path.join(dirs.images, f"samples_epoch_{label}.png"), samples, c.batch_size)
 
     def noise_as_image(noise: torch.Tensor) -> torch.Tensor:  # the latent is a vector here: show it as 1x32x32 tiles
@@ -272,12 +298,16 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
             disc_losses.append(d_real + d_fake)
             gen_losses.append(g)
             history.append((d_real + d_fake, g))
-            fid_score = float(fid_fn(gan, epoch)) if fid_fn is not None else float("nan")
+            if fid_fn is not None:
+                refresh_ema()
+            fid_score = float(fid_fn(gan if gan_ema is None else gan_ema, epoch)) if fid_fn is not None else float("nan")
             fid_scores.append(fid_score)
             if fid_score < best_fid:
                 best_fid = fid_score
                 if save_artifacts:
                     torch.save(gan.state_dict(), os.path.join(dirs.checkpoints, f"best_model_epoch_{epoch}_fid_{int(fid_score)}.pth"))
+                    if G_ema is not None:  # refreshed just above, for fid_fn
+                        torch.save(G_ema.state_dict(), os.path.join(dirs.checkpoints, "generator_ema.pth"))
             log(f"Epoch [{epoch}/{epochs}] | Disc Loss: {d_real + d_fake:.8f}, Gen Loss: {g:.4f} | FID: {fid_score:.4f}")
             if save_artifacts:
                 save_figures(dirs.save, disc_losses=disc_losses, gen_losses=gen_losses, fid_scores=fid_scores)
@@ -293,7 +323,10 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
         if save_artifacts and fatal is None:  # no further GPU work, no checkpoint of a broken run
             save_figures(dirs.save, disc_losses=disc_losses, gen_losses=gen_losses, fid_scores=fid_scores)
             torch.save(gan.state_dict(), model_path)
+            torch.save(eng.state_dict(), os.path.join(dirs.save, "engine_state.pth"))
             save_samples(epoch, construct_noise())
+            if G_ema is not None:  # refreshed by save_samples
+                torch.save(G_ema.state_dict(), os.path.join(dirs.save, "generator_ema.pth"))
         took = datetime.datetime.now() - dirs.start
         if fatal is None and save_artifacts:
             log(f"Run took {took}. Saving the model to: {model_path}")
@@ -304,4 +337,8 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
         _log_file = None
     if fatal is not None:
         raise fatal
-    return {"discriminator": D, "generator": G, "gan": gan, "engine": eng, "history": history, "dirs": dirs}
+    out = {"discriminator": D, "generator": G, "gan": gan, "engine": eng, "history": history, "dirs": dirs}
+    if G_ema is not None:
+        refresh_ema()
+        out["generator_ema"] = G_ema
+    return out
