@@ -338,6 +338,44 @@ int vg_diversity_loss(const void* images, void* d_images, float* loss_out, float
 int vg_grad_clip(float* g, long long n, float gscale, float max_norm, float* scratch, void* stream);
 int vg_cast_f32_bf16(const float* src, void* dst_bf16, long long n, void* stream);
 
+/* Spectral normalisation of a set of weight matrices that live inside one flat parameter buffer (ViTGAN's form,
+ * W_eff = sigma_max(W_init) W / sigma_max(W); one power iteration per step as torch.nn.utils.spectral_norm runs in training).
+ * The GEMMs read the bf16 shadow only, so normalising is a scaled cast of the fp32 master into the shadow plus one linear
+ * correction of the gradient buffer before the optimizer.
+ *
+ * A table entry names one matrix W [N, K], row-major at element offset w_off of the flat buffers.  The caller fills w_off, N, K;
+ * vg_spectral_plan (host only) fills every other field and returns the sizes, in floats, of
+ *   state:   per matrix u [N] at u_off, v [K] at v_off, sigma at s_off, sigma0 at s_off + 1 (offsets are multiples of 4)
+ *   scratch: per matrix t [K], w [N] and one partial sum per VG_SPEC_CHUNK elements; needs no initialisation.
+ * The caller keeps the table twice, on the host (validated by every call) and as the same bytes on the device (read by the kernels).
+ *
+ * vg_spectral_update, iterate = 1, on the master W (3 launches for the whole table):
+ *   t = W^T u ; v = t / max(|t|, 1e-12) ; w = W v ; sigma = |w| ; u = w / max(sigma, 1e-12)
+ *   shadow[w_off + i] = bf16_rne(fp32(sigma0 / max(sigma, 1e-12)) * W[i])       for the table's ranges only
+ * iterate = 0 (1 launch): the same cast from the stored sigma; u, v, sigma unchanged (after a plain cast of the whole buffer).
+ * vg_spectral_project (2 launches), G = dL/dW_eff in the gradient buffer, with the stored (u, v, sigma), s = sigma0 / sigma:
+ *   G[w_off + nK + k] <- s * fma(-(<G, W> / sigma) * u[n], v[k], G[..])         (u and v constants, as in torch)
+ * fp32 throughout, fixed summation order, no atomics: two runs are bit-equal.  Elements outside the table's ranges are not written.
+ * Errors, before any launch: -1 a null pointer or n < 1; -2 N < 1, K < 1, a range outside [0, total), a buffer smaller than the
+ * plan's, or a table whose planned fields are not vg_spectral_plan's; -3 overlapping ranges, W / G / state / scratch not 16-byte or
+ * shadow not 8-byte aligned; -4 iterate not 0 or 1. */
+#define VG_SPEC_COLS 64     /* columns per workgroup of the W^T u pass */
+#define VG_SPEC_ROWS 16     /* rows per workgroup of the W v pass */
+#define VG_SPEC_CHUNK 8192  /* elements per workgroup of the cast / dot / projection passes */
+typedef struct VgSpectralDesc {
+  long long w_off;
+  int N, K;
+  long long u_off, v_off, s_off;        /* state */
+  long long t_off, w_tmp_off, dot_off;  /* scratch */
+  int blk_a, blk_b, blk_c, reserved;    /* first workgroup of this matrix in the three grids */
+} VgSpectralDesc;
+int vg_spectral_plan(VgSpectralDesc* table_host, int n, long long* state_floats, long long* scratch_floats); /* host only */
+int vg_spectral_update(const float* W, void* shadow_bf16, long long total, float* state, long long state_floats, float* scratch,
+                       long long scratch_floats, const VgSpectralDesc* table_host, const VgSpectralDesc* table_dev, int n, int iterate,
+                       void* stream);
+int vg_spectral_project(float* G, const float* W, long long total, const float* state, long long state_floats, float* scratch,
+                        long long scratch_floats, const VgSpectralDesc* table_host, const VgSpectralDesc* table_dev, int n, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Whole-network passes (what the nn.Modules call: one C call per forward / backward)
  * ---------------------------------------------------------------------------------------- */

@@ -26,6 +26,8 @@ MODES = {
     "wasserstein + gp (operator set)": dict(loss="wasserstein", gp_weight=10.0, gp_autograd=True),
     "dense top block": dict(dense_top_block=True),
     "no dropout": dict(d_dropout=0.0, g_dropout=0.0),
+    "spectral normalisation (all), wasserstein + gp (C call)": dict(spectral_norm="all", loss="wasserstein", clip_d=5.0, gp_weight=10.0),
+    "spectral normalisation (qkv)": dict(spectral_norm="qkv"),
 }
 bad = []
 for name, kw in MODES.items():

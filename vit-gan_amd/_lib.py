@@ -61,6 +61,11 @@ class VgGenNet(C.Structure):
                 ("dropout_p", c_float), ("dropout_seed", C.c_ulonglong), ("dropout_step", c_void_p), ("pos_table", c_void_p)]
 
 
+class VgSpectralDesc(C.Structure):
+    _fields_ = ([("w_off", c_ll), ("N", c_int), ("K", c_int)] + [(n, c_ll) for n in ("u_off", "v_off", "s_off", "t_off", "w_tmp_off", "dot_off")]
+                + [(n, c_int) for n in ("blk_a", "blk_b", "blk_c", "reserved")])
+
+
 P = c_void_p
 _SIGNATURES = {
     "vg_abi_version": (c_int, []),
@@ -126,6 +131,9 @@ _SIGNATURES = {
     "vg_diversity_loss": (c_int, [P, P, P, P, c_int, c_int, c_float, P]),
     "vg_grad_clip": (c_int, [P, c_ll, c_float, c_float, P, P]),
     "vg_cast_f32_bf16": (c_int, [P, P, c_ll, P]),
+    "vg_spectral_plan": (c_int, [P, c_int, C.POINTER(c_ll), C.POINTER(c_ll)]),
+    "vg_spectral_update": (c_int, [P, P, c_ll, P, c_ll, P, c_ll, P, P, c_int, c_int, P]),
+    "vg_spectral_project": (c_int, [P, P, c_ll, P, c_ll, P, c_ll, P, P, c_int, P]),
     "vg_ctx_create": (c_int, [C.POINTER(c_void_p)]),
     "vg_ctx_destroy": (c_int, [c_void_p]),
     "vg_vit_layout": (c_int, [C.POINTER(VgVitDims), C.POINTER(VgVitLayout)]),

@@ -3,6 +3,10 @@
 #include "vg_kernels.h"
 #include "vg_row.h"
 #include "vg_chain.h"
+#include "vg_spectral.h"
+#include <algorithm>
+#include <cstring>
+#include <vector>
 
 extern "C" int vg_abi_version(void) { return VG_ABI_VERSION; }
 
@@ -382,6 +386,50 @@ extern "C" int vg_ema_update(float* ema, const float* p, long long n, float ema_
                              void* stream) {
   if (!ema || !p || n < 1 || (step < 1 && !step_dev)) return -1;
   return vg_ema_launch(ema, p, n, ema_decay, ema_start, step, step_dev, (hipStream_t)stream);
+}
+// ---- spectral normalisation (spectral.hip)
+extern "C" int vg_spectral_plan(VgSpectralDesc* table_host, int n, long long* state_floats, long long* scratch_floats) {
+  if (!table_host || n < 1) return -1;
+  return vg_spectral_plan_host(table_host, n, state_floats, scratch_floats, nullptr);
+}
+// every argument error of vg_spectral_update / vg_spectral_project (see the header); blocks receives the three grid sizes
+static int spectral_check(const VgSpectralDesc* th, int n, long long total, long long state_floats, long long scratch_floats, int* blocks) {
+  std::vector<VgSpectralDesc> plan(th, th + n);
+  long long need_state = 0, need_scratch = 0;
+  const int rc = vg_spectral_plan_host(plan.data(), n, &need_state, &need_scratch, blocks);
+  if (rc != 0) return rc;
+  if (std::memcmp(plan.data(), th, sizeof(VgSpectralDesc) * (size_t)n) != 0) return -2;
+  if (state_floats < need_state || scratch_floats < need_scratch) return -2;
+  std::vector<std::pair<long long, long long>> r((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    const long long nk = (long long)th[i].N * th[i].K;
+    if (nk > total || th[i].w_off > total - nk) return -2;
+    r[(size_t)i] = {th[i].w_off, th[i].w_off + nk};
+  }
+  std::sort(r.begin(), r.end());
+  for (int i = 1; i < n; ++i)
+    if (r[(size_t)i].first < r[(size_t)i - 1].second) return -3;
+  return 0;
+}
+static inline bool misaligned(const void* p, unsigned a) { return ((uintptr_t)p & (a - 1)) != 0; }
+extern "C" int vg_spectral_update(const float* W, void* shadow_bf16, long long total, float* state, long long state_floats, float* scratch,
+                                  long long scratch_floats, const VgSpectralDesc* table_host, const VgSpectralDesc* table_dev, int n, int iterate,
+                                  void* stream) {
+  if (!W || !shadow_bf16 || !state || !scratch || !table_host || !table_dev || n < 1) return -1;
+  if (iterate != 0 && iterate != 1) return -4;
+  int blocks[3];
+  VG_TRY(spectral_check(table_host, n, total, state_floats, scratch_floats, blocks));
+  if (misaligned(W, 16) || misaligned(state, 16) || misaligned(scratch, 16) || misaligned(shadow_bf16, 8)) return -3;
+  return vg_spectral_update_launch(W, (bf16*)shadow_bf16, state, scratch, table_dev, n, blocks, iterate, (hipStream_t)stream);
+}
+extern "C" int vg_spectral_project(float* G, const float* W, long long total, const float* state, long long state_floats, float* scratch,
+                                   long long scratch_floats, const VgSpectralDesc* table_host, const VgSpectralDesc* table_dev, int n,
+                                   void* stream) {
+  if (!G || !W || !state || !scratch || !table_host || !table_dev || n < 1) return -1;
+  int blocks[3];
+  VG_TRY(spectral_check(table_host, n, total, state_floats, scratch_floats, blocks));
+  if (misaligned(G, 16) || misaligned(W, 16) || misaligned(state, 16) || misaligned(scratch, 16)) return -3;
+  return vg_spectral_project_launch(G, W, state, scratch, table_dev, n, blocks, (hipStream_t)stream);
 }
 extern "C" int vg_diversity_loss(const void* images, void* d_images, float* loss_out, float* scratch, int B, int D, float weight,
                                 void* stream) {

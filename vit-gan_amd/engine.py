@@ -28,6 +28,7 @@ from . import _lib, flat, ops
 from .dist import GradSync, backward_pieces
 from .generator import SirenGenerator
 from .modules import ViTDiscriminator, VisionTransformer
+from .spectral import SpectralState, parse_spectral_set, vit_matrix_keys
 
 LOSS_KINDS = {"ns": 0, "hinge": 1, "wasserstein": 2}  # "wasserstein": the critic losses of src/v2/training.py:72,97
 
@@ -46,7 +47,7 @@ class GanEngine:
                  process_group: Optional["dist.ProcessGroup"] = None, external_noise: bool = False,
                  two_stream: bool = False, compress_mapping_grad: bool = False, shard_mapping_update: bool = False, gp_weight: float = 0.0,
                  exchange_single_rank: bool = False, dense_top_block: bool = False, gp_autograd: bool = False, diffaug: str = "",
-                 ema_decay: float = 0.0, ema_start: int = 0):
+                 ema_decay: float = 0.0, ema_start: int = 0, spectral_norm: str = ""):
         """concurrent_wgrad: the discriminator's weight gradients on a side stream beside its input gradients.  Off by default
         since the persistent GEMMs (csrc/gemm_wr.hip, gemm_tn.hip: their workgroups hold the CUs for a whole launch) - the
         side stream measured 6.70 against 6.67 ms/step.
@@ -110,8 +111,21 @@ class GanEngine:
         0.0 (default) = no average: no buffer, and the step is launch for launch the plain one.  The discriminator is not averaged.
         Under ``shard_mapping_update`` the mapping Linear's average is updated from the gathered master (vg_ema_update), so every
         rank holds the average of a replicated run, bit for bit.  ``sample(z)`` draws from the average, ``ema_state_dict()`` exports
-        it under the generator's keys, ``state_dict()`` carries it across a restart."""
+        it under the generator's keys, ``state_dict()`` carries it across a restart.
+        spectral_norm: spectral normalisation of the DISCRIMINATOR's weight matrices in ViTGAN's form, W_eff = sigma0 W / sigma with
+        sigma0 = sigma_max(W) at construction (so the network is unchanged there) and sigma one power iteration per step behind
+        sigma_max(W), as ``torch.nn.utils.spectral_norm`` runs in training.  "qkv": queries / keys / values of every block, each [E, E]
+        on its own (the reference's v1 set); "all": also out_projection, fc1, fc2, classifier.fc1 and embedding.conv1 as [E, C P P]
+        (not classifier.fc2, which the head kernels read from the fp32 master); "" (default): nothing - no buffer, and the step is
+        launch for launch the plain one.  The kernels read only the bf16 shadow, so the normalised network is a scaled cast of the
+        master (vg_spectral_update, right after D's AdamW: the generator's pass of the same step sees the new shadow) and the
+        optimizer sees the raw-weight gradient after one rank-one correction of the exchanged gradient total (vg_spectral_project,
+        before clipping); weight decay acts on the raw weights.  The state (u, v, sigma, sigma0 per matrix) is attached to the
+        discriminator's FlatParams, so a module forward, ``sync_from_modules`` and the load_state_dict hook keep the normalised
+        shadow; ``state_dict()`` carries it, ``effective_state_dict()`` exports the trained function for a plain ViTDiscriminator.
+        ``close()`` detaches it.  Not with ``two_stream``."""
         self.aug = ops.parse_aug_policy(diffaug)  # ValueError names the three members; argument errors come before any device check
+        self.spectral_norm = parse_spectral_set(spectral_norm)  # ValueError names the two sets
         self.ema_decay, self.ema_start = float(ema_decay), int(ema_start)
         if not 0.0 <= self.ema_decay < 1.0:
             raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
@@ -119,6 +133,8 @@ class GanEngine:
             raise ValueError(f"ema_start must be a non-negative integer, got {ema_start!r}")
         if self.aug and two_stream:
             raise ValueError("diffaug: the augmented step is verified on the single-chain schedule only; switch two_stream off")
+        if self.spectral_norm and two_stream:
+            raise ValueError("spectral_norm: the normalised step is verified on the single-chain schedule only; switch two_stream off")
         vit = discriminator.vit if isinstance(discriminator, ViTDiscriminator) else discriminator
         if not isinstance(vit, VisionTransformer) or not isinstance(generator, SirenGenerator):
             raise TypeError("GanEngine needs a ViTDiscriminator/VisionTransformer and a SirenGenerator")
@@ -126,7 +142,7 @@ class GanEngine:
             raise ValueError("GanEngine: the fused step is bf16; it does not take a discriminator in precision='fp32'")
         if float(gp_weight) != 0.0:
             vit.require_short_attention("gp_weight > 0 (the gradient penalty)")
-        self.vit, self.gen = vit, generator
+        self.vit, self.gen, self._disc = vit, generator, discriminator
         self.dev = vit._flat.flat.device
         if self.dev.type != "cuda" or generator._flat.flat.device != self.dev:
             raise RuntimeError("GanEngine: both networks must be on the same cuda device (no CPU fallback)")
@@ -220,6 +236,13 @@ class GanEngine:
         self._ema_cast_key = None                        # (steps, loads) the cast was made at
         self._ema_loads = 0
         self._sample_ws: Optional[torch.Tensor] = None
+        self.spec: Optional[SpectralState] = None
+        if self.spectral_norm:
+            keys = vit_matrix_keys(d.L, self.spectral_norm)
+            ent = [(fd.slots[k][0], fd.slots[k][1][0], flat.numel(fd.slots[k][1][1:])) for k in keys]
+            self.spec = SpectralState(ent, fd.total, dev, names=keys)
+            self.spec.measure(fd.flat)
+            fd.spectral = self.spec  # from here on every refresh_shadow() of the discriminator writes the normalised cast
         fd.refresh_shadow()
         fg.refresh_shadow()
         self.ctx = _lib.context() if concurrent_wgrad else None
@@ -260,6 +283,9 @@ class GanEngine:
             h.remove()
         self._hooks = []
         self._graph = None
+        fd = self.vit._flat
+        if getattr(self, "spec", None) is not None and fd.spectral is self.spec:
+            fd.spectral = None  # the modules hold the raw weights again: export effective_state_dict() first
 
     def __del__(self):
         try:
@@ -528,7 +554,11 @@ class GanEngine:
                 else:  # second pass finishes D.grad: exchange it as it completes
                     self._d_backward(net, B, dl, 1, None, st)
         self.sync.wait()
+        if self.spec is not None:  # dL/dW_eff -> dL/dW on the exchanged total of both passes and the penalty (the map is linear)
+            self.spec.project(fd.grad, fd.flat, st)
         self._adamw(fd, self.m_d, self.v_d, self.hyp["lr_d"], st, self.clip_d, 0)
+        if self.spec is not None:  # one power iteration on the updated master; AdamW's plain cast of the normalised ranges is overwritten
+            self.spec.update(fd.flat, fd.shadow, True, st)
         fg.grad.zero_()            # gan.generator.zero_grad(), training.py:199
         g_in, g_dimg = fake_ptr, _p(self.dfake)
         if self.aug:  # D sees T_2(fake) (site 1); its input gradient goes back through the adjoint into dfake
@@ -556,6 +586,8 @@ class GanEngine:
         """Everything a step changes that the next step reads (the training state held on the device)."""
         fd, fg = self.vit._flat, self.gen._flat
         state = [fd.flat, fd.shadow, fg.flat, fg.shadow, self.m_d, self.v_d, self.m_g, self.v_g, self.step_t]
+        if self.spec is not None:
+            state.append(self.spec.state)
         return state if self.ema_g is None else state + [self.ema_g]
 
     def sync_from_modules(self, reset_optimizer: bool = False) -> None:
@@ -563,7 +595,11 @@ class GanEngine:
         edit): refreshes the bf16 shadows the GEMMs read; ``reset_optimizer`` also clears AdamW's moments and step count
         (a fresh optimizer, which is what the reference has after a restart: it saves no optimizer state,
         training.py:218-226,262-263).  The generator's moving average needs no code here: a plain refresh leaves it alone, and a
-        cleared step counter makes the next step's kernel copy the updated weights into it - the average restarts with the optimizer."""
+        cleared step counter makes the next step's kernel copy the updated weights into it - the average restarts with the optimizer.
+        With ``spectral_norm`` a plain refresh keeps the normalisation (the scaled cast from the stored sigma); ``reset_optimizer``
+        measures it again: sigma0 = sigma_max of the current weights, so the network is the plain one at that point."""
+        if reset_optimizer and self.spec is not None:
+            self.spec.measure(self.vit._flat.flat)
         self.vit._flat.refresh_shadow()
         self.gen._flat.refresh_shadow()
         if reset_optimizer:
@@ -643,19 +679,42 @@ class GanEngine:
             sd[k] = getattr(self, k).detach().clone()
         if self.ema_g is not None:
             sd["ema_g"] = self.ema_g.detach().clone()
+        if self.spec is not None:
+            sd["spectral_norm"], sd["spectral_state"] = self.spectral_norm, self.spec.state.detach().clone()
+        return sd
+
+    def effective_state_dict(self) -> dict:
+        """The discriminator's ``state_dict()`` (the keys of the module the engine was given) with fp32(s * W), s = sigma0 / sigma, in
+        place of every normalised W - the kernel's own expression, so a plain bf16 cast of it is this engine's shadow bit for bit.
+        It loads into a plain ViTDiscriminator (or the reference's) and computes the trained function.  Without ``spectral_norm``
+        it is the plain state."""
+        fd = self.vit._flat
+        eff = fd.flat.detach().clone() if self.spec is None else self.spec.effective(fd.flat)
+        sd = self._disc.state_dict()
+        pre = "vit." if self._disc is not self.vit else ""
+        for k, (off, shape) in fd.slots.items():
+            sd[pre + k] = eff[off:off + flat.numel(shape)].view(shape).clone()
         return sd
 
     def load_state_dict(self, sd, strict: bool = True) -> None:
         """Restore ``state_dict()`` in place (a captured graph stays valid) and refresh the shadows from the modules' current
         weights - so: load the ``gan`` state, then this, then go on stepping.  Wrong sizes, a missing entry or another format
         version raise ValueError.  An engine with the moving average on that is given a state without ``ema_g`` raises under
-        ``strict``; with ``strict=False`` the average restarts as a copy of the weights at the next step (the step is captured again)."""
+        ``strict``; with ``strict=False`` the average restarts as a copy of the weights at the next step (the step is captured again).  The
+        spectral-normalisation state follows the same rule: missing under ``strict`` raises, with ``strict=False`` it is measured
+        again from the current weights."""
         if sd.get("format_version") != self.STATE_FORMAT:
             raise ValueError(f"engine state format {sd.get('format_version')!r}, this engine reads format {self.STATE_FORMAT}")
         names = ("m_d", "v_d", "m_g", "v_g", "step_t")
         missing = [k for k in names + ("steps", "noise_seed") if k not in sd]
         if missing:
             raise ValueError(f"engine state lacks {missing}")
+        has_spec = sd.get("spectral_state") is not None
+        if has_spec and self.spec is not None and sd.get("spectral_norm") != self.spectral_norm:
+            raise ValueError(f"engine state was saved with spectral_norm={sd.get('spectral_norm')!r}, this engine has {self.spectral_norm!r}")
+        if strict and has_spec != (self.spec is not None):
+            raise ValueError("engine state has no spectral_state but this engine normalises its discriminator (strict=False measures it again "
+                             "from the current weights)" if not has_spec else "engine state has a spectral_state but this engine has spectral_norm off")
         has_ema = sd.get("ema_g") is not None
         if strict and has_ema != (self.ema_g is not None):
             raise ValueError("engine state has no ema_g but this engine keeps a moving average (strict=False restarts it)" if not has_ema
@@ -663,6 +722,8 @@ class GanEngine:
         pairs = [(getattr(self, k), sd[k], k) for k in names]
         if has_ema and self.ema_g is not None:
             pairs.append((self.ema_g, sd["ema_g"], "ema_g"))
+        if has_spec and self.spec is not None:
+            pairs.append((self.spec.state, sd["spectral_state"], "spectral_state"))
         for dst, src, k in pairs:
             if not torch.is_tensor(src) or src.numel() != dst.numel():
                 raise ValueError(f"engine state {k}: {tuple(getattr(src, 'shape', ()))} does not fit this engine's {tuple(dst.shape)}")
@@ -677,6 +738,8 @@ class GanEngine:
             start = self.ema_start if has_ema else max(self.ema_start, int(sd["step_t"].reshape(-1)[0]) + 1)
             if start != self._ema_from:
                 self._ema_from, self._graph = start, None
+        if self.spec is not None and not has_spec:  # no state to restore: the current weights become the reference point
+            self.spec.measure(self.vit._flat.flat)
         self.sync_from_modules()
 
     def step(self, real: torch.Tensor, z: Optional[torch.Tensor] = None) -> torch.Tensor:

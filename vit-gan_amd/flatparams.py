@@ -33,6 +33,7 @@ class FlatParams:
         self.flat = None
         self.grad = None
         self.shadow = None
+        self.spectral = None  # a spectral.SpectralState (GanEngine(spectral_norm=...) attaches it): refresh_shadow() then keeps the normalised cast
         self.rebuild()
 
     # ------------------------------------------------------------------ storage
@@ -70,6 +71,8 @@ class FlatParams:
             raise RuntimeError("the HIP path needs the parameters on a cuda device")
         _lib.check(_lib.lib().vg_cast_f32_bf16(self.flat.data_ptr(), self.shadow.data_ptr(), self.total, _stream()),
                    "vg_cast_f32_bf16")
+        if self.spectral is not None:  # the normalised matrices: the scaled cast from the stored sigma (no iteration)
+            self.spectral.update(self.flat, self.shadow, iterate=False)
 
     def attach_grads(self) -> None:
         """Make every p.grad a view of the flat gradient buffer, preserving accumulate semantics:

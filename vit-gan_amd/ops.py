@@ -328,3 +328,39 @@ def diff_augment(x, policy, seed: int, site: int, step: Optional[torch.Tensor] =
     """Differentiable augmentation of images [B, C, IH, IH]: ``policy`` a comma-separated subset of color, translation, cutout (or
     its bit mask); the transform of image n is a pure function of (seed, site, step[0], n) - ``step``: a cuda int32 counter, or None."""
     return DiffAugmentFn.apply(x, parse_aug_policy(policy), int(seed) & 0xFFFFFFFFFFFFFFFF, int(site), step)
+
+
+def _spectral_one(W, u, sigma0):
+    """A one-matrix SpectralState holding (u, sigma0) for the fp32 matrix W [N, K] (a contiguous cuda tensor)."""
+    from .spectral import SpectralState
+    _need_cuda(W, "spectral")
+    if W.dim() != 2 or W.dtype != torch.float32 or not W.is_contiguous():
+        raise ValueError("spectral: W is a contiguous fp32 [N, K] matrix")
+    N, K = W.shape
+    st = SpectralState([(0, N, K)], N * K, W.device)
+    st.u(0).copy_(u.reshape(N))
+    st.sigma0(0).fill_(float(sigma0))
+    return st
+
+
+def spectral_sigma(W, u):
+    """One power iteration on W [N, K] from u [N] (vg_spectral_update): (sigma, u', v') with v' = W^T u / |W^T u|, sigma = |W v'|,
+    u' = W v' / sigma."""
+    st = _spectral_one(W, u, 1.0)
+    st.update(W.reshape(-1), torch.empty(W.numel(), dtype=torch.bfloat16, device=W.device))
+    return st.sigma(0).clone(), st.u(0).clone(), st.v(0).clone()
+
+
+def spectral_normalize(W, u, sigma0, grad=None):
+    """The same iteration and the normalised bf16 shadow bf16(fp32(sigma0 / sigma) * W).  With ``grad`` = dL/dW_eff [N, K] also the
+    raw-weight gradient s (G - (<G, W> / sigma) u' v'^T) from the pair that produced the shadow (vg_spectral_project).
+    Returns (shadow, sigma, u', v') or (shadow, sigma, u', v', projected)."""
+    st = _spectral_one(W, u, sigma0)
+    shadow = torch.empty(W.numel(), dtype=torch.bfloat16, device=W.device)
+    st.update(W.reshape(-1), shadow)
+    out = (shadow.view_as(W), st.sigma(0).clone(), st.u(0).clone(), st.v(0).clone())
+    if grad is None:
+        return out
+    g = grad.detach().to(torch.float32).contiguous().clone().reshape(-1)
+    st.project(g, W.reshape(-1))
+    return out + (g.view_as(W),)

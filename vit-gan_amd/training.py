@@ -204,7 +204,7 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                 fid_fn: Optional[Callable[[nn.Module, int], float]] = None, output_base: Optional[str] = None,
                 save_artifacts: bool = True, clip_d: Optional[float] = None, clip_g: Optional[float] = None,
                 diversity_weight: float = 0.0, instance_noise: float = 0.0, gp_weight: float = 0.0, diffaug: str = "",
-                ema_decay: float = 0.0, ema_start: int = 0):
+                ema_decay: float = 0.0, ema_start: int = 0, spectral_norm: str = ""):
     """``loss``: "ns" (default: the executable v1 loss), "hinge", or "wasserstein" - the critic losses of the reference's
     unreached step (training.py:67-125); ``clip_d`` / ``clip_g``: its clip_grad_norm_ limits (5.0 / 0.5 there);
     ``diversity_weight``: its diversity term (0.1 there); ``instance_noise``: sigma of the noise on D's inputs (0.1
@@ -216,10 +216,17 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     generator - an eval-mode ``SirenGenerator`` refreshed from the engine before each use, returned as ``"generator_ema"`` -
     and ``generator_ema.pth`` (its state_dict) is written beside ``final_model.ckpt`` and beside each best-FID checkpoint.
     ``engine_state.pth`` (``GanEngine.state_dict()``: optimizer moments, step counter, the average) is written beside
-    ``final_model.ckpt`` in every run; the ``gan.state_dict()`` files keep the reference's keys."""
+    ``final_model.ckpt`` in every run; the ``gan.state_dict()`` files keep the reference's keys.
+    ``spectral_norm``: "qkv" or "all" - spectral normalisation of the discriminator's weights inside the step
+    (``GanEngine(spectral_norm=...)``).  When it is on, the best-FID and final checkpoints hold the discriminator's EFFECTIVE weights
+    (``GanEngine.effective_state_dict()``), so they load into a plain ``ViTGAN`` - or the reference's - and compute the trained
+    function; the raw weights a resumed run needs (with ``engine_state.pth``) go to ``discriminator_raw.pth`` beside
+    ``final_model.ckpt``, and ``training.log`` says so."""
     global _log_file
     from .ops import parse_aug_policy
     parse_aug_policy(diffaug)  # a bad policy string is the caller's error whatever the machine: before the device check
+    from .spectral import parse_spectral_set
+    parse_spectral_set(spectral_norm)
     if not 0.0 <= float(ema_decay) < 1.0:
         raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
     if int(ema_start) != ema_start or ema_start < 0:
@@ -237,7 +244,15 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     D, G = gan.discriminator, gan.generator
     eng = GanEngine(D, G, batch=c.batch_size, loss=loss, lr_d=c.discriminator_learning_rate, lr_g=c.generator_learning_rate,
                     weight_decay=1e-3, seed=seed, clip_d=clip_d, clip_g=clip_g, diversity_weight=diversity_weight,
-                    instance_noise=instance_noise, gp_weight=gp_weight, diffaug=diffaug, ema_decay=ema_decay, ema_start=ema_start)
+                    instance_noise=instance_noise, gp_weight=gp_weight, diffaug=diffaug, ema_decay=ema_decay, ema_start=ema_start,
+                    spectral_norm=spectral_norm)
+
+    def gan_checkpoint():  # gan.state_dict(), the discriminator's normalised matrices as the network applies them
+        sd = gan.state_dict()
+        if eng.spec is not None:
+            for k, v in eng.effective_state_dict().items():
+                sd["discriminator." + k] = v
+        return sd
     G_ema: Optional[nn.Module] = None
     gan_ema: Optional[nn.Module] = None
     if eng.ema_g is not None:  # the averaged generator as a module of its own: same constructor arguments, eval mode, never trained
@@ -282,6 +297,9 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
         log("Parameters:\n" + str(c))
         if diffaug:
             log(f"Differentiable augmentation: {diffaug}")
+        if eng.spec is not None:
+            log(f"Spectral normalisation of the discriminator: set '{spectral_norm}', {eng.spec.n} matrices; checkpoints hold the EFFECTIVE "
+                "weights sigma0 W / sigma (discriminator_raw.pth: the raw weights for a resumed run)")
         for epoch in range(epochs):
             noise = construct_noise()
             if save_artifacts:
@@ -305,7 +323,7 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
             if fid_score < best_fid:
                 best_fid = fid_score
                 if save_artifacts:
-                    torch.save(gan.state_dict(), os.path.join(dirs.checkpoints, f"best_model_epoch_{epoch}_fid_{int(fid_score)}.pth"))
+                    torch.save(gan_checkpoint(), os.path.join(dirs.checkpoints, f"best_model_epoch_{epoch}_fid_{int(fid_score)}.pth"))
                     if G_ema is not None:  # refreshed just above, for fid_fn
                         torch.save(G_ema.state_dict(), os.path.join(dirs.checkpoints, "generator_ema.pth"))
             log(f"Epoch [{epoch}/{epochs}] | Disc Loss: {d_real + d_fake:.8f}, Gen Loss: {g:.4f} | FID: {fid_score:.4f}")
@@ -322,7 +340,9 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
         model_path = os.path.join(dirs.save, "final_model.ckpt")
         if save_artifacts and fatal is None:  # no further GPU work, no checkpoint of a broken run
             save_figures(dirs.save, disc_losses=disc_losses, gen_losses=gen_losses, fid_scores=fid_scores)
-            torch.save(gan.state_dict(), model_path)
+            torch.save(gan_checkpoint(), model_path)
+            if eng.spec is not None:
+                torch.save(D.state_dict(), os.path.join(dirs.save, "discriminator_raw.pth"))
             torch.save(eng.state_dict(), os.path.join(dirs.save, "engine_state.pth"))
             save_samples(epoch, construct_noise())
             if G_ema is not None:  # refreshed by save_samples
