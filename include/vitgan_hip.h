@@ -304,6 +304,22 @@ int vg_gan_loss(const float* logits, float* dlogits, float* loss_out, int n, int
 int vg_gan_loss_pair(const float* logits, float* dlogits, float* loss_out, int n0, int role0, int n1, int role1,
                      int kind, float grad_scale, void* stream);
 
+/* Balanced consistency regularisation (bCR, Zhao et al. 2020; the reference has none, so this header is its definition) between the
+ * discriminator's logits on a batch x and on its augmented partner a = T(x).  logits_x, logits_a, dlog_x, dlog_a: fp32 [B_real + B_fake, Kc],
+ * the B_real real images first; the four must not overlap.  Per segment s (real: images [0, B_real), weight w_real; fake: the B_fake images
+ * behind them, weight w_fake), with d = logits_x - logits_a elementwise (the difference first, then the square):
+ *   loss_out[s] = 1/B_s sum_{n in s} sum_k d[n, k]^2                     the UNWEIGHTED mean over the B_s images (not over B_s Kc)
+ *   dlog_x[n, k] (+)= g,   dlog_a[n, k] (-)= g,   g = ((2 w_s) / B_s) grad_scale d[n, k]      both branches carry gradient
+ * accumulate_x / accumulate_a = 1 adds into what the adversarial loss kernel wrote, 0 overwrites and writes every element.  A zero
+ * weight writes +0 (overwrite) or leaves the target untouched (accumulate); the loss is reported all the same.
+ * ONE launch of two workgroups (one per segment), fp32, fixed order - per thread a strided chain, the wave butterfly, the four waves
+ * in order, one product with the rounded 1 / B_s - no atomics: bitwise reproducible.
+ * Returns -1: a null pointer or a non-positive size;  -2: a negative or NaN weight, an accumulate flag other than 0 / 1, or
+ * (B_real + B_fake) Kc >= 2^31 - all before any launch. */
+int vg_bcr_loss(const float* logits_x, const float* logits_a, float* dlog_x, float* dlog_a, float* loss_out /*[2]*/,
+                int B_real, int B_fake, int Kc, float w_real, float w_fake,
+                int accumulate_x, int accumulate_a, float grad_scale, void* stream);
+
 /* torch.optim.AdamW step over a flat fp32 buffer (src/v2/training.py:150-157), also refreshing the
  * bf16 shadow the GEMMs read.  n % 4 == 0.  grads are multiplied by gscale first.  The step number
  * (1-based) comes from step_dev[0] (device int) when step_dev != NULL - for hipGraph replay - else

@@ -125,6 +125,7 @@ _SIGNATURES = {
     "vg_diffaug_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, C.c_ulonglong, c_int, P, P]),
     "vg_gan_loss": (c_int, [P, P, P, c_int, c_int, c_int, c_float, P]),
     "vg_gan_loss_pair": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P]),
+    "vg_bcr_loss": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_float, P]),
     "vg_adamw_step": (c_int, [P, P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_float, c_int, P, c_float, P]),
     "vg_adamw_ema_step": (c_int, [P, P, P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_float, c_int, P, c_float, c_float, c_int, P]),
     "vg_ema_update": (c_int, [P, P, c_ll, c_float, c_int, c_int, P, P]),

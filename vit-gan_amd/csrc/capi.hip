@@ -368,6 +368,12 @@ extern "C" int vg_gan_loss_pair(const float* logits, float* dlogits, float* loss
   if (!logits || !dlogits || !loss_out) return -1;
   return vg_gan_loss_pair_launch(logits, dlogits, loss_out, n0, role0, n1, role1, kind, grad_scale, (hipStream_t)stream);
 }
+extern "C" int vg_bcr_loss(const float* logits_x, const float* logits_a, float* dlog_x, float* dlog_a, float* loss_out, int B_real, int B_fake,
+                           int Kc, float w_real, float w_fake, int accumulate_x, int accumulate_a, float grad_scale, void* stream) {
+  if (!logits_x || !logits_a || !dlog_x || !dlog_a || !loss_out || B_real < 1 || B_fake < 1 || Kc < 1) return -1;
+  return vg_bcr_loss_launch(logits_x, logits_a, dlog_x, dlog_a, loss_out, B_real, B_fake, Kc, w_real, w_fake, accumulate_x, accumulate_a,
+                            grad_scale, (hipStream_t)stream);
+}
 extern "C" int vg_adamw_step(float* p, const float* g, float* m, float* v, void* shadow_bf16, long long n, float lr, float beta1,
                              float beta2, float eps, float weight_decay, int step, const int* step_dev, float gscale,
                              void* stream) {

@@ -350,6 +350,50 @@ __global__ __launch_bounds__(256) void vg_gan_loss_pair_kernel(const float* __re
   else vg_gan_loss_body(logit + n0, dlog + n0, loss_out + 1, n1, kind, role1, grad_scale);
 }
 
+// ---- balanced consistency regularisation on two logit vectors [nb, Kc] (clean x, augmented a) -------------------
+// One segment (nb images, n = nb * Kc elements):  loss_out[0] = 1/nb sum_i d_i^2 with d_i = lx[i] - la[i] (the difference first, then
+// the square), dlog_x[i] (+)= g_i and dlog_a[i] (-)= g_i with g_i = c d_i, c = ((2 w) / nb) grad_scale.  The operation order is what
+// tests/bcr_ref.kappa counts: one strided chain per thread, the wave butterfly, the four waves in order, one product with 1/nb.
+// w == 0: an overwritten gradient is +0 exactly (whatever the logits hold), an accumulate target is not touched.
+__device__ __forceinline__ void vg_bcr_loss_body(const float* __restrict__ lx, const float* __restrict__ la, float* __restrict__ dlog_x,
+                                                 float* __restrict__ dlog_a, float* __restrict__ loss_out, int nb, int Kc, float w,
+                                                 int accumulate_x, int accumulate_a, float grad_scale) {
+  __shared__ float red[4];
+  const int n = nb * Kc;
+  const float inv = 1.0f / (float)nb;
+  const float c = ((2.0f * w) / (float)nb) * grad_scale;
+  const bool live = w != 0.f;
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const float d = lx[i] - la[i];
+    acc += d * d;
+    const float g = c * d;
+    if (live) {
+      dlog_x[i] = accumulate_x ? dlog_x[i] + g : g;
+      dlog_a[i] = accumulate_a ? dlog_a[i] - g : -g;
+    } else {
+      if (!accumulate_x) dlog_x[i] = 0.f;
+      if (!accumulate_a) dlog_a[i] = 0.f;
+    }
+  }
+  acc = vg_wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) loss_out[0] = (((red[0] + red[1]) + red[2]) + red[3]) * inv;
+}
+// Workgroup 0 takes the real segment (the first n_real images of both vectors), workgroup 1 the fake segment behind it.
+__global__ __launch_bounds__(256) void vg_bcr_loss_kernel(const float* __restrict__ lx, const float* __restrict__ la,
+                                                          float* __restrict__ dlog_x, float* __restrict__ dlog_a,
+                                                          float* __restrict__ loss_out, int n_real, int n_fake, int Kc, float w_real,
+                                                          float w_fake, int accumulate_x, int accumulate_a, float grad_scale) {
+  if (blockIdx.x == 0) {
+    vg_bcr_loss_body(lx, la, dlog_x, dlog_a, loss_out, n_real, Kc, w_real, accumulate_x, accumulate_a, grad_scale);
+  } else {
+    const int o = n_real * Kc;
+    vg_bcr_loss_body(lx + o, la + o, dlog_x + o, dlog_a + o, loss_out + 1, n_fake, Kc, w_fake, accumulate_x, accumulate_a, grad_scale);
+  }
+}
+
 // ---- torch.nn.utils.clip_grad_norm_ over a flat gradient buffer (src/v2/training.py:78,104) -------------------------
 // Two deterministic stages: per-workgroup sums of squares, then every workgroup folds the partials in the same fixed
 // order, derives coef = min(1, max_norm / (gscale*|g| + 1e-6)) and scales its slice in place.
@@ -745,6 +789,15 @@ int vg_gan_loss_pair_launch(const float* logit, float* dlog, float* loss_out, in
                             hipStream_t st) {
   if (kind < 0 || kind > 2 || role0 < 0 || role0 > 2 || role1 < 0 || role1 > 2 || n0 < 1 || n1 < 1) return -2;
   hipLaunchKernelGGL(vg_gan_loss_pair_kernel, dim3(2), dim3(256), 0, st, logit, dlog, loss_out, n0, role0, n1, role1, kind, grad_scale);
+  return (int)hipGetLastError();
+}
+int vg_bcr_loss_launch(const float* lx, const float* la, float* dlog_x, float* dlog_a, float* loss_out, int n_real, int n_fake, int Kc,
+                       float w_real, float w_fake, int accumulate_x, int accumulate_a, float grad_scale, hipStream_t st) {
+  if (n_real < 1 || n_fake < 1 || Kc < 1) return -1;
+  if (((long long)n_real + n_fake) * Kc > 0x7FFFFFFFLL) return -2;  // element offsets are 32-bit
+  if (!(w_real >= 0.f) || !(w_fake >= 0.f) || (accumulate_x & ~1) || (accumulate_a & ~1)) return -2;
+  hipLaunchKernelGGL(vg_bcr_loss_kernel, dim3(2), dim3(256), 0, st, lx, la, dlog_x, dlog_a, loss_out, n_real, n_fake, Kc, w_real, w_fake,
+                     accumulate_x, accumulate_a, grad_scale);
   return (int)hipGetLastError();
 }
 int vg_gan_loss_launch(const float* logit, float* dlog, float* loss_out, int n, int kind, int role, float grad_scale,

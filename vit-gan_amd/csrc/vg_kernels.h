@@ -66,6 +66,10 @@ int vg_gan_loss_pair_launch(const float* logit, float* dlog, float* loss_out, in
                             hipStream_t st);
 int vg_gan_loss_launch(const float* logit, float* dlog, float* loss_out, int n, int kind, int role, float grad_scale,
                        hipStream_t st);
+// consistency loss between two logit vectors [n_real + n_fake, Kc], one workgroup per segment: loss_out[0 / 1] = the segments' means of
+// |lx - la|^2 over their images; dlog_x (+)= g, dlog_a (-)= g with g = (2 w / n) (lx - la) grad_scale
+int vg_bcr_loss_launch(const float* lx, const float* la, float* dlog_x, float* dlog_a, float* loss_out, int n_real, int n_fake, int Kc,
+                       float w_real, float w_fake, int accumulate_x, int accumulate_a, float grad_scale, hipStream_t st);
 int vg_adamw_launch(float* p, const float* g, float* m, float* v, bf16* shadow, long long n, float lr, float b1, float b2,
                     float eps, float wd, int step, const int* step_dev, float gscale, hipStream_t st);
 int vg_adamw_ema_launch(float* p, const float* g, float* m, float* v, bf16* shadow, float* ema, long long n, float lr, float b1, float b2,

@@ -47,7 +47,7 @@ class GanEngine:
                  process_group: Optional["dist.ProcessGroup"] = None, external_noise: bool = False,
                  two_stream: bool = False, compress_mapping_grad: bool = False, shard_mapping_update: bool = False, gp_weight: float = 0.0,
                  exchange_single_rank: bool = False, dense_top_block: bool = False, gp_autograd: bool = False, diffaug: str = "",
-                 ema_decay: float = 0.0, ema_start: int = 0, spectral_norm: str = ""):
+                 ema_decay: float = 0.0, ema_start: int = 0, spectral_norm: str = "", bcr=(0.0, 0.0), bcr_aug: str = ""):
         """concurrent_wgrad: the discriminator's weight gradients on a side stream beside its input gradients.  Off by default
         since the persistent GEMMs (csrc/gemm_wr.hip, gemm_tn.hip: their workgroups hold the CUs for a whole launch) - the
         side stream measured 6.70 against 6.67 ms/step.
@@ -123,9 +123,33 @@ class GanEngine:
         before clipping); weight decay acts on the raw weights.  The state (u, v, sigma, sigma0 per matrix) is attached to the
         discriminator's FlatParams, so a module forward, ``sync_from_modules`` and the load_state_dict hook keep the normalised
         shadow; ``state_dict()`` carries it, ``effective_state_dict()`` exports the trained function for a plain ViTDiscriminator.
-        ``close()`` detaches it.  Not with ``two_stream``."""
+        ``close()`` detaches it.  Not with ``two_stream``.
+        bcr: ``(lambda_real, lambda_fake)``, the weights of balanced consistency regularisation (Zhao et al. 2020; the reference has
+        none): L_cr = lambda_real 1/B sum_real |D(x_n) - D(T(x_n))|^2 + lambda_fake 1/B sum_fake |D(x_n) - D(T(x_n))|^2 joins the
+        discriminator's loss, both branches carrying gradient.  x is the pair D's own step is given ([real ; fake.detach()], after the
+        instance noise).  With ``diffaug`` the partner is the step's own T_1(x) - the adversarial loss and the penalty stay on it, the
+        clean x is the consistency partner, no augmentation launch more; without it the adversarial loss and the penalty stay on x
+        and T(x) is one vg_diffaug_fwd with policy ``bcr_aug`` at site 2 (``aug_params["c"]``).  D runs ONCE on the 4B images
+        [x ; T(x)] - one forward, one backward, one exchange; the dropout masks are those of a 4B pass - and vg_bcr_loss adds the
+        consistency gradients to the adversarial rows' and writes the partner rows'.  ``bcr_losses`` holds the two unweighted means.
+        (0, 0) (default): nothing - no buffer, and the step is launch for launch the plain one.  The generator's pass is untouched.
+        Not with ``two_stream`` nor ``fuse_real_fake=False``.
+        bcr_aug: the consistency transform when ``diffaug`` is off, a comma-separated subset of ``color,translation,cutout``."""
         self.aug = ops.parse_aug_policy(diffaug)  # ValueError names the three members; argument errors come before any device check
         self.spectral_norm = parse_spectral_set(spectral_norm)  # ValueError names the two sets
+        self.bcr_w = ops.parse_bcr_weights(bcr)
+        self.bcr_policy = ops.parse_aug_policy(bcr_aug)
+        self.bcr = self.bcr_w != (0.0, 0.0)
+        if self.bcr_policy and self.aug:
+            raise ValueError("bcr_aug: with diffaug on, diffaug's own transform T_1 is the consistency partner; leave bcr_aug empty")
+        if self.bcr_policy and not self.bcr:
+            raise ValueError("bcr_aug: a consistency transform without consistency weights (bcr=(0, 0)) would do nothing; set bcr")
+        if self.bcr and not (self.aug or self.bcr_policy):
+            raise ValueError("bcr: the consistency loss needs a transform - switch diffaug on (its T_1 is the partner) or name one in bcr_aug")
+        if self.bcr and two_stream:
+            raise ValueError("bcr: the consistency step runs the discriminator once on 4B images, on the single-chain schedule; switch two_stream off")
+        if self.bcr and not fuse_real_fake:
+            raise ValueError("bcr: the consistency step runs the discriminator once on 4B images; it needs fuse_real_fake=True")
         self.ema_decay, self.ema_start = float(ema_decay), int(ema_start)
         if not 0.0 <= self.ema_decay < 1.0:
             raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
@@ -199,7 +223,7 @@ class GanEngine:
             if B % 2:
                 raise ValueError("two_stream needs an even batch")
             self.fuse = False
-        nD = 2 * B if self.fuse else B
+        nD = 4 * B if self.bcr else (2 * B if self.fuse else B)
         self.Kc = d.Kc
         self.ws_d = torch.empty(L.vg_vit_ws_bytes(C.byref(d), nD), dtype=torch.uint8, device=dev)
         if self.two_stream:  # second chain: its own workspace, gradient buffer and stream
@@ -210,19 +234,33 @@ class GanEngine:
             self.ws_gp = torch.empty(L.vg_vit_penalty_ws_bytes(C.byref(d), B), dtype=torch.uint8, device=dev)
             self.gp_eps = torch.empty(B, dtype=torch.float32, device=dev)
         self.ws_g = torch.empty(L.vg_gen_ws_bytes(C.byref(g), B), dtype=torch.uint8, device=dev)
-        self.imgs = torch.empty(2 * B, d.C, d.IH, d.IH, dtype=torch.bfloat16, device=dev)  # [real ; fake]
+        nL = 4 * B if self.bcr else 2 * B  # logit rows of the discriminator's own pass
+        if self.bcr:
+            # the 4B images of D's pass, [x ; T(x)], in one buffer: x = the (noisy) pair, T(x) = imgs_aug (diffaug) or imgs_bcr - the
+            # step's own buffers are views of it, so no copy launch forms the batch
+            self.imgs4 = torch.empty(4 * B, d.C, d.IH, d.IH, dtype=torch.bfloat16, device=dev)
+        noisy = self.inst_sigma > 0.0
+        # [real ; fake]; the instance noise needs the clean fake behind it (the generator's pass), so then x is imgs_noisy
+        self.imgs = self.imgs4[:2 * B] if self.bcr and not noisy else torch.empty(2 * B, d.C, d.IH, d.IH, dtype=torch.bfloat16, device=dev)
         self.dfake = torch.empty(B, d.C, d.IH, d.IH, dtype=torch.bfloat16, device=dev)
         if self.inst_sigma > 0.0:  # noisy copy of [real ; fake] for the D step, and the noise itself (kept for inspection / tests)
             self.inoise = torch.empty(2 * B, d.C, d.IH, d.IH, dtype=torch.float32, device=dev)
-            self.imgs_noisy = torch.empty_like(self.imgs)
+            self.imgs_noisy = self.imgs4[:2 * B] if self.bcr else torch.empty_like(self.imgs)
         if self.aug:
             # D step: imgs_aug = T_1(D's input pair).  Generator pass: imgs_aug[:B] = T_2(fake), imgs_aug[B:] = dL/d T_2(fake)
-            self.imgs_aug = torch.empty_like(self.imgs)
+            self.imgs_aug = self.imgs4[2 * B:] if self.bcr else torch.empty_like(self.imgs)
             self.aug_params = {"d": torch.zeros(2 * B, 8, dtype=torch.float32, device=dev),  # (b, s, k, tx, ty, cx, cy, policy) per row
                                "g": torch.zeros(B, 8, dtype=torch.float32, device=dev)}
+        if self.bcr_policy:  # T_c(x), site 2
+            self.imgs_bcr = self.imgs4[2 * B:]
+            self.aug_params = {"c": torch.zeros(2 * B, 8, dtype=torch.float32, device=dev)}
+        if self.bcr:
+            self.bcr_losses = torch.zeros(2, dtype=torch.float32, device=dev)  # the unweighted means: real, fake
         self.div_scratch = torch.zeros((d.C * d.IH * d.IH + 15) // 16, dtype=torch.float32, device=dev)
-        self.logits = torch.empty(2 * B, d.Kc, dtype=torch.float32, device=dev)
-        self.dlogits = torch.empty(2 * B, d.Kc, dtype=torch.float32, device=dev)
+        self.logits = torch.empty(nL, d.Kc, dtype=torch.float32, device=dev)
+        self.dlogits = torch.empty(nL, d.Kc, dtype=torch.float32, device=dev)
+        if self.bcr:  # the generator's pass gets rows of its own, so ``logits`` still holds D's whole 4B pass after the step
+            self.logits_g, self.dlogits_g = torch.empty(B, d.Kc, dtype=torch.float32, device=dev), torch.empty(B, d.Kc, dtype=torch.float32, device=dev)
         self.z = torch.empty(B, g.Z, dtype=torch.float32, device=dev)
         self.losses = torch.zeros(3, dtype=torch.float32, device=dev)  # d_real, d_fake, g
         self.step_t = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -517,6 +555,9 @@ class GanEngine:
             _lib.check(L.vg_diffaug_fwd(_p(d_in), _p(self.imgs_aug), _p(self.aug_params["d"]), 2 * B, d_.C, d_.IH, self.aug, self._aug_seed, 0,
                                         _p(self.step_t), st), "vg_diffaug_fwd")
             d_in = self.imgs_aug
+        if self.bcr_policy:  # the consistency partner T_c(x) (site 2) behind x in the 4B buffer; the losses and the penalty stay on x
+            _lib.check(L.vg_diffaug_fwd(_p(d_in), _p(self.imgs_bcr), _p(self.aug_params["c"]), 2 * B, d_.C, d_.IH, self.bcr_policy,
+                                        self._aug_seed, 2, _p(self.step_t), st), "vg_diffaug_fwd")
         if self.gp_c_call:  # gradient_penalty(D, noisy_real, noisy_fake) joins the D loss (training.py:101-106): one C call
             if self.gp_epsilon is not None:
                 torch.add(self.gp_epsilon.reshape(-1).float(), 0.0, out=self.gp_eps)  # (an elementwise kernel, not a D2D copy: no memcpy / memset nodes in the captured step)
@@ -535,7 +576,20 @@ class GanEngine:
             with ops2.deferred_weight_grads(fd.grad):  # the block Linears' weight gradients: grouped per block, straight into the flat buffer
                 (self.gp_w * pen).backward()   # the rest accumulates into the same buffer through the parameters' .grad (views of it)
             self.gp_loss.copy_(pen.detach().reshape(1))
-        if self.fuse:
+        if self.bcr:
+            # ONE pass over [x ; T(x)]: rows [0, 2B) the clean pair, rows [2B, 4B) its transform.  The adversarial rows are T_1(x) with
+            # diffaug and x without it; the consistency loss adds to their gradient and writes the partner rows' (every element)
+            adv_a = int(bool(self.aug))
+            half = 4 * 2 * B * self.Kc  # bytes of 2B logit rows
+            lx, la = _p(self.logits), C.c_void_p(self.logits.data_ptr() + half)
+            dx, da = _p(self.dlogits), C.c_void_p(self.dlogits.data_ptr() + half)
+            _lib.check(L.vg_vit_forward(C.byref(nd), 4 * B, _p(self.imgs4), 1, _p(self.ws_d), lx, st), "vg_vit_forward")
+            _lib.check(L.vg_gan_loss_pair(la if adv_a else lx, da if adv_a else dx, _p(self.losses), B * self.Kc, 0, B * self.Kc, 1, self.kind,
+                                          1.0, st), "vg_gan_loss_pair")
+            _lib.check(L.vg_bcr_loss(lx, la, dx, da, _p(self.bcr_losses), B, B, self.Kc, self.bcr_w[0], self.bcr_w[1], 1 - adv_a, adv_a, 1.0, st),
+                       "vg_bcr_loss")
+            self._d_backward(nd, 4 * B, dx, 1, None, st)
+        elif self.fuse:
             _lib.check(L.vg_vit_forward(C.byref(nd), 2 * B, _p(d_in), 1, _p(self.ws_d), _p(self.logits), st), "vg_vit_forward")
             # D(real) -> slot 0, D(fake) -> slot 1: both halves of the fused pass in one launch
             _lib.check(_lib.lib().vg_gan_loss_pair(_p(self.logits), _p(self.dlogits), _p(self.losses), B * self.Kc, 0, B * self.Kc, 1, self.kind,
@@ -565,9 +619,15 @@ class GanEngine:
             g_in, g_dimg = _p(self.imgs_aug), C.c_void_p(self.imgs_aug.data_ptr() + B * img_bytes)
             _lib.check(L.vg_diffaug_fwd(fake_ptr, g_in, _p(self.aug_params["g"]), B, d_.C, d_.IH, self.aug, self._aug_seed, 1, _p(self.step_t), st),
                        "vg_diffaug_fwd")
-        _lib.check(L.vg_vit_forward(C.byref(nd_c), B, g_in, 1, _p(self.ws_d), _p(self.logits), st), "vg_vit_forward")
-        self._loss(0, B, 2, 2, st)
-        _lib.check(L.vg_vit_backward(C.byref(nd_c), B, _p(self.ws_d), _p(self.dlogits), g_dimg, 0, st), "vg_vit_backward")
+        if self.bcr:
+            _lib.check(L.vg_vit_forward(C.byref(nd_c), B, g_in, 1, _p(self.ws_d), _p(self.logits_g), st), "vg_vit_forward")
+            _lib.check(L.vg_gan_loss(_p(self.logits_g), _p(self.dlogits_g), C.c_void_p(self.losses.data_ptr() + 8), B * self.Kc, self.kind, 2, 1.0, st),
+                       "vg_gan_loss")
+            _lib.check(L.vg_vit_backward(C.byref(nd_c), B, _p(self.ws_d), _p(self.dlogits_g), g_dimg, 0, st), "vg_vit_backward")
+        else:
+            _lib.check(L.vg_vit_forward(C.byref(nd_c), B, g_in, 1, _p(self.ws_d), _p(self.logits), st), "vg_vit_forward")
+            self._loss(0, B, 2, 2, st)
+            _lib.check(L.vg_vit_backward(C.byref(nd_c), B, _p(self.ws_d), _p(self.dlogits), g_dimg, 0, st), "vg_vit_backward")
         if self.aug:
             _lib.check(L.vg_diffaug_bwd(g_dimg, _p(self.dfake), 0, B, d_.C, d_.IH, self.aug, self._aug_seed, 1, _p(self.step_t), st), "vg_diffaug_bwd")
         if self.div_w != 0.0:  # total_gen_loss = loss + w * diversity_loss(fake_images): its gradient joins dL/d fake
@@ -681,7 +741,12 @@ class GanEngine:
             sd["ema_g"] = self.ema_g.detach().clone()
         if self.spec is not None:
             sd["spectral_norm"], sd["spectral_state"] = self.spectral_norm, self.spec.state.detach().clone()
+        if self.bcr:  # no training state of its own: the options, so that a resumed run is the same run
+            sd["bcr"] = self._bcr_options()
         return sd
+
+    def _bcr_options(self):
+        return None if not self.bcr else (self.bcr_w[0], self.bcr_w[1], self.bcr_policy)
 
     def effective_state_dict(self) -> dict:
         """The discriminator's ``state_dict()`` (the keys of the module the engine was given) with fp32(s * W), s = sigma0 / sigma, in
@@ -702,7 +767,8 @@ class GanEngine:
         version raise ValueError.  An engine with the moving average on that is given a state without ``ema_g`` raises under
         ``strict``; with ``strict=False`` the average restarts as a copy of the weights at the next step (the step is captured again).  The
         spectral-normalisation state follows the same rule: missing under ``strict`` raises, with ``strict=False`` it is measured
-        again from the current weights."""
+        again from the current weights.  Consistency regularisation has no state; the saved ``bcr`` options must equal this engine's under
+        ``strict``."""
         if sd.get("format_version") != self.STATE_FORMAT:
             raise ValueError(f"engine state format {sd.get('format_version')!r}, this engine reads format {self.STATE_FORMAT}")
         names = ("m_d", "v_d", "m_g", "v_g", "step_t")
@@ -715,6 +781,10 @@ class GanEngine:
         if strict and has_spec != (self.spec is not None):
             raise ValueError("engine state has no spectral_state but this engine normalises its discriminator (strict=False measures it again "
                              "from the current weights)" if not has_spec else "engine state has a spectral_state but this engine has spectral_norm off")
+        saved_bcr = None if sd.get("bcr") is None else tuple(sd["bcr"])
+        if strict and saved_bcr != self._bcr_options():
+            raise ValueError(f"engine state was saved with consistency regularisation (lambda_real, lambda_fake, bcr_aug bits) = {saved_bcr!r}, "
+                             f"this engine has {self._bcr_options()!r} (strict=False loads it all the same: bCR holds no training state)")
         has_ema = sd.get("ema_g") is not None
         if strict and has_ema != (self.ema_g is not None):
             raise ValueError("engine state has no ema_g but this engine keeps a moving average (strict=False restarts it)" if not has_ema

@@ -330,6 +330,54 @@ def diff_augment(x, policy, seed: int, site: int, step: Optional[torch.Tensor] =
     return DiffAugmentFn.apply(x, parse_aug_policy(policy), int(seed) & 0xFFFFFFFFFFFFFFFF, int(site), step)
 
 
+def parse_bcr_weights(bcr):
+    """``(lambda_real, lambda_fake)`` of the consistency loss -> two floats; negative or non-finite weights are a ValueError."""
+    try:
+        w_real, w_fake = (float(v) for v in bcr)
+    except (TypeError, ValueError):
+        raise ValueError(f"bcr must be a pair of weights (lambda_real, lambda_fake), got {bcr!r}") from None
+    if not (math.isfinite(w_real) and math.isfinite(w_fake) and w_real >= 0.0 and w_fake >= 0.0):
+        raise ValueError(f"bcr: the weights (lambda_real, lambda_fake) must be finite and non-negative, got {bcr!r}")
+    return w_real, w_fake
+
+
+class ConsistencyLossFn(torch.autograd.Function):
+    """Balanced consistency regularisation between D(x) and D(T(x)) (include/vitgan_hip.h, vg_bcr_loss): one launch computes both segment
+    means and both gradients, so the backward only scales what the forward saved."""
+
+    @staticmethod
+    def forward(ctx, logits_x, logits_a, n_real, w_real, w_fake):
+        _need_cuda(logits_x, "consistency_loss")
+        if logits_x.shape != logits_a.shape or logits_x.dim() != 2 or logits_a.device != logits_x.device:
+            raise ValueError("consistency_loss: logits_x and logits_a are [n, Kc] tensors of one shape on one device")
+        n, Kc = logits_x.shape
+        if not 0 < n_real < n:
+            raise ValueError(f"consistency_loss: n_real must leave a real and a fake segment, got {n_real} of {n} rows")
+        lx, la = logits_x.detach().float().contiguous(), logits_a.detach().float().contiguous()
+        dx, da = torch.empty_like(lx), torch.empty_like(la)
+        parts = torch.empty(2, dtype=torch.float32, device=lx.device)
+        _lib.check(_lib.lib().vg_bcr_loss(_p(lx), _p(la), _p(dx), _p(da), _p(parts), n_real, n - n_real, Kc, w_real, w_fake, 0, 0, 1.0, _st()),
+                   "vg_bcr_loss")
+        ctx.save_for_backward(dx, da)
+        ctx.dts = (logits_x.dtype, logits_a.dtype)
+        ctx.mark_non_differentiable(parts)
+        return w_real * parts[0] + w_fake * parts[1], parts
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout, _dparts):
+        dx, da = ctx.saved_tensors
+        return (dx * dout).to(ctx.dts[0]), (da * dout).to(ctx.dts[1]), None, None, None
+
+
+def consistency_loss(logits_x, logits_a, n_real: int, w_real: float, w_fake: float):
+    """``(loss, parts)``: loss = w_real L_real + w_fake L_fake with L_s = 1/B_s sum_{n in s} |D(x_n) - D(a_n)|^2 over the first ``n_real``
+    rows (real) and the rest (fake) of the logits [n, Kc] on a batch and on its augmented partner; ``parts`` = the two unweighted
+    means [L_real, L_fake] (not differentiable).  Both inputs receive gradient: there is no stop-gradient."""
+    w_real, w_fake = parse_bcr_weights((w_real, w_fake))
+    return ConsistencyLossFn.apply(logits_x, logits_a, int(n_real), w_real, w_fake)
+
+
 def _spectral_one(W, u, sigma0):
     """A one-matrix SpectralState holding (u, sigma0) for the fp32 matrix W [N, K] (a contiguous cuda tensor)."""
     from .spectral import SpectralState

@@ -204,7 +204,7 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                 fid_fn: Optional[Callable[[nn.Module, int], float]] = None, output_base: Optional[str] = None,
                 save_artifacts: bool = True, clip_d: Optional[float] = None, clip_g: Optional[float] = None,
                 diversity_weight: float = 0.0, instance_noise: float = 0.0, gp_weight: float = 0.0, diffaug: str = "",
-                ema_decay: float = 0.0, ema_start: int = 0, spectral_norm: str = ""):
+                ema_decay: float = 0.0, ema_start: int = 0, spectral_norm: str = "", bcr=(0.0, 0.0), bcr_aug: str = ""):
     """``loss``: "ns" (default: the executable v1 loss), "hinge", or "wasserstein" - the critic losses of the reference's
     unreached step (training.py:67-125); ``clip_d`` / ``clip_g``: its clip_grad_norm_ limits (5.0 / 0.5 there);
     ``diversity_weight``: its diversity term (0.1 there); ``instance_noise``: sigma of the noise on D's inputs (0.1
@@ -221,10 +221,18 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     (``GanEngine(spectral_norm=...)``).  When it is on, the best-FID and final checkpoints hold the discriminator's EFFECTIVE weights
     (``GanEngine.effective_state_dict()``), so they load into a plain ``ViTGAN`` - or the reference's - and compute the trained
     function; the raw weights a resumed run needs (with ``engine_state.pth``) go to ``discriminator_raw.pth`` beside
-    ``final_model.ckpt``, and ``training.log`` says so."""
+    ``final_model.ckpt``, and ``training.log`` says so.
+    ``bcr`` / ``bcr_aug``: the weights (lambda_real, lambda_fake) of balanced consistency regularisation of the discriminator and, when
+    ``diffaug`` is off, its transform (``GanEngine(bcr=..., bcr_aug=...)``; the reference has none).  When it is on, every epoch's line
+    of ``training.log`` also carries the two consistency losses (the unweighted means over the real and the fake images)."""
     global _log_file
-    from .ops import parse_aug_policy
+    from .ops import parse_aug_policy, parse_bcr_weights
     parse_aug_policy(diffaug)  # a bad policy string is the caller's error whatever the machine: before the device check
+    bcr_on = parse_bcr_weights(bcr) != (0.0, 0.0)
+    if parse_aug_policy(bcr_aug) and diffaug:
+        raise ValueError("bcr_aug: with diffaug on, diffaug's own transform is the consistency partner; leave bcr_aug empty")
+    if bool(parse_aug_policy(bcr_aug)) != (bcr_on and not parse_aug_policy(diffaug)):
+        raise ValueError("bcr: consistency weights need a transform (diffaug, or bcr_aug without it), and bcr_aug needs non-zero weights in bcr")
     from .spectral import parse_spectral_set
     parse_spectral_set(spectral_norm)
     if not 0.0 <= float(ema_decay) < 1.0:
@@ -245,7 +253,7 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     eng = GanEngine(D, G, batch=c.batch_size, loss=loss, lr_d=c.discriminator_learning_rate, lr_g=c.generator_learning_rate,
                     weight_decay=1e-3, seed=seed, clip_d=clip_d, clip_g=clip_g, diversity_weight=diversity_weight,
                     instance_noise=instance_noise, gp_weight=gp_weight, diffaug=diffaug, ema_decay=ema_decay, ema_start=ema_start,
-                    spectral_norm=spectral_norm)
+                    spectral_norm=spectral_norm, bcr=bcr, bcr_aug=bcr_aug)
 
     def gan_checkpoint():  # gan.state_dict(), the discriminator's normalised matrices as the network applies them
         sd = gan.state_dict()
@@ -297,6 +305,9 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
         log("Parameters:\n" + str(c))
         if diffaug:
             log(f"Differentiable augmentation: {diffaug}")
+        if eng.bcr:
+            log(f"Balanced consistency regularisation: lambda_real {eng.bcr_w[0]:g}, lambda_fake {eng.bcr_w[1]:g}, partner "
+                + (f"diffaug's own transform ({diffaug})" if diffaug else f"bcr_aug {bcr_aug}"))
         if eng.spec is not None:
             log(f"Spectral normalisation of the discriminator: set '{spectral_norm}', {eng.spec.n} matrices; checkpoints hold the EFFECTIVE "
                 "weights sigma0 W / sigma (discriminator_raw.pth: the raw weights for a resumed run)")
@@ -326,7 +337,11 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                     torch.save(gan_checkpoint(), os.path.join(dirs.checkpoints, f"best_model_epoch_{epoch}_fid_{int(fid_score)}.pth"))
                     if G_ema is not None:  # refreshed just above, for fid_fn
                         torch.save(G_ema.state_dict(), os.path.join(dirs.checkpoints, "generator_ema.pth"))
-            log(f"Epoch [{epoch}/{epochs}] | Disc Loss: {d_real + d_fake:.8f}, Gen Loss: {g:.4f} | FID: {fid_score:.4f}")
+            cr = ""
+            if eng.bcr:
+                cr_real, cr_fake = eng.bcr_losses.tolist()
+                cr = f" | Consistency real: {cr_real:.6f}, fake: {cr_fake:.6f}"
+            log(f"Epoch [{epoch}/{epochs}] | Disc Loss: {d_real + d_fake:.8f}, Gen Loss: {g:.4f} | FID: {fid_score:.4f}{cr}")
             if save_artifacts:
                 save_figures(dirs.save, disc_losses=disc_losses, gen_losses=gen_losses, fid_scores=fid_scores)
     except KeyboardInterrupt as ke:
