@@ -294,6 +294,23 @@ int vg_diffaug_fwd(const void* x, void* y, float* params_out, int B, int C, int 
 int vg_diffaug_bwd(const void* dy, void* dx, int accumulate, int B, int C, int IH, int policy, unsigned long long seed,
                    int site, const unsigned* step_dev, void* stream);
 
+/* The gated forms of the two calls above (adaptive discriminator augmentation; the reference has none, so this header is its
+ * definition): every member of `policy` is applied to an image with probability p = prob_dev[0], a DEVICE pointer the kernel reads
+ * itself - a replayed hipGraph sees the value of the moment, no host round trip and no recapture.  Per image n and member m (0 color,
+ * 1 translation, 2 cutout), with kn and h of the definition above:
+ *   member m is on  iff  bit m of `policy` is set  and  k_{8+m} < T,     k_{8+m} = h(kn, 8 + m) >> 8   (the parameters use draw indices 0..6)
+ *   T = (uint32) floorf(clamp(p, 0, 1) 2^24);  a NaN clamps to 0.  An integer compare: p = 1 (T = 2^24) switches every member of the
+ *   policy on, p = 0 every member off, and the set at p contains the set at any smaller p.
+ * The members that are on form the image's EFFECTIVE policy, and the image is then processed exactly as vg_diffaug_fwd / _bwd process
+ * an image under that policy: the parameter draws do not depend on the policy, the arithmetic is the same code - bit for bit the same
+ * output.  An image with every gate off is a bitwise copy (adjoint: copy / add).  params_out[n, 7] holds the effective policy and
+ * columns 0..6 the identities of what is off.  The adjoint takes the same (policy, seed, site, step, p) and uses the same gates.
+ * Returns what vg_diffaug_fwd / _bwd return, and -1 for a null prob_dev - all before any launch. */
+int vg_diffaug_p_fwd(const void* x, void* y, float* params_out, int B, int C, int IH, int policy, unsigned long long seed,
+                     int site, const unsigned* step_dev, const float* prob_dev, void* stream);
+int vg_diffaug_p_bwd(const void* dy, void* dx, int accumulate, int B, int C, int IH, int policy, unsigned long long seed,
+                     int site, const unsigned* step_dev, const float* prob_dev, void* stream);
+
 /* GAN losses on logits (src/v1/gan.py:16-20,227,238,250 for kind 0; hinge for kind 1;
  * kind 2 = the Wasserstein critic losses of src/v2/training.py:72,97).
  * role 0 D-real, 1 D-fake, 2 G.  loss_out[0] = mean loss, dlogits = d loss / d logits * grad_scale. */
@@ -319,6 +336,23 @@ int vg_gan_loss_pair(const float* logits, float* dlogits, float* loss_out, int n
 int vg_bcr_loss(const float* logits_x, const float* logits_a, float* dlog_x, float* dlog_a, float* loss_out /*[2]*/,
                 int B_real, int B_fake, int Kc, float w_real, float w_fake,
                 int accumulate_x, int accumulate_a, float grad_scale, void* stream);
+
+/* The controller of the augmentation probability (ADA, Karras et al. 2020; the reference has none, so this header is its definition),
+ * driven by the discriminator's overfitting signal r_t = E[sign(D(real))].  logits_real: fp32 [n], the real rows of the adversarial logits
+ * of one step; state: fp32 [4] on the device, 16-byte aligned, = (p, acc_sign, acc_count, r_last); step_dev: the device step counter.
+ * Every call, in fp32:
+ *   acc_sign += sum_i sgn(logits_real[i]),  sgn(+-0) = sgn(NaN) = 0  (integer-valued, exact for n < 2^24: the order cannot matter)
+ *   acc_count += n
+ * and when step_dev[0] % interval == 0:
+ *   s = sgn(acc_sign - target * acc_count)                     one multiply, one subtract (not fused)
+ *   p = min(max(p + s * (step_per_image * acc_count), 0), 1)   (s is -1, 0 or 1, so the product with it is exact)
+ *   r_last = acc_sign / acc_count;   acc_sign = acc_count = 0
+ * ONE launch of one workgroup, no atomics, the state written as one 16-byte vector store; p is state[0], so &state[0] is the prob_dev
+ * of vg_diffaug_p_fwd / _bwd and launches behind this one see the new value.
+ * Returns -1: a null pointer or n < 1;  -2: interval < 1, target outside (-1, 1) or NaN, step_per_image not positive and finite, or
+ * n >= 2^24;  -3: state not 16-byte aligned - all before any launch. */
+int vg_ada_update(const float* logits_real, int n, float* state /*[4]*/, float target, float step_per_image, int interval,
+                  const int* step_dev, void* stream);
 
 /* torch.optim.AdamW step over a flat fp32 buffer (src/v2/training.py:150-157), also refreshing the
  * bf16 shadow the GEMMs read.  n % 4 == 0.  grads are multiplied by gscale first.  The step number

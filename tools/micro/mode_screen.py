@@ -28,6 +28,8 @@ MODES = {
     "no dropout": dict(d_dropout=0.0, g_dropout=0.0),
     "spectral normalisation (all), wasserstein + gp (C call)": dict(spectral_norm="all", loss="wasserstein", clip_d=5.0, gp_weight=10.0),
     "spectral normalisation (qkv)": dict(spectral_norm="qkv"),
+    "adaptive augmentation (ADA) + bCR, hinge": dict(diffaug="color,translation,cutout", ada_target=0.6, ada_interval=4, ada_kimg=20.0,
+                                                    bcr=(10.0, 10.0), loss="hinge"),
 }
 bad = []
 for name, kw in MODES.items():

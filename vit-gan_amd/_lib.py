@@ -123,6 +123,9 @@ _SIGNATURES = {
     "vg_step_inputs": (c_int, [P, P, c_ll, P, c_ll, C.c_ulonglong, P, P]),
     "vg_diffaug_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, C.c_ulonglong, c_int, P, P]),
     "vg_diffaug_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, C.c_ulonglong, c_int, P, P]),
+    "vg_diffaug_p_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, C.c_ulonglong, c_int, P, P, P]),
+    "vg_diffaug_p_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, C.c_ulonglong, c_int, P, P, P]),
+    "vg_ada_update": (c_int, [P, c_int, P, c_float, c_float, c_int, P, P]),
     "vg_gan_loss": (c_int, [P, P, P, c_int, c_int, c_int, c_float, P]),
     "vg_gan_loss_pair": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P]),
     "vg_bcr_loss": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_float, P]),

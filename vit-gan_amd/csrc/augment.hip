@@ -59,10 +59,16 @@ __device__ __forceinline__ void vg_aug_store8(uint16_t* __restrict__ p, bool vec
 
 // CT: the channel count when it is 1 or 3 (a chunk's channels stay in registers between the channel mean and the output), 0: any C
 // (the chunk is read a second time).  ADJ: the adjoint.
-template <int CT, bool ADJ>
+// GATED (vg_diffaug_p_fwd / _bwd): every member of `policy_in` is applied to an image with probability prob[0], read HERE so that a
+// replayed hipGraph sees the current value.  The workgroup is the image, so its effective policy is block-uniform, and from there on
+// the image is processed as the plain kernel processes it under that policy: same draws, same code, same bits.  The plain
+// instantiations never touch `prob` (a trailing argument, nullptr).
+template <int CT, bool ADJ, bool GATED>
 __global__ __launch_bounds__(1024) void vg_diffaug_kernel(const uint16_t* __restrict__ in, uint16_t* __restrict__ out,
-                                                          float* __restrict__ params_out, int C, int IH, int policy, uint32_t key,
-                                                          const unsigned* __restrict__ dstep, int accumulate) {
+                                                          float* __restrict__ params_out, int C, int IH, int policy_in, uint32_t key,
+                                                          const unsigned* __restrict__ dstep, int accumulate,
+                                                          const float* __restrict__ prob) {
+  const int policy = GATED ? vg_aug_gate(key, dstep, (uint32_t)blockIdx.x, policy_in, prob[0]) : policy_in;
   const int n = blockIdx.x, tid = threadIdx.x, NT = blockDim.x;
   const int Cn = CT ? CT : C;
   const int HW = IH * IH;
@@ -204,28 +210,31 @@ __global__ __launch_bounds__(1024) void vg_diffaug_kernel(const uint16_t* __rest
   }
 }
 
-template <bool ADJ>
+template <bool ADJ, bool GATED>
 int vg_diffaug_launch_t(const bf16* in, bf16* out, float* params_out, int accumulate, int B, int C, int IH, int policy, unsigned key,
-                        const unsigned* dstep, hipStream_t st) {
+                        const unsigned* dstep, const float* prob, hipStream_t st) {
   const dim3 grid(B), block(vg_aug_threads(IH));
   const uint16_t* i16 = (const uint16_t*)in;
   uint16_t* o16 = (uint16_t*)out;
   if (C == 3)
-    hipLaunchKernelGGL((vg_diffaug_kernel<3, ADJ>), grid, block, 0, st, i16, o16, params_out, C, IH, policy, key, dstep, accumulate);
+    hipLaunchKernelGGL((vg_diffaug_kernel<3, ADJ, GATED>), grid, block, 0, st, i16, o16, params_out, C, IH, policy, key, dstep, accumulate, prob);
   else if (C == 1)
-    hipLaunchKernelGGL((vg_diffaug_kernel<1, ADJ>), grid, block, 0, st, i16, o16, params_out, C, IH, policy, key, dstep, accumulate);
+    hipLaunchKernelGGL((vg_diffaug_kernel<1, ADJ, GATED>), grid, block, 0, st, i16, o16, params_out, C, IH, policy, key, dstep, accumulate, prob);
   else
-    hipLaunchKernelGGL((vg_diffaug_kernel<0, ADJ>), grid, block, 0, st, i16, o16, params_out, C, IH, policy, key, dstep, accumulate);
+    hipLaunchKernelGGL((vg_diffaug_kernel<0, ADJ, GATED>), grid, block, 0, st, i16, o16, params_out, C, IH, policy, key, dstep, accumulate, prob);
   return (int)hipGetLastError();
 }
 
 }  // namespace
 
+// prob == nullptr: the plain kernels; else the gated ones, which read the probability from prob[0] on the device
 int vg_diffaug_fwd_launch(const bf16* x, bf16* y, float* params_out, int B, int C, int IH, int policy, unsigned key, const unsigned* dstep,
-                          hipStream_t st) {
-  return vg_diffaug_launch_t<false>(x, y, params_out, 0, B, C, IH, policy, key, dstep, st);
+                          hipStream_t st, const float* prob) {
+  return prob ? vg_diffaug_launch_t<false, true>(x, y, params_out, 0, B, C, IH, policy, key, dstep, prob, st)
+              : vg_diffaug_launch_t<false, false>(x, y, params_out, 0, B, C, IH, policy, key, dstep, nullptr, st);
 }
 int vg_diffaug_bwd_launch(const bf16* dy, bf16* dx, int accumulate, int B, int C, int IH, int policy, unsigned key, const unsigned* dstep,
-                          hipStream_t st) {
-  return vg_diffaug_launch_t<true>(dy, dx, nullptr, accumulate, B, C, IH, policy, key, dstep, st);
+                          hipStream_t st, const float* prob) {
+  return prob ? vg_diffaug_launch_t<true, true>(dy, dx, nullptr, accumulate, B, C, IH, policy, key, dstep, prob, st)
+              : vg_diffaug_launch_t<true, false>(dy, dx, nullptr, accumulate, B, C, IH, policy, key, dstep, nullptr, st);
 }

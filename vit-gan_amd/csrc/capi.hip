@@ -467,3 +467,23 @@ extern "C" int vg_diffaug_bwd(const void* dy, void* dx, int accumulate, int B, i
   VG_TRY(vg_diffaug_args(dy, dx, B, C, IH, policy));
   return vg_diffaug_bwd_launch((const bf16*)dy, (bf16*)dx, accumulate, B, C, IH, policy, vg_site_key(seed, site), step_dev, (hipStream_t)stream);
 }
+// the gated forms: every member of the policy applied per image with probability prob_dev[0] (read on the device)
+extern "C" int vg_diffaug_p_fwd(const void* x, void* y, float* params_out, int B, int C, int IH, int policy, unsigned long long seed, int site,
+                                const unsigned* step_dev, const float* prob_dev, void* stream) {
+  VG_TRY(vg_diffaug_args(x, y, B, C, IH, policy));
+  if (!prob_dev) return -1;
+  return vg_diffaug_fwd_launch((const bf16*)x, (bf16*)y, params_out, B, C, IH, policy, vg_site_key(seed, site), step_dev, (hipStream_t)stream,
+                               prob_dev);
+}
+extern "C" int vg_diffaug_p_bwd(const void* dy, void* dx, int accumulate, int B, int C, int IH, int policy, unsigned long long seed, int site,
+                                const unsigned* step_dev, const float* prob_dev, void* stream) {
+  VG_TRY(vg_diffaug_args(dy, dx, B, C, IH, policy));
+  if (!prob_dev) return -1;
+  return vg_diffaug_bwd_launch((const bf16*)dy, (bf16*)dx, accumulate, B, C, IH, policy, vg_site_key(seed, site), step_dev, (hipStream_t)stream,
+                               prob_dev);
+}
+// ---- adaptive discriminator augmentation: the controller (elementwise.hip) ----
+extern "C" int vg_ada_update(const float* logits_real, int n, float* state, float target, float step_per_image, int interval, const int* step_dev,
+                             void* stream) {
+  return vg_ada_update_launch(logits_real, n, state, target, step_per_image, interval, step_dev, (hipStream_t)stream);
+}

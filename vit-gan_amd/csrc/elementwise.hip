@@ -394,6 +394,41 @@ __global__ __launch_bounds__(256) void vg_bcr_loss_kernel(const float* __restric
   }
 }
 
+// ---- adaptive discriminator augmentation: the controller of the augmentation probability (include/vitgan_hip.h, vg_ada_update) ----
+// state = (p, acc_sign, acc_count, r_last).  The sign sum is integer-valued in fp32 (|sum| <= n < 2^24), so its order cannot matter; the
+// update is thread 0's, written as ONE 16-byte vector store.  Contraction is off in the update: s = sgn(acc_sign - target * acc_count)
+// is one multiply and one subtract as the header states it - a fused multiply-add could see a non-zero where the two roundings see 0.
+__global__ __launch_bounds__(256) void vg_ada_update_kernel(const float* __restrict__ logit, int n, float* __restrict__ state, float target,
+                                                            float step_per_image, int interval, const int* __restrict__ step) {
+  __shared__ float red[4];
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const float x = logit[i];
+    acc += x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f);  // sgn(+-0) = sgn(NaN) = 0
+  }
+  acc = vg_wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma clang fp contract(off)
+    const f32x4 s0 = *reinterpret_cast<const f32x4*>(state);
+    float p = s0[0], r_last = s0[3];
+    float acc_sign = s0[1] + (((red[0] + red[1]) + red[2]) + red[3]);
+    float acc_count = s0[2] + (float)n;
+    if (step[0] % interval == 0) {
+      const float t = target * acc_count;
+      const float d = acc_sign - t;
+      const float s = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+      const float dp = step_per_image * acc_count;
+      p = fminf(fmaxf(p + s * dp, 0.f), 1.f);
+      r_last = acc_sign / acc_count;
+      acc_sign = 0.f;
+      acc_count = 0.f;
+    }
+    *reinterpret_cast<f32x4*>(state) = f32x4{p, acc_sign, acc_count, r_last};
+  }
+}
+
 // ---- torch.nn.utils.clip_grad_norm_ over a flat gradient buffer (src/v2/training.py:78,104) -------------------------
 // Two deterministic stages: per-workgroup sums of squares, then every workgroup folds the partials in the same fixed
 // order, derives coef = min(1, max_norm / (gscale*|g| + 1e-6)) and scales its slice in place.
@@ -798,6 +833,14 @@ int vg_bcr_loss_launch(const float* lx, const float* la, float* dlog_x, float* d
   if (!(w_real >= 0.f) || !(w_fake >= 0.f) || (accumulate_x & ~1) || (accumulate_a & ~1)) return -2;
   hipLaunchKernelGGL(vg_bcr_loss_kernel, dim3(2), dim3(256), 0, st, lx, la, dlog_x, dlog_a, loss_out, n_real, n_fake, Kc, w_real, w_fake,
                      accumulate_x, accumulate_a, grad_scale);
+  return (int)hipGetLastError();
+}
+int vg_ada_update_launch(const float* logit, int n, float* state, float target, float step_per_image, int interval, const int* step_dev,
+                         hipStream_t st) {
+  if (!logit || !state || !step_dev || n < 1) return -1;
+  if (interval < 1 || !(target > -1.f && target < 1.f) || !(step_per_image > 0.f && step_per_image <= 3.402823466e+38f) || n >= (1 << 24)) return -2;
+  if ((uintptr_t)state & 15) return -3;  // the state is read and written as one 16-byte vector
+  hipLaunchKernelGGL(vg_ada_update_kernel, dim3(1), dim3(256), 0, st, logit, n, state, target, step_per_image, interval, step_dev);
   return (int)hipGetLastError();
 }
 int vg_gan_loss_launch(const float* logit, float* dlog, float* loss_out, int n, int kind, int role, float grad_scale,

@@ -149,6 +149,19 @@ __device__ __forceinline__ VgAug vg_aug_draw(uint32_t key, const unsigned* __res
   }
   return a;
 }
+// Gated augmentation (vg_diffaug_p_fwd / _bwd): the effective policy of image n at probability p.  Member m (0 color, 1 translation,
+// 2 cutout) of `policy` stays on iff k_{8+m} < T, T = (uint32) floorf(clamp(p, 0, 1) 2^24): an integer compare of draws of their own
+// (the parameters use 0..6), p = 1 passes every draw, p = 0 none, a NaN clamps to 0.  A function of blockIdx-wide values only.
+__device__ __forceinline__ int vg_aug_gate(uint32_t key, const unsigned* __restrict__ dstep, uint32_t n, int policy, float p) {
+  const uint32_t kn = vg_drop_word(vg_drop_word(vg_drop_key(key, dstep), 0u), n);
+  const float pc = p > 0.f ? (p < 1.f ? p : 1.f) : 0.f;
+  const uint32_t T = (uint32_t)floorf(pc * 0x1p24f);
+  int eff = 0;
+#pragma unroll
+  for (int m = 0; m < 3; ++m)
+    if (((policy >> m) & 1) && (vg_drop_word(kn, 8u + (uint32_t)m) >> 8) < T) eff |= 1 << m;
+  return eff;
+}
 // workgroup size of the augmentation kernels: one thread per chunk of 8 pixels of the IH*IH plane, in whole waves, 64 to 1024
 __host__ __device__ inline int vg_aug_threads(int IH) {
   const int nch = (IH * IH + 7) >> 3;

@@ -70,6 +70,9 @@ int vg_gan_loss_launch(const float* logit, float* dlog, float* loss_out, int n, 
 // |lx - la|^2 over their images; dlog_x (+)= g, dlog_a (-)= g with g = (2 w / n) (lx - la) grad_scale
 int vg_bcr_loss_launch(const float* lx, const float* la, float* dlog_x, float* dlog_a, float* loss_out, int n_real, int n_fake, int Kc,
                        float w_real, float w_fake, int accumulate_x, int accumulate_a, float grad_scale, hipStream_t st);
+// controller of the augmentation probability (ADA): state = (p, acc_sign, acc_count, r_last); one workgroup
+int vg_ada_update_launch(const float* logit, int n, float* state, float target, float step_per_image, int interval, const int* step_dev,
+                         hipStream_t st);
 int vg_adamw_launch(float* p, const float* g, float* m, float* v, bf16* shadow, long long n, float lr, float b1, float b2,
                     float eps, float wd, int step, const int* step_dev, float gscale, hipStream_t st);
 int vg_adamw_ema_launch(float* p, const float* g, float* m, float* v, bf16* shadow, float* ema, long long n, float lr, float b1, float b2,
@@ -117,7 +120,8 @@ int vg_pen_head2_launch(const bf16* u, const bf16* t, const float* W2, bf16* u_g
 int vg_add_bf16_launch(const bf16* a, const bf16* b, bf16* out, long long n, hipStream_t st);
 int vg_fill_f32_launch(float* p, long long n, float v, hipStream_t st);
 // differentiable augmentation of the discriminator's input and its adjoint (augment.hip); key = vg_site_key(seed, site)
+// prob: nullptr = every member of the policy on every image; else a device pointer to the application probability (the gated kernels)
 int vg_diffaug_fwd_launch(const bf16* x, bf16* y, float* params_out, int B, int C, int IH, int policy, unsigned key, const unsigned* dstep,
-                          hipStream_t st);
+                          hipStream_t st, const float* prob = nullptr);
 int vg_diffaug_bwd_launch(const bf16* dy, bf16* dx, int accumulate, int B, int C, int IH, int policy, unsigned key, const unsigned* dstep,
-                          hipStream_t st);
+                          hipStream_t st, const float* prob = nullptr);

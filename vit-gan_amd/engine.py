@@ -25,7 +25,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib, flat, ops
-from .dist import GradSync, backward_pieces
+from .dist import GradSync, backward_pieces, world_size
 from .generator import SirenGenerator
 from .modules import ViTDiscriminator, VisionTransformer
 from .spectral import SpectralState, parse_spectral_set, vit_matrix_keys
@@ -47,7 +47,8 @@ class GanEngine:
                  process_group: Optional["dist.ProcessGroup"] = None, external_noise: bool = False,
                  two_stream: bool = False, compress_mapping_grad: bool = False, shard_mapping_update: bool = False, gp_weight: float = 0.0,
                  exchange_single_rank: bool = False, dense_top_block: bool = False, gp_autograd: bool = False, diffaug: str = "",
-                 ema_decay: float = 0.0, ema_start: int = 0, spectral_norm: str = "", bcr=(0.0, 0.0), bcr_aug: str = ""):
+                 ema_decay: float = 0.0, ema_start: int = 0, spectral_norm: str = "", bcr=(0.0, 0.0), bcr_aug: str = "",
+                 aug_p: Optional[float] = None, ada_target: float = 0.0, ada_interval: int = 4, ada_kimg: float = 500.0):
         """concurrent_wgrad: the discriminator's weight gradients on a side stream beside its input gradients.  Off by default
         since the persistent GEMMs (csrc/gemm_wr.hip, gemm_tn.hip: their workgroups hold the CUs for a whole launch) - the
         side stream measured 6.70 against 6.67 ms/step.
@@ -134,7 +135,23 @@ class GanEngine:
         consistency gradients to the adversarial rows' and writes the partner rows'.  ``bcr_losses`` holds the two unweighted means.
         (0, 0) (default): nothing - no buffer, and the step is launch for launch the plain one.  The generator's pass is untouched.
         Not with ``two_stream`` nor ``fuse_real_fake=False``.
-        bcr_aug: the consistency transform when ``diffaug`` is off, a comma-separated subset of ``color,translation,cutout``."""
+        bcr_aug: the consistency transform when ``diffaug`` is off, a comma-separated subset of ``color,translation,cutout``.
+        aug_p: the probability with which every member of ``diffaug`` is applied to an image (sites 0 and 1; vg_diffaug_p_fwd /
+        vg_diffaug_p_bwd: a per-image, per-member gate from the same counter hash, so replays and ranks draw their own).  It lives
+        on the device, in ``ada_state[0]``, and the kernels read it there.  None (default) = 1.0 without ADA - and then, with
+        ``ada_target=0``, the engine calls the ungated kernels, allocates nothing and the step is launch for launch what it was - and
+        0.0 with ADA, where it is the starting value.  ``aug_params[...][:, 7]`` holds every image's effective policy.  With ``bcr``
+        the partner T_1(x) is the gated transform: an image whose gates are all off contributes a plain copy, no launch more.
+        ada_target: > 0 switches adaptive discriminator augmentation on (Karras et al. 2020): one launch per step of one workgroup,
+        vg_ada_update, right behind the discriminator's loss launch, accumulates sign(D(real)) of the adversarial logits' real rows
+        and, on every step whose device counter divides by ``ada_interval``, moves p by (images since the last update) /
+        (1000 ``ada_kimg``) towards r_t = E[sign(D(real))] = ``ada_target``, clamped to [0, 1].  All of it on the device: a replayed
+        hipGraph sees a fresh p with no host round trip.  The generator's pass of a step in which the controller fires ALREADY SEES
+        THE NEW p (it runs behind the update); D's own pass of that step saw the old one.  ``ada_p`` / ``ada_rt`` read the state
+        (they synchronise: for logging).  ``state_dict()`` carries the state and the four options.  Not with ``loss="wasserstein"``
+        (a critic's sign carries no overfitting signal) and not under data parallelism (the statistics are per process; a fixed
+        ``aug_p`` is allowed there).
+        ada_interval: steps between two updates of p.  ada_kimg: thousands of real images it takes p to go from 0 to 1."""
         self.aug = ops.parse_aug_policy(diffaug)  # ValueError names the three members; argument errors come before any device check
         self.spectral_norm = parse_spectral_set(spectral_norm)  # ValueError names the two sets
         self.bcr_w = ops.parse_bcr_weights(bcr)
@@ -150,6 +167,14 @@ class GanEngine:
             raise ValueError("bcr: the consistency step runs the discriminator once on 4B images, on the single-chain schedule; switch two_stream off")
         if self.bcr and not fuse_real_fake:
             raise ValueError("bcr: the consistency step runs the discriminator once on 4B images; it needs fuse_real_fake=True")
+        p0, self.ada_target, self.ada_interval, self.ada_kimg = ops.parse_ada_options(aug_p, ada_target, ada_interval, ada_kimg, self.aug, loss)
+        self.ada = self.ada_target > 0.0
+        self.gated = p0 is not None  # the gated kernels and a device-resident probability
+        self.aug_p0 = 1.0 if p0 is None else p0
+        if self.ada and (world_size(process_group) > 1 or (exchange_single_rank and dist.is_available() and dist.is_initialized())):
+            raise ValueError("ada_target: the controller's statistics are per process and are not exchanged; under data parallelism use a "
+                             "fixed aug_p")
+        self.ada_step_per_image = 1.0 / (1000.0 * self.ada_kimg)
         self.ema_decay, self.ema_start = float(ema_decay), int(ema_start)
         if not 0.0 <= self.ema_decay < 1.0:
             raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
@@ -259,7 +284,11 @@ class GanEngine:
         self.div_scratch = torch.zeros((d.C * d.IH * d.IH + 15) // 16, dtype=torch.float32, device=dev)
         self.logits = torch.empty(nL, d.Kc, dtype=torch.float32, device=dev)
         self.dlogits = torch.empty(nL, d.Kc, dtype=torch.float32, device=dev)
-        if self.bcr:  # the generator's pass gets rows of its own, so ``logits`` still holds D's whole 4B pass after the step
+        # (p, acc_sign, acc_count, r_last) of include/vitgan_hip.h, vg_ada_update: element 0 is the gated kernels' prob_dev
+        self.ada_state: Optional[torch.Tensor] = None
+        if self.gated:
+            self.ada_state = torch.tensor([self.aug_p0, 0.0, 0.0, 0.0], dtype=torch.float32, device=dev)
+        if self.bcr or self.ada:  # the generator's pass gets rows of its own, so ``logits`` still holds D's whole pass after the step
             self.logits_g, self.dlogits_g = torch.empty(B, d.Kc, dtype=torch.float32, device=dev), torch.empty(B, d.Kc, dtype=torch.float32, device=dev)
         self.z = torch.empty(B, g.Z, dtype=torch.float32, device=dev)
         self.losses = torch.zeros(3, dtype=torch.float32, device=dev)  # d_real, d_fake, g
@@ -446,6 +475,40 @@ class GanEngine:
         _lib.check(L.vg_gan_loss(C.c_void_p(self.logits.data_ptr() + off), C.c_void_p(self.dlogits.data_ptr() + off),
                                  C.c_void_p(self.losses.data_ptr() + 4 * slot), n * self.Kc, self.kind, role, 1.0, st), "vg_gan_loss")
 
+    def _augment(self, src, dst, params, n: int, site: int, st) -> None:
+        """T(src) -> dst for n images at an augmentation site of the step: the gated kernel with the device-resident probability when
+        the engine has one, else the existing call."""
+        d_, L = self.vit._dims, _lib.lib()
+        if self.gated:
+            _lib.check(L.vg_diffaug_p_fwd(src, dst, params, n, d_.C, d_.IH, self.aug, self._aug_seed, site, _p(self.step_t), _p(self.ada_state), st),
+                       "vg_diffaug_p_fwd")
+        else:
+            _lib.check(L.vg_diffaug_fwd(src, dst, params, n, d_.C, d_.IH, self.aug, self._aug_seed, site, _p(self.step_t), st), "vg_diffaug_fwd")
+
+    def _ada_update(self, logits_real, st) -> None:
+        """The controller on the real rows of the adversarial logits (the first B rows at ``logits_real``); nothing without ADA."""
+        if self.ada:
+            _lib.check(_lib.lib().vg_ada_update(logits_real, self.B * self.Kc, _p(self.ada_state), self.ada_target, self.ada_step_per_image,
+                                                self.ada_interval, _p(self.step_t), st), "vg_ada_update")
+
+    @property
+    def ada_p(self) -> float:
+        """The augmentation probability now in force (synchronises: for logging)."""
+        return float(self._need_ada("ada_p")[0])
+
+    @property
+    def ada_rt(self) -> float:
+        """r_t = E[sign(D(real))] over the window of the controller's last update (synchronises: for logging)."""
+        return float(self._need_ada("ada_rt")[3])
+
+    def _need_ada(self, what: str) -> torch.Tensor:
+        if self.ada_state is None:
+            raise RuntimeError(f"{what}: this engine holds no augmentation probability (built without aug_p / ada_target)")
+        return self.ada_state
+
+    def _ada_options(self):
+        return None if not self.gated else (self.aug_p0, self.ada_target, self.ada_interval, self.ada_kimg)
+
     def _enqueue_two_stream(self) -> None:
         """The step as two concurrent chains (see ``two_stream``).  Everything is enqueued from this thread; the second chain
         forks from and joins the current stream through events, so the whole step is still one capturable graph."""
@@ -552,8 +615,7 @@ class GanEngine:
             self.imgs_noisy.copy_(self.inoise)
             d_in = self.imgs_noisy
         if self.aug:  # D sees T_1([real ; fake]) (site 0), and so does the penalty below
-            _lib.check(L.vg_diffaug_fwd(_p(d_in), _p(self.imgs_aug), _p(self.aug_params["d"]), 2 * B, d_.C, d_.IH, self.aug, self._aug_seed, 0,
-                                        _p(self.step_t), st), "vg_diffaug_fwd")
+            self._augment(_p(d_in), _p(self.imgs_aug), _p(self.aug_params["d"]), 2 * B, 0, st)
             d_in = self.imgs_aug
         if self.bcr_policy:  # the consistency partner T_c(x) (site 2) behind x in the 4B buffer; the losses and the penalty stay on x
             _lib.check(L.vg_diffaug_fwd(_p(d_in), _p(self.imgs_bcr), _p(self.aug_params["c"]), 2 * B, d_.C, d_.IH, self.bcr_policy,
@@ -586,6 +648,7 @@ class GanEngine:
             _lib.check(L.vg_vit_forward(C.byref(nd), 4 * B, _p(self.imgs4), 1, _p(self.ws_d), lx, st), "vg_vit_forward")
             _lib.check(L.vg_gan_loss_pair(la if adv_a else lx, da if adv_a else dx, _p(self.losses), B * self.Kc, 0, B * self.Kc, 1, self.kind,
                                           1.0, st), "vg_gan_loss_pair")
+            self._ada_update(la if adv_a else lx, st)
             _lib.check(L.vg_bcr_loss(lx, la, dx, da, _p(self.bcr_losses), B, B, self.Kc, self.bcr_w[0], self.bcr_w[1], 1 - adv_a, adv_a, 1.0, st),
                        "vg_bcr_loss")
             self._d_backward(nd, 4 * B, dx, 1, None, st)
@@ -594,6 +657,7 @@ class GanEngine:
             # D(real) -> slot 0, D(fake) -> slot 1: both halves of the fused pass in one launch
             _lib.check(_lib.lib().vg_gan_loss_pair(_p(self.logits), _p(self.dlogits), _p(self.losses), B * self.Kc, 0, B * self.Kc, 1, self.kind,
                                                    1.0, st), "vg_gan_loss_pair")
+            self._ada_update(_p(self.logits), st)
             self._d_backward(nd, 2 * B, _p(self.dlogits), 1, None, st)
         else:
             for half, role in ((0, 0), (1, 1)):
@@ -604,6 +668,7 @@ class GanEngine:
                 _lib.check(L.vg_vit_forward(C.byref(net), B, src, 1, _p(self.ws_d), lg, st), "vg_vit_forward")
                 self._loss(half * B, B, role, role, st)
                 if half == 0:
+                    self._ada_update(lg, st)
                     _lib.check(L.vg_vit_backward(C.byref(net), B, _p(self.ws_d), dl, None, 1, st), "vg_vit_backward")
                 else:  # second pass finishes D.grad: exchange it as it completes
                     self._d_backward(net, B, dl, 1, None, st)
@@ -617,9 +682,8 @@ class GanEngine:
         g_in, g_dimg = fake_ptr, _p(self.dfake)
         if self.aug:  # D sees T_2(fake) (site 1); its input gradient goes back through the adjoint into dfake
             g_in, g_dimg = _p(self.imgs_aug), C.c_void_p(self.imgs_aug.data_ptr() + B * img_bytes)
-            _lib.check(L.vg_diffaug_fwd(fake_ptr, g_in, _p(self.aug_params["g"]), B, d_.C, d_.IH, self.aug, self._aug_seed, 1, _p(self.step_t), st),
-                       "vg_diffaug_fwd")
-        if self.bcr:
+            self._augment(fake_ptr, g_in, _p(self.aug_params["g"]), B, 1, st)
+        if self.bcr or self.ada:
             _lib.check(L.vg_vit_forward(C.byref(nd_c), B, g_in, 1, _p(self.ws_d), _p(self.logits_g), st), "vg_vit_forward")
             _lib.check(L.vg_gan_loss(_p(self.logits_g), _p(self.dlogits_g), C.c_void_p(self.losses.data_ptr() + 8), B * self.Kc, self.kind, 2, 1.0, st),
                        "vg_gan_loss")
@@ -628,7 +692,10 @@ class GanEngine:
             _lib.check(L.vg_vit_forward(C.byref(nd_c), B, g_in, 1, _p(self.ws_d), _p(self.logits), st), "vg_vit_forward")
             self._loss(0, B, 2, 2, st)
             _lib.check(L.vg_vit_backward(C.byref(nd_c), B, _p(self.ws_d), _p(self.dlogits), g_dimg, 0, st), "vg_vit_backward")
-        if self.aug:
+        if self.aug and self.gated:
+            _lib.check(L.vg_diffaug_p_bwd(g_dimg, _p(self.dfake), 0, B, d_.C, d_.IH, self.aug, self._aug_seed, 1, _p(self.step_t),
+                                          _p(self.ada_state), st), "vg_diffaug_p_bwd")
+        elif self.aug:
             _lib.check(L.vg_diffaug_bwd(g_dimg, _p(self.dfake), 0, B, d_.C, d_.IH, self.aug, self._aug_seed, 1, _p(self.step_t), st), "vg_diffaug_bwd")
         if self.div_w != 0.0:  # total_gen_loss = loss + w * diversity_loss(fake_images): its gradient joins dL/d fake
             Dn = self.dfake[0].numel()
@@ -648,6 +715,8 @@ class GanEngine:
         state = [fd.flat, fd.shadow, fg.flat, fg.shadow, self.m_d, self.v_d, self.m_g, self.v_g, self.step_t]
         if self.spec is not None:
             state.append(self.spec.state)
+        if self.ada_state is not None:
+            state.append(self.ada_state)
         return state if self.ema_g is None else state + [self.ema_g]
 
     def sync_from_modules(self, reset_optimizer: bool = False) -> None:
@@ -733,7 +802,8 @@ class GanEngine:
     def state_dict(self) -> dict:
         """The engine's training state - what ``gan.state_dict()`` (the networks' weights) does not hold: AdamW's moments, the
         device step counter (it keys the bias corrections, the dropout masks, the latent noise and the augmentation), the host's
-        step count, the current latent-noise stream and, when it is on, the generator's moving average."""
+        step count, the current latent-noise stream and, when they are on, the generator's moving average and the augmentation
+        probability with its controller."""
         sd = {"format_version": self.STATE_FORMAT, "steps": int(self.steps), "noise_seed": int(self._noise_seed)}
         for k in ("m_d", "v_d", "m_g", "v_g", "step_t"):
             sd[k] = getattr(self, k).detach().clone()
@@ -743,6 +813,8 @@ class GanEngine:
             sd["spectral_norm"], sd["spectral_state"] = self.spectral_norm, self.spec.state.detach().clone()
         if self.bcr:  # no training state of its own: the options, so that a resumed run is the same run
             sd["bcr"] = self._bcr_options()
+        if self.gated:  # the probability and the controller's accumulators, and the options they were run under
+            sd["ada"], sd["ada_state"] = self._ada_options(), self.ada_state.detach().clone()
         return sd
 
     def _bcr_options(self):
@@ -768,7 +840,8 @@ class GanEngine:
         ``strict``; with ``strict=False`` the average restarts as a copy of the weights at the next step (the step is captured again).  The
         spectral-normalisation state follows the same rule: missing under ``strict`` raises, with ``strict=False`` it is measured
         again from the current weights.  Consistency regularisation has no state; the saved ``bcr`` options must equal this engine's under
-        ``strict``."""
+        ``strict``.  The augmentation probability and its controller (``aug_p`` / ``ada_target``) follow bCR's rule for the options, and
+        their state is restored whenever both sides hold one."""
         if sd.get("format_version") != self.STATE_FORMAT:
             raise ValueError(f"engine state format {sd.get('format_version')!r}, this engine reads format {self.STATE_FORMAT}")
         names = ("m_d", "v_d", "m_g", "v_g", "step_t")
@@ -785,6 +858,11 @@ class GanEngine:
         if strict and saved_bcr != self._bcr_options():
             raise ValueError(f"engine state was saved with consistency regularisation (lambda_real, lambda_fake, bcr_aug bits) = {saved_bcr!r}, "
                              f"this engine has {self._bcr_options()!r} (strict=False loads it all the same: bCR holds no training state)")
+        saved_ada = None if sd.get("ada") is None else tuple(sd["ada"])
+        if strict and saved_ada != self._ada_options():
+            raise ValueError(f"engine state was saved with (aug_p, ada_target, ada_interval, ada_kimg) = {saved_ada!r}, this engine has "
+                             f"{self._ada_options()!r} (strict=False loads the probability all the same when both sides hold one)")
+        has_ada = sd.get("ada_state") is not None and self.ada_state is not None
         has_ema = sd.get("ema_g") is not None
         if strict and has_ema != (self.ema_g is not None):
             raise ValueError("engine state has no ema_g but this engine keeps a moving average (strict=False restarts it)" if not has_ema
@@ -794,6 +872,8 @@ class GanEngine:
             pairs.append((self.ema_g, sd["ema_g"], "ema_g"))
         if has_spec and self.spec is not None:
             pairs.append((self.spec.state, sd["spectral_state"], "spectral_state"))
+        if has_ada:
+            pairs.append((self.ada_state, sd["ada_state"], "ada_state"))
         for dst, src, k in pairs:
             if not torch.is_tensor(src) or src.numel() != dst.numel():
                 raise ValueError(f"engine state {k}: {tuple(getattr(src, 'shape', ()))} does not fit this engine's {tuple(dst.shape)}")

@@ -295,12 +295,47 @@ def parse_aug_policy(policy) -> int:
     return bits
 
 
+def parse_aug_p(aug_p) -> float:
+    """The application probability of the augmentation members as a float in [0, 1]; anything else (NaN included) is a ValueError."""
+    try:
+        p = float(aug_p)
+    except (TypeError, ValueError):
+        raise ValueError(f"aug_p must be a probability in [0, 1], got {aug_p!r}") from None
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"aug_p must be a probability in [0, 1], got {aug_p!r}")
+    return p
+
+
+def parse_ada_options(aug_p, ada_target, ada_interval, ada_kimg, policy: int, loss: str):
+    """``(aug_p0, ada_target, ada_interval, ada_kimg)`` of the gated augmentation and its controller, checked as GanEngine and
+    train_model both state them; ``policy`` is the parsed ``diffaug`` mask.  ``aug_p0`` is None when neither ``aug_p`` nor ADA is on
+    (the ungated kernels), else the fixed or starting probability (``aug_p=None``: 1.0 without ADA, 0.0 with it)."""
+    try:
+        target, kimg = float(ada_target), float(ada_kimg)
+    except (TypeError, ValueError):
+        raise ValueError(f"ada_target and ada_kimg are numbers, got {ada_target!r}, {ada_kimg!r}") from None
+    if not 0.0 <= target < 1.0:
+        raise ValueError(f"ada_target must be in [0, 1) (0 = no adaptive augmentation), got {ada_target!r}")
+    ada = target > 0.0
+    if (aug_p is not None or ada) and not policy:
+        raise ValueError("aug_p / ada_target: the augmentation probability gates the members of diffaug; name them in diffaug")
+    p0 = parse_aug_p(aug_p) if aug_p is not None else (0.0 if ada else None)
+    if isinstance(ada_interval, bool) or not isinstance(ada_interval, int) or ada_interval < 1:
+        raise ValueError(f"ada_interval must be a positive integer, got {ada_interval!r}")
+    if not (0.0 < kimg < float("inf")):
+        raise ValueError(f"ada_kimg must be positive and finite, got {ada_kimg!r}")
+    if ada and loss == "wasserstein":
+        raise ValueError("ada_target: a Wasserstein critic's sign carries no overfitting signal; use loss='ns' or 'hinge', or a fixed aug_p")
+    return p0, target, int(ada_interval), kimg
+
+
 class DiffAugmentFn(torch.autograd.Function):
     """T = cutout o translation o contrast o saturation o brightness per image (include/vitgan_hip.h, vg_diffaug_fwd); T is affine
-    in x, so the backward is the adjoint kernel on dy with the same (policy, seed, site, step) and nothing is saved."""
+    in x, so the backward is the adjoint kernel on dy with the same (policy, seed, site, step) and nothing is saved.  With ``p`` (a
+    one-element cuda fp32 tensor) the gated kernels vg_diffaug_p_fwd / vg_diffaug_p_bwd run instead."""
 
     @staticmethod
-    def forward(ctx, x, policy, seed, site, step):
+    def forward(ctx, x, policy, seed, site, step, p=None):
         _need_cuda(x, "diff_augment")
         B, Cc, IH, IW = x.shape
         assert IH == IW, "The provided images are not square shaped"
@@ -308,26 +343,46 @@ class DiffAugmentFn(torch.autograd.Function):
             raise ValueError("diff_augment: step is the device step counter, a cuda int32 tensor")
         xb = _bf(x)
         y = torch.empty_like(xb)
-        _lib.check(_lib.lib().vg_diffaug_fwd(_p(xb), _p(y), None, B, Cc, IH, policy, seed, site, _p(step), _st()), "vg_diffaug_fwd")
-        # the adjoint must see the counter value of THIS forward, whatever the caller does to the counter before backward()
-        ctx.key = (policy, seed, site, None if step is None else step.clone(), x.dtype)
+        if p is None:
+            _lib.check(_lib.lib().vg_diffaug_fwd(_p(xb), _p(y), None, B, Cc, IH, policy, seed, site, _p(step), _st()), "vg_diffaug_fwd")
+        else:
+            _lib.check(_lib.lib().vg_diffaug_p_fwd(_p(xb), _p(y), None, B, Cc, IH, policy, seed, site, _p(step), _p(p), _st()),
+                       "vg_diffaug_p_fwd")
+        # the adjoint must see the counter value (and the probability) of THIS forward, whatever the caller does to them before backward()
+        ctx.key = (policy, seed, site, None if step is None else step.clone(), x.dtype, None if p is None else p.clone())
         return y.to(x.dtype)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
-        policy, seed, site, step, dt = ctx.key
+        policy, seed, site, step, dt, p = ctx.key
         B, Cc, IH, _ = dy.shape
         d = _bf(dy)
         dx = torch.empty_like(d)
-        _lib.check(_lib.lib().vg_diffaug_bwd(_p(d), _p(dx), 0, B, Cc, IH, policy, seed, site, _p(step), _st()), "vg_diffaug_bwd")
-        return dx.to(dt), None, None, None, None
+        if p is None:
+            _lib.check(_lib.lib().vg_diffaug_bwd(_p(d), _p(dx), 0, B, Cc, IH, policy, seed, site, _p(step), _st()), "vg_diffaug_bwd")
+        else:
+            _lib.check(_lib.lib().vg_diffaug_p_bwd(_p(d), _p(dx), 0, B, Cc, IH, policy, seed, site, _p(step), _p(p), _st()),
+                       "vg_diffaug_p_bwd")
+        return dx.to(dt), None, None, None, None, None
 
 
-def diff_augment(x, policy, seed: int, site: int, step: Optional[torch.Tensor] = None):
+def diff_augment(x, policy, seed: int, site: int, step: Optional[torch.Tensor] = None, p=None):
     """Differentiable augmentation of images [B, C, IH, IH]: ``policy`` a comma-separated subset of color, translation, cutout (or
-    its bit mask); the transform of image n is a pure function of (seed, site, step[0], n) - ``step``: a cuda int32 counter, or None."""
-    return DiffAugmentFn.apply(x, parse_aug_policy(policy), int(seed) & 0xFFFFFFFFFFFFFFFF, int(site), step)
+    its bit mask); the transform of image n is a pure function of (seed, site, step[0], n) - ``step``: a cuda int32 counter, or None.
+    ``p``: None = every member on every image (vg_diffaug_fwd); a float in [0, 1] or a one-element cuda fp32 tensor = every member
+    applied per image with that probability (vg_diffaug_p_fwd: the kernel reads the tensor itself, so a captured launch follows it)."""
+    policy = parse_aug_policy(policy)
+    if p is not None:
+        if torch.is_tensor(p):
+            if p.numel() != 1 or p.dtype != torch.float32 or p.device != x.device:
+                raise ValueError("diff_augment: p as a tensor is ONE fp32 element on the images' device")
+            p = p.detach().reshape(1)
+        else:
+            p = parse_aug_p(p)
+            _need_cuda(x, "diff_augment")
+            p = torch.full((1,), p, dtype=torch.float32, device=x.device)
+    return DiffAugmentFn.apply(x, policy, int(seed) & 0xFFFFFFFFFFFFFFFF, int(site), step, p)
 
 
 def parse_bcr_weights(bcr):

@@ -204,7 +204,8 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                 fid_fn: Optional[Callable[[nn.Module, int], float]] = None, output_base: Optional[str] = None,
                 save_artifacts: bool = True, clip_d: Optional[float] = None, clip_g: Optional[float] = None,
                 diversity_weight: float = 0.0, instance_noise: float = 0.0, gp_weight: float = 0.0, diffaug: str = "",
-                ema_decay: float = 0.0, ema_start: int = 0, spectral_norm: str = "", bcr=(0.0, 0.0), bcr_aug: str = ""):
+                ema_decay: float = 0.0, ema_start: int = 0, spectral_norm: str = "", bcr=(0.0, 0.0), bcr_aug: str = "",
+                aug_p: Optional[float] = None, ada_target: float = 0.0, ada_interval: int = 4, ada_kimg: float = 500.0):
     """``loss``: "ns" (default: the executable v1 loss), "hinge", or "wasserstein" - the critic losses of the reference's
     unreached step (training.py:67-125); ``clip_d`` / ``clip_g``: its clip_grad_norm_ limits (5.0 / 0.5 there);
     ``diversity_weight``: its diversity term (0.1 there); ``instance_noise``: sigma of the noise on D's inputs (0.1
@@ -224,7 +225,10 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     ``final_model.ckpt``, and ``training.log`` says so.
     ``bcr`` / ``bcr_aug``: the weights (lambda_real, lambda_fake) of balanced consistency regularisation of the discriminator and, when
     ``diffaug`` is off, its transform (``GanEngine(bcr=..., bcr_aug=...)``; the reference has none).  When it is on, every epoch's line
-    of ``training.log`` also carries the two consistency losses (the unweighted means over the real and the fake images)."""
+    of ``training.log`` also carries the two consistency losses (the unweighted means over the real and the fake images).
+    ``aug_p`` / ``ada_target`` / ``ada_interval`` / ``ada_kimg``: the application probability of ``diffaug``'s members and its adaptive
+    controller (``GanEngine(aug_p=..., ada_target=...)``; the reference has none).  With ``ada_target > 0`` every epoch's line also
+    carries the probability in force and the overfitting signal r_t of the last update."""
     global _log_file
     from .ops import parse_aug_policy, parse_bcr_weights
     parse_aug_policy(diffaug)  # a bad policy string is the caller's error whatever the machine: before the device check
@@ -235,6 +239,9 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
         raise ValueError("bcr: consistency weights need a transform (diffaug, or bcr_aug without it), and bcr_aug needs non-zero weights in bcr")
     from .spectral import parse_spectral_set
     parse_spectral_set(spectral_norm)
+    # the probability's and the controller's argument errors are the caller's whatever the machine: before the device check
+    from .ops import parse_ada_options
+    parse_ada_options(aug_p, ada_target, ada_interval, ada_kimg, parse_aug_policy(diffaug), loss)
     if not 0.0 <= float(ema_decay) < 1.0:
         raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
     if int(ema_start) != ema_start or ema_start < 0:
@@ -253,7 +260,8 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     eng = GanEngine(D, G, batch=c.batch_size, loss=loss, lr_d=c.discriminator_learning_rate, lr_g=c.generator_learning_rate,
                     weight_decay=1e-3, seed=seed, clip_d=clip_d, clip_g=clip_g, diversity_weight=diversity_weight,
                     instance_noise=instance_noise, gp_weight=gp_weight, diffaug=diffaug, ema_decay=ema_decay, ema_start=ema_start,
-                    spectral_norm=spectral_norm, bcr=bcr, bcr_aug=bcr_aug)
+                    spectral_norm=spectral_norm, bcr=bcr, bcr_aug=bcr_aug, aug_p=aug_p, ada_target=ada_target, ada_interval=ada_interval,
+                    ada_kimg=ada_kimg)
 
     def gan_checkpoint():  # gan.state_dict(), the discriminator's normalised matrices as the network applies them
         sd = gan.state_dict()
@@ -305,6 +313,9 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
         log("Parameters:\n" + str(c))
         if diffaug:
             log(f"Differentiable augmentation: {diffaug}")
+        if eng.gated:
+            log(f"Augmentation probability: {eng.aug_p0:g}" + (f", adaptive: target r_t {eng.ada_target:g}, every {eng.ada_interval} steps, "
+                                                              f"{eng.ada_kimg:g} kimg from 0 to 1" if eng.ada else " (fixed)"))
         if eng.bcr:
             log(f"Balanced consistency regularisation: lambda_real {eng.bcr_w[0]:g}, lambda_fake {eng.bcr_w[1]:g}, partner "
                 + (f"diffaug's own transform ({diffaug})" if diffaug else f"bcr_aug {bcr_aug}"))
@@ -341,6 +352,8 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
             if eng.bcr:
                 cr_real, cr_fake = eng.bcr_losses.tolist()
                 cr = f" | Consistency real: {cr_real:.6f}, fake: {cr_fake:.6f}"
+            if eng.ada:
+                cr += f" | ada_p: {eng.ada_p:.6f}, ada_rt: {eng.ada_rt:.4f}"
             log(f"Epoch [{epoch}/{epochs}] | Disc Loss: {d_real + d_fake:.8f}, Gen Loss: {g:.4f} | FID: {fid_score:.4f}{cr}")
             if save_artifacts:
                 save_figures(dirs.save, disc_losses=disc_losses, gen_losses=gen_losses, fid_scores=fid_scores)
