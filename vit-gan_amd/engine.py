@@ -34,7 +34,12 @@ LOSS_KINDS = {"ns": 0, "hinge": 1, "wasserstein": 2}  # "wasserstein": the criti
 
 
 def _p(t):
+    """A tensor's device pointer.  Every sub-range the step addresses is a VIEW made once in ``_carve``: no call site adds byte offsets."""
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _call(name: str, *args) -> None:
+    _lib.check(getattr(_lib.lib(), name)(*args), name)
 
 
 class GanEngine:
@@ -106,7 +111,7 @@ class GanEngine:
         and every replay of the captured step draw their own; ``aug_params`` holds the last step's parameters of both sites.  Not
         with ``two_stream``.
         ema_decay: decay d of an exponential moving average of the GENERATOR's fp32 master weights, kept in ``ema_g`` by the generator's
-        optimizer kernel itself (vg_adamw_ema_step: one pass, 38 B per parameter against AdamW's 30; no extra launch, nothing a
+        optimizer kernel itself (the fused AdamW + EMA call of ``_adamw_range``: one pass, 38 B per parameter against AdamW's 30; no extra launch, nothing a
         replayed graph could miss).  With t the device step counter and p_t the weights after step t:  e_t = p_t while
         t <= max(1, ema_start) (the average follows the weights through the warm-up), then e_t = e_{t-1} + (1 - d)(p_t - e_{t-1}).
         0.0 (default) = no average: no buffer, and the step is launch for launch the plain one.  The discriminator is not averaged.
@@ -136,8 +141,8 @@ class GanEngine:
         (0, 0) (default): nothing - no buffer, and the step is launch for launch the plain one.  The generator's pass is untouched.
         Not with ``two_stream`` nor ``fuse_real_fake=False``.
         bcr_aug: the consistency transform when ``diffaug`` is off, a comma-separated subset of ``color,translation,cutout``.
-        aug_p: the probability with which every member of ``diffaug`` is applied to an image (sites 0 and 1; vg_diffaug_p_fwd /
-        vg_diffaug_p_bwd: a per-image, per-member gate from the same counter hash, so replays and ranks draw their own).  It lives
+        aug_p: the probability with which every member of ``diffaug`` is applied to an image (sites 0 and 1; the gated kernels of
+        ``_augment`` / ``_augment_adjoint``: a per-image, per-member gate from the same counter hash, so replays and ranks draw their own).  It lives
         on the device, in ``ada_state[0]``, and the kernels read it there.  None (default) = 1.0 without ADA - and then, with
         ``ada_target=0``, the engine calls the ungated kernels, allocates nothing and the step is launch for launch what it was - and
         0.0 with ADA, where it is the starting value.  ``aug_params[...][:, 7]`` holds every image's effective policy.  With ``bcr``
@@ -152,10 +157,18 @@ class GanEngine:
         (a critic's sign carries no overfitting signal) and not under data parallelism (the statistics are per process; a fixed
         ``aug_p`` is allowed there).
         ada_interval: steps between two updates of p.  ada_kimg: thousands of real images it takes p to go from 0 to 1."""
-        self.aug = ops.parse_aug_policy(diffaug)  # ValueError names the three members; argument errors come before any device check
-        self.spectral_norm = parse_spectral_set(spectral_norm)  # ValueError names the two sets
-        self.bcr_w = ops.parse_bcr_weights(bcr)
-        self.bcr_policy = ops.parse_aug_policy(bcr_aug)
+        self._check_options(discriminator, generator, dict(locals()))
+        self._carve()
+        self._attach()
+
+    def _check_options(self, discriminator, generator, o) -> None:
+        """Constructor, part 1: every argument error, in a fixed order, from host code alone - no device is touched, so a bad argument
+        is reported as such on any machine - and the parsed options on ``self``.  ``o``: the constructor's arguments by name."""
+        two_stream, loss, pg = bool(o["two_stream"]), o["loss"], o["process_group"]
+        self.aug = ops.parse_aug_policy(o["diffaug"])  # ValueError names the three members
+        self.spectral_norm = parse_spectral_set(o["spectral_norm"])  # ValueError names the two sets
+        self.bcr_w = ops.parse_bcr_weights(o["bcr"])
+        self.bcr_policy = ops.parse_aug_policy(o["bcr_aug"])
         self.bcr = self.bcr_w != (0.0, 0.0)
         if self.bcr_policy and self.aug:
             raise ValueError("bcr_aug: with diffaug on, diffaug's own transform T_1 is the consistency partner; leave bcr_aug empty")
@@ -165,21 +178,22 @@ class GanEngine:
             raise ValueError("bcr: the consistency loss needs a transform - switch diffaug on (its T_1 is the partner) or name one in bcr_aug")
         if self.bcr and two_stream:
             raise ValueError("bcr: the consistency step runs the discriminator once on 4B images, on the single-chain schedule; switch two_stream off")
-        if self.bcr and not fuse_real_fake:
+        if self.bcr and not o["fuse_real_fake"]:
             raise ValueError("bcr: the consistency step runs the discriminator once on 4B images; it needs fuse_real_fake=True")
-        p0, self.ada_target, self.ada_interval, self.ada_kimg = ops.parse_ada_options(aug_p, ada_target, ada_interval, ada_kimg, self.aug, loss)
-        self.ada = self.ada_target > 0.0
+        p0, self.ada_target, self.ada_interval, self.ada_kimg = ops.parse_ada_options(o["aug_p"], o["ada_target"], o["ada_interval"], o["ada_kimg"],
+                                                                                      self.aug, loss)
+        self.ada, self.aug_p0 = self.ada_target > 0.0, 1.0 if p0 is None else p0
         self.gated = p0 is not None  # the gated kernels and a device-resident probability
-        self.aug_p0 = 1.0 if p0 is None else p0
-        if self.ada and (world_size(process_group) > 1 or (exchange_single_rank and dist.is_available() and dist.is_initialized())):
+        world = world_size(pg)
+        if self.ada and (world > 1 or (o["exchange_single_rank"] and dist.is_available() and dist.is_initialized())):
             raise ValueError("ada_target: the controller's statistics are per process and are not exchanged; under data parallelism use a "
                              "fixed aug_p")
         self.ada_step_per_image = 1.0 / (1000.0 * self.ada_kimg)
-        self.ema_decay, self.ema_start = float(ema_decay), int(ema_start)
+        self.ema_decay, self.ema_start = float(o["ema_decay"]), int(o["ema_start"])
         if not 0.0 <= self.ema_decay < 1.0:
-            raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
-        if self.ema_start < 0 or self.ema_start != ema_start:
-            raise ValueError(f"ema_start must be a non-negative integer, got {ema_start!r}")
+            raise ValueError(f"ema_decay must be in [0, 1), got {o['ema_decay']!r}")
+        if self.ema_start < 0 or self.ema_start != o["ema_start"]:
+            raise ValueError(f"ema_start must be a non-negative integer, got {o['ema_start']!r}")
         if self.aug and two_stream:
             raise ValueError("diffaug: the augmented step is verified on the single-chain schedule only; switch two_stream off")
         if self.spectral_norm and two_stream:
@@ -189,67 +203,68 @@ class GanEngine:
             raise TypeError("GanEngine needs a ViTDiscriminator/VisionTransformer and a SirenGenerator")
         if getattr(vit, "precision", "bf16") != "bf16":
             raise ValueError("GanEngine: the fused step is bf16; it does not take a discriminator in precision='fp32'")
-        if float(gp_weight) != 0.0:
+        self.gp_w = float(o["gp_weight"])
+        if self.gp_w != 0.0:
             vit.require_short_attention("gp_weight > 0 (the gradient penalty)")
         self.vit, self.gen, self._disc = vit, generator, discriminator
-        self.dev = vit._flat.flat.device
-        if self.dev.type != "cuda" or generator._flat.flat.device != self.dev:
-            raise RuntimeError("GanEngine: both networks must be on the same cuda device (no CPU fallback)")
         if loss not in LOSS_KINDS:
             raise ValueError(f"loss must be one of {sorted(LOSS_KINDS)}")
-        self.B, self.kind = int(batch), LOSS_KINDS[loss]
-        # dropout probabilities: default = what the modules would apply in their current train/eval mode
-        self.p_d = float(vit._dropout_p if vit.training else 0.0) if d_dropout is None else float(d_dropout)
-        self.p_g = float(generator.dropout_p if generator.training else 0.0) if g_dropout is None else float(g_dropout)
-        self.seed = int(seed)
-        self.fuse = bool(fuse_real_fake)
-        self.hyp = dict(lr_d=lr_d, lr_g=lr_g, wd=weight_decay, b1=betas[0], b2=betas[1], eps=eps)
-        self.clip_d, self.clip_g = clip_d, clip_g
-        self.dp_chunks = 3  # pieces of the D / G backward whose gradient exchange overlaps the remaining backward
-        self.compress_map = bool(compress_mapping_grad)
-        self._want_shard_map = bool(shard_mapping_update)
-        if self._want_shard_map and (self.compress_map or clip_g is not None):
+        self.B, self.kind = int(o["batch"]), LOSS_KINDS[loss]
+        self.clip_d, self.clip_g = o["clip_d"], o["clip_g"]
+        self.compress_map, self._want_shard_map = bool(o["compress_mapping_grad"]), bool(o["shard_mapping_update"])
+        if self._want_shard_map and (self.compress_map or self.clip_g is not None):
             raise ValueError("shard_mapping_update excludes compress_mapping_grad and clip_g")
-        self.dense_top = int(bool(dense_top_block))
-        self.gp_w = float(gp_weight)
-        self.gp_loss = torch.zeros(1, dtype=torch.float32, device=self.dev)
-        self.gp_epsilon: Optional[torch.Tensor] = None  # tests: a fixed epsilon [B,1,1,1] instead of torch.rand
+        fp8 = bool(getattr(vit, "attention_fp8", False))
         if self.gp_w != 0.0 and two_stream:
             raise ValueError("gp_weight: the gradient penalty runs through torch autograd on one stream and cannot be forked")
-        if self.gp_w != 0.0 and bool(getattr(vit, "attention_fp8", False)):
+        if self.gp_w != 0.0 and fp8:
             # the penalty path (ops2.py) differentiates the bf16 attention kernels: with fp8 operands in the trained network
             # it would penalise a slightly different function than the one being trained
             raise ValueError("gp_weight: the gradient penalty is built on the bf16 attention kernels; switch attention_fp8 off")
-        self.gp_c_call = self.gp_w != 0.0 and not gp_autograd and not bool(getattr(vit, "attention_fp8", False))
-        self.div_w = float(diversity_weight)
-        self.inst_sigma = float(instance_noise)
-        self.external_noise = bool(external_noise)
-        self.two_stream = bool(two_stream)
-        self.div_loss = torch.zeros(1, dtype=torch.float32, device=self.dev)
-        self.clip_scratch = torch.zeros(2, 1 + 1024, dtype=torch.float32, device=self.dev)  # [net][norm, partials]
-        self.pg = process_group
-        self.sync = GradSync(process_group, self.dev, overlap=True, single_rank=exchange_single_rank)
+        d, g = vit._dims, generator._dims
+        if g.T * g.CW != d.C * d.IH * d.IH:
+            raise ValueError("generator output does not match the discriminator's image shape")
+        if two_stream and world > 1:
+            raise ValueError("two_stream is a single-GPU schedule (the data-parallel path overlaps the exchange instead)")
+        if two_stream and self.B % 2:
+            raise ValueError("two_stream needs an even batch")
+        self.two_stream = two_stream
+        self.fuse = bool(o["fuse_real_fake"]) and not two_stream
+        self.gp_c_call = self.gp_w != 0.0 and not o["gp_autograd"] and not fp8
+        # dropout probabilities: default = what the modules would apply in their current train/eval mode
+        self.p_d = float(vit._dropout_p if vit.training else 0.0) if o["d_dropout"] is None else float(o["d_dropout"])
+        self.p_g = float(generator.dropout_p if generator.training else 0.0) if o["g_dropout"] is None else float(o["g_dropout"])
+        self.hyp = dict(lr_d=o["lr_d"], lr_g=o["lr_g"], wd=o["weight_decay"], b1=o["betas"][0], b2=o["betas"][1], eps=o["eps"])
+        self.dp_chunks = 3  # pieces of the D / G backward whose gradient exchange overlaps the remaining backward
+        self.seed, self.dense_top, self.external_noise = int(o["seed"]), int(bool(o["dense_top_block"])), bool(o["external_noise"])
+        self.div_w, self.inst_sigma = float(o["diversity_weight"]), float(o["instance_noise"])
+        self.pg, self._single_rank = pg, o["exchange_single_rank"]
+        self._want_ctx, self._use_graph = bool(o["concurrent_wgrad"]), bool(o["use_graph"])
+
+    def _carve(self) -> None:
+        """Constructor, part 2: the device check, the exchange, every buffer the step owns - and every SUB-RANGE the step addresses as a
+        view of its buffer, made here once: the step itself slices nothing and computes no pointer."""
+        vit, generator = self.vit, self.gen
+        self.dev = dev = vit._flat.flat.device
+        if dev.type != "cuda" or generator._flat.flat.device != dev:
+            raise RuntimeError("GanEngine: both networks must be on the same cuda device (no CPU fallback)")
+        self.sync = GradSync(self.pg, dev, overlap=True, single_rank=self._single_rank)
         self.world = self.sync.world
-        g_ = generator._dims
+        d, g, B = vit._dims, generator._dims, self.B
         # (a layer that does not divide over the ranks keeps the all-reduce; a one-rank group - `exchange_single_rank` - runs the same calls)
-        self.shard_map = self._want_shard_map and self.sync.active and (g_.T * g_.E * g_.Z) % (4 * self.world) == 0
+        self.shard_map = self._want_shard_map and self.sync.active and (g.T * g.E * g.Z) % (4 * self.world) == 0
         # latent noise drawn on the device (vg_step_inputs): one stream per (seed, rank)
         self._noise_seed = (self.seed * 0x9E3779B97F4A7C15 + 0xD1B54A32D192ED03 * (self.sync.rank + 1)) & 0xFFFFFFFFFFFFFFFF
         # differentiable augmentation (vg_diffaug_fwd): its own stream per (seed, rank), apart from the latent noise's
         self._aug_seed = (self._noise_seed ^ 0xA0761D6478BD642F) & 0xFFFFFFFFFFFFFFFF
-        d, g = vit._dims, generator._dims
-        if g.T * g.CW != d.C * d.IH * d.IH:
-            raise ValueError("generator output does not match the discriminator's image shape")
         L = _lib.lib()
-        B, dev = self.B, self.dev
-        if self.two_stream:
-            if self.world > 1:
-                raise ValueError("two_stream is a single-GPU schedule (the data-parallel path overlaps the exchange instead)")
-            if B % 2:
-                raise ValueError("two_stream needs an even batch")
-            self.fuse = False
+        f32 = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)  # noqa: E731
+        images = lambda n: torch.empty(n, d.C, d.IH, d.IH, dtype=torch.bfloat16, device=dev)  # noqa: E731
+        self.gp_loss, self.div_loss = f32(1), f32(1)
+        self.gp_epsilon: Optional[torch.Tensor] = None  # tests: a fixed epsilon [B,1,1,1] instead of torch.rand
+        self.clip_scratch = f32(2, 1 + 1024)  # [net][norm, partials]
+        self.clip_slot = tuple(self.clip_scratch)
         nD = 4 * B if self.bcr else (2 * B if self.fuse else B)
-        self.Kc = d.Kc
         self.ws_d = torch.empty(L.vg_vit_ws_bytes(C.byref(d), nD), dtype=torch.uint8, device=dev)
         if self.two_stream:  # second chain: its own workspace, gradient buffer and stream
             self.ws_d2 = torch.empty(L.vg_vit_ws_bytes(C.byref(d), B), dtype=torch.uint8, device=dev)
@@ -259,60 +274,91 @@ class GanEngine:
             self.ws_gp = torch.empty(L.vg_vit_penalty_ws_bytes(C.byref(d), B), dtype=torch.uint8, device=dev)
             self.gp_eps = torch.empty(B, dtype=torch.float32, device=dev)
         self.ws_g = torch.empty(L.vg_gen_ws_bytes(C.byref(g), B), dtype=torch.uint8, device=dev)
-        nL = 4 * B if self.bcr else 2 * B  # logit rows of the discriminator's own pass
+        nL, self.Kc = 4 * B if self.bcr else 2 * B, d.Kc  # logit rows of the discriminator's own pass
         if self.bcr:
             # the 4B images of D's pass, [x ; T(x)], in one buffer: x = the (noisy) pair, T(x) = imgs_aug (diffaug) or imgs_bcr - the
             # step's own buffers are views of it, so no copy launch forms the batch
-            self.imgs4 = torch.empty(4 * B, d.C, d.IH, d.IH, dtype=torch.bfloat16, device=dev)
+            self.imgs4 = images(4 * B)
         noisy = self.inst_sigma > 0.0
         # [real ; fake]; the instance noise needs the clean fake behind it (the generator's pass), so then x is imgs_noisy
-        self.imgs = self.imgs4[:2 * B] if self.bcr and not noisy else torch.empty(2 * B, d.C, d.IH, d.IH, dtype=torch.bfloat16, device=dev)
-        self.dfake = torch.empty(B, d.C, d.IH, d.IH, dtype=torch.bfloat16, device=dev)
-        if self.inst_sigma > 0.0:  # noisy copy of [real ; fake] for the D step, and the noise itself (kept for inspection / tests)
+        self.imgs = self.imgs4[:2 * B] if self.bcr and not noisy else images(2 * B)
+        self.dfake = images(B)
+        self.img_numel = self.dfake[0].numel()
+        self.x = self.imgs  # the pair D's own step is given
+        if noisy:  # noisy copy of [real ; fake] for the D step, and the noise itself (kept for inspection / tests)
             self.inoise = torch.empty(2 * B, d.C, d.IH, d.IH, dtype=torch.float32, device=dev)
-            self.imgs_noisy = self.imgs4[:2 * B] if self.bcr else torch.empty_like(self.imgs)
+            self.x = self.imgs_noisy = self.imgs4[:2 * B] if self.bcr else torch.empty_like(self.imgs)
+            whole = (self.imgs, self.inoise, self.imgs_noisy)  # (clean, noise, noisy): the step's one part, or the two chains' halves
+            self.noise_parts = [tuple(t[:B] for t in whole), tuple(t[B:] for t in whole)] if self.two_stream else [whole]
         if self.aug:
             # D step: imgs_aug = T_1(D's input pair).  Generator pass: imgs_aug[:B] = T_2(fake), imgs_aug[B:] = dL/d T_2(fake)
             self.imgs_aug = self.imgs4[2 * B:] if self.bcr else torch.empty_like(self.imgs)
-            self.aug_params = {"d": torch.zeros(2 * B, 8, dtype=torch.float32, device=dev),  # (b, s, k, tx, ty, cx, cy, policy) per row
-                               "g": torch.zeros(B, 8, dtype=torch.float32, device=dev)}
+            self.aug_params = {"d": f32(2 * B, 8), "g": f32(B, 8)}  # (b, s, k, tx, ty, cx, cy, policy) per row
         if self.bcr_policy:  # T_c(x), site 2
             self.imgs_bcr = self.imgs4[2 * B:]
-            self.aug_params = {"c": torch.zeros(2 * B, 8, dtype=torch.float32, device=dev)}
+            self.aug_params = {"c": f32(2 * B, 8)}
         if self.bcr:
-            self.bcr_losses = torch.zeros(2, dtype=torch.float32, device=dev)  # the unweighted means: real, fake
-        self.div_scratch = torch.zeros((d.C * d.IH * d.IH + 15) // 16, dtype=torch.float32, device=dev)
-        self.logits = torch.empty(nL, d.Kc, dtype=torch.float32, device=dev)
-        self.dlogits = torch.empty(nL, d.Kc, dtype=torch.float32, device=dev)
+            self.bcr_losses = f32(2)  # the unweighted means: real, fake
+        self.div_scratch = f32((d.C * d.IH * d.IH + 15) // 16)
+        rows = lambda n: torch.empty(n, d.Kc, dtype=torch.float32, device=dev)  # noqa: E731
+        self.logits, self.dlogits = rows(nL), rows(nL)
         # (p, acc_sign, acc_count, r_last) of include/vitgan_hip.h, vg_ada_update: element 0 is the gated kernels' prob_dev
-        self.ada_state: Optional[torch.Tensor] = None
-        if self.gated:
-            self.ada_state = torch.tensor([self.aug_p0, 0.0, 0.0, 0.0], dtype=torch.float32, device=dev)
+        self.ada_state: Optional[torch.Tensor] = torch.tensor([self.aug_p0, 0.0, 0.0, 0.0], dtype=torch.float32, device=dev) if self.gated else None
         if self.bcr or self.ada:  # the generator's pass gets rows of its own, so ``logits`` still holds D's whole pass after the step
-            self.logits_g, self.dlogits_g = torch.empty(B, d.Kc, dtype=torch.float32, device=dev), torch.empty(B, d.Kc, dtype=torch.float32, device=dev)
+            self.logits_g, self.dlogits_g = rows(B), rows(B)
         self.z = torch.empty(B, g.Z, dtype=torch.float32, device=dev)
-        self.losses = torch.zeros(3, dtype=torch.float32, device=dev)  # d_real, d_fake, g
+        self.losses = f32(3)  # d_real, d_fake, g
         self.step_t = torch.zeros(1, dtype=torch.int32, device=dev)
         fd, fg = vit._flat, generator._flat
         self.m_d, self.v_d = torch.zeros_like(fd.flat), torch.zeros_like(fd.flat)
         self.m_g, self.v_g = torch.zeros_like(fg.flat), torch.zeros_like(fg.flat)
         # the generator's averaged weights (a copy of the master until the first step, which copies again: see ema_decay)
         self.ema_g: Optional[torch.Tensor] = fg.flat.detach().clone() if self.ema_decay > 0.0 else None
+        # ---- the views: what each pass reads and writes, chosen here once
+        halves = lambda t: (t[:B], t[B:2 * B])  # noqa: E731
+        self.fake = self.imgs[B:]
+        self.loss_slot = tuple(self.losses[i:i + 1] for i in range(3))
+        self.d_in = self.imgs_aug if self.aug else self.x  # what D's own pass, and the penalty, see
+        self.d_in_half, self.lg_half, self.dlg_half = halves(self.d_in), halves(self.logits), halves(self.dlogits)
+        if self.bcr:
+            # ONE pass over [x ; T(x)]: rows [0, 2B) the clean pair, rows [2B, 4B) its transform.  The adversarial rows are T_1(x) with
+            # diffaug and x without it; the consistency loss adds to their gradient and writes the partner rows' (every element)
+            self.cr_rows = (self.logits[:2 * B], self.logits[2 * B:], self.dlogits[:2 * B], self.dlogits[2 * B:])  # D(x), D(T(x)), and their gradients
+            self.d_pass = (4 * B, self.imgs4) + (self.cr_rows[1::2] if self.aug else self.cr_rows[0::2])
+        else:
+            self.d_pass = (2 * B, self.d_in, self.logits, self.dlogits)  # (images, input, adversarial logits, their gradient)
+        # the generator's pass through D: D sees T_2(fake) (site 1) under diffaug, its input gradient goes back through the adjoint
+        self.g_in, self.g_dimg = (self.imgs_aug[:B], self.imgs_aug[B:]) if self.aug else (self.fake, self.dfake)
+        self.g_rows = (self.logits_g, self.dlogits_g) if self.bcr or self.ada else (self.lg_half[0], self.dlg_half[0])
+        if self.two_stream:  # the generator's pass as two half-batches: (fake rows, logits, their gradient, dfake rows) of each chain
+            h = B // 2
+            self.g_half = [tuple(t[i * h:(i + 1) * h] for t in (self.fake, self.logits, self.dlogits, self.dfake)) for i in (0, 1)]
+        # AdamW's ranges: a whole network, or with the mapping Linear sharded the three pieces of the generator and the layer itself
+        cut = lambda lo, hi, ema=self.ema_g: self._range(fg, self.m_g, self.v_g, ema, lo, hi)  # noqa: E731
+        self.r_d, self.r_g = self._range(fd, self.m_d, self.v_d, None, 0, fd.total), cut(0, fg.total)
+        if self.shard_map:
+            w0, w1 = self._map_range()
+            a, b = self.sync.share(w0, w1)
+            self.r_g_pieces, self.r_g_map = (cut(0, w0), cut(a, b, None), cut(w1, fg.total)), cut(w0, w1)
+
+    def _attach(self) -> None:
+        """Constructor, part 3: what ties the engine to its modules and to the run - the spectral state, the shadows, the
+        load_state_dict hooks, the graph flags."""
+        vit, fd, fg = self.vit, self.vit._flat, self.gen._flat
         self._ema_from = self.ema_start  # the kernels' ema_start (a non-strict load_state_dict without an average moves it)
         self._ema_shadow: Optional[torch.Tensor] = None  # bf16 cast of ema_g for sample(): allocated on first use
-        self._ema_cast_key = None                        # (steps, loads) the cast was made at
-        self._ema_loads = 0
+        self._ema_cast_key, self._ema_loads = None, 0    # (steps, loads) the cast was made at
         self._sample_ws: Optional[torch.Tensor] = None
         self.spec: Optional[SpectralState] = None
         if self.spectral_norm:
-            keys = vit_matrix_keys(d.L, self.spectral_norm)
+            keys = vit_matrix_keys(vit._dims.L, self.spectral_norm)
             ent = [(fd.slots[k][0], fd.slots[k][1][0], flat.numel(fd.slots[k][1][1:])) for k in keys]
-            self.spec = SpectralState(ent, fd.total, dev, names=keys)
+            self.spec = SpectralState(ent, fd.total, self.dev, names=keys)
             self.spec.measure(fd.flat)
             fd.spectral = self.spec  # from here on every refresh_shadow() of the discriminator writes the normalised cast
         fd.refresh_shadow()
         fg.refresh_shadow()
-        self.ctx = _lib.context() if concurrent_wgrad else None
+        self.ctx = _lib.context() if self._want_ctx else None
         # a load_state_dict into either network (directly or through a container such as ViTGAN) copies into the flat
         # master buffers in place: refresh the bf16 shadows the GEMMs read, or the next step runs on stale weights
         # (the hook holds the engine weakly: a strong reference from the module would keep every engine ever built on it -
@@ -323,21 +369,18 @@ class GanEngine:
             eng = me()
             if eng is not None:
                 eng.sync_from_modules()
-        self._hooks = [m.register_load_state_dict_post_hook(_hook) for m in (vit, generator)]
-        self.steps = 0
-        self._graph = None
-        self._use_graph = bool(use_graph)
+        self._hooks = [m.register_load_state_dict_post_hook(_hook) for m in (vit, self.gen)]
+        self.steps, self._graph = 0, None
         self.graph_fallback_reason: Optional[str] = None
         if self._use_graph and self.sync.active:
-            backend = dist.get_backend(process_group)
+            backend = dist.get_backend(self.pg)
             if backend != "nccl":
-                self._graph_fallback(f"process-group backend '{backend}' cannot be captured in a hipGraph (only nccl = RCCL can)")
+                self._graph_fallback(f"process-group backend '{backend}' cannot be captured in a hipGraph (only nccl = RCCL can)", stacklevel=4)
 
-    def _graph_fallback(self, reason: str) -> None:
-        self._use_graph = False
-        self._graph = None
+    def _graph_fallback(self, reason: str, stacklevel: int = 3) -> None:
+        self._use_graph, self._graph = False, None
         self.graph_fallback_reason = reason
-        warnings.warn(f"GanEngine: hipGraph replay was requested but the step runs EAGER: {reason}", RuntimeWarning, stacklevel=3)
+        warnings.warn(f"GanEngine: hipGraph replay was requested but the step runs EAGER: {reason}", RuntimeWarning, stacklevel=stacklevel)
 
     @property
     def graph_active(self) -> bool:
@@ -348,8 +391,7 @@ class GanEngine:
         """Detach from the modules (load_state_dict hooks) and drop the captured graph and workspaces."""
         for h in self._hooks:
             h.remove()
-        self._hooks = []
-        self._graph = None
+        self._hooks, self._graph = [], None
         fd = self.vit._flat
         if getattr(self, "spec", None) is not None and fd.spectral is self.spec:
             fd.spectral = None  # the modules hold the raw weights again: export effective_state_dict() first
@@ -369,46 +411,125 @@ class GanEngine:
         mk = lambda i, g=None, ctx=True: _lib.VgVitNet(self.vit._dims, fd.flat.data_ptr(), fd.shadow.data_ptr(),  # noqa: E731
                                                        (fd.grad if g is None else g).data_ptr(), self.p_d, self.seed * 8 + i, step_ptr,
                                                        self.ctx if ctx else None, int(self.vit.attention_fp8), self.dense_top)
+        tab = self.gen.fourier_table
+        ng = _lib.VgGenNet(self.gen._dims, fg.flat.data_ptr(), fg.shadow.data_ptr(), fg.grad.data_ptr(), self.p_g, self.seed * 8 + 7, step_ptr,
+                           None if tab is None else tab.data_ptr())
         if self.two_stream:  # chains run side by side: no third stream inside a pass; the fake chain accumulates into grad2
-            return (mk(0, ctx=False), mk(1, self.grad2, ctx=False), mk(2, ctx=False), mk(3, ctx=False)), self._gen_net(step_ptr)
-        return (mk(0), mk(1), mk(2)), self._gen_net(step_ptr)
+            return (mk(0, ctx=False), mk(1, self.grad2, ctx=False), mk(2, ctx=False), mk(3, ctx=False)), ng
+        return (mk(0), mk(1), mk(2)), ng
 
-    def _gen_net(self, step_ptr):
-        fg, tab = self.gen._flat, self.gen.fourier_table
-        return _lib.VgGenNet(self.gen._dims, fg.flat.data_ptr(), fg.shadow.data_ptr(), fg.grad.data_ptr(), self.p_g, self.seed * 8 + 7, step_ptr,
-                             None if tab is None else tab.data_ptr())
+    # ---- the helpers every schedule is written in: one call site per job
+    def _d_forward(self, net, n: int, src, ws, logits, st) -> None:
+        _call("vg_vit_forward", C.byref(net), n, _p(src), 1, _p(ws), _p(logits), st)
 
-    def _d_backward(self, nd, n_img: int, dl, want_w: int, dimg, st) -> None:
-        """D backward; under data parallelism in ``dp_chunks`` pieces (head + upper blocks first) so that the all-reduce
-        of each finished piece - a contiguous tail of the flat gradient buffer - overlaps the backward of the blocks
-        below it; only the last piece's exchange is exposed."""
-        L = _lib.lib()
-        nL = self.vit._dims.L
-        if not self.sync.active or not want_w:
-            _lib.check(L.vg_vit_backward(C.byref(nd), n_img, _p(self.ws_d), dl, dimg, want_w, st), "vg_vit_backward")
+    def _loss(self, logits, dlogits, n: int, role: int, st) -> None:
+        """The loss of n logit rows in ``role`` (0 = D on real, 1 = D on fake, 2 = the generator's) into the role's slot of ``losses``."""
+        _call("vg_gan_loss", _p(logits), _p(dlogits), _p(self.loss_slot[role]), n * self.Kc, self.kind, role, 1.0, st)
+
+    def _d_backward(self, nd, n_img: int, ws, dl, want_w: int, dimg, st, exchange: bool = True) -> None:
+        """D backward; under data parallelism, when the pass completes D.grad (``exchange``), in ``dp_chunks`` pieces (head + upper
+        blocks first) so that the all-reduce of each finished piece - a contiguous tail of the flat gradient buffer - overlaps the
+        backward of the blocks below it; only the last piece's exchange is exposed."""
+        if not (self.sync.active and want_w and exchange):
+            _call("vg_vit_backward", C.byref(nd), n_img, _p(ws), _p(dl), _p(dimg), want_w, st)
             return
         fd = self.vit._flat
         lay = flat.vit_layout(self.vit._dims)
-        for s0, s1, lo, hi in backward_pieces(nL, self.dp_chunks, lay.layer0, lay.layer_stride, fd.total):
-            _lib.check(L.vg_vit_backward_stages(C.byref(nd), n_img, _p(self.ws_d), dl, dimg, want_w, s0, s1, st), "vg_vit_backward_stages")
+        for s0, s1, lo, hi in backward_pieces(self.vit._dims.L, self.dp_chunks, lay.layer0, lay.layer_stride, fd.total):
+            _call("vg_vit_backward_stages", C.byref(nd), n_img, _p(ws), _p(dl), _p(dimg), want_w, s0, s1, st)
             self.sync.reduce_range(fd.grad, lo, hi)
+
+    def _instance_noise(self, part) -> None:
+        """noisy_real / noisy_fake of training.py:83-90 for one part of the pair (the clean fake stays in ``imgs`` for the generator's pass)"""
+        clean, noise, noisy = part
+        noise.normal_()
+        torch.add(clean.float(), noise, alpha=self.inst_sigma, out=noise)
+        noisy.copy_(noise)
+
+    def _augment(self, src, dst, params, n: int, policy: int, site: int, st) -> None:
+        """T(src) -> dst for n images at an augmentation site of the step: the gated kernel with the device-resident probability when
+        the engine has one (sites 0 and 1: an engine with a probability has no site 2), else the plain call."""
+        _call("vg_diffaug_p_fwd" if self.gated else "vg_diffaug_fwd", _p(src), _p(dst), _p(params), *self._aug_site(n, policy, site, st))
+
+    def _augment_adjoint(self, dy, dx, n: int, policy: int, site: int, st) -> None:
+        """dx = T^T(dy), the transform of ``_augment`` at the same site and step, gated like it."""
+        _call("vg_diffaug_p_bwd" if self.gated else "vg_diffaug_bwd", _p(dy), _p(dx), 0, *self._aug_site(n, policy, site, st))
+
+    def _aug_site(self, n: int, policy: int, site: int, st):
+        """what the four augmentation calls share: geometry, policy, the draw's key, and for the gated ones the probability"""
+        d_ = self.vit._dims
+        return (n, d_.C, d_.IH, policy, self._aug_seed, site, _p(self.step_t)) + ((_p(self.ada_state), st) if self.gated else (st,))
+
+    def _ada_update(self, logits_real, st) -> None:
+        """The controller on the real rows of the adversarial logits (the first B rows of ``logits_real``); nothing without ADA."""
+        if self.ada:
+            _call("vg_ada_update", _p(logits_real), self.B * self.Kc, _p(self.ada_state), self.ada_target, self.ada_step_per_image,
+                  self.ada_interval, _p(self.step_t), st)
+
+    def _diversity(self, st) -> None:
+        """total_gen_loss = loss + w * diversity_loss(fake_images): its gradient joins dL/d fake; nothing at weight 0."""
+        if self.div_w != 0.0:
+            _call("vg_diversity_loss", _p(self.fake), _p(self.dfake), _p(self.div_loss), _p(self.div_scratch), self.B, self.img_numel, self.div_w, st)
+
+    def _map_range(self):
+        lay, d = flat.gen_layout(self.gen._dims), self.gen._dims
+        return lay.map_w, lay.map_w + d.T * d.E * d.Z
+
+    def _range(self, fp, m, v, ema, lo: int, hi: int):
+        """(master, gradient, m, v, shadow, average or None, elements) of [lo, hi) of a network's flat buffers: AdamW's operands"""
+        return tuple(None if t is None else t[lo:hi] for t in (fp.flat, fp.grad, m, v, fp.shadow, ema)) + (hi - lo,)
+
+    def _adamw_range(self, r, lr, st) -> None:
+        """AdamW on one range (``_range``) - with the weights' moving average in the same pass when the range carries one."""
+        *bufs, ema, n = r
+        if n <= 0:
+            return
+        h = self.hyp
+        tail = (n, lr, h["b1"], h["b2"], h["eps"], h["wd"], 0, _p(self.step_t), 1.0 / self.world)
+        if ema is None:
+            _call("vg_adamw_step", *map(_p, bufs), *tail, st)
+        else:
+            _call("vg_adamw_ema_step", *map(_p, bufs), _p(ema), *tail, self.ema_decay, self._ema_from, st)
+
+    def _adamw(self, r, lr, st, clip=None, slot=0) -> None:
+        """A whole network's optimizer step: the clipping (on the exchanged, global gradient, like clip_grad_norm_ before
+        optimizer.step()), then AdamW on the whole range."""
+        if clip is not None:
+            _call("vg_grad_clip", _p(r[1]), r[-1], 1.0 / self.world, float(clip), _p(self.clip_slot[slot]), st)
+        self._adamw_range(r, lr, st)
+
+    def _adamw_g_sharded(self, st) -> None:
+        """The generator's AdamW with the mapping Linear sharded: the whole buffer but that layer as usual, of the layer this rank's
+        share only; then the updated fp32 master shares to every rank and the layer's bf16 shadow cast from them there (the GEMMs of
+        every rank read the whole shadow; gathering the master, not the shadow, keeps every rank's master current)."""
+        for r in self.r_g_pieces:  # below the layer, this rank's share of it (its average comes from the gathered master), above it
+            self._adamw_range(r, self.hyp["lr_g"], st)
+        w0, w1 = self._map_range()
+        self.sync.all_gather_range(self.gen._flat.flat, w0, w1)
+        self.sync.wait()
+        master, _, _, _, shadow, ema, n = self.r_g_map
+        _call("vg_cast_f32_bf16", _p(master), _p(shadow), n, st)
+        if ema is not None:  # the layer's average from the gathered master: what the fused kernel of a replicated run writes
+            _call("vg_ema_update", _p(ema), _p(master), n, self.ema_decay, self._ema_from, 0, _p(self.step_t), st)
+
+    def gather_master(self) -> None:
+        """A no-op, kept for callers: the sharded update of the mapping Linear all-gathers its fp32 master inside the step, so every
+        rank's master is current after every step.  (It issues no collective, so it is safe on a branch that differs by rank.)"""
 
     def _g_backward(self, ng, st) -> None:
         """G backward; under data parallelism in ``dp_chunks`` pieces like D's: SIREN head + upper blocks first, their
         gradients (a contiguous tail of the flat buffer) are exchanged while the lower blocks still run.  What is left
         exposed is the front of the buffer - learned embedding, mapping Linear, lowest blocks - which only completes
         with the last kernel; its 50 MB mapping-weight part goes over the links as bf16."""
-        L = _lib.lib()
         fg = self.gen._flat
         if not self.sync.active:
-            _lib.check(L.vg_gen_backward(C.byref(ng), self.B, _p(self.ws_g), _p(self.dfake), st), "vg_gen_backward")
+            _call("vg_gen_backward", C.byref(ng), self.B, _p(self.ws_g), _p(self.dfake), st)
             return
         lay = flat.gen_layout(self.gen._dims)
-        d = self.gen._dims
-        for s0, s1, lo, hi in backward_pieces(d.L, self.dp_chunks, lay.layer0, lay.layer_stride, fg.total):
-            _lib.check(L.vg_gen_backward_stages(C.byref(ng), self.B, _p(self.ws_g), _p(self.dfake), s0, s1, st), "vg_gen_backward_stages")
+        for s0, s1, lo, hi in backward_pieces(self.gen._dims.L, self.dp_chunks, lay.layer0, lay.layer_stride, fg.total):
+            _call("vg_gen_backward_stages", C.byref(ng), self.B, _p(self.ws_g), _p(self.dfake), s0, s1, st)
             if lo == 0 and (self.compress_map or self.shard_map):  # [embedding | mapping weight | mapping bias, lowest blocks]
-                w0, w1 = lay.map_w, lay.map_w + d.T * d.E * d.Z
+                w0, w1 = self._map_range()
                 self.sync.reduce_range(fg.grad, 0, w0)
                 if self.shard_map:
                     self.sync.reduce_scatter_range(fg.grad, w0, w1)   # this rank keeps the sum of its share only
@@ -417,79 +538,6 @@ class GanEngine:
                 self.sync.reduce_range(fg.grad, w1, hi)
             else:
                 self.sync.reduce_range(fg.grad, lo, hi)
-
-    def _map_range(self):
-        lay, d = flat.gen_layout(self.gen._dims), self.gen._dims
-        return lay.map_w, lay.map_w + d.T * d.E * d.Z
-
-    def _adamw_g_sharded(self, st) -> None:
-        """The generator's AdamW with the mapping Linear sharded: the whole buffer but that layer as usual, of the layer this rank's
-        share only; then the updated fp32 master shares to every rank and the layer's bf16 shadow cast from them there (the GEMMs of
-        every rank read the whole shadow; gathering the master, not the shadow, keeps every rank's master current)."""
-        fg, h, L = self.gen._flat, self.hyp, _lib.lib()
-        w0, w1 = self._map_range()
-        a, b = self.sync.share(w0, w1)
-
-        def upd(lo, hi, ema=None):
-            if hi <= lo:
-                return
-            off = lambda t, es: C.c_void_p(t.data_ptr() + es * lo)  # noqa: E731
-            if ema is None:
-                _lib.check(L.vg_adamw_step(off(fg.flat, 4), off(fg.grad, 4), off(self.m_g, 4), off(self.v_g, 4), off(fg.shadow, 2), hi - lo,
-                                           self.hyp["lr_g"], h["b1"], h["b2"], h["eps"], h["wd"], 0, _p(self.step_t), 1.0 / self.world, st), "vg_adamw_step")
-            else:
-                _lib.check(L.vg_adamw_ema_step(off(fg.flat, 4), off(fg.grad, 4), off(self.m_g, 4), off(self.v_g, 4), off(fg.shadow, 2), off(ema, 4),
-                                               hi - lo, self.hyp["lr_g"], h["b1"], h["b2"], h["eps"], h["wd"], 0, _p(self.step_t), 1.0 / self.world,
-                                               self.ema_decay, self._ema_from, st), "vg_adamw_ema_step")
-        upd(0, w0, self.ema_g)
-        upd(a, b)
-        upd(w1, fg.total, self.ema_g)
-        self.sync.all_gather_range(fg.flat, w0, w1)
-        self.sync.wait()
-        _lib.check(L.vg_cast_f32_bf16(C.c_void_p(fg.flat.data_ptr() + 4 * w0), C.c_void_p(fg.shadow.data_ptr() + 2 * w0), w1 - w0, st),
-                   "vg_cast_f32_bf16")
-        if self.ema_g is not None:  # the layer's average from the gathered master: what the fused kernel of a replicated run writes
-            _lib.check(L.vg_ema_update(C.c_void_p(self.ema_g.data_ptr() + 4 * w0), C.c_void_p(fg.flat.data_ptr() + 4 * w0), w1 - w0,
-                                       self.ema_decay, self._ema_from, 0, _p(self.step_t), st), "vg_ema_update")
-
-    def gather_master(self) -> None:
-        """A no-op, kept for callers: the sharded update of the mapping Linear all-gathers its fp32 master inside the step, so every
-        rank's master is current after every step.  (It issues no collective, so it is safe on a branch that differs by rank.)"""
-
-    def _adamw(self, fp, m, v, lr, st, clip=None, slot=0, ema=None):
-        h = self.hyp
-        if clip is not None:  # on the exchanged (global) gradient, like clip_grad_norm_ before optimizer.step()
-            _lib.check(_lib.lib().vg_grad_clip(_p(fp.grad), fp.total, 1.0 / self.world, float(clip), _p(self.clip_scratch[slot]), st),
-                       "vg_grad_clip")
-        if ema is None:
-            _lib.check(_lib.lib().vg_adamw_step(_p(fp.flat), _p(fp.grad), _p(m), _p(v), _p(fp.shadow), fp.total, lr, h["b1"], h["b2"],
-                                                h["eps"], h["wd"], 0, _p(self.step_t), 1.0 / self.world, st), "vg_adamw_step")
-        else:  # the same update and the weights' moving average in one pass
-            _lib.check(_lib.lib().vg_adamw_ema_step(_p(fp.flat), _p(fp.grad), _p(m), _p(v), _p(fp.shadow), _p(ema), fp.total, lr, h["b1"],
-                                                    h["b2"], h["eps"], h["wd"], 0, _p(self.step_t), 1.0 / self.world, self.ema_decay,
-                                                    self._ema_from, st), "vg_adamw_ema_step")
-
-    def _loss(self, lo, n, role, slot, st):
-        L = _lib.lib()
-        off = 4 * lo * self.Kc
-        _lib.check(L.vg_gan_loss(C.c_void_p(self.logits.data_ptr() + off), C.c_void_p(self.dlogits.data_ptr() + off),
-                                 C.c_void_p(self.losses.data_ptr() + 4 * slot), n * self.Kc, self.kind, role, 1.0, st), "vg_gan_loss")
-
-    def _augment(self, src, dst, params, n: int, site: int, st) -> None:
-        """T(src) -> dst for n images at an augmentation site of the step: the gated kernel with the device-resident probability when
-        the engine has one, else the existing call."""
-        d_, L = self.vit._dims, _lib.lib()
-        if self.gated:
-            _lib.check(L.vg_diffaug_p_fwd(src, dst, params, n, d_.C, d_.IH, self.aug, self._aug_seed, site, _p(self.step_t), _p(self.ada_state), st),
-                       "vg_diffaug_p_fwd")
-        else:
-            _lib.check(L.vg_diffaug_fwd(src, dst, params, n, d_.C, d_.IH, self.aug, self._aug_seed, site, _p(self.step_t), st), "vg_diffaug_fwd")
-
-    def _ada_update(self, logits_real, st) -> None:
-        """The controller on the real rows of the adversarial logits (the first B rows at ``logits_real``); nothing without ADA."""
-        if self.ada:
-            _lib.check(_lib.lib().vg_ada_update(logits_real, self.B * self.Kc, _p(self.ada_state), self.ada_target, self.ada_step_per_image,
-                                                self.ada_interval, _p(self.step_t), st), "vg_ada_update")
 
     @property
     def ada_p(self) -> float:
@@ -502,222 +550,182 @@ class GanEngine:
         return float(self._need_ada("ada_rt")[3])
 
     def _need_ada(self, what: str) -> torch.Tensor:
-        if self.ada_state is None:
-            raise RuntimeError(f"{what}: this engine holds no augmentation probability (built without aug_p / ada_target)")
-        return self.ada_state
+        return self._need(self.ada_state, f"{what}: this engine holds no augmentation probability (built without aug_p / ada_target)")
+
+    @staticmethod
+    def _need(t, complaint: str) -> torch.Tensor:
+        if t is None:
+            raise RuntimeError(complaint)
+        return t
 
     def _ada_options(self):
         return None if not self.gated else (self.aug_p0, self.ada_target, self.ada_interval, self.ada_kimg)
 
+    def _bcr_options(self):
+        return None if not self.bcr else (self.bcr_w[0], self.bcr_w[1], self.bcr_policy)
+
+    # ---- the schedules
     def _enqueue_two_stream(self) -> None:
         """The step as two concurrent chains (see ``two_stream``).  Everything is enqueued from this thread; the second chain
         forks from and joins the current stream through events, so the whole step is still one capturable graph."""
-        L, B = _lib.lib(), self.B
+        B = self.B
         s0, s1 = torch.cuda.current_stream(), self.side
         st0, st1 = C.c_void_p(s0.cuda_stream), C.c_void_p(s1.cuda_stream)
         (nd_a, nd_b, nd_c, nd_d), ng = self._nets()
         fd, fg = self.vit._flat, self.gen._flat
-        img_bytes = self.imgs[0].numel() * 2
-        Kc4 = 4 * self.Kc
-        off_img = lambda t, n: C.c_void_p(t.data_ptr() + n * img_bytes)  # noqa: E731
-        off_log = lambda t, n: C.c_void_p(t.data_ptr() + n * Kc4)       # noqa: E731
-        fake_ptr = off_img(self.imgs, B)
-        _lib.check(L.vg_zero_tick(_p(fd.grad), fd.total, _p(self.step_t), st0), "vg_zero_tick")
+        noisy = self.inst_sigma > 0.0
+        _call("vg_zero_tick", _p(fd.grad), fd.total, _p(self.step_t), st0)
         self.grad2.zero_()
-        d_in = self.imgs
         s1.wait_stream(s0)
         # chain 1 (side stream): G forward, then D on the fake batch (weight gradients into grad2)
         with torch.cuda.stream(s1):
-            _lib.check(L.vg_gen_forward(C.byref(ng), B, _p(self.z), _p(self.ws_g), fake_ptr, st1), "vg_gen_forward")
-            if self.inst_sigma > 0.0:
-                self.inoise[B:].normal_()
-                torch.add(self.imgs[B:].float(), self.inoise[B:], alpha=self.inst_sigma, out=self.inoise[B:])
-                self.imgs_noisy[B:].copy_(self.inoise[B:])
-            src = off_img(self.imgs_noisy if self.inst_sigma > 0.0 else self.imgs, B)
-            _lib.check(L.vg_vit_forward(C.byref(nd_b), B, src, 1, _p(self.ws_d2), off_log(self.logits, B), st1), "vg_vit_forward")
-            _lib.check(L.vg_gan_loss(off_log(self.logits, B), off_log(self.dlogits, B), C.c_void_p(self.losses.data_ptr() + 4), B * self.Kc,
-                                     self.kind, 1, 1.0, st1), "vg_gan_loss")
-            _lib.check(L.vg_vit_backward(C.byref(nd_b), B, _p(self.ws_d2), off_log(self.dlogits, B), None, 1, st1), "vg_vit_backward")
+            _call("vg_gen_forward", C.byref(ng), B, _p(self.z), _p(self.ws_g), _p(self.fake), st1)
+            if noisy:
+                self._instance_noise(self.noise_parts[1])
+            self._d_forward(nd_b, B, self.d_in_half[1], self.ws_d2, self.lg_half[1], st1)
+            self._loss(self.lg_half[1], self.dlg_half[1], B, 1, st1)
+            self._d_backward(nd_b, B, self.ws_d2, self.dlg_half[1], 1, None, st1, exchange=False)
         # chain 0 (this stream): D on the real batch
-        if self.inst_sigma > 0.0:
-            self.inoise[:B].normal_()
-            torch.add(self.imgs[:B].float(), self.inoise[:B], alpha=self.inst_sigma, out=self.inoise[:B])
-            self.imgs_noisy[:B].copy_(self.inoise[:B])
-            d_in = self.imgs_noisy
-        _lib.check(L.vg_vit_forward(C.byref(nd_a), B, _p(d_in), 1, _p(self.ws_d), _p(self.logits), st0), "vg_vit_forward")
-        self._loss(0, B, 0, 0, st0)
-        _lib.check(L.vg_vit_backward(C.byref(nd_a), B, _p(self.ws_d), _p(self.dlogits), None, 1, st0), "vg_vit_backward")
+        if noisy:
+            self._instance_noise(self.noise_parts[0])
+        self._d_forward(nd_a, B, self.d_in_half[0], self.ws_d, self.lg_half[0], st0)
+        self._loss(self.lg_half[0], self.dlg_half[0], B, 0, st0)
+        self._d_backward(nd_a, B, self.ws_d, self.dlg_half[0], 1, None, st0, exchange=False)
         s0.wait_stream(s1)
         fd.grad.add_(self.grad2)  # the two passes accumulate into one .grad in the reference (training.py:184,194)
-        self._adamw(fd, self.m_d, self.v_d, self.hyp["lr_d"], st0, self.clip_d, 0)
+        self._adamw(self.r_d, self.hyp["lr_d"], st0, self.clip_d, 0)
         fg.grad.zero_()
         # generator's pass through the updated D: two half-batches side by side (no weight gradients, nothing shared)
         h = B // 2
+        (img0, lg0, dlg0, df0), (img1, lg1, dlg1, df1) = self.g_half
         s1.wait_stream(s0)
         with torch.cuda.stream(s1):
-            _lib.check(L.vg_vit_forward(C.byref(nd_d), h, off_img(self.imgs, B + h), 1, _p(self.ws_d2), off_log(self.logits, h), st1), "vg_vit_forward")
-        _lib.check(L.vg_vit_forward(C.byref(nd_c), h, fake_ptr, 1, _p(self.ws_d), _p(self.logits), st0), "vg_vit_forward")
+            self._d_forward(nd_d, h, img1, self.ws_d2, lg1, st1)
+        self._d_forward(nd_c, h, img0, self.ws_d, lg0, st0)
         s0.wait_stream(s1)
-        self._loss(0, B, 2, 2, st0)  # one mean over the whole batch
+        self._loss(*self.g_rows, B, 2, st0)  # one mean over the whole batch
         s1.wait_stream(s0)
         with torch.cuda.stream(s1):
-            _lib.check(L.vg_vit_backward(C.byref(nd_d), h, _p(self.ws_d2), off_log(self.dlogits, h), off_img(self.dfake, h), 0, st1), "vg_vit_backward")
-        _lib.check(L.vg_vit_backward(C.byref(nd_c), h, _p(self.ws_d), _p(self.dlogits), _p(self.dfake), 0, st0), "vg_vit_backward")
+            self._d_backward(nd_d, h, self.ws_d2, dlg1, 0, df1, st1)
+        self._d_backward(nd_c, h, self.ws_d, dlg0, 0, df0, st0)
         s0.wait_stream(s1)
-        if self.div_w != 0.0:
-            Dn = self.dfake[0].numel()
-            _lib.check(L.vg_diversity_loss(fake_ptr, _p(self.dfake), _p(self.div_loss), _p(self.div_scratch), B, Dn, self.div_w, st0),
-                       "vg_diversity_loss")
-        _lib.check(L.vg_gen_backward(C.byref(ng), B, _p(self.ws_g), _p(self.dfake), st0), "vg_gen_backward")
-        self._adamw(fg, self.m_g, self.v_g, self.hyp["lr_g"], st0, self.clip_g, 1, self.ema_g)
+        self._diversity(st0)
+        _call("vg_gen_backward", C.byref(ng), B, _p(self.ws_g), _p(self.dfake), st0)
+        self._adamw(self.r_g, self.hyp["lr_g"], st0, self.clip_g, 1)
 
     def _inputs(self, real: torch.Tensor) -> None:
         """The step's inputs, ONE launch in front of the step proper (and outside its hipGraph, so it reads the caller's tensor
         directly - no staging copy): imgs[:B] = bf16(real), and unless the caller supplies it, the latent batch z ~ N(0, 1)
         (construct_noise(), training.py:35-42 / gan.py:231-232), counter-based on (seed, rank, steps done so far)."""
-        B = self.B
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         # the kernel dereferences the caller's pointer with 16-byte loads on THIS engine's device: anything else (another GPU's
         # tensor, an unaligned view) goes through torch's copy, which handles it
         direct = (real.dtype == torch.float32 and real.is_contiguous() and real[0].numel() == self.imgs[0].numel() and real.numel() % 4 == 0
                   and real.device == self.imgs.device and real.data_ptr() % 16 == 0)
         if not direct:
-            self.imgs[:B].copy_(real)
+            self.imgs[:self.B].copy_(real)
         want_z = not self.external_noise
         if direct or want_z:
-            _lib.check(_lib.lib().vg_step_inputs(_p(real) if direct else None, _p(self.imgs), real.numel() if direct else 0,
-                                                 _p(self.z) if want_z else None, self.z.numel() if want_z else 0, self._noise_seed,
-                                                 _p(self.step_t), st), "vg_step_inputs")
+            _call("vg_step_inputs", _p(real) if direct else None, _p(self.imgs), real.numel() if direct else 0,
+                  _p(self.z) if want_z else None, self.z.numel() if want_z else 0, self._noise_seed, _p(self.step_t), st)
 
-    def _enqueue(self, real: torch.Tensor) -> None:
-        """Enqueue one full step on the current stream (no host sync)."""
-        self._inputs(real)
-        self._enqueue_body()
-
-    def _enqueue_body(self) -> None:
-        """Everything of a step behind its inputs (``_inputs``): what the hipGraph captures."""
-        if self.two_stream:
-            return self._enqueue_two_stream()
-        L, B = _lib.lib(), self.B
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        (nd, nd_b, nd_c), ng = self._nets()
-        fd, fg = self.vit._flat, self.gen._flat
-        d_ = self.vit._dims
-        img_bytes = self.imgs[0].numel() * 2
-        fake_ptr = C.c_void_p(self.imgs.data_ptr() + B * img_bytes)
-        # gan.discriminator.zero_grad() (training.py:177) and the device step counter += 1, one launch
-        _lib.check(L.vg_zero_tick(_p(fd.grad), fd.total, _p(self.step_t), st), "vg_zero_tick")
-        _lib.check(L.vg_gen_forward(C.byref(ng), B, _p(self.z), _p(self.ws_g), fake_ptr, st), "vg_gen_forward")
-        d_in = self.imgs
-        if self.inst_sigma > 0.0:  # noisy_real / noisy_fake of training.py:83-90 (the clean fake stays in self.imgs for pass C)
-            self.inoise.normal_()
-            torch.add(self.imgs.float(), self.inoise, alpha=self.inst_sigma, out=self.inoise)
-            self.imgs_noisy.copy_(self.inoise)
-            d_in = self.imgs_noisy
-        if self.aug:  # D sees T_1([real ; fake]) (site 0), and so does the penalty below
-            self._augment(_p(d_in), _p(self.imgs_aug), _p(self.aug_params["d"]), 2 * B, 0, st)
-            d_in = self.imgs_aug
-        if self.bcr_policy:  # the consistency partner T_c(x) (site 2) behind x in the 4B buffer; the losses and the penalty stay on x
-            _lib.check(L.vg_diffaug_fwd(_p(d_in), _p(self.imgs_bcr), _p(self.aug_params["c"]), 2 * B, d_.C, d_.IH, self.bcr_policy,
-                                        self._aug_seed, 2, _p(self.step_t), st), "vg_diffaug_fwd")
-        if self.gp_c_call:  # gradient_penalty(D, noisy_real, noisy_fake) joins the D loss (training.py:101-106): one C call
+    def _penalty(self, st) -> None:
+        """gradient_penalty(D, noisy_real, noisy_fake) joins the D loss (training.py:101-106), on what D's own pass sees."""
+        fd = self.vit._flat
+        real, fake = self.d_in_half
+        if self.gp_c_call:  # one C call
             if self.gp_epsilon is not None:
                 torch.add(self.gp_epsilon.reshape(-1).float(), 0.0, out=self.gp_eps)  # (an elementwise kernel, not a D2D copy: no memcpy / memset nodes in the captured step)
             else:
                 self.gp_eps.uniform_()  # epsilon = torch.rand(B, 1, 1, 1), utils.py:129
             pnet = _lib.VgVitNet(self.vit._dims, fd.flat.data_ptr(), fd.shadow.data_ptr(), fd.grad.data_ptr(), self.p_d, self.seed * 8 + 3,
                                  self.step_t.data_ptr(), None, 0, 1)
-            _lib.check(L.vg_vit_penalty(C.byref(pnet), B, _p(d_in), C.c_void_p(d_in.data_ptr() + B * img_bytes), _p(self.gp_eps), self.gp_w,
-                                        _p(self.ws_d), _p(self.ws_gp), _p(self.gp_loss), st), "vg_vit_penalty")
-        elif self.gp_w != 0.0:
+            _call("vg_vit_penalty", C.byref(pnet), self.B, _p(real), _p(fake), _p(self.gp_eps), self.gp_w, _p(self.ws_d), _p(self.ws_gp),
+                  _p(self.gp_loss), st)
+        else:
+            from . import ops2
             from .penalty import gradient_penalty
             fd.attach_grads()
-            disc = self.vit
-            from . import ops2
-            pen = gradient_penalty(disc, d_in[:B], d_in[B:], epsilon=self.gp_epsilon)
+            pen = gradient_penalty(self.vit, real, fake, epsilon=self.gp_epsilon)
             with ops2.deferred_weight_grads(fd.grad):  # the block Linears' weight gradients: grouped per block, straight into the flat buffer
                 (self.gp_w * pen).backward()   # the rest accumulates into the same buffer through the parameters' .grad (views of it)
             self.gp_loss.copy_(pen.detach().reshape(1))
-        if self.bcr:
-            # ONE pass over [x ; T(x)]: rows [0, 2B) the clean pair, rows [2B, 4B) its transform.  The adversarial rows are T_1(x) with
-            # diffaug and x without it; the consistency loss adds to their gradient and writes the partner rows' (every element)
-            adv_a = int(bool(self.aug))
-            half = 4 * 2 * B * self.Kc  # bytes of 2B logit rows
-            lx, la = _p(self.logits), C.c_void_p(self.logits.data_ptr() + half)
-            dx, da = _p(self.dlogits), C.c_void_p(self.dlogits.data_ptr() + half)
-            _lib.check(L.vg_vit_forward(C.byref(nd), 4 * B, _p(self.imgs4), 1, _p(self.ws_d), lx, st), "vg_vit_forward")
-            _lib.check(L.vg_gan_loss_pair(la if adv_a else lx, da if adv_a else dx, _p(self.losses), B * self.Kc, 0, B * self.Kc, 1, self.kind,
-                                          1.0, st), "vg_gan_loss_pair")
-            self._ada_update(la if adv_a else lx, st)
-            _lib.check(L.vg_bcr_loss(lx, la, dx, da, _p(self.bcr_losses), B, B, self.Kc, self.bcr_w[0], self.bcr_w[1], 1 - adv_a, adv_a, 1.0, st),
-                       "vg_bcr_loss")
-            self._d_backward(nd, 4 * B, dx, 1, None, st)
-        elif self.fuse:
-            _lib.check(L.vg_vit_forward(C.byref(nd), 2 * B, _p(d_in), 1, _p(self.ws_d), _p(self.logits), st), "vg_vit_forward")
-            # D(real) -> slot 0, D(fake) -> slot 1: both halves of the fused pass in one launch
-            _lib.check(_lib.lib().vg_gan_loss_pair(_p(self.logits), _p(self.dlogits), _p(self.losses), B * self.Kc, 0, B * self.Kc, 1, self.kind,
-                                                   1.0, st), "vg_gan_loss_pair")
-            self._ada_update(_p(self.logits), st)
-            self._d_backward(nd, 2 * B, _p(self.dlogits), 1, None, st)
-        else:
-            for half, role in ((0, 0), (1, 1)):
-                src = C.c_void_p(d_in.data_ptr() + half * B * img_bytes)
-                lg = C.c_void_p(self.logits.data_ptr() + 4 * half * B * self.Kc)
-                dl = C.c_void_p(self.dlogits.data_ptr() + 4 * half * B * self.Kc)
-                net = nd if half == 0 else nd_b
-                _lib.check(L.vg_vit_forward(C.byref(net), B, src, 1, _p(self.ws_d), lg, st), "vg_vit_forward")
-                self._loss(half * B, B, role, role, st)
+
+    def _enqueue_body(self) -> None:
+        """Everything of a step behind its inputs (``_inputs``): what the hipGraph captures."""
+        if self.two_stream:
+            return self._enqueue_two_stream()
+        B = self.B
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        (nd, nd_b, nd_c), ng = self._nets()
+        fd, fg = self.vit._flat, self.gen._flat
+        # gan.discriminator.zero_grad() (training.py:177) and the device step counter += 1, one launch
+        _call("vg_zero_tick", _p(fd.grad), fd.total, _p(self.step_t), st)
+        _call("vg_gen_forward", C.byref(ng), B, _p(self.z), _p(self.ws_g), _p(self.fake), st)
+        if self.inst_sigma > 0.0:
+            self._instance_noise(self.noise_parts[0])
+        if self.aug:  # D sees T_1([real ; fake]) (site 0), and so does the penalty below
+            self._augment(self.x, self.imgs_aug, self.aug_params["d"], 2 * B, self.aug, 0, st)
+        if self.bcr_policy:  # the consistency partner T_c(x) (site 2) behind x in the 4B buffer; the losses and the penalty stay on x
+            self._augment(self.d_in, self.imgs_bcr, self.aug_params["c"], 2 * B, self.bcr_policy, 2, st)
+        if self.gp_w != 0.0:
+            self._penalty(st)
+        if self.fuse:  # D's own pass, real and fake rows in one batch (with bCR: the pair and its transform, 4B images)
+            n, src, adv, dadv = self.d_pass
+            self._d_forward(nd, n, src, self.ws_d, self.logits, st)
+            # D(real) -> slot 0, D(fake) -> slot 1: both halves of the adversarial rows in one launch
+            _call("vg_gan_loss_pair", _p(adv), _p(dadv), _p(self.losses), B * self.Kc, 0, B * self.Kc, 1, self.kind, 1.0, st)
+            self._ada_update(adv, st)
+            if self.bcr:
+                _call("vg_bcr_loss", *map(_p, self.cr_rows), _p(self.bcr_losses), B, B, self.Kc, self.bcr_w[0], self.bcr_w[1],
+                      int(not self.aug), int(bool(self.aug)), 1.0, st)
+            self._d_backward(nd, n, self.ws_d, self.dlogits, 1, None, st)
+        else:  # the reference's two passes; the second one finishes D.grad: exchange it as it completes
+            for half, net in ((0, nd), (1, nd_b)):
+                self._d_forward(net, B, self.d_in_half[half], self.ws_d, self.lg_half[half], st)
+                self._loss(self.lg_half[half], self.dlg_half[half], B, half, st)
                 if half == 0:
-                    self._ada_update(lg, st)
-                    _lib.check(L.vg_vit_backward(C.byref(net), B, _p(self.ws_d), dl, None, 1, st), "vg_vit_backward")
-                else:  # second pass finishes D.grad: exchange it as it completes
-                    self._d_backward(net, B, dl, 1, None, st)
+                    self._ada_update(self.lg_half[0], st)
+                self._d_backward(net, B, self.ws_d, self.dlg_half[half], 1, None, st, exchange=half == 1)
         self.sync.wait()
         if self.spec is not None:  # dL/dW_eff -> dL/dW on the exchanged total of both passes and the penalty (the map is linear)
             self.spec.project(fd.grad, fd.flat, st)
-        self._adamw(fd, self.m_d, self.v_d, self.hyp["lr_d"], st, self.clip_d, 0)
+        self._adamw(self.r_d, self.hyp["lr_d"], st, self.clip_d, 0)
         if self.spec is not None:  # one power iteration on the updated master; AdamW's plain cast of the normalised ranges is overwritten
             self.spec.update(fd.flat, fd.shadow, True, st)
         fg.grad.zero_()            # gan.generator.zero_grad(), training.py:199
-        g_in, g_dimg = fake_ptr, _p(self.dfake)
         if self.aug:  # D sees T_2(fake) (site 1); its input gradient goes back through the adjoint into dfake
-            g_in, g_dimg = _p(self.imgs_aug), C.c_void_p(self.imgs_aug.data_ptr() + B * img_bytes)
-            self._augment(fake_ptr, g_in, _p(self.aug_params["g"]), B, 1, st)
-        if self.bcr or self.ada:
-            _lib.check(L.vg_vit_forward(C.byref(nd_c), B, g_in, 1, _p(self.ws_d), _p(self.logits_g), st), "vg_vit_forward")
-            _lib.check(L.vg_gan_loss(_p(self.logits_g), _p(self.dlogits_g), C.c_void_p(self.losses.data_ptr() + 8), B * self.Kc, self.kind, 2, 1.0, st),
-                       "vg_gan_loss")
-            _lib.check(L.vg_vit_backward(C.byref(nd_c), B, _p(self.ws_d), _p(self.dlogits_g), g_dimg, 0, st), "vg_vit_backward")
-        else:
-            _lib.check(L.vg_vit_forward(C.byref(nd_c), B, g_in, 1, _p(self.ws_d), _p(self.logits), st), "vg_vit_forward")
-            self._loss(0, B, 2, 2, st)
-            _lib.check(L.vg_vit_backward(C.byref(nd_c), B, _p(self.ws_d), _p(self.dlogits), g_dimg, 0, st), "vg_vit_backward")
-        if self.aug and self.gated:
-            _lib.check(L.vg_diffaug_p_bwd(g_dimg, _p(self.dfake), 0, B, d_.C, d_.IH, self.aug, self._aug_seed, 1, _p(self.step_t),
-                                          _p(self.ada_state), st), "vg_diffaug_p_bwd")
-        elif self.aug:
-            _lib.check(L.vg_diffaug_bwd(g_dimg, _p(self.dfake), 0, B, d_.C, d_.IH, self.aug, self._aug_seed, 1, _p(self.step_t), st), "vg_diffaug_bwd")
-        if self.div_w != 0.0:  # total_gen_loss = loss + w * diversity_loss(fake_images): its gradient joins dL/d fake
-            Dn = self.dfake[0].numel()
-            _lib.check(L.vg_diversity_loss(fake_ptr, _p(self.dfake), _p(self.div_loss), _p(self.div_scratch), B, Dn, self.div_w, st),
-                       "vg_diversity_loss")
+            self._augment(self.fake, self.g_in, self.aug_params["g"], B, self.aug, 1, st)
+        lg, dlg = self.g_rows
+        self._d_forward(nd_c, B, self.g_in, self.ws_d, lg, st)
+        self._loss(lg, dlg, B, 2, st)
+        self._d_backward(nd_c, B, self.ws_d, dlg, 0, self.g_dimg, st)
+        if self.aug:
+            self._augment_adjoint(self.g_dimg, self.dfake, B, self.aug, 1, st)
+        self._diversity(st)
         self._g_backward(ng, st)
         self.sync.wait()
         if self.shard_map:
             self._adamw_g_sharded(st)
         else:
-            self._adamw(fg, self.m_g, self.v_g, self.hyp["lr_g"], st, self.clip_g, 1, self.ema_g)
+            self._adamw(self.r_g, self.hyp["lr_g"], st, self.clip_g, 1)
 
     # ------------------------------------------------------------------------------------------
+    def _optional_state(self):
+        """THE table of training state an option adds: (key, tensor or None when the option is off, options key, options getter).  It
+        drives ``_state_tensors`` (what the graph warm-up must put back), ``state_dict`` and ``load_state_dict``: an option's state is
+        one entry here.  (bCR holds no state, only options; the average is saved without options.)"""
+        spec = self.spec is not None
+        return (("spectral_state", self.spec.state if spec else None, "spectral_norm", lambda: self.spectral_norm if spec else None),
+                (None, None, "bcr", self._bcr_options),
+                ("ada_state", self.ada_state, "ada", self._ada_options),
+                ("ema_g", self.ema_g, None, None))
+
     def _state_tensors(self):
         """Everything a step changes that the next step reads (the training state held on the device)."""
         fd, fg = self.vit._flat, self.gen._flat
-        state = [fd.flat, fd.shadow, fg.flat, fg.shadow, self.m_d, self.v_d, self.m_g, self.v_g, self.step_t]
-        if self.spec is not None:
-            state.append(self.spec.state)
-        if self.ada_state is not None:
-            state.append(self.ada_state)
-        return state if self.ema_g is None else state + [self.ema_g]
+        return ([fd.flat, fd.shadow, fg.flat, fg.shadow, self.m_d, self.v_d, self.m_g, self.v_g, self.step_t]
+                + [t for _, t, _, _ in self._optional_state() if t is not None])
 
     def sync_from_modules(self, reset_optimizer: bool = False) -> None:
         """Call after the modules' parameters were changed behind the engine's back (``load_state_dict``, an in-place
@@ -740,9 +748,7 @@ class GanEngine:
 
     # ------------------------------------------------------------------------------------------ averaged generator, sampling
     def _need_ema(self, what: str) -> torch.Tensor:
-        if self.ema_g is None:
-            raise RuntimeError(f"{what}: this engine keeps no averaged generator (built with ema_decay=0)")
-        return self.ema_g
+        return self._need(self.ema_g, f"{what}: this engine keeps no averaged generator (built with ema_decay=0)")
 
     def sample(self, z: torch.Tensor, ema: bool = True) -> torch.Tensor:
         """Images [n, C, IH, IW] (``generator.out_dtype``) of the latent batch ``z`` [n, Z], n any batch size: one forward-only
@@ -754,14 +760,14 @@ class GanEngine:
             self._need_ema("sample(ema=True)")
         if z.dim() != 2 or z.shape[1] != gen._dims.Z or z.shape[0] < 1 or z.device != self.dev:
             raise ValueError(f"z must be a [n, {gen._dims.Z}] tensor on {self.dev}")
-        L, n = _lib.lib(), int(z.shape[0])
+        n = int(z.shape[0])
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         if ema:
             if self._ema_shadow is None:
                 self._ema_shadow = torch.empty(fg.total, dtype=torch.bfloat16, device=self.dev)
             key = (self.steps, self._ema_loads)
             if self._ema_cast_key != key:
-                _lib.check(L.vg_cast_f32_bf16(_p(self.ema_g), _p(self._ema_shadow), fg.total, st), "vg_cast_f32_bf16")
+                _call("vg_cast_f32_bf16", _p(self.ema_g), _p(self._ema_shadow), fg.total, st)
                 self._ema_cast_key = key
             master, shadow = self.ema_g, self._ema_shadow
         else:
@@ -774,7 +780,7 @@ class GanEngine:
         net = _lib.VgGenNet(gen._dims, master.data_ptr(), shadow.data_ptr(), fg.grad.data_ptr(), 0.0, 0, None, None if tab is None else tab.data_ptr())
         zin = z.detach().float().contiguous()
         img = torch.empty(n, gen.channels, gen.image_size, gen.image_size, dtype=torch.bfloat16, device=self.dev)
-        _lib.check(L.vg_gen_forward(C.byref(net), n, _p(zin), _p(self._sample_ws), _p(img), st), "vg_gen_forward")
+        _call("vg_gen_forward", C.byref(net), n, _p(zin), _p(self._sample_ws), _p(img), st)
         return img.to(gen.out_dtype)
 
     def ema_state_dict(self) -> dict:
@@ -807,18 +813,12 @@ class GanEngine:
         sd = {"format_version": self.STATE_FORMAT, "steps": int(self.steps), "noise_seed": int(self._noise_seed)}
         for k in ("m_d", "v_d", "m_g", "v_g", "step_t"):
             sd[k] = getattr(self, k).detach().clone()
-        if self.ema_g is not None:
-            sd["ema_g"] = self.ema_g.detach().clone()
-        if self.spec is not None:
-            sd["spectral_norm"], sd["spectral_state"] = self.spectral_norm, self.spec.state.detach().clone()
-        if self.bcr:  # no training state of its own: the options, so that a resumed run is the same run
-            sd["bcr"] = self._bcr_options()
-        if self.gated:  # the probability and the controller's accumulators, and the options they were run under
-            sd["ada"], sd["ada_state"] = self._ada_options(), self.ada_state.detach().clone()
+        for key, t, okey, options in self._optional_state():
+            if okey is not None and options() is not None:  # the options the state was run under, so that a resumed run is the same run
+                sd[okey] = options()
+            if t is not None:
+                sd[key] = t.detach().clone()
         return sd
-
-    def _bcr_options(self):
-        return None if not self.bcr else (self.bcr_w[0], self.bcr_w[1], self.bcr_policy)
 
     def effective_state_dict(self) -> dict:
         """The discriminator's ``state_dict()`` (the keys of the module the engine was given) with fp32(s * W), s = sigma0 / sigma, in
@@ -862,18 +862,13 @@ class GanEngine:
         if strict and saved_ada != self._ada_options():
             raise ValueError(f"engine state was saved with (aug_p, ada_target, ada_interval, ada_kimg) = {saved_ada!r}, this engine has "
                              f"{self._ada_options()!r} (strict=False loads the probability all the same when both sides hold one)")
-        has_ada = sd.get("ada_state") is not None and self.ada_state is not None
         has_ema = sd.get("ema_g") is not None
         if strict and has_ema != (self.ema_g is not None):
             raise ValueError("engine state has no ema_g but this engine keeps a moving average (strict=False restarts it)" if not has_ema
                              else "engine state has an ema_g but this engine keeps no moving average")
+        # restored: the fixed state, and every optional state that both sides hold; first every size check, then the copies
         pairs = [(getattr(self, k), sd[k], k) for k in names]
-        if has_ema and self.ema_g is not None:
-            pairs.append((self.ema_g, sd["ema_g"], "ema_g"))
-        if has_spec and self.spec is not None:
-            pairs.append((self.spec.state, sd["spectral_state"], "spectral_state"))
-        if has_ada:
-            pairs.append((self.ada_state, sd["ada_state"], "ada_state"))
+        pairs += [(t, sd[k], k) for k, t, _, _ in self._optional_state() if t is not None and sd.get(k) is not None]
         for dst, src, k in pairs:
             if not torch.is_tensor(src) or src.numel() != dst.numel():
                 raise ValueError(f"engine state {k}: {tuple(getattr(src, 'shape', ()))} does not fit this engine's {tuple(dst.shape)}")
@@ -906,7 +901,8 @@ class GanEngine:
             self.z.copy_(z)
         self.steps += 1
         if not self._use_graph:
-            self._enqueue(real)
+            self._inputs(real)
+            self._enqueue_body()  # the whole step on the current stream, no host sync
             return self.losses
         if self._graph is None:
             # Warm-up on a side stream (allocator, lazily loaded code objects), then capture.  The warm-up is a real step:
@@ -944,7 +940,8 @@ class GanEngine:
                 self.sync._pending.clear()
                 self._graph_fallback(f"capturing the step ({'collectives' if self.sync.active else 'gradient penalty through torch autograd'}) failed: "
                                      f"{type(exc).__name__}: {exc}")
-                self._enqueue(real)
+                self._inputs(real)
+                self._enqueue_body()
                 return self.losses
             self._graph = graph
         self._inputs(real)
