@@ -518,6 +518,14 @@ int vg_vit_backward_stages(const VgVitNet* net, int B, void* ws, const float* dl
 long long vg_vit_penalty_ws_bytes(const VgVitDims* d, int B);
 int vg_vit_penalty(const VgVitNet* net, int B, const void* real, const void* fake, const float* eps, float weight, void* ws, void* ws_pen,
                    float* penalty_out, void* stream);
+/* The zero-centred R1 penalty on real images (Mescheder et al. 2018), the regulariser of the non-saturating / hinge recipes, as ONE
+ * call (additive to ABI v9; the body is vg_vit_penalty's with another front and another seed of the second backward):
+ *   penalty = mean_b || d sum_k D(x_b)_k / d x_b ||_2^2;   net->G += weight * d penalty / d theta;   *penalty_out = penalty (device
+ *   float, unweighted).  The caller folds gamma / 2 and a lazy-regularisation interval into weight (weight = interval * gamma / 2).
+ * x: bf16 [B, C, IH, IH], fed to the forward as it is (no interpolation launch, no fp32 copy).  ws / ws_pen: exactly vg_vit_ws_bytes(d, B)
+ * and vg_vit_penalty_ws_bytes(d, B) bytes.  Dropout, dense_top, ctx and the return codes as in vg_vit_penalty: -1 a null argument,
+ * B < 1 or net->G missing (decided on the host before any launch); -3 attn_fp8, more than 80 tokens, or the same alignment conditions. */
+int vg_vit_r1(const VgVitNet* net, int B, const void* x, float weight, void* ws, void* ws_pen, float* penalty_out, void* stream);
 
 /* fp32 mode of the same network (opt-in; the bf16 entry points above are unchanged): activations, saved tensors, gradients and GEMM
  * operands are fp32, the GEMMs run on the exact f32-input MFMA (v_mfma_f32_16x16x4_f32).  Reads net->P (fp32 master), accumulates

@@ -30,6 +30,7 @@ MODES = {
     "spectral normalisation (qkv)": dict(spectral_norm="qkv"),
     "adaptive augmentation (ADA) + bCR, hinge": dict(diffaug="color,translation,cutout", ada_target=0.6, ada_interval=4, ada_kimg=20.0,
                                                     bcr=(10.0, 10.0), loss="hinge"),
+    "R1 penalty, lazy (interval 4: two captured graphs)": dict(r1_gamma=10.0, r1_interval=4),
 }
 bad = []
 for name, kw in MODES.items():

@@ -150,6 +150,7 @@ _SIGNATURES = {
     "vg_vit_backward_stages": (c_int, [C.POINTER(VgVitNet), c_int, P, P, P, c_int, c_int, c_int, P]),
     "vg_vit_penalty_ws_bytes": (c_ll, [C.POINTER(VgVitDims), c_int]),
     "vg_vit_penalty": (c_int, [C.POINTER(VgVitNet), c_int, P, P, P, c_float, P, P, P, P]),
+    "vg_vit_r1": (c_int, [C.POINTER(VgVitNet), c_int, P, c_float, P, P, P, P]),
     "vg_vit_ws_bytes_f32": (c_ll, [C.POINTER(VgVitDims), c_int]),
     "vg_vit_forward_f32": (c_int, [C.POINTER(VgVitNet), c_int, P, P, P, P]),
     "vg_vit_backward_f32": (c_int, [C.POINTER(VgVitNet), c_int, P, P, P, c_int, P]),

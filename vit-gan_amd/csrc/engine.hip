@@ -826,9 +826,12 @@ extern "C" long long vg_vit_penalty_ws_bytes(const VgVitDims* d, int B) {
   PenWs q;
   return carve_pen(*d, B, nullptr, q);
 }
-extern "C" int vg_vit_penalty(const VgVitNet* net0, int B, const void* real, const void* fake, const float* eps, float weight, void* ws,
-                              void* ws_pen, float* penalty_out, void* stream) {
-  if (!net0 || !real || !fake || !eps || !ws || !ws_pen || !penalty_out || B < 1 || !net0->G) return -1;
+// One body, two fronts.  r1 = 0: WGAN-GP - `real`, `fake`, `eps` make the fp32 interpolate and pass 3 penalises (||g|| - 1)^2 (vg_vit_penalty).
+// r1 = 1: the zero-centred R1 penalty of Mescheder et al. 2018 - `real` is the batch itself (bf16, patchified as it is: no interpolation
+// launch, no fp32 copy; fake / eps unused) and pass 3 penalises ||g||^2 (vg_vit_r1).  Passes 2, 4 and 5 are the same launches.
+static int vit_penalty_impl(const VgVitNet* net0, int B, int r1, const void* real, const void* fake, const float* eps, float weight, void* ws,
+                            void* ws_pen, float* penalty_out, void* stream) {
+  if (!net0 || !real || (!r1 && (!fake || !eps)) || !ws || !ws_pen || !penalty_out || B < 1 || !net0->G) return -1;
   if (!pen_shape_ok(net0, B)) return -3;
   VgVitNet net_ = *net0;
   net_.dense_top = 1; net_.ctx = nullptr;
@@ -847,9 +850,13 @@ extern "C" int vg_vit_penalty(const VgVitNet* net0, int B, const void* real, con
   const bool drop = dr.thr != 0;
   const int top = L - 1;
 
-  // ---- 1. forward of the interpolated images ----
-  VG_TRY(vg_pen_interp_launch((const bf16*)real, (const bf16*)fake, eps, q.xhat, B, (long long)d.C * d.IH * d.IH, st));
-  VG_TRY(vit_forward_impl(net, B, q.xhat, 0, ws, q.logits, stream, q.h));
+  // ---- 1. forward of the interpolated images (R1: of the images themselves) ----
+  if (r1) {
+    VG_TRY(vit_forward_impl(net, B, real, 1, ws, q.logits, stream, q.h));
+  } else {
+    VG_TRY(vg_pen_interp_launch((const bf16*)real, (const bf16*)fake, eps, q.xhat, B, (long long)d.C * d.IH * d.IH, st));
+    VG_TRY(vit_forward_impl(net, B, q.xhat, 0, ws, q.logits, stream, q.h));
+  }
 
   // ---- 2. first backward: d sum(logits) / d x^, every intermediate kept ----
   VG_TRY(vg_fill_f32_launch(q.ones, (long long)B * d.Kc, 1.0f, st));
@@ -904,7 +911,7 @@ extern "C" int vg_vit_penalty(const VgVitNet* net0, int B, const void* real, con
   VG_TRY(lin_dgrad(w.gp, Pb + lay.conv_w, w.dA, B * NP, E, Kp, 0, nullptr, nullptr, 0.f, st));  // = the image gradient, patch by patch
 
   // ---- 3. the penalty and the direction of the second backward ----
-  VG_TRY(vg_pen_norm_launch(w.dA, q.u_dA, q.pen_img, penalty_out, B, (long long)NP * Kp, weight, st));
+  VG_TRY(vg_pen_norm_launch(w.dA, q.u_dA, q.pen_img, penalty_out, B, (long long)NP * Kp, weight, r1, st));
 
   // ---- 4. backward of pass 2, bottom to top ----
   VgFoldJobs folds; folds.n = 0;
@@ -998,6 +1005,15 @@ extern "C" int vg_vit_penalty(const VgVitNet* net0, int B, const void* real, con
   VitInject inj = {};
   inj.preact = q.h; inj.head_given = 1; inj.s_xcls = q.s_xcls; inj.s_h = q.s_h; inj.s_xmid = q.s_xmid; inj.s_qkv = q.s_qkv; inj.s_x = q.s_x; inj.tmp = q.tmp;
   return vit_backward_impl(net, B, ws, q.ones, nullptr, 1, 0, L + 2, stream, &inj);
+}
+extern "C" int vg_vit_penalty(const VgVitNet* net, int B, const void* real, const void* fake, const float* eps, float weight, void* ws,
+                              void* ws_pen, float* penalty_out, void* stream) {
+  return vit_penalty_impl(net, B, 0, real, fake, eps, weight, ws, ws_pen, penalty_out, stream);
+}
+// R1: penalty = mean_b ||d sum_k D(x_b)_k / d x_b||^2 on the caller's bf16 images; G += weight * d penalty / d theta (the caller folds
+// gamma / 2 and the lazy interval into weight), *penalty_out = the unweighted penalty.  Same workspaces and return codes as vg_vit_penalty.
+extern "C" int vg_vit_r1(const VgVitNet* net, int B, const void* x, float weight, void* ws, void* ws_pen, float* penalty_out, void* stream) {
+  return vit_penalty_impl(net, B, 1, x, nullptr, nullptr, weight, ws, ws_pen, penalty_out, stream);
 }
 
 // =============================================================================================

@@ -289,6 +289,9 @@ int vg_pen_interp_launch(const bf16* real, const bf16* fake, const float* eps, f
 // One workgroup per image: n_b = ||g_b||_2 over the image's `per` gradient elements (the patch rows of d A - the same numbers as the
 // image gradient, permuted), pen_img[b] = (n_b - 1)^2 / B, and the direction the second backward starts from,
 // u_b = coef (n_b - 1) / n_b g_b = d(weight * mean_b (n_b - 1)^2) / d g_b with coef = 2 weight / B  (utils.py:143-144).
+// R1 = 1, the zero-centred penalty on the images themselves: pen_img[b] = n_b^2 / B and u_b = coef g_b = d(weight * mean_b n_b^2) / d g_b -
+// the same sum in the same order, no square root and no division (a zero gradient needs no special case).
+template <int R1>
 __global__ __launch_bounds__(256) void vg_pen_norm_kernel(const bf16* __restrict__ g, bf16* __restrict__ u, float* __restrict__ pen_img, long long per,
                                                           float coef, float inv_b) {
   __shared__ float red[4];
@@ -304,13 +307,19 @@ __global__ __launch_bounds__(256) void vg_pen_norm_kernel(const bf16* __restrict
   a = vg_wave_sum(a);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
   __syncthreads();
-  if (threadIdx.x == 0) {
-    const float nb = sqrtf((red[0] + red[1]) + (red[2] + red[3]));
-    pen_img[blockIdx.x] = (nb - 1.0f) * (nb - 1.0f) * inv_b;
-    fac = nb > 0.f ? coef * (nb - 1.0f) / nb : 0.f;  // (torch's norm has the zero subgradient at 0)
+  float f;
+  if constexpr (R1) {
+    if (threadIdx.x == 0) pen_img[blockIdx.x] = ((red[0] + red[1]) + (red[2] + red[3])) * inv_b;
+    f = coef;
+  } else {
+    if (threadIdx.x == 0) {
+      const float nb = sqrtf((red[0] + red[1]) + (red[2] + red[3]));
+      pen_img[blockIdx.x] = (nb - 1.0f) * (nb - 1.0f) * inv_b;
+      fac = nb > 0.f ? coef * (nb - 1.0f) / nb : 0.f;  // (torch's norm has the zero subgradient at 0)
+    }
+    __syncthreads();
+    f = fac;
   }
-  __syncthreads();
-  const float f = fac;
   for (long long i = (long long)threadIdx.x * 4; i < per; i += 1024) {
     const bf16x4 v = *(const bf16x4*)(gb + i);
     bf16x4 o;
@@ -328,9 +337,11 @@ __global__ __launch_bounds__(256) void vg_pen_sum_kernel(const float* __restrict
   __syncthreads();
   if (threadIdx.x == 0) out[0] = (red[0] + red[1]) + (red[2] + red[3]);
 }
-int vg_pen_norm_launch(const bf16* g, bf16* u, float* pen_img, float* pen_out, int B, long long per, float weight, hipStream_t st) {
+int vg_pen_norm_launch(const bf16* g, bf16* u, float* pen_img, float* pen_out, int B, long long per, float weight, int r1, hipStream_t st) {
   if (B < 1 || per < 4 || (per & 3)) return -3;
-  hipLaunchKernelGGL(vg_pen_norm_kernel, dim3(B), dim3(256), 0, st, g, u, pen_img, per, 2.0f * weight / (float)B, 1.0f / (float)B);
+  const float coef = 2.0f * weight / (float)B, inv_b = 1.0f / (float)B;
+  if (r1) hipLaunchKernelGGL(vg_pen_norm_kernel<1>, dim3(B), dim3(256), 0, st, g, u, pen_img, per, coef, inv_b);
+  else hipLaunchKernelGGL(vg_pen_norm_kernel<0>, dim3(B), dim3(256), 0, st, g, u, pen_img, per, coef, inv_b);
   hipLaunchKernelGGL(vg_pen_sum_kernel, dim3(1), dim3(256), 0, st, pen_img, B, pen_out);
   return (int)hipGetLastError();
 }

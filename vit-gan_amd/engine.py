@@ -53,7 +53,8 @@ class GanEngine:
                  two_stream: bool = False, compress_mapping_grad: bool = False, shard_mapping_update: bool = False, gp_weight: float = 0.0,
                  exchange_single_rank: bool = False, dense_top_block: bool = False, gp_autograd: bool = False, diffaug: str = "",
                  ema_decay: float = 0.0, ema_start: int = 0, spectral_norm: str = "", bcr=(0.0, 0.0), bcr_aug: str = "",
-                 aug_p: Optional[float] = None, ada_target: float = 0.0, ada_interval: int = 4, ada_kimg: float = 500.0):
+                 aug_p: Optional[float] = None, ada_target: float = 0.0, ada_interval: int = 4, ada_kimg: float = 500.0,
+                 r1_gamma: float = 0.0, r1_interval: int = 1):
         """concurrent_wgrad: the discriminator's weight gradients on a side stream beside its input gradients.  Off by default
         since the persistent GEMMs (csrc/gemm_wr.hip, gemm_tn.hip: their workgroups hold the CUs for a whole launch) - the
         side stream measured 6.70 against 6.67 ms/step.
@@ -156,7 +157,19 @@ class GanEngine:
         (they synchronise: for logging).  ``state_dict()`` carries the state and the four options.  Not with ``loss="wasserstein"``
         (a critic's sign carries no overfitting signal) and not under data parallelism (the statistics are per process; a fixed
         ``aug_p`` is allowed there).
-        ada_interval: steps between two updates of p.  ada_kimg: thousands of real images it takes p to go from 0 to 1."""
+        ada_interval: steps between two updates of p.  ada_kimg: thousands of real images it takes p to go from 0 to 1.
+        r1_gamma: weight gamma of the zero-centred R1 penalty on real images, gamma / 2 E_real ||grad_x D(x)||^2 (Mescheder et al.
+        2018; the reference has none) - the regulariser that goes with ``loss="ns"`` / ``"hinge"``, where WGAN-GP's (||g|| - 1)^2 on
+        interpolates is the wrong operator.  ONE C call, ``vg_vit_r1`` (the penalty call's passes with the real images in front and
+        u = 2 w / B g as the seed of the second backward), where the gradient penalty runs: behind the augmentations, before D's own
+        pass, on the real images as that pass sees them (after instance noise and DiffAugment; bCR's partner is not penalised), with
+        the penalty call's dropout key.  ``r1_loss`` holds the last computed unweighted penalty.  0.0 (default): nothing - no buffer,
+        no call, and the step is launch for launch the plain one.  Not with ``gp_weight`` (one gradient penalty per step: they share
+        the workspaces), ``two_stream`` or fp8 attention.
+        r1_interval: lazy regularisation (Karras et al. 2020) - the penalty runs on step 1 and every ``r1_interval``-th step after it
+        (``ops.r1_due`` on the host's step count, which ``state_dict()`` carries), weighted ``r1_interval * r1_gamma / 2``; the other
+        steps are plain steps and leave ``r1_loss`` alone.  Under ``use_graph`` the two launch lists are two captured graphs, each
+        warmed up and captured the first time its kind of step occurs."""
         self._check_options(discriminator, generator, dict(locals()))
         self._carve()
         self._attach()
@@ -170,6 +183,8 @@ class GanEngine:
         self.bcr_w = ops.parse_bcr_weights(o["bcr"])
         self.bcr_policy = ops.parse_aug_policy(o["bcr_aug"])
         self.bcr = self.bcr_w != (0.0, 0.0)
+        self.r1_gamma, self.r1_interval = ops.parse_r1_options(o["r1_gamma"], o["r1_interval"], o["gp_weight"])
+        self.r1 = self.r1_gamma > 0.0
         if self.bcr_policy and self.aug:
             raise ValueError("bcr_aug: with diffaug on, diffaug's own transform T_1 is the consistency partner; leave bcr_aug empty")
         if self.bcr_policy and not self.bcr:
@@ -206,6 +221,12 @@ class GanEngine:
         self.gp_w = float(o["gp_weight"])
         if self.gp_w != 0.0:
             vit.require_short_attention("gp_weight > 0 (the gradient penalty)")
+        if self.r1:
+            if two_stream:
+                raise ValueError("r1_gamma: the R1 penalty runs on the single-chain schedule only; switch two_stream off")
+            if bool(getattr(vit, "attention_fp8", False)):
+                raise ValueError("r1_gamma: the R1 penalty is built on the bf16 attention kernels; switch attention_fp8 off")
+            vit.require_short_attention("r1_gamma > 0 (the R1 penalty)")
         self.vit, self.gen, self._disc = vit, generator, discriminator
         if loss not in LOSS_KINDS:
             raise ValueError(f"loss must be one of {sorted(LOSS_KINDS)}")
@@ -270,9 +291,11 @@ class GanEngine:
             self.ws_d2 = torch.empty(L.vg_vit_ws_bytes(C.byref(d), B), dtype=torch.uint8, device=dev)
             self.grad2 = torch.zeros_like(vit._flat.grad)
             self.side = torch.cuda.Stream(device=dev)
-        if self.gp_c_call:  # the penalty's own passes: its forward runs in ws_d (the step's passes come after it), the rest here
+        if self.gp_c_call or self.r1:  # the penalty's own passes: its forward runs in ws_d (the step's passes come after it), the rest here
             self.ws_gp = torch.empty(L.vg_vit_penalty_ws_bytes(C.byref(d), B), dtype=torch.uint8, device=dev)
+        if self.gp_c_call:
             self.gp_eps = torch.empty(B, dtype=torch.float32, device=dev)
+        self.r1_loss: Optional[torch.Tensor] = f32(1) if self.r1 else None  # the last computed unweighted penalty
         self.ws_g = torch.empty(L.vg_gen_ws_bytes(C.byref(g), B), dtype=torch.uint8, device=dev)
         nL, self.Kc = 4 * B if self.bcr else 2 * B, d.Kc  # logit rows of the discriminator's own pass
         if self.bcr:
@@ -370,7 +393,7 @@ class GanEngine:
             if eng is not None:
                 eng.sync_from_modules()
         self._hooks = [m.register_load_state_dict_post_hook(_hook) for m in (vit, self.gen)]
-        self.steps, self._graph = 0, None
+        self.steps, self._graphs = 0, {}  # the captured step(s), by kind: False = the plain launch list, True = with the R1 call
         self.graph_fallback_reason: Optional[str] = None
         if self._use_graph and self.sync.active:
             backend = dist.get_backend(self.pg)
@@ -378,20 +401,22 @@ class GanEngine:
                 self._graph_fallback(f"process-group backend '{backend}' cannot be captured in a hipGraph (only nccl = RCCL can)", stacklevel=4)
 
     def _graph_fallback(self, reason: str, stacklevel: int = 3) -> None:
-        self._use_graph, self._graph = False, None
+        self._use_graph, self._graphs = False, {}
         self.graph_fallback_reason = reason
         warnings.warn(f"GanEngine: hipGraph replay was requested but the step runs EAGER: {reason}", RuntimeWarning, stacklevel=stacklevel)
 
     @property
     def graph_active(self) -> bool:
-        """True when step() replays a captured hipGraph (after the first call), False in eager mode."""
+        """True when step() replays a captured hipGraph, False in eager mode (as before, it is already True between construction and the
+        first call, which captures).  With lazy R1 there are two kinds of step; ``step()`` captures a kind inside the call in which it
+        first occurs, or falls back to eager for good, so after any ``step()`` every kind that has occurred is captured."""
         return self._use_graph
 
     def close(self) -> None:
         """Detach from the modules (load_state_dict hooks) and drop the captured graph and workspaces."""
         for h in self._hooks:
             h.remove()
-        self._hooks, self._graph = [], None
+        self._hooks, self._graphs = [], {}
         fd = self.vit._flat
         if getattr(self, "spec", None) is not None and fd.spectral is self.spec:
             fd.spectral = None  # the modules hold the raw weights again: export effective_state_dict() first
@@ -561,6 +586,9 @@ class GanEngine:
     def _ada_options(self):
         return None if not self.gated else (self.aug_p0, self.ada_target, self.ada_interval, self.ada_kimg)
 
+    def _r1_options(self):
+        return None if not self.r1 else (self.r1_gamma, self.r1_interval)
+
     def _bcr_options(self):
         return None if not self.bcr else (self.bcr_w[0], self.bcr_w[1], self.bcr_policy)
 
@@ -651,8 +679,17 @@ class GanEngine:
                 (self.gp_w * pen).backward()   # the rest accumulates into the same buffer through the parameters' .grad (views of it)
             self.gp_loss.copy_(pen.detach().reshape(1))
 
-    def _enqueue_body(self) -> None:
-        """Everything of a step behind its inputs (``_inputs``): what the hipGraph captures."""
+    def _r1(self, st) -> None:
+        """gamma / 2 E ||grad_x D(x)||^2 on the real images D's own pass sees joins the D loss: one C call, the lazy interval in its weight."""
+        fd = self.vit._flat
+        pnet = _lib.VgVitNet(self.vit._dims, fd.flat.data_ptr(), fd.shadow.data_ptr(), fd.grad.data_ptr(), self.p_d, self.seed * 8 + 3,
+                             self.step_t.data_ptr(), None, 0, 1)
+        _call("vg_vit_r1", C.byref(pnet), self.B, _p(self.d_in_half[0]), 0.5 * self.r1_gamma * self.r1_interval, _p(self.ws_d), _p(self.ws_gp),
+              _p(self.r1_loss), st)
+
+    def _enqueue_body(self, r1_due: bool = False) -> None:
+        """Everything of a step behind its inputs (``_inputs``): what the hipGraph captures.  ``r1_due``: the kind of step - with the
+        R1 call (lazy regularisation: step 1 and every ``r1_interval``-th after it) or the plain launch list."""
         if self.two_stream:
             return self._enqueue_two_stream()
         B = self.B
@@ -670,6 +707,8 @@ class GanEngine:
             self._augment(self.d_in, self.imgs_bcr, self.aug_params["c"], 2 * B, self.bcr_policy, 2, st)
         if self.gp_w != 0.0:
             self._penalty(st)
+        if r1_due:
+            self._r1(st)
         if self.fuse:  # D's own pass, real and fake rows in one batch (with bCR: the pair and its transform, 4B images)
             n, src, adv, dadv = self.d_pass
             self._d_forward(nd, n, src, self.ws_d, self.logits, st)
@@ -714,10 +753,11 @@ class GanEngine:
     def _optional_state(self):
         """THE table of training state an option adds: (key, tensor or None when the option is off, options key, options getter).  It
         drives ``_state_tensors`` (what the graph warm-up must put back), ``state_dict`` and ``load_state_dict``: an option's state is
-        one entry here.  (bCR holds no state, only options; the average is saved without options.)"""
+        one entry here.  (bCR and R1 hold no state, only options; the average is saved without options.)"""
         spec = self.spec is not None
         return (("spectral_state", self.spec.state if spec else None, "spectral_norm", lambda: self.spectral_norm if spec else None),
                 (None, None, "bcr", self._bcr_options),
+                (None, None, "r1", self._r1_options),
                 ("ada_state", self.ada_state, "ada", self._ada_options),
                 ("ema_g", self.ema_g, None, None))
 
@@ -840,7 +880,7 @@ class GanEngine:
         ``strict``; with ``strict=False`` the average restarts as a copy of the weights at the next step (the step is captured again).  The
         spectral-normalisation state follows the same rule: missing under ``strict`` raises, with ``strict=False`` it is measured
         again from the current weights.  Consistency regularisation has no state; the saved ``bcr`` options must equal this engine's under
-        ``strict``.  The augmentation probability and its controller (``aug_p`` / ``ada_target``) follow bCR's rule for the options, and
+        ``strict``, and so must the saved ``r1`` options (the lazy schedule continues from the restored ``steps``).  The augmentation probability and its controller (``aug_p`` / ``ada_target``) follow bCR's rule for the options, and
         their state is restored whenever both sides hold one."""
         if sd.get("format_version") != self.STATE_FORMAT:
             raise ValueError(f"engine state format {sd.get('format_version')!r}, this engine reads format {self.STATE_FORMAT}")
@@ -862,6 +902,10 @@ class GanEngine:
         if strict and saved_ada != self._ada_options():
             raise ValueError(f"engine state was saved with (aug_p, ada_target, ada_interval, ada_kimg) = {saved_ada!r}, this engine has "
                              f"{self._ada_options()!r} (strict=False loads the probability all the same when both sides hold one)")
+        saved_r1 = None if sd.get("r1") is None else tuple(sd["r1"])
+        if strict and saved_r1 != self._r1_options():
+            raise ValueError(f"engine state was saved with the R1 penalty (r1_gamma, r1_interval) = {saved_r1!r}, this engine has "
+                             f"{self._r1_options()!r} (strict=False loads it all the same: R1 holds no training state)")
         has_ema = sd.get("ema_g") is not None
         if strict and has_ema != (self.ema_g is not None):
             raise ValueError("engine state has no ema_g but this engine keeps a moving average (strict=False restarts it)" if not has_ema
@@ -882,7 +926,7 @@ class GanEngine:
             # node, so that (rare) case drops the graph; the next step captures it again
             start = self.ema_start if has_ema else max(self.ema_start, int(sd["step_t"].reshape(-1)[0]) + 1)
             if start != self._ema_from:
-                self._ema_from, self._graph = start, None
+                self._ema_from, self._graphs = start, {}
         if self.spec is not None and not has_spec:  # no state to restore: the current weights become the reference point
             self.spec.measure(self.vit._flat.flat)
         self.sync_from_modules()
@@ -900,11 +944,12 @@ class GanEngine:
         if z is not None:
             self.z.copy_(z)
         self.steps += 1
+        due = self.r1 and ops.r1_due(self.steps, self.r1_interval)  # the kind of step: a launch list, and a captured graph, of its own
         if not self._use_graph:
             self._inputs(real)
-            self._enqueue_body()  # the whole step on the current stream, no host sync
+            self._enqueue_body(due)  # the whole step on the current stream, no host sync
             return self.losses
-        if self._graph is None:
+        if due not in self._graphs:
             # Warm-up on a side stream (allocator, lazily loaded code objects), then capture.  The warm-up is a real step:
             # the training state is saved before it and restored after it, so N calls of step() are N steps in graph
             # mode exactly as in eager mode (tests compare the two bit for bit).
@@ -913,7 +958,7 @@ class GanEngine:
             self._inputs(real)
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
-                self._enqueue_body()
+                self._enqueue_body(due)
             torch.cuda.current_stream().wait_stream(s)
             for t, keep in zip(self._state_tensors(), saved):
                 t.copy_(keep)
@@ -930,7 +975,7 @@ class GanEngine:
                 time.sleep(0.5)
             try:
                 with torch.cuda.graph(graph, capture_error_mode=mode):
-                    self._enqueue_body()
+                    self._enqueue_body(due)
             except Exception as exc:  # only reachable with collectives or the autograd-driven penalty in the step: otherwise it is all our own enqueue-only calls
                 if not self.sync.active and self.gp_w == 0.0:
                     raise
@@ -941,9 +986,9 @@ class GanEngine:
                 self._graph_fallback(f"capturing the step ({'collectives' if self.sync.active else 'gradient penalty through torch autograd'}) failed: "
                                      f"{type(exc).__name__}: {exc}")
                 self._inputs(real)
-                self._enqueue_body()
+                self._enqueue_body(due)
                 return self.losses
-            self._graph = graph
+            self._graphs[due] = graph
         self._inputs(real)
-        self._graph.replay()
+        self._graphs[due].replay()
         return self.losses

@@ -396,6 +396,30 @@ def parse_bcr_weights(bcr):
     return w_real, w_fake
 
 
+def parse_r1_options(gamma, interval, gp_weight=0.0):
+    """``(r1_gamma, r1_interval)`` of the R1 penalty and its lazy schedule, checked as GanEngine and train_model both state them:
+    gamma finite and >= 0 (0 = off), interval a positive integer - and 1 when the penalty is off; not together with ``gp_weight``."""
+    try:
+        g = float(gamma)
+    except (TypeError, ValueError):
+        raise ValueError(f"r1_gamma must be a finite, non-negative number, got {gamma!r}") from None
+    if not (math.isfinite(g) and g >= 0.0):
+        raise ValueError(f"r1_gamma must be a finite, non-negative number, got {gamma!r}")
+    if isinstance(interval, bool) or not isinstance(interval, int) or interval < 1:
+        raise ValueError(f"r1_interval must be a positive integer, got {interval!r}")
+    if interval != 1 and g == 0.0:
+        raise ValueError(f"r1_interval={interval!r} without a penalty (r1_gamma=0) would do nothing; set r1_gamma")
+    if g > 0.0 and float(gp_weight) != 0.0:
+        raise ValueError("r1_gamma: one gradient penalty per step - R1 and gp_weight share the penalty workspaces; switch one of them off")
+    return g, int(interval)
+
+
+def r1_due(step_index: int, interval: int) -> bool:
+    """Lazy regularisation: is the R1 penalty due on step ``step_index`` (1-based: the engine's ``steps`` after its increment)?  The
+    first step of a run is due, then every ``interval``-th one after it."""
+    return (int(step_index) - 1) % int(interval) == 0
+
+
 class ConsistencyLossFn(torch.autograd.Function):
     """Balanced consistency regularisation between D(x) and D(T(x)) (include/vitgan_hip.h, vg_bcr_loss): one launch computes both segment
     means and both gradients, so the backward only scales what the forward saved."""

@@ -32,3 +32,21 @@ def gradient_penalty(discriminator, real_images: torch.Tensor, fake_images: torc
                                            retain_graph=True, only_inputs=True)
     gradient_norm = gradients.reshape(batch_size, -1).norm(2, dim=1)
     return ((gradient_norm - 1) ** 2).mean()
+
+
+def r1_penalty(discriminator, real_images: torch.Tensor) -> torch.Tensor:
+    """The zero-centred R1 penalty on real images (Mescheder et al. 2018), ``mean_b ||d sum_k D(x_b)_k / d x_b||_2^2`` - without the
+    ``gamma / 2`` of the loss it joins - through the twice-differentiable operator set, so ``.backward()`` reaches the parameters.
+    The one-call form is ``vg_vit_r1`` (what ``GanEngine(r1_gamma=...)`` runs); this is the autograd form it is tested against."""
+    vit = discriminator.vit if hasattr(discriminator, "vit") else discriminator
+    if getattr(vit, "precision", "bf16") != "bf16":
+        raise ValueError("r1_penalty runs the bf16 operator set; it does not take a discriminator in precision='fp32'")
+    vit.require_short_attention("r1_penalty")
+    batch_size = real_images.size(0)
+    x = real_images.detach().float().requires_grad_(True)
+    out = vit.twice_differentiable_forward(x)
+    from . import ops2
+    with ops2.input_grad_only():  # this backward is for d out / d x alone: no parameter gradients
+        (gradients,) = torch.autograd.grad(outputs=out, inputs=x, grad_outputs=torch.ones_like(out), create_graph=True,
+                                           retain_graph=True, only_inputs=True)
+    return gradients.reshape(batch_size, -1).pow(2).sum(dim=1).mean()

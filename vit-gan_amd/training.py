@@ -205,7 +205,8 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                 save_artifacts: bool = True, clip_d: Optional[float] = None, clip_g: Optional[float] = None,
                 diversity_weight: float = 0.0, instance_noise: float = 0.0, gp_weight: float = 0.0, diffaug: str = "",
                 ema_decay: float = 0.0, ema_start: int = 0, spectral_norm: str = "", bcr=(0.0, 0.0), bcr_aug: str = "",
-                aug_p: Optional[float] = None, ada_target: float = 0.0, ada_interval: int = 4, ada_kimg: float = 500.0):
+                aug_p: Optional[float] = None, ada_target: float = 0.0, ada_interval: int = 4, ada_kimg: float = 500.0,
+                r1_gamma: float = 0.0, r1_interval: int = 1):
     """``loss``: "ns" (default: the executable v1 loss), "hinge", or "wasserstein" - the critic losses of the reference's
     unreached step (training.py:67-125); ``clip_d`` / ``clip_g``: its clip_grad_norm_ limits (5.0 / 0.5 there);
     ``diversity_weight``: its diversity term (0.1 there); ``instance_noise``: sigma of the noise on D's inputs (0.1
@@ -228,7 +229,10 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     of ``training.log`` also carries the two consistency losses (the unweighted means over the real and the fake images).
     ``aug_p`` / ``ada_target`` / ``ada_interval`` / ``ada_kimg``: the application probability of ``diffaug``'s members and its adaptive
     controller (``GanEngine(aug_p=..., ada_target=...)``; the reference has none).  With ``ada_target > 0`` every epoch's line also
-    carries the probability in force and the overfitting signal r_t of the last update."""
+    carries the probability in force and the overfitting signal r_t of the last update.
+    ``r1_gamma`` / ``r1_interval``: the zero-centred R1 penalty on real images and its lazy-regularisation interval
+    (``GanEngine(r1_gamma=..., r1_interval=...)``; the reference has none).  When it is on, every epoch's line also carries the last
+    computed unweighted penalty."""
     global _log_file
     from .ops import parse_aug_policy, parse_bcr_weights
     parse_aug_policy(diffaug)  # a bad policy string is the caller's error whatever the machine: before the device check
@@ -242,6 +246,8 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     # the probability's and the controller's argument errors are the caller's whatever the machine: before the device check
     from .ops import parse_ada_options
     parse_ada_options(aug_p, ada_target, ada_interval, ada_kimg, parse_aug_policy(diffaug), loss)
+    from .ops import parse_r1_options
+    parse_r1_options(r1_gamma, r1_interval, gp_weight)
     if not 0.0 <= float(ema_decay) < 1.0:
         raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
     if int(ema_start) != ema_start or ema_start < 0:
@@ -261,7 +267,7 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                     weight_decay=1e-3, seed=seed, clip_d=clip_d, clip_g=clip_g, diversity_weight=diversity_weight,
                     instance_noise=instance_noise, gp_weight=gp_weight, diffaug=diffaug, ema_decay=ema_decay, ema_start=ema_start,
                     spectral_norm=spectral_norm, bcr=bcr, bcr_aug=bcr_aug, aug_p=aug_p, ada_target=ada_target, ada_interval=ada_interval,
-                    ada_kimg=ada_kimg)
+                    ada_kimg=ada_kimg, r1_gamma=r1_gamma, r1_interval=r1_interval)
 
     def gan_checkpoint():  # gan.state_dict(), the discriminator's normalised matrices as the network applies them
         sd = gan.state_dict()
@@ -322,6 +328,8 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
         if eng.spec is not None:
             log(f"Spectral normalisation of the discriminator: set '{spectral_norm}', {eng.spec.n} matrices; checkpoints hold the EFFECTIVE "
                 "weights sigma0 W / sigma (discriminator_raw.pth: the raw weights for a resumed run)")
+        if eng.r1:
+            log(f"R1 penalty on real images: gamma {eng.r1_gamma:g}, every {eng.r1_interval} step(s) with weight {0.5 * eng.r1_gamma * eng.r1_interval:g}")
         for epoch in range(epochs):
             noise = construct_noise()
             if save_artifacts:
@@ -354,6 +362,8 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                 cr = f" | Consistency real: {cr_real:.6f}, fake: {cr_fake:.6f}"
             if eng.ada:
                 cr += f" | ada_p: {eng.ada_p:.6f}, ada_rt: {eng.ada_rt:.4f}"
+            if eng.r1:
+                cr += f" | R1: {float(eng.r1_loss):.6f}"
             log(f"Epoch [{epoch}/{epochs}] | Disc Loss: {d_real + d_fake:.8f}, Gen Loss: {g:.4f} | FID: {fid_score:.4f}{cr}")
             if save_artifacts:
                 save_figures(dirs.save, disc_losses=disc_losses, gen_losses=gen_losses, fid_scores=fid_scores)
