@@ -234,6 +234,8 @@ struct VitWs {
   bf16 *t_gb2, *t_dz1, *t_dxn2, *t_dxmid, *t_gb1, *t_dao;
   bf16* t_ao; float* t_lse;  // and its attention for the CLS query only (dot-product scores; the fp8 mode keeps the full kernels)
 };
+// The embedding and its backward run as the fused launches of embed.hip where the geometry is theirs (C1-C3).
+static inline bool vit_embed_fused(const VgVitDims& d) { return vg_embed_fused_ok(d.C, d.IH, d.P, d.E) != 0; }
 // The full-row GEMMs (LayerNorm in the epilogue) take the block Linears whose output is the embedding when E = 384 and the
 // rows come in whole units of 16; their workgroup count is also the number of LayerNorm-backward partial rows.
 static inline int vit_row_nwg(const VgVitDims& d, int M) { return vg_row_width_ok(d.E) ? vg_row_nwg(M) : 0; }  // (E = 384, and 512 since round 4)
@@ -327,6 +329,13 @@ static int vit_forward_impl(const VgVitNet* net, int B, const void* img, int img
   const Drop dr = mk_drop(net->dropout_p, net->dropout_seed, net->dropout_step);  // sites: 0 embedding, 1+2l attention branch, 2+2l MLP branch
 
   // patch embedding (src/v2/modules.py:82-98): gather -> GEMM(+bias +pos, rows remapped past CLS) ; CLS row
+  // C1-C3 (E = 384, 4 x 4 patches): ONE launch with block 0's norm1 (embed.hip); every other geometry keeps the launches below
+  const bool emb_fused = vit_embed_fused(d);
+  if (emb_fused) {
+    VG_TRY(vg_embed_fwd_launch(img, img_is_bf16, Pb + lay.conv_w, P + lay.conv_b, P + lay.pos, P + lay.cls, P + lay.layer0 + lay.ln1_w,
+                               P + lay.layer0 + lay.ln1_b, w.Apatch, w.X, w.xn1, w.mean1, w.rstd1, B, d.C, d.IH, 1e-5f, dr.thr, site_key(dr, 0),
+                               dr.scale, dr.step, st));
+  } else {
   VG_TRY(vg_patchify_launch(img, img_is_bf16, w.Apatch, B, d.C, d.IH, d.P, st));
   {
     VgGemmProb p = mk(w.Apatch, Kp, Pb + lay.conv_w, Kp, B * NP, E, Kp);
@@ -336,6 +345,7 @@ static int vit_forward_impl(const VgVitNet* net, int B, const void* img, int img
     VG_TRY(vg_gemm_launch(&p, 1, VG_NT, st));
   }
   VG_TRY(vg_fill_cls_launch(w.X, P + lay.cls, B, S, E, dr.thr, site_key(dr, 0), dr.scale, dr.step, st));
+  }
 
   // full-row path: pack this call's weights (the backward of this workspace reads the transposed images)
   const int rown = vit_row_nwg(d, M);
@@ -373,8 +383,9 @@ static int vit_forward_impl(const VgVitNet* net, int B, const void* img, int img
     unsigned char* z1 = w.z1 + (size_t)l * M * rE;
     bf16* a1 = w.a1 + (size_t)l * M * rE;
     const bf16* wp = w.wpack + (size_t)l * lay.layer_weights;
-    // norm1: standalone for block 0 (and on the tiled path); on the full-row path the fc2 epilogue of block l-1 wrote it
-    if (!rown || l == 0)
+    // norm1: standalone for block 0 (and on the tiled path); on the full-row path the fc2 epilogue of block l-1 wrote it,
+    // and block 0's came with the fused embedding
+    if ((!rown || l == 0) && !(l == 0 && emb_fused))
       VG_TRY(vg_ln_fwd_launch(x, E, P + lo + lay.ln1_w, P + lo + lay.ln1_b, xn1, E, w.mean1 + (size_t)l * M,
                               w.rstd1 + (size_t)l * M, M, E, 1e-5f, st));
     VG_TRY(lin_fwd(xn1, E, Pb + lo + lay.wqkv, P + lo + lay.bqkv, qkv, M, 3 * E, VG_ACT_NONE, 0.f, nullptr, nullptr, nullptr, st));
@@ -738,6 +749,13 @@ static int vit_backward_impl(const VgVitNet* net, int B, void* ws, const float* 
   if (stage_end < d.L + 2) return 0;
   // ---- patch embedding ----
   if (drop) g = (bf16*)g0m;  // dL/dX[0] masked by the embedding dropout (second output of block 0's LN1 backward)
+  if (vit_embed_fused(d)) {  // C1-C3: dL/dX[0] read in place, one launch per side + one fold (embed.hip); the K slices of the launches below
+    if (want_wgrad)
+      VG_TRY(vg_embed_wgrad_launch(g, w.Apatch, w.slab, w.tok_sum, G + lay.conv_w, G + lay.conv_b, G + lay.pos, G + lay.cls, B, d.C, d.IH,
+                                   pick_splits(tiles128(E, Kp), B * NP, EMB_SPLIT_CAP), st));
+    if (d_img) VG_TRY(vg_embed_dimg_launch(g, Pb + lay.conv_w, (bf16*)d_img, B, d.C, d.IH, st));
+    return 0;
+  }
   if (want_wgrad) {
     VG_TRY(vg_batch_sum_launch(g, w.tok_sum, B, S, E, st));
     VG_TRY(vg_embed_small_grads_launch(w.tok_sum, G + lay.cls, G + lay.pos, G + lay.conv_b, S, E, st));

@@ -37,6 +37,14 @@ int vg_colsum_bf16_launch(const bf16* X, long long ld, int R, int N, float* part
 
 int vg_patchify_launch(const void* img, int img_is_bf16, bf16* A, int B, int C, int IH, int P, hipStream_t st);
 int vg_unpatchify_launch(const bf16* dA, bf16* dimg, int B, int C, int IH, int P, hipStream_t st);
+// the patch embedding and its backward as one launch per side where vg_embed_fused_ok() (embed.hip): E = 384, 4 x 4 patches, C <= 4
+int vg_embed_fused_ok(int C, int IH, int P, int E);
+int vg_embed_fwd_launch(const void* img, int img_is_bf16, const bf16* W, const float* bias, const float* pos, const float* cls, const float* gamma,
+                        const float* beta, bf16* Apatch, bf16* X, bf16* Xn, float* mean, float* rstd, int B, int C, int IH, float eps, unsigned dthr,
+                        unsigned dkey, float dscale, const unsigned* dstep, hipStream_t st);
+int vg_embed_dimg_launch(const bf16* g, const bf16* W, bf16* dimg, int B, int C, int IH, hipStream_t st);
+int vg_embed_wgrad_launch(const bf16* g, const bf16* Apatch, float* slab, float* tok_sum, float* d_w, float* d_bias, float* d_pos, float* d_cls, int B,
+                          int C, int IH, int splits, hipStream_t st);
 int vg_unfold_tokens_launch(const void* img, int img_is_bf16, bf16* out, int B, int C, int IH, int P, int overlap, hipStream_t st);
 int vg_unfold_tokens_bwd_launch(const bf16* dout, bf16* dimg, int B, int C, int IH, int P, int overlap, hipStream_t st);
 int vg_fill_cls_launch(bf16* x, const float* cls, int B, int S, int E, unsigned dthr, unsigned dkey, float dscale, const unsigned* dstep,
