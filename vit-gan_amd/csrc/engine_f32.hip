@@ -14,51 +14,36 @@ struct F32Ws {
   float *g[2], *gm, *gmid, *dz1, *dxn, *dao, *dqkv, *gt, *dtiles, *du, *dcn, *part, *slab;
 };
 
-struct Carve {
-  unsigned char* base; long long off;
-  float* take(long long n) {
-    float* p = base ? (float*)(base + off) : nullptr;
-    off += (n * 4 + 255) & ~255LL;
-    return p;
-  }
-};
-
 long long lmax(long long a, long long b) { return a > b ? a : b; }
 
 long long carve_f32(const VgVitDims& d, int B, void* base, F32Ws& w) {
   const long long E = d.E, NP = (long long)(d.IH / d.P) * (d.IH / d.P), S = NP + 1, M = (long long)B * S, L = d.L;
   const long long Kp = (long long)d.C * d.P * d.P, rE = (long long)d.R * E, T = (long long)B * NP;
-  Carve c{(unsigned char*)base, 0};
-  w.tiles = c.take(T * Kp); w.tok = c.take(T * E);
-  w.X = c.take((L + 1) * M * E);
-  w.xn1 = c.take(L * M * E); w.qkv = c.take(L * M * 3 * E); w.ao = c.take(L * M * E);
-  w.xmid = c.take(L * M * E); w.xn2 = c.take(L * M * E);
-  w.z1 = c.take(L * M * rE); w.a1 = c.take(L * M * rE);
-  w.lse = c.take(L * B * d.H * S);
-  w.mean1 = c.take(L * M); w.rstd1 = c.take(L * M); w.mean2 = c.take(L * M); w.rstd2 = c.take(L * M);
-  w.cn = c.take(B * E); w.meanf = c.take(B); w.rstdf = c.take(B); w.th = c.take(B * E);
-  w.g[0] = c.take(M * E); w.g[1] = c.take(M * E);
-  w.gm = c.take(M * E); w.gmid = c.take(M * E); w.dz1 = c.take(M * rE); w.dxn = c.take(M * E); w.dao = c.take(M * E);
-  w.dqkv = c.take(M * 3 * E); w.gt = c.take(T * E); w.dtiles = c.take(T * Kp);
-  w.du = c.take(B * E); w.dcn = c.take(B * E);
+  Carver c{(unsigned char*)base, 0};
+  w.tiles = c.take<float>(T * Kp); w.tok = c.take<float>(T * E);
+  w.X = c.take<float>((L + 1) * M * E);
+  w.xn1 = c.take<float>(L * M * E); w.qkv = c.take<float>(L * M * 3 * E); w.ao = c.take<float>(L * M * E);
+  w.xmid = c.take<float>(L * M * E); w.xn2 = c.take<float>(L * M * E);
+  w.z1 = c.take<float>(L * M * rE); w.a1 = c.take<float>(L * M * rE);
+  w.lse = c.take<float>(L * B * d.H * S);
+  w.mean1 = c.take<float>(L * M); w.rstd1 = c.take<float>(L * M); w.mean2 = c.take<float>(L * M); w.rstd2 = c.take<float>(L * M);
+  w.cn = c.take<float>(B * E); w.meanf = c.take<float>(B); w.rstdf = c.take<float>(B); w.th = c.take<float>(B * E);
+  w.g[0] = c.take<float>(M * E); w.g[1] = c.take<float>(M * E);
+  w.gm = c.take<float>(M * E); w.gmid = c.take<float>(M * E); w.dz1 = c.take<float>(M * rE); w.dxn = c.take<float>(M * E); w.dao = c.take<float>(M * E);
+  w.dqkv = c.take<float>(M * 3 * E); w.gt = c.take<float>(T * E); w.dtiles = c.take<float>(T * Kp);
+  w.du = c.take<float>(B * E); w.dcn = c.take<float>(B * E);
   long long part = (long long)vg_f32_colsum_parts((int)M) * lmax(lmax(3 * E, rE), 2 * E);
   part = lmax(part, (long long)vg_f32_colsum_parts(B) * S * E);
   part = lmax(part, (long long)vg_f32_colsum_parts((int)T) * E);
-  w.part = c.take(part);
+  w.part = c.take<float>(part);
   long long slab = vg_f32_wgrad_slab_floats((int)M, (int)(3 * E), (int)E);
   slab = lmax(slab, vg_f32_wgrad_slab_floats((int)M, (int)rE, (int)E));
   slab = lmax(slab, vg_f32_wgrad_slab_floats((int)M, (int)E, (int)rE));
   slab = lmax(slab, vg_f32_wgrad_slab_floats((int)T, (int)E, (int)Kp));
   slab = lmax(slab, vg_f32_wgrad_slab_floats(B, (int)E, (int)E));
   slab = lmax(slab, vg_f32_wgrad_slab_floats(B, d.Kc, (int)E));
-  w.slab = c.take(slab);
+  w.slab = c.take<float>(slab);
   return c.off;
-}
-
-struct F32Drop { unsigned thr; float scale; unsigned long long seed; const unsigned* step; };
-F32Drop f32_drop(float p, unsigned long long seed, const unsigned* step) {
-  F32Drop d; int t = (int)lrintf(p * 256.f); if (t < 0) t = 0; if (t > 255) t = 255;  // quantised to 1/256 like the bf16 engine
-  d.thr = (unsigned)t; d.scale = t ? 256.f / (256.f - (float)t) : 1.f; d.seed = seed; d.step = step; return d;
 }
 
 int f32_tokens(const VgVitDims& d) { return (d.IH / d.P) * (d.IH / d.P) + 1; }
@@ -90,7 +75,7 @@ extern "C" int vg_vit_forward_f32(const VgVitNet* net, int B, const float* img, 
   const long long ME = (long long)M * E;
   F32Ws w; carve_f32(d, B, ws, w);
   const float* P = net->P;
-  const F32Drop dr = f32_drop(net->dropout_p, net->dropout_seed, net->dropout_step);  // sites: 0 embedding, 1+2l attention, 2+2l MLP
+  const Drop dr = mk_drop(net->dropout_p, net->dropout_seed, net->dropout_step);  // sites: 0 embedding, 1+2l attention, 2+2l MLP
   auto key = [&](int site) { return dr.thr ? vg_site_key(dr.seed, site) : 0u; };
 
   // patch embedding (modules.py:82-100): per-patch GEMM + bias, + pos_embedding, CLS row, dropout
@@ -134,7 +119,7 @@ extern "C" int vg_vit_backward_f32(const VgVitNet* net, int B, void* ws, const f
   F32Ws w; carve_f32(d, B, ws, w);
   const float* P = net->P;
   float* G = net->G;
-  const F32Drop dr = f32_drop(net->dropout_p, net->dropout_seed, net->dropout_step);
+  const Drop dr = mk_drop(net->dropout_p, net->dropout_seed, net->dropout_step);
   auto key = [&](int site) { return dr.thr ? vg_site_key(dr.seed, site) : 0u; };
   const bool wg = want_wgrad != 0;
 
@@ -197,7 +182,7 @@ extern "C" int vg_linear_f32_fwd(const float* X, const float* W, const float* bi
   if (!X || !W || !Y) return -1;
   if (M < 1 || N < 1 || K < 1) return -2;
   if (act < 0 || act > 2 || drop_p < 0.f || drop_p >= 1.f) return -4;
-  const F32Drop dr = f32_drop(drop_p, seed, step_dev);
+  const Drop dr = mk_drop(drop_p, seed, step_dev);
   return vg_f32_linear_fwd(X, W, bias, res, Y, Z, M, N, K, act, dr.thr, dr.thr ? vg_site_key(seed, site) : 0u, dr.scale, dr.step,
                            (hipStream_t)stream);
 }

@@ -100,6 +100,21 @@ static inline unsigned vg_site_key(unsigned long long seed, int site) {
   return (unsigned)(z ^ (z >> 32));
 }
 
+// host helpers of the whole-network passes (engine.hip, engine_f32.hip): the workspace carver and the dropout of a call
+struct Carver {
+  unsigned char* base; long long off;
+  template <typename T> T* take(long long n) {
+    T* p = base ? (T*)(base + off) : nullptr;
+    off += ((long long)n * (long long)sizeof(T) + 255) & ~255LL;
+    return p;
+  }
+};
+struct Drop { unsigned thr; float scale; unsigned long long seed; const unsigned* step; };
+static inline Drop mk_drop(float p, unsigned long long seed, const unsigned* step) {  // p quantised to 1/256
+  Drop d; int t = (int)lrintf(p * 256.f); if (t < 0) t = 0; if (t > 255) t = 255;
+  d.thr = (unsigned)t; d.scale = t ? 256.f / (256.f - (float)t) : 1.f; d.seed = seed; d.step = step; return d;
+}
+
 #define VG_TRY(expr)            \
   do {                          \
     int _rc = (expr);           \
