@@ -321,6 +321,39 @@ int vg_gan_loss(const float* logits, float* dlogits, float* loss_out, int n, int
 int vg_gan_loss_pair(const float* logits, float* dlogits, float* loss_out, int n0, int role0, int n1, int role1,
                      int kind, float grad_scale, void* stream);
 
+/* Class conditioning (the reference's live loop hands [B, 10] logits and labels to a loss that cannot take them, so this header is the
+ * definition).  Labels are int32, one per sample; EVERY kernel clamps a label into [0, K) before it indexes anything, so a bad label
+ * selects class 0 or K - 1 and never leaves a buffer.  1 <= K <= 16 throughout (the head kernels' width).
+ *
+ * vg_draw_labels: labels[i] = (k_i K) >> 24,  k_i = h(ks, i) >> 8,  with ks and h exactly the launch key and the counter hash defined for
+ *   vg_diffaug_fwd above (key from (seed, site), mixed with step_dev[0] when step_dev != NULL).  k_i is 24 bits and K <= 16, so the product
+ *   stays inside 32 bits.  Reproducible per (seed, site, step), fresh on every replay of a captured graph.  The fused step draws its fake
+ *   labels with the seed of its augmentation draws and site 3 (DiffAugment uses sites 0 and 1, bCR's transform site 2).
+ *   -1: null labels or n < 1;  -2: K outside [1, 16].
+ * vg_class_add: wmod[n, j] = bf16_rne(float(wmod[n, j]) + float(table[y_n, j])) in place (one fp32 addition, one rounding), wmod bf16 [B, N],
+ *   table bf16 [K, N], y_n = clamp(labels[n]).  16-byte accesses.  -1: a null pointer, B < 1 or N < 1;  -2: K outside [1, 16];
+ *   -3: N % 8 != 0 or wmod / table not 16-byte aligned.
+ * vg_class_grad: s[k, j] = the fp32 sum of dw[n, j] over the n with clamp(labels[n]) == k, formed by ONE accumulator per output element that
+ *   starts at +0 and adds the rows in ascending n (rows of other classes take no part).  accumulate == 0: dtable[k, j] = s[k, j] - a class
+ *   with no sample writes +0;  accumulate == 1: dtable[k, j] = dtable[k, j] + s[k, j] (one addition) - a class with no sample leaves its row
+ *   untouched.  dw fp32 [B, N], dtable fp32 [K, N].  No atomics: bitwise defined.  -1: a null pointer, B < 1 or N < 1;  -2: K outside
+ *   [1, 16] or accumulate not 0 / 1;  -3: N % 4 != 0 or dw / dtable not 16-byte aligned.
+ * vg_gan_loss_cond: the label-selected loss of a K-way head, D(x, y) = D(x)[y] (Mescheder et al. 2018).  logits, dlogits fp32 [n, Kc]; with
+ *   s_i = logits[i, clamp(labels[i])]:  loss_out[0] and d_i are what vg_gan_loss computes on the n values s_i - the same code, the same
+ *   order, the mean over n (not n Kc) - and dlogits[i, k] = (k == y_i) ? d_i : +0, every element written; selected (nullable, fp32 [n])
+ *   receives s_i.  vg_gan_loss_cond_pair: rows [0, n0) with role0 -> loss_out[0], rows [n0, n0 + n1) with role1 -> loss_out[1], ONE launch of
+ *   two workgroups like vg_gan_loss_pair; bit-equal to two single calls.  -1: a null logits / labels / dlogits / loss_out or a size < 1;
+ *   -2: kind or a role outside [0, 2], Kc outside [1, 16], or (n0 + n1) Kc >= 2^31.
+ * All argument errors come back before any launch. */
+int vg_draw_labels(int* labels, int n, int K, unsigned long long seed, int site, const unsigned* step_dev, void* stream);
+int vg_class_add(void* wmod_bf16 /*[B, N]*/, const void* table_bf16 /*[K, N]*/, const int* labels, int B, int N, int K, void* stream);
+int vg_class_grad(const float* dw /*[B, N]*/, const int* labels, float* dtable /*[K, N]*/, int B, int N, int K, int accumulate,
+                  void* stream);
+int vg_gan_loss_cond(const float* logits /*[n, Kc]*/, const int* labels, float* dlogits /*[n, Kc]*/, float* selected /*[n], nullable*/,
+                     float* loss_out, int n, int Kc, int kind, int role, float grad_scale, void* stream);
+int vg_gan_loss_cond_pair(const float* logits, const int* labels, float* dlogits, float* selected, float* loss_out /*[2]*/, int n0,
+                          int role0, int n1, int role1, int Kc, int kind, float grad_scale, void* stream);
+
 /* Balanced consistency regularisation (bCR, Zhao et al. 2020; the reference has none, so this header is its definition) between the
  * discriminator's logits on a batch x and on its augmented partner a = T(x).  logits_x, logits_a, dlog_x, dlog_a: fp32 [B_real + B_fake, Kc],
  * the B_real real images first; the four must not overlap.  Per segment s (real: images [0, B_real), weight w_real; fake: the B_fake images
@@ -613,6 +646,22 @@ int vg_gen_backward(const VgGenNet* net, int B, void* ws, const void* d_img, voi
  * gradients from layer0 + (L-s)*layer_stride to the end of the flat buffer are final for this backward. */
 int vg_gen_backward_stages(const VgGenNet* net, int B, void* ws, const void* d_img, int stage_begin,
                            int stage_end, void* stream);
+/* The class-conditional generator: w = mapping(z) + class_embedding[y] - the classic cGAN input Linear([z ; onehot(y)]) with its K one-hot
+ * columns evaluated as a gather.  table_bf16 / table_grad: the embedding [K, T*E] as the bf16 shadow the forward reads and the fp32
+ * gradient the backward ACCUMULATES into (table_grad may be NULL for a forward); labels int32 [B] on the device.  The forward is
+ * vg_gen_forward plus one vg_class_add on the mapping output; the backward adds one vg_class_grad in stage L+1, beside the mapping bias's
+ * column sum.  cond == NULL is exactly the plain call (vg_gen_forward / _backward / _backward_stages ARE these with NULL).
+ * -1: a null labels / table (backward: table_grad);  -2: K outside [1, 16] - before any launch. */
+typedef struct VgGenCond {
+  const int* labels;
+  const void* table_bf16;
+  float* table_grad;
+  int K;
+} VgGenCond;
+int vg_gen_forward_cond(const VgGenNet* net, int B, const float* z, void* ws, void* img, const VgGenCond* cond, void* stream);
+int vg_gen_backward_cond(const VgGenNet* net, int B, void* ws, const void* d_img, const VgGenCond* cond, void* stream);
+int vg_gen_backward_stages_cond(const VgGenNet* net, int B, void* ws, const void* d_img, int stage_begin, int stage_end,
+                                const VgGenCond* cond, void* stream);
 
 #ifdef __cplusplus
 }

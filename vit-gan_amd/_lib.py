@@ -61,6 +61,10 @@ class VgGenNet(C.Structure):
                 ("dropout_p", c_float), ("dropout_seed", C.c_ulonglong), ("dropout_step", c_void_p), ("pos_table", c_void_p)]
 
 
+class VgGenCond(C.Structure):
+    _fields_ = [("labels", c_void_p), ("table_bf16", c_void_p), ("table_grad", c_void_p), ("K", c_int)]
+
+
 class VgSpectralDesc(C.Structure):
     _fields_ = ([("w_off", c_ll), ("N", c_int), ("K", c_int)] + [(n, c_ll) for n in ("u_off", "v_off", "s_off", "t_off", "w_tmp_off", "dot_off")]
                 + [(n, c_int) for n in ("blk_a", "blk_b", "blk_c", "reserved")])
@@ -167,6 +171,14 @@ _SIGNATURES = {
     "vg_gen_ws_bytes": (c_ll, [C.POINTER(VgGenDims), c_int]),
     "vg_gen_forward": (c_int, [C.POINTER(VgGenNet), c_int, P, P, P, P]),
     "vg_gen_backward": (c_int, [C.POINTER(VgGenNet), c_int, P, P, P]),
+    "vg_draw_labels": (c_int, [P, c_int, c_int, C.c_ulonglong, c_int, P, P]),
+    "vg_class_add": (c_int, [P, P, P, c_int, c_int, c_int, P]),
+    "vg_class_grad": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
+    "vg_gan_loss_cond": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
+    "vg_gan_loss_cond_pair": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P]),
+    "vg_gen_forward_cond": (c_int, [C.POINTER(VgGenNet), c_int, P, P, P, C.POINTER(VgGenCond), P]),
+    "vg_gen_backward_cond": (c_int, [C.POINTER(VgGenNet), c_int, P, P, C.POINTER(VgGenCond), P]),
+    "vg_gen_backward_stages_cond": (c_int, [C.POINTER(VgGenNet), c_int, P, P, c_int, c_int, C.POINTER(VgGenCond), P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -487,3 +487,22 @@ extern "C" int vg_ada_update(const float* logits_real, int n, float* state, floa
                              void* stream) {
   return vg_ada_update_launch(logits_real, n, state, target, step_per_image, interval, step_dev, (hipStream_t)stream);
 }
+// ---- class conditioning (elementwise.hip): every argument error comes back from the launchers before any launch ----
+extern "C" int vg_draw_labels(int* labels, int n, int K, unsigned long long seed, int site, const unsigned* step_dev, void* stream) {
+  return vg_draw_labels_launch(labels, n, K, vg_site_key(seed, site), step_dev, (hipStream_t)stream);
+}
+extern "C" int vg_class_add(void* wmod_bf16, const void* table_bf16, const int* labels, int B, int N, int K, void* stream) {
+  return vg_class_add_launch((bf16*)wmod_bf16, (const bf16*)table_bf16, labels, B, N, K, (hipStream_t)stream);
+}
+extern "C" int vg_class_grad(const float* dw, const int* labels, float* dtable, int B, int N, int K, int accumulate, void* stream) {
+  return vg_class_grad_launch(dw, labels, dtable, B, N, K, accumulate, (hipStream_t)stream);
+}
+extern "C" int vg_gan_loss_cond(const float* logits, const int* labels, float* dlogits, float* selected, float* loss_out, int n, int Kc, int kind,
+                                int role, float grad_scale, void* stream) {
+  return vg_gan_loss_cond_launch(logits, labels, dlogits, selected, loss_out, Kc, n, role, 0, 0, kind, grad_scale, (hipStream_t)stream);
+}
+extern "C" int vg_gan_loss_cond_pair(const float* logits, const int* labels, float* dlogits, float* selected, float* loss_out, int n0, int role0,
+                                     int n1, int role1, int Kc, int kind, float grad_scale, void* stream) {
+  if (n1 < 1) return -1;
+  return vg_gan_loss_cond_launch(logits, labels, dlogits, selected, loss_out, Kc, n0, role0, n1, role1, kind, grad_scale, (hipStream_t)stream);
+}

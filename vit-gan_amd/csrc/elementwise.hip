@@ -310,8 +310,12 @@ __global__ __launch_bounds__(256) void vg_step_inputs_kernel(const float* __rest
 // kind: 0 = non-saturating BCE-with-logits (v1 gan.py:16-20 semantics), 1 = hinge.
 // role: 0 = D on real (target 1), 1 = D on fake (target 0), 2 = G (target 1 / -mean).
 // loss_out[0] = mean loss; dlog[i] = d(mean loss)/d logit[i] * grad_scale.
-__device__ __forceinline__ void vg_gan_loss_body(const float* __restrict__ logit, float* __restrict__ dlog, float* __restrict__ loss_out, int n,
-                                                 int kind, int role, float grad_scale) {
+// COND (the label-selected form, D(x, y) = D(x)[y] on a [n, Kc] head): sample i is x = logit[i Kc + y_i], y_i = labels[i] clamped into
+// [0, Kc) before it indexes anything; dlog row i is written whole (the selected element as below, +0 elsewhere), sel[i] = x (nullable).
+// The arithmetic and the reduction order are the one body's: COND changes only where x is read and where d is written.
+template <bool COND>
+__device__ __forceinline__ void vg_gan_loss_body(const float* __restrict__ logit, const int* __restrict__ labels, int Kc, float* __restrict__ dlog,
+                                                 float* __restrict__ sel, float* __restrict__ loss_out, int n, int kind, int role, float grad_scale) {
   __shared__ float red[4];
   float acc = 0.f;
   const float inv = 1.0f / (float)n;
@@ -319,7 +323,9 @@ __device__ __forceinline__ void vg_gan_loss_body(const float* __restrict__ logit
   const float t = (role == 1) ? 0.f : 1.f;      // BCE target
   const float sgn = (role == 1) ? 1.f : -1.f;   // hinge: relu(1 + sgn*x)
   for (int i = threadIdx.x; i < n; i += 256) {
-    const float x = logit[i];
+    int y = 0;
+    if (COND) { y = labels[i]; y = y < 0 ? 0 : (y >= Kc ? Kc - 1 : y); }
+    const float x = COND ? logit[i * Kc + y] : logit[i];
     const float l_ns = fmaxf(x, 0.f) - x * t + log1pf(__expf(-fabsf(x)));
     const float d_ns = 1.f / (1.f + __expf(-x)) - t;
     const float hm = 1.f + sgn * x;
@@ -330,7 +336,13 @@ __device__ __forceinline__ void vg_gan_loss_body(const float* __restrict__ logit
     const float l = (kind == 0) ? l_ns : ((kind == 1) ? l_h : l_w);
     const float d = (kind == 0) ? d_ns : ((kind == 1) ? d_h : d_w);
     acc += l;
-    dlog[i] = d * inv * grad_scale;
+    if (COND) {
+      const float g = d * inv * grad_scale;
+      for (int k = 0; k < Kc; ++k) dlog[i * Kc + k] = (k == y) ? g : 0.f;
+      if (sel) sel[i] = x;
+    } else {
+      dlog[i] = d * inv * grad_scale;
+    }
   }
   acc = vg_wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
@@ -340,14 +352,73 @@ __device__ __forceinline__ void vg_gan_loss_body(const float* __restrict__ logit
 __global__ __launch_bounds__(256) void vg_gan_loss_kernel(const float* __restrict__ logit, float* __restrict__ dlog,
                                                           float* __restrict__ loss_out, int n, int kind, int role,
                                                           float grad_scale) {
-  vg_gan_loss_body(logit, dlog, loss_out, n, kind, role, grad_scale);
+  vg_gan_loss_body<false>(logit, nullptr, 1, dlog, nullptr, loss_out, n, kind, role, grad_scale);
 }
 // Two segments of one logit vector (the fused real + fake discriminator pass): workgroup i takes segment i.
 __global__ __launch_bounds__(256) void vg_gan_loss_pair_kernel(const float* __restrict__ logit, float* __restrict__ dlog,
                                                                float* __restrict__ loss_out, int n0, int role0, int n1, int role1, int kind,
                                                                float grad_scale) {
-  if (blockIdx.x == 0) vg_gan_loss_body(logit, dlog, loss_out, n0, kind, role0, grad_scale);
-  else vg_gan_loss_body(logit + n0, dlog + n0, loss_out + 1, n1, kind, role1, grad_scale);
+  if (blockIdx.x == 0) vg_gan_loss_body<false>(logit, nullptr, 1, dlog, nullptr, loss_out, n0, kind, role0, grad_scale);
+  else vg_gan_loss_body<false>(logit + n0, nullptr, 1, dlog + n0, nullptr, loss_out + 1, n1, kind, role1, grad_scale);
+}
+// The label-selected losses: n rows of [Kc] logits, one label per row.  n1 == 0: one workgroup, one segment; else two, like the pair above
+// (segment 1 = the n1 rows behind the first n0, loss_out[1]).
+__global__ __launch_bounds__(256) void vg_gan_loss_cond_kernel(const float* __restrict__ logit, const int* __restrict__ labels,
+                                                               float* __restrict__ dlog, float* __restrict__ sel, float* __restrict__ loss_out, int Kc,
+                                                               int n0, int role0, int n1, int role1, int kind, float grad_scale) {
+  if (blockIdx.x == 0) vg_gan_loss_body<true>(logit, labels, Kc, dlog, sel, loss_out, n0, kind, role0, grad_scale);
+  else vg_gan_loss_body<true>(logit + n0 * Kc, labels + n0, Kc, dlog + n0 * Kc, sel ? sel + n0 : nullptr, loss_out + 1, n1, kind, role1, grad_scale);
+}
+
+// ---- class conditioning: labels, the class-embedding add of the generator's modulation vector, and its gradient --------------------
+__device__ __forceinline__ int vg_clamp_label(int y, int K) { return y < 0 ? 0 : (y >= K ? K - 1 : y); }
+// labels[i] = (k_i K) >> 24,  k_i = h(ks, i) >> 8  with the launch key ks of the augmentation draws (vg_common.h): uniform over [0, K)
+__global__ __launch_bounds__(256) void vg_draw_labels_kernel(int* __restrict__ labels, int n, int K, unsigned key, const unsigned* __restrict__ dstep) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t ks = vg_drop_word(vg_drop_key(key, dstep), 0u);
+  labels[i] = (int)(((vg_drop_word(ks, (uint32_t)i) >> 8) * (uint32_t)K) >> 24);
+}
+// wmod[n, j] = bf16(float(wmod[n, j]) + float(table[y_n, j])) in place; one thread per 8 columns (16-byte accesses), N % 8 == 0
+__global__ __launch_bounds__(256) void vg_class_add_kernel(bf16* __restrict__ wmod, const bf16* __restrict__ table, const int* __restrict__ labels,
+                                                           int B, int N8, int K) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)B * N8) return;
+  const int n = (int)(i / N8), c = (int)(i - (long long)n * N8);
+  const int y = vg_clamp_label(labels[n], K);
+  bf16x8* dst = (bf16x8*)wmod + i;
+  const bf16x8 a = *dst, t = *((const bf16x8*)table + (long long)y * N8 + c);
+  bf16x8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = vg_f2bf(vg_bf2f(a[j]) + vg_bf2f(t[j]));
+  *dst = o;
+}
+// dtable[k, j] (+)= sum_{n : y_n = k} dw[n, j]: workgroup (column tile, k) walks n = 0 .. B-1 in order, one fp32 accumulator per output
+// element starting at +0, and takes the rows of its class on a wave-uniform branch (the label is a scalar load), so dw is read once
+// over the grid.  Four rows per trip, their loads independent; a row of another class contributes nothing (no add at all).  No atomics.
+__global__ __launch_bounds__(64) void vg_class_grad_kernel(const float* __restrict__ dw, const int* __restrict__ labels, float* __restrict__ dtable,
+                                                          int B, int N4, int K, int accumulate) {
+  const int c = blockIdx.x * 64 + threadIdx.x, k = blockIdx.y;
+  if (c >= N4) return;
+  const f32x4* src = (const f32x4*)dw + c;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  bool any = false;
+  for (int n0 = 0; n0 < B; n0 += 4) {
+    f32x4 v[4];
+    bool m[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int n = n0 + u;
+      m[u] = n < B && vg_clamp_label(labels[n < B ? n : B - 1], K) == k;  // the same in every lane
+      if (m[u]) v[u] = src[(long long)n * N4];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (m[u]) { acc += v[u]; any = true; }
+  }
+  f32x4* dst = (f32x4*)dtable + (long long)k * N4 + c;
+  if (!accumulate) *dst = acc;
+  else if (any) *dst = *dst + acc;
 }
 
 // ---- balanced consistency regularisation on two logit vectors [nb, Kc] (clean x, augmented a) -------------------
@@ -847,6 +918,36 @@ int vg_gan_loss_launch(const float* logit, float* dlog, float* loss_out, int n, 
                        hipStream_t st) {
   if (kind < 0 || kind > 2 || role < 0 || role > 2) return -2;
   hipLaunchKernelGGL(vg_gan_loss_kernel, dim3(1), dim3(256), 0, st, logit, dlog, loss_out, n, kind, role, grad_scale);
+  return (int)hipGetLastError();
+}
+// n1 == 0: the single form (one workgroup).  Every argument error comes back before the launch.
+int vg_gan_loss_cond_launch(const float* logit, const int* labels, float* dlog, float* sel, float* loss_out, int Kc, int n0, int role0, int n1,
+                            int role1, int kind, float grad_scale, hipStream_t st) {
+  if (!logit || !labels || !dlog || !loss_out || n0 < 1 || n1 < 0) return -1;
+  if (kind < 0 || kind > 2 || role0 < 0 || role0 > 2 || role1 < 0 || role1 > 2 || Kc < 1 || Kc > 16) return -2;
+  if (((long long)n0 + n1) * Kc > 0x7FFFFFFFLL) return -2;  // element offsets are 32-bit
+  hipLaunchKernelGGL(vg_gan_loss_cond_kernel, dim3(n1 ? 2 : 1), dim3(256), 0, st, logit, labels, dlog, sel, loss_out, Kc, n0, role0, n1, role1, kind,
+                     grad_scale);
+  return (int)hipGetLastError();
+}
+int vg_draw_labels_launch(int* labels, int n, int K, unsigned key, const unsigned* dstep, hipStream_t st) {
+  if (!labels || n < 1) return -1;
+  if (K < 1 || K > 16) return -2;
+  hipLaunchKernelGGL(vg_draw_labels_kernel, dim3(nblk(n)), dim3(256), 0, st, labels, n, K, key, dstep);
+  return (int)hipGetLastError();
+}
+int vg_class_add_launch(bf16* wmod, const bf16* table, const int* labels, int B, int N, int K, hipStream_t st) {
+  if (!wmod || !table || !labels || B < 1 || N < 1) return -1;
+  if (K < 1 || K > 16) return -2;
+  if ((N & 7) || ((uintptr_t)wmod & 15) || ((uintptr_t)table & 15)) return -3;
+  hipLaunchKernelGGL(vg_class_add_kernel, dim3(nblk((long long)B * (N / 8))), dim3(256), 0, st, wmod, table, labels, B, N / 8, K);
+  return (int)hipGetLastError();
+}
+int vg_class_grad_launch(const float* dw, const int* labels, float* dtable, int B, int N, int K, int accumulate, hipStream_t st) {
+  if (!dw || !labels || !dtable || B < 1 || N < 1) return -1;
+  if (K < 1 || K > 16 || (accumulate & ~1)) return -2;
+  if ((N & 3) || ((uintptr_t)dw & 15) || ((uintptr_t)dtable & 15)) return -3;
+  hipLaunchKernelGGL(vg_class_grad_kernel, dim3(nblk(N / 4, 64), K), dim3(64), 0, st, dw, labels, dtable, B, N / 4, K, accumulate);
   return (int)hipGetLastError();
 }
 static VgAdamwArgs vg_adamw_args(float lr, float b1, float b2, float eps, float wd, int step, const int* step_dev, float gscale) {

@@ -1209,8 +1209,16 @@ int GenPass::dgrad_sln_bwd(const DgradSln& j, int step) const {
   return 0;
 }
 
-extern "C" int vg_gen_forward(const VgGenNet* net, int B, const float* z, void* ws, void* img, void* stream) {
+// the class-conditioning argument of the _cond passes: nullptr = the unconditioned network; else every field is checked before any launch
+static int gen_cond_check(const VgGenNet* net, const VgGenCond* cond, bool backward) {
+  if (!cond) return 0;
+  if (!net || !cond->labels || !cond->table_bf16 || (backward && !cond->table_grad)) return -1;
+  if (cond->K < 1 || cond->K > 16) return -2;
+  return 0;
+}
+extern "C" int vg_gen_forward_cond(const VgGenNet* net, int B, const float* z, void* ws, void* img, const VgGenCond* cond, void* stream) {
   if (!net || !z || !ws || !img || B < 1) return -1;
+  VG_TRY(gen_cond_check(net, cond, false));
   GenPass c;
   VG_TRY(c.begin(net, B, ws, stream));
   const VgGenDims& d = net->d;
@@ -1223,6 +1231,8 @@ extern "C" int vg_gen_forward(const VgGenNet* net, int B, const float* z, void* 
   // mapping network (generator.py:59-61): w = Linear(z) viewed [B*T, E]
   VG_TRY(vg_cast_f32_bf16_launch(z, w.zb, (long long)B * d.Z, st));
   VG_TRY(lin_fwd(w.zb, d.Z, Pb + lay.map_w, P + lay.map_b, w.wmod, B, T * E, VG_ACT_NONE, 0.f, nullptr, nullptr, nullptr, st));
+  if (cond)  // w += class_embedding[y]: the K one-hot input columns of the mapping Linear, as a gather
+    VG_TRY(vg_class_add_launch(w.wmod, (const bf16*)cond->table_bf16, cond->labels, B, T * E, cond->K, st));
   if (sh.rown) VG_TRY(gen_pack_weights(sh, lay, Pb, w.wpack, st));
 
   for (int l = 0; l < sh.L; ++l) {
@@ -1263,6 +1273,10 @@ extern "C" int vg_gen_forward(const VgGenNet* net, int B, const float* z, void* 
   return 0;
 }
 
+extern "C" int vg_gen_forward(const VgGenNet* net, int B, const float* z, void* ws, void* img, void* stream) {
+  return vg_gen_forward_cond(net, B, z, ws, img, nullptr, stream);
+}
+
 // K slices of a grouped weight-gradient launch over `nblocks` generator blocks (three problems each)
 static int gen_block_splits(const GenShape& sh, int nblocks, int cap) {
   const int E = sh.E;
@@ -1293,10 +1307,11 @@ int GenPass::bwd_wgrad(int la, int nb, int splits, const bf16* gb1, const bf16* 
 // Backward stages: 0 = SIREN output layers + final SLN, 1..L = blocks L-1 .. 0, L+1 = learned embedding + mapping Linear.
 // After a call returning stages up to s (1 <= s <= L) the gradients of blocks >= L-s and of everything behind the blocks
 // (final SLN, SIREN) - a contiguous tail of the flat buffer from layer0 + (L-s)*layer_stride - are final.
-extern "C" int vg_gen_backward_stages(const VgGenNet* net, int B, void* ws, const void* d_img, int stage_begin, int stage_end,
-                                      void* stream) {
+extern "C" int vg_gen_backward_stages_cond(const VgGenNet* net, int B, void* ws, const void* d_img, int stage_begin, int stage_end,
+                                           const VgGenCond* cond, void* stream) {
   if (!net || !ws || !d_img || !net->G || B < 1) return -1;
   if (stage_begin < 0 || stage_end > net->d.L + 2 || stage_begin >= stage_end) return -2;
+  VG_TRY(gen_cond_check(net, cond, true));
   GenPass c;
   VG_TRY(c.begin(net, B, ws, stream));
   const VgGenDims& d = net->d;
@@ -1373,6 +1388,8 @@ extern "C" int vg_gen_backward_stages(const VgGenNet* net, int B, void* ws, cons
   VG_TRY(vg_slab_reduce_launch(w.emb_sum, 0, 1, G + lay.emb, (long long)T * E, 1, st));
   // mapping Linear: d W = d w^T z ; d b = colsum(d w)   (d w accumulated in fp32 over the 2L+1 SLN uses)
   VG_TRY(vg_colsum_f32_launch(w.dw_acc, B, T * E, G + lay.map_b, T * E, nullptr, 0, nullptr, 0, nullptr, 0, 1, st));
+  if (cond)  // class embedding: row k = the sum of d w over the samples of class k (accumulated, like every gradient)
+    VG_TRY(vg_class_grad_launch(w.dw_acc, cond->labels, cond->table_grad, B, T * E, cond->K, 1, st));
   VG_TRY(vg_cast_f32_bf16_launch(w.dw_acc, w.dwb, sh.RE, st));
   {
     // K = B rows only: one K slice, accumulated straight into the gradient buffer (a 50 MB slab and its fold pass saved)
@@ -1383,7 +1400,14 @@ extern "C" int vg_gen_backward_stages(const VgGenNet* net, int B, void* ws, cons
   return 0;
 }
 
-extern "C" int vg_gen_backward(const VgGenNet* net, int B, void* ws, const void* d_img, void* stream) {
+extern "C" int vg_gen_backward_stages(const VgGenNet* net, int B, void* ws, const void* d_img, int stage_begin, int stage_end,
+                                      void* stream) {
+  return vg_gen_backward_stages_cond(net, B, ws, d_img, stage_begin, stage_end, nullptr, stream);
+}
+extern "C" int vg_gen_backward_cond(const VgGenNet* net, int B, void* ws, const void* d_img, const VgGenCond* cond, void* stream) {
   if (!net) return -1;
-  return vg_gen_backward_stages(net, B, ws, d_img, 0, net->d.L + 2, stream);
+  return vg_gen_backward_stages_cond(net, B, ws, d_img, 0, net->d.L + 2, cond, stream);
+}
+extern "C" int vg_gen_backward(const VgGenNet* net, int B, void* ws, const void* d_img, void* stream) {
+  return vg_gen_backward_cond(net, B, ws, d_img, nullptr, stream);
 }

@@ -74,6 +74,15 @@ int vg_gan_loss_pair_launch(const float* logit, float* dlog, float* loss_out, in
                             hipStream_t st);
 int vg_gan_loss_launch(const float* logit, float* dlog, float* loss_out, int n, int kind, int role, float grad_scale,
                        hipStream_t st);
+// the label-selected losses on [n0 + n1, Kc] logits (sample i = logit[i, labels[i]], the label clamped into [0, Kc)): n1 == 0 one segment,
+// else two like the pair above; dlog is written whole (+0 off the label), sel (nullable) receives the selected logits
+int vg_gan_loss_cond_launch(const float* logit, const int* labels, float* dlog, float* sel, float* loss_out, int Kc, int n0, int role0, int n1,
+                            int role1, int kind, float grad_scale, hipStream_t st);
+// class conditioning (elementwise.hip): label draws keyed like the augmentation (key = vg_site_key(seed, site)), the class-embedding add
+// on the generator's modulation vector and its table gradient
+int vg_draw_labels_launch(int* labels, int n, int K, unsigned key, const unsigned* dstep, hipStream_t st);
+int vg_class_add_launch(bf16* wmod, const bf16* table, const int* labels, int B, int N, int K, hipStream_t st);
+int vg_class_grad_launch(const float* dw, const int* labels, float* dtable, int B, int N, int K, int accumulate, hipStream_t st);
 // consistency loss between two logit vectors [n_real + n_fake, Kc], one workgroup per segment: loss_out[0 / 1] = the segments' means of
 // |lx - la|^2 over their images; dlog_x (+)= g, dlog_a (-)= g with g = (2 w / n) (lx - la) grad_scale
 int vg_bcr_loss_launch(const float* lx, const float* la, float* dlog_x, float* dlog_a, float* loss_out, int n_real, int n_fake, int Kc,

@@ -54,7 +54,7 @@ class GanEngine:
                  exchange_single_rank: bool = False, dense_top_block: bool = False, gp_autograd: bool = False, diffaug: str = "",
                  ema_decay: float = 0.0, ema_start: int = 0, spectral_norm: str = "", bcr=(0.0, 0.0), bcr_aug: str = "",
                  aug_p: Optional[float] = None, ada_target: float = 0.0, ada_interval: int = 4, ada_kimg: float = 500.0,
-                 r1_gamma: float = 0.0, r1_interval: int = 1):
+                 r1_gamma: float = 0.0, r1_interval: int = 1, n_classes: int = 0):
         """concurrent_wgrad: the discriminator's weight gradients on a side stream beside its input gradients.  Off by default
         since the persistent GEMMs (csrc/gemm_wr.hip, gemm_tn.hip: their workgroups hold the CUs for a whole launch) - the
         side stream measured 6.70 against 6.67 ms/step.
@@ -169,7 +169,23 @@ class GanEngine:
         r1_interval: lazy regularisation (Karras et al. 2020) - the penalty runs on step 1 and every ``r1_interval``-th step after it
         (``ops.r1_due`` on the host's step count, which ``state_dict()`` carries), weighted ``r1_interval * r1_gamma / 2``; the other
         steps are plain steps and leave ``r1_loss`` alone.  Under ``use_graph`` the two launch lists are two captured graphs, each
-        warmed up and captured the first time its kind of step occurs."""
+        warmed up and captured the first time its kind of step occurs.
+        n_classes: K > 0 trains a class-conditional pair (the reference hands labels to a loss that cannot take them); it must equal
+        the discriminator's ``classes_count`` and the generator's ``n_classes``.  The discriminator is conditioned by the
+        label-selected logit of its K-way head, D(x, y) = D(x)[y] (Mescheder et al. 2018): vg_gan_loss_cond_pair / vg_gan_loss_cond
+        take the place of the loss launches - the means are over the B samples, every other logit's gradient is +0 - with the real
+        labels on the real rows and the fake labels on the fake rows and in the generator's pass.  The generator adds
+        ``class_embedding[y]`` to its modulation vector (the _cond generator calls: one launch more per direction).  ``step(real,
+        labels=...)`` takes the real labels; the fake labels are drawn on the device, uniform over the classes, by one
+        vg_draw_labels in front of the step, keyed on (seed, rank, device step counter) like the latent batch (augmentation seed,
+        site 3) - or supplied as ``step(real, z, labels, fake_labels)`` under ``external_noise``.  ``real_labels`` / ``fake_labels``
+        hold the last step's, ``selected`` the 2B selected logits of D's own pass.  ADA reads the B selected real logits.  bCR stays on
+        ALL Kc logits of both partners: consistency under augmentation is asked of the whole head, not of one class's logit.
+        ``sample(z, labels)`` draws from the average; ``state_dict()`` records the class count.  0 (default): no buffer, and the
+        step is launch for launch the plain one - a Kc-way head is then B Kc independent samples, as before.  Not with ``gp_weight``
+        / ``r1_gamma`` (the penalty call seeds its first backward with ones over all Kc logits and folds that into its second-order
+        head: a label-selected seed is a follow-up), ``two_stream``, or a process group of more than one rank (the staged exchange of
+        the generator's gradient treats the tail of the flat buffer as final after stage 1; the table is final after stage L+1)."""
         self._check_options(discriminator, generator, dict(locals()))
         self._carve()
         self._attach()
@@ -227,6 +243,22 @@ class GanEngine:
             if bool(getattr(vit, "attention_fp8", False)):
                 raise ValueError("r1_gamma: the R1 penalty is built on the bf16 attention kernels; switch attention_fp8 off")
             vit.require_short_attention("r1_gamma > 0 (the R1 penalty)")
+        self.n_classes = K = o["n_classes"]
+        if isinstance(K, bool) or not isinstance(K, int) or not 0 <= K <= 16:
+            raise ValueError(f"n_classes must be an integer in [0, 16] (0 = unconditional), got {K!r}")
+        if K or generator.n_classes:
+            if not (vit._dims.Kc == generator.n_classes == K):
+                raise ValueError(f"n_classes: the discriminator's head, the generator's table and the engine must agree - classes_count="
+                                 f"{vit._dims.Kc}, generator.n_classes={generator.n_classes}, n_classes={K}")
+            if self.gp_w != 0.0 or self.r1:
+                raise ValueError("n_classes: the gradient penalties (gp_weight, r1_gamma) seed their first backward with ones over all Kc "
+                                 "logits; a label-selected penalty is not built - switch the penalty off")
+            if two_stream:
+                raise ValueError("n_classes: the conditional step is verified on the single-chain schedule only; switch two_stream off")
+            if world > 1:
+                raise ValueError("n_classes: the staged gradient exchange treats the tail of the generator's flat buffer as final after "
+                                 "stage 1, the class table is final after stage L+1; data parallelism over more than one rank is not built")
+        self.cond = K > 0
         self.vit, self.gen, self._disc = vit, generator, discriminator
         if loss not in LOSS_KINDS:
             raise ValueError(f"loss must be one of {sorted(LOSS_KINDS)}")
@@ -330,6 +362,13 @@ class GanEngine:
         if self.bcr or self.ada:  # the generator's pass gets rows of its own, so ``logits`` still holds D's whole pass after the step
             self.logits_g, self.dlogits_g = rows(B), rows(B)
         self.z = torch.empty(B, g.Z, dtype=torch.float32, device=dev)
+        # class conditioning: the labels of D's pair [real ; fake] in one buffer (the pair launch reads it whole) and the selected logits
+        self.real_labels = self.fake_labels = self.selected = None
+        if self.cond:
+            self.labels_d = torch.zeros(2 * B, dtype=torch.int32, device=dev)
+            self.real_labels, self.fake_labels = self.labels_d[:B], self.labels_d[B:]
+            self.selected = f32(2 * B)
+            self.sel_half = (self.selected[:B], self.selected[B:])
         self.losses = f32(3)  # d_real, d_fake, g
         self.step_t = torch.zeros(1, dtype=torch.int32, device=dev)
         fd, fg = vit._flat, generator._flat
@@ -439,6 +478,8 @@ class GanEngine:
         tab = self.gen.fourier_table
         ng = _lib.VgGenNet(self.gen._dims, fg.flat.data_ptr(), fg.shadow.data_ptr(), fg.grad.data_ptr(), self.p_g, self.seed * 8 + 7, step_ptr,
                            None if tab is None else tab.data_ptr())
+        if self.cond:  # the generator's passes take the fake labels and the table's shadow and gradient (the _cond calls)
+            self._gcond = self.gen._cond(self.fake_labels)
         if self.two_stream:  # chains run side by side: no third stream inside a pass; the fake chain accumulates into grad2
             return (mk(0, ctx=False), mk(1, self.grad2, ctx=False), mk(2, ctx=False), mk(3, ctx=False)), ng
         return (mk(0), mk(1), mk(2)), ng
@@ -449,7 +490,18 @@ class GanEngine:
 
     def _loss(self, logits, dlogits, n: int, role: int, st) -> None:
         """The loss of n logit rows in ``role`` (0 = D on real, 1 = D on fake, 2 = the generator's) into the role's slot of ``losses``."""
+        if self.cond:  # the label-selected logit of each row: real labels for D on real, the fake labels for D on fake and for G
+            _call("vg_gan_loss_cond", _p(logits), _p(self.fake_labels if role else self.real_labels), _p(dlogits),
+                  _p(self.sel_half[role] if role < 2 else None), _p(self.loss_slot[role]), n, self.Kc, self.kind, role, 1.0, st)
+            return
         _call("vg_gan_loss", _p(logits), _p(dlogits), _p(self.loss_slot[role]), n * self.Kc, self.kind, role, 1.0, st)
+
+    def _g_forward(self, ng, st) -> None:
+        """fake = G(z), conditioned on the fake labels when the engine is class-conditional"""
+        if self.cond:
+            _call("vg_gen_forward_cond", C.byref(ng), self.B, _p(self.z), _p(self.ws_g), _p(self.fake), C.byref(self._gcond), st)
+        else:
+            _call("vg_gen_forward", C.byref(ng), self.B, _p(self.z), _p(self.ws_g), _p(self.fake), st)
 
     def _d_backward(self, nd, n_img: int, ws, dl, want_w: int, dimg, st, exchange: bool = True) -> None:
         """D backward; under data parallelism, when the pass completes D.grad (``exchange``), in ``dp_chunks`` pieces (head + upper
@@ -487,7 +539,10 @@ class GanEngine:
 
     def _ada_update(self, logits_real, st) -> None:
         """The controller on the real rows of the adversarial logits (the first B rows of ``logits_real``); nothing without ADA."""
-        if self.ada:
+        if self.ada and self.cond:  # the B selected real logits D(x, y): what the conditional loss was taken on
+            _call("vg_ada_update", _p(self.sel_half[0]), self.B, _p(self.ada_state), self.ada_target, self.ada_step_per_image,
+                  self.ada_interval, _p(self.step_t), st)
+        elif self.ada:
             _call("vg_ada_update", _p(logits_real), self.B * self.Kc, _p(self.ada_state), self.ada_target, self.ada_step_per_image,
                   self.ada_interval, _p(self.step_t), st)
 
@@ -548,11 +603,18 @@ class GanEngine:
         with the last kernel; its 50 MB mapping-weight part goes over the links as bf16."""
         fg = self.gen._flat
         if not self.sync.active:
-            _call("vg_gen_backward", C.byref(ng), self.B, _p(self.ws_g), _p(self.dfake), st)
+            if self.cond:
+                _call("vg_gen_backward_cond", C.byref(ng), self.B, _p(self.ws_g), _p(self.dfake), C.byref(self._gcond), st)
+            else:
+                _call("vg_gen_backward", C.byref(ng), self.B, _p(self.ws_g), _p(self.dfake), st)
             return
         lay = flat.gen_layout(self.gen._dims)
-        for s0, s1, lo, hi in backward_pieces(self.gen._dims.L, self.dp_chunks, lay.layer0, lay.layer_stride, fg.total):
-            _call("vg_gen_backward_stages", C.byref(ng), self.B, _p(self.ws_g), _p(self.dfake), s0, s1, st)
+        # (a class table sits behind the C layout and is final with the LAST stage: the pieces tile the C layout, the table follows them)
+        for s0, s1, lo, hi in backward_pieces(self.gen._dims.L, self.dp_chunks, lay.layer0, lay.layer_stride, lay.total if self.cond else fg.total):
+            if self.cond:
+                _call("vg_gen_backward_stages_cond", C.byref(ng), self.B, _p(self.ws_g), _p(self.dfake), s0, s1, C.byref(self._gcond), st)
+            else:
+                _call("vg_gen_backward_stages", C.byref(ng), self.B, _p(self.ws_g), _p(self.dfake), s0, s1, st)
             if lo == 0 and (self.compress_map or self.shard_map):  # [embedding | mapping weight | mapping bias, lowest blocks]
                 w0, w1 = self._map_range()
                 self.sync.reduce_range(fg.grad, 0, w0)
@@ -563,6 +625,8 @@ class GanEngine:
                 self.sync.reduce_range(fg.grad, w1, hi)
             else:
                 self.sync.reduce_range(fg.grad, lo, hi)
+        if self.cond:
+            self.sync.reduce_range(fg.grad, lay.total, fg.total)
 
     @property
     def ada_p(self) -> float:
@@ -641,7 +705,7 @@ class GanEngine:
         _call("vg_gen_backward", C.byref(ng), B, _p(self.ws_g), _p(self.dfake), st0)
         self._adamw(self.r_g, self.hyp["lr_g"], st0, self.clip_g, 1)
 
-    def _inputs(self, real: torch.Tensor) -> None:
+    def _inputs(self, real: torch.Tensor, labels=None, fake_labels=None) -> None:
         """The step's inputs, ONE launch in front of the step proper (and outside its hipGraph, so it reads the caller's tensor
         directly - no staging copy): imgs[:B] = bf16(real), and unless the caller supplies it, the latent batch z ~ N(0, 1)
         (construct_noise(), training.py:35-42 / gan.py:231-232), counter-based on (seed, rank, steps done so far)."""
@@ -656,6 +720,12 @@ class GanEngine:
         if direct or want_z:
             _call("vg_step_inputs", _p(real) if direct else None, _p(self.imgs), real.numel() if direct else 0,
                   _p(self.z) if want_z else None, self.z.numel() if want_z else 0, self._noise_seed, _p(self.step_t), st)
+        if self.cond:  # the real labels into their static buffer; the fake ones supplied with z, or drawn like z: one launch, keyed on the counter
+            self.real_labels.copy_(labels)
+            if fake_labels is not None:
+                self.fake_labels.copy_(fake_labels)
+            else:
+                _call("vg_draw_labels", _p(self.fake_labels), self.B, self.n_classes, self._aug_seed, 3, _p(self.step_t), st)
 
     def _penalty(self, st) -> None:
         """gradient_penalty(D, noisy_real, noisy_fake) joins the D loss (training.py:101-106), on what D's own pass sees."""
@@ -698,7 +768,7 @@ class GanEngine:
         fd, fg = self.vit._flat, self.gen._flat
         # gan.discriminator.zero_grad() (training.py:177) and the device step counter += 1, one launch
         _call("vg_zero_tick", _p(fd.grad), fd.total, _p(self.step_t), st)
-        _call("vg_gen_forward", C.byref(ng), B, _p(self.z), _p(self.ws_g), _p(self.fake), st)
+        self._g_forward(ng, st)
         if self.inst_sigma > 0.0:
             self._instance_noise(self.noise_parts[0])
         if self.aug:  # D sees T_1([real ; fake]) (site 0), and so does the penalty below
@@ -713,7 +783,11 @@ class GanEngine:
             n, src, adv, dadv = self.d_pass
             self._d_forward(nd, n, src, self.ws_d, self.logits, st)
             # D(real) -> slot 0, D(fake) -> slot 1: both halves of the adversarial rows in one launch
-            _call("vg_gan_loss_pair", _p(adv), _p(dadv), _p(self.losses), B * self.Kc, 0, B * self.Kc, 1, self.kind, 1.0, st)
+            if self.cond:  # ... on the label-selected logit of each row: the means are over B samples, the other logits get +0
+                _call("vg_gan_loss_cond_pair", _p(adv), _p(self.labels_d), _p(dadv), _p(self.selected), _p(self.losses), B, 0, B, 1, self.Kc,
+                      self.kind, 1.0, st)
+            else:
+                _call("vg_gan_loss_pair", _p(adv), _p(dadv), _p(self.losses), B * self.Kc, 0, B * self.Kc, 1, self.kind, 1.0, st)
             self._ada_update(adv, st)
             if self.bcr:
                 _call("vg_bcr_loss", *map(_p, self.cr_rows), _p(self.bcr_losses), B, B, self.Kc, self.bcr_w[0], self.bcr_w[1],
@@ -758,6 +832,7 @@ class GanEngine:
         return (("spectral_state", self.spec.state if spec else None, "spectral_norm", lambda: self.spectral_norm if spec else None),
                 (None, None, "bcr", self._bcr_options),
                 (None, None, "r1", self._r1_options),
+                (None, None, "n_classes", lambda: self.n_classes or None),
                 ("ada_state", self.ada_state, "ada", self._ada_options),
                 ("ema_g", self.ema_g, None, None))
 
@@ -790,12 +865,15 @@ class GanEngine:
     def _need_ema(self, what: str) -> torch.Tensor:
         return self._need(self.ema_g, f"{what}: this engine keeps no averaged generator (built with ema_decay=0)")
 
-    def sample(self, z: torch.Tensor, ema: bool = True) -> torch.Tensor:
-        """Images [n, C, IH, IW] (``generator.out_dtype``) of the latent batch ``z`` [n, Z], n any batch size: one forward-only
+    def sample(self, z: torch.Tensor, labels=None, ema: bool = True) -> torch.Tensor:
+        """Images [n, C, IH, IW] (``generator.out_dtype``) of the latent batch ``z`` [n, Z], n any batch size - of the classes ``labels``
+        (an integer tensor [n] on the device, required iff the engine is class-conditional; checked on the host): one forward-only
         vg_gen_forward without dropout on the current stream, from the averaged weights (``ema=True``: ``ema_g`` and a bf16 cast of
         it, recast only after a step or a load) or from the live master and shadow (``ema=False``: what ``G.eval()(z)`` computes).
         It has its own workspace - the step's belongs to the captured graph - and changes no training state."""
         gen, fg = self.gen, self.gen._flat
+        if isinstance(labels, bool):  # sample(z, False): the flag in its old position
+            labels, ema = None, labels
         if ema:
             self._need_ema("sample(ema=True)")
         if z.dim() != 2 or z.shape[1] != gen._dims.Z or z.shape[0] < 1 or z.device != self.dev:
@@ -820,7 +898,12 @@ class GanEngine:
         net = _lib.VgGenNet(gen._dims, master.data_ptr(), shadow.data_ptr(), fg.grad.data_ptr(), 0.0, 0, None, None if tab is None else tab.data_ptr())
         zin = z.detach().float().contiguous()
         img = torch.empty(n, gen.channels, gen.image_size, gen.image_size, dtype=torch.bfloat16, device=self.dev)
-        _call("vg_gen_forward", C.byref(net), n, _p(zin), _p(self._sample_ws), _p(img), st)
+        y = gen._labels(labels, int(z.shape[0]), self.dev)
+        if y is None:
+            _call("vg_gen_forward", C.byref(net), n, _p(zin), _p(self._sample_ws), _p(img), st)
+        else:
+            cond = _lib.VgGenCond(y.data_ptr(), shadow.data_ptr() + 2 * gen._class_off, None, self.n_classes)
+            _call("vg_gen_forward_cond", C.byref(net), n, _p(zin), _p(self._sample_ws), _p(img), C.byref(cond), st)
         return img.to(gen.out_dtype)
 
     def ema_state_dict(self) -> dict:
@@ -902,6 +985,8 @@ class GanEngine:
         if strict and saved_ada != self._ada_options():
             raise ValueError(f"engine state was saved with (aug_p, ada_target, ada_interval, ada_kimg) = {saved_ada!r}, this engine has "
                              f"{self._ada_options()!r} (strict=False loads the probability all the same when both sides hold one)")
+        if int(sd.get("n_classes") or 0) != self.n_classes:  # (strict or not: the generator's buffers differ in size)
+            raise ValueError(f"engine state was saved with n_classes={int(sd.get('n_classes') or 0)}, this engine has n_classes={self.n_classes}")
         saved_r1 = None if sd.get("r1") is None else tuple(sd["r1"])
         if strict and saved_r1 != self._r1_options():
             raise ValueError(f"engine state was saved with the R1 penalty (r1_gamma, r1_interval) = {saved_r1!r}, this engine has "
@@ -931,22 +1016,33 @@ class GanEngine:
             self.spec.measure(self.vit._flat.flat)
         self.sync_from_modules()
 
-    def step(self, real: torch.Tensor, z: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def step(self, real: torch.Tensor, z: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
+             fake_labels: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Run one G/D step on ``real`` [B,C,IH,IW] (cuda).  Returns the device tensor
         [loss_d_real, loss_d_fake, loss_g] of this step without synchronising.  ``z`` [B, Z]: the latent batch, required
-        iff the engine was built with ``external_noise=True``."""
+        iff the engine was built with ``external_noise=True``.  ``labels`` [B]: the classes of ``real``, an integer cuda tensor,
+        required iff the engine is class-conditional; ``fake_labels`` [B]: the classes the generator is asked for, required together
+        with ``z`` and drawn on the device otherwise.  The values are not read on the host (no synchronisation): the kernels clamp
+        a label into [0, n_classes) before they use it."""
         if real.shape[0] != self.B or not real.is_cuda:
             raise ValueError("real must be a cuda tensor with the engine's batch size")
         if (z is not None) != self.external_noise:
             raise ValueError("pass z exactly when the engine was built with external_noise=True")
         if not (self.vit._flat.aliased() and self.gen._flat.aliased()):
             raise RuntimeError("module parameters were re-allocated; rebuild the GanEngine")
+        if (labels is not None) != self.cond:
+            raise ValueError(f"pass labels exactly when the engine is class-conditional (n_classes={self.n_classes})")
+        if (fake_labels is not None) != (self.cond and self.external_noise):
+            raise ValueError("pass fake_labels exactly when a class-conditional engine was built with external_noise=True")
+        for name, t in (("labels", labels), ("fake_labels", fake_labels)):
+            if t is not None and (not torch.is_tensor(t) or t.is_floating_point() or t.dtype == torch.bool or tuple(t.shape) != (self.B,) or not t.is_cuda):
+                raise ValueError(f"{name} must be an integer cuda tensor of shape [{self.B}]")
         if z is not None:
             self.z.copy_(z)
         self.steps += 1
         due = self.r1 and ops.r1_due(self.steps, self.r1_interval)  # the kind of step: a launch list, and a captured graph, of its own
         if not self._use_graph:
-            self._inputs(real)
+            self._inputs(real, labels, fake_labels)
             self._enqueue_body(due)  # the whole step on the current stream, no host sync
             return self.losses
         if due not in self._graphs:
@@ -955,7 +1051,7 @@ class GanEngine:
             # mode exactly as in eager mode (tests compare the two bit for bit).
             saved = [t.clone() for t in self._state_tensors()]
             s = torch.cuda.Stream()
-            self._inputs(real)
+            self._inputs(real, labels, fake_labels)
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
                 self._enqueue_body(due)
@@ -985,10 +1081,10 @@ class GanEngine:
                 self.sync._pending.clear()
                 self._graph_fallback(f"capturing the step ({'collectives' if self.sync.active else 'gradient penalty through torch autograd'}) failed: "
                                      f"{type(exc).__name__}: {exc}")
-                self._inputs(real)
+                self._inputs(real, labels, fake_labels)
                 self._enqueue_body(due)
                 return self.losses
             self._graphs[due] = graph
-        self._inputs(real)
+        self._inputs(real, labels, fake_labels)
         self._graphs[due].replay()
         return self.losses

@@ -101,6 +101,16 @@ def gen_slots(d: _lib.VgGenDims) -> "OrderedDict[str, Slot]":
     return s
 
 
+CLASS_TABLE_KEY = "class_embedding.weight"
+
+
+def gen_class_table(d: _lib.VgGenDims, n_classes: int) -> Tuple[int, int]:
+    """(offset, total) of a class-conditional generator's flat buffer: the embedding table [K, T*E] sits behind ``vg_gen_layout``'s
+    ``total`` (rounded up to 64 elements - the 16-byte accesses of vg_class_add / vg_class_grad), so every offset of the C layout stays."""
+    off = (gen_layout(d).total + 63) // 64 * 64
+    return off, off + int(n_classes) * d.T * d.E
+
+
 def numel(shape) -> int:
     n = 1
     for x in shape:

@@ -51,7 +51,7 @@ def _sln_holder(E):
 
 class _GenFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, mod: "SirenGenerator", z, anchor, drop_p):
+    def forward(ctx, mod: "SirenGenerator", z, anchor, drop_p, labels=None):
         fp = mod._flat
         fp.refresh_shadow()
         ctx.drop = (float(drop_p), int(torch.randint(0, 2 ** 62, (1,)).item()) if drop_p > 0 else 0)
@@ -60,9 +60,13 @@ class _GenFn(torch.autograd.Function):
         ws = torch.empty(mod._ws_bytes(B), dtype=torch.uint8, device=z.device)
         img = torch.empty(B, mod.channels, mod.image_size, mod.image_size, dtype=torch.bfloat16, device=z.device)
         net = mod._net(ctx.drop)
-        _lib.check(_lib.lib().vg_gen_forward(C.byref(net), B, zin.data_ptr(), ws.data_ptr(), img.data_ptr(),
-                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vg_gen_forward")
-        ctx.mod, ctx.ws, ctx.B = mod, ws, B
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if labels is None:
+            _lib.check(_lib.lib().vg_gen_forward(C.byref(net), B, zin.data_ptr(), ws.data_ptr(), img.data_ptr(), st), "vg_gen_forward")
+        else:
+            _lib.check(_lib.lib().vg_gen_forward_cond(C.byref(net), B, zin.data_ptr(), ws.data_ptr(), img.data_ptr(), C.byref(mod._cond(labels)), st),
+                       "vg_gen_forward_cond")
+        ctx.mod, ctx.ws, ctx.B, ctx.labels = mod, ws, B, labels
         return img.to(mod.out_dtype)
 
     @staticmethod
@@ -71,10 +75,14 @@ class _GenFn(torch.autograd.Function):
         mod._flat.attach_grads()
         d = dimg.detach().to(torch.bfloat16).contiguous()
         net = mod._net(ctx.drop)
-        _lib.check(_lib.lib().vg_gen_backward(C.byref(net), ctx.B, ctx.ws.data_ptr(), d.data_ptr(),
-                                              C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vg_gen_backward")
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if ctx.labels is None:
+            _lib.check(_lib.lib().vg_gen_backward(C.byref(net), ctx.B, ctx.ws.data_ptr(), d.data_ptr(), st), "vg_gen_backward")
+        else:
+            _lib.check(_lib.lib().vg_gen_backward_cond(C.byref(net), ctx.B, ctx.ws.data_ptr(), d.data_ptr(), C.byref(mod._cond(ctx.labels)), st),
+                       "vg_gen_backward_cond")
         ctx.ws = None
-        return None, None, None, None
+        return None, None, None, None, None
 
 
 def fourier_position_table(T: int, E: int, image_size: int, patch_size: int) -> torch.Tensor:
@@ -94,13 +102,21 @@ def fourier_position_table(T: int, E: int, image_size: int, patch_size: int) -> 
 
 class SirenGenerator(nn.Module):
     def __init__(self, latent=1024, image_size=32, channels=3, embed=384, heads=4, layers=4, siren_hidden=768,
-                 omega_0=30.0, out_dtype=torch.float32, dropout=0.2, patch_size=0, fourier_features=False):
+                 omega_0=30.0, out_dtype=torch.float32, dropout=0.2, patch_size=0, fourier_features=False, n_classes=0):
         """``patch_size == 0`` (default): the reference's v1 generator - one token per image row, each emitting
         ``channels * image_size`` values, assembled by a flat ``view`` (src/v1/generator.py:19,25,51,66-68).
         ``patch_size > 0`` (not in the reference): the same blocks on the discriminator's patch
         grid - ``(image_size / patch_size)**2`` tokens, each emitting one ``channels x P x P`` patch in conv1's
-        (c, py, px) order, assembled by the un-patchify scatter.  Scales to 64x64 / 128x128 images (64 tokens)."""
+        (c, py, px) order, assembled by the un-patchify scatter.  Scales to 64x64 / 128x128 images (64 tokens).
+        ``n_classes = K > 0`` (the reference has none): class-modulated self-modulation, w = mapping(z) + class_embedding[y] with a
+        learned table ``class_embedding.weight`` [K, T*E] - the classic cGAN input Linear([z ; onehot(y)]), its K one-hot columns
+        evaluated as a gather (vg_class_add / vg_class_grad).  ``forward(z, labels)`` then needs the labels, an integer tensor [B]
+        on the device with values in [0, K).  The table lives behind the C layout in the same flat buffer, so whatever runs over
+        the buffer (AdamW, the average, clipping, the checkpoint) covers it.  0: the state_dict is the reference's."""
         super().__init__()
+        if isinstance(n_classes, bool) or not isinstance(n_classes, int) or not 0 <= n_classes <= 16:
+            raise ValueError(f"n_classes must be an integer in [0, 16] (0 = unconditional), got {n_classes!r}")
+        self.n_classes = n_classes
         E, hd = embed, embed // heads
         if patch_size:
             if image_size % patch_size:
@@ -140,9 +156,15 @@ class SirenGenerator(nn.Module):
         self.output_network = nn.Sequential(s0, s1)
         self._dims = _lib.VgGenDims(latent, T, E, heads, layers, siren_hidden, out_features, float(omega_0),
                                     self.patch_size, channels, image_size)
-        lay = flat.gen_layout(self._dims)
+        slots, total = flat.gen_slots(self._dims), flat.gen_layout(self._dims).total
+        self._class_off = None
+        if n_classes:  # registered last: the other parameters keep their names, order and init draws
+            self.class_embedding = _Holder()
+            self.class_embedding.weight = nn.Parameter(torch.empty(n_classes, T * E))
+            self._class_off, total = flat.gen_class_table(self._dims, n_classes)
+            slots[flat.CLASS_TABLE_KEY] = (self._class_off, (n_classes, T * E))
         self.reset_parameters()
-        self._flat = FlatParams(dict(self.named_parameters()), flat.gen_slots(self._dims), lay.total)
+        self._flat = FlatParams(dict(self.named_parameters()), slots, total)
 
     def reset_parameters(self):
         """Init distributions of the reference: nn.Linear default U(+-1/sqrt(in)); SIREN U(+-1/in) for
@@ -153,6 +175,9 @@ class SirenGenerator(nn.Module):
             for name, p in self.named_parameters():
                 if name == "embedding" or name.endswith((".beta", ".gamma")):
                     p.normal_()
+                elif name == flat.CLASS_TABLE_KEY:  # the K extra input columns of the mapping Linear it stands for: fan-in = latent
+                    b = 1.0 / math.sqrt(self.latent)
+                    p.uniform_(-b, b)
                 elif "layer_norm.weight" in name:
                     p.fill_(1.0)
                 elif "layer_norm.bias" in name:
@@ -192,10 +217,24 @@ class SirenGenerator(nn.Module):
         return _lib.VgGenNet(self._dims, fp.flat.data_ptr(), fp.shadow.data_ptr(), fp.grad.data_ptr(), float(drop[0]), int(drop[1]), None,
                              None if tab is None else tab.data_ptr())
 
-    def forward(self, z):
+    def _cond(self, labels) -> "_lib.VgGenCond":
+        """the class-conditioning argument of the _cond C calls: the labels, and the table's bf16 shadow and fp32 gradient"""
+        fp, off = self._flat, self._class_off
+        return _lib.VgGenCond(labels.data_ptr(), fp.shadow.data_ptr() + 2 * off, fp.grad.data_ptr() + 4 * off, self.n_classes)
+
+    def _labels(self, labels, B: int, device):
+        """``labels`` checked against this generator (required iff it is class-conditional) as the int32 tensor the kernels read"""
+        if (labels is not None) != bool(self.n_classes):
+            raise ValueError(f"labels are required exactly for a class-conditional generator (n_classes={self.n_classes})")
+        if labels is None:
+            return None
+        from . import ops
+        return ops.check_labels(labels, B, self.n_classes, "SirenGenerator", device)
+
+    def forward(self, z, labels=None):
         if not z.is_cuda:
             raise RuntimeError("SirenGenerator.forward: the HIP engine needs cuda tensors; there is no CPU fallback")
         if not self._flat.aliased():
             self._flat.named = dict(self.named_parameters())
             self._flat.rebuild()
-        return _GenFn.apply(self, z, self.embedding, self.dropout_p if self.training else 0.0)
+        return _GenFn.apply(self, z, self.embedding, self.dropout_p if self.training else 0.0, self._labels(labels, z.shape[0], z.device))

@@ -441,34 +441,39 @@ class ViTDiscriminator(nn.Module):
         return self.vit(x)
 
 
-def generator_from_config(config: Config) -> nn.Module:
-    """``config.generator_kind`` (the one extra Config field, default "v2" = reference behaviour) picks the generator."""
+def generator_from_config(config: Config, n_classes: int = 0) -> nn.Module:
+    """``config.generator_kind`` (the one extra Config field, default "v2" = reference behaviour) picks the generator.
+    ``n_classes > 0``: a class-conditional SLN/SIREN generator (``SirenGenerator(n_classes=...)``)."""
     kind = config.generator_kind
+    if n_classes and kind == "v2":
+        raise ValueError("a class-conditional generator is one of the SLN/SIREN kinds; generator_kind='v2' has no labels")
     if kind not in GENERATOR_KINDS:
         raise ValueError(f"generator_kind must be one of {GENERATOR_KINDS}, got {kind!r}")
     if kind == "v2":
         return ViTGenerator(config)
     if kind == "sln_siren":  # v1 defaults (src/v1/config.py:45-49,60-66): z 1024, E 384, 4 heads, 4 blocks, SIREN 768
-        return SirenGenerator(image_size=config.image_size, channels=config.input_channels)
+        return SirenGenerator(image_size=config.image_size, channels=config.input_channels, n_classes=n_classes)
     return SirenGenerator(image_size=config.image_size, channels=config.input_channels, embed=config.embeddings_dimension,
-                          heads=config.attention_heads_count, patch_size=config.patch_size)
+                          heads=config.attention_heads_count, patch_size=config.patch_size, n_classes=n_classes)
 
 
 class ViTGAN(nn.Module):
     """src/v2/modules.py:398-410.  ``Config(generator_kind="sln_siren")`` makes ``.generator`` the working SLN/SIREN
-    network (latent input ``[B, generator.latent]``) instead of the reference's ViTGenerator, whose tail raises."""
+    network (latent input ``[B, generator.latent]``) instead of the reference's ViTGenerator, whose tail raises.
+    ``conditional=True``: the generator takes ``config.classes_count`` classes (``forward(z, labels)``), the discriminator's
+    ``classes_count``-way head is read at the label (``GanEngine(n_classes=...)``)."""
 
-    def __init__(self, config: Config):
+    def __init__(self, config: Config, conditional: bool = False):
         super().__init__()
-        self.generator = generator_from_config(config)
+        self.generator = generator_from_config(config, config.classes_count if conditional else 0)
         self.discriminator = ViTDiscriminator(config)
 
     def zero_grad(self, set_to_none: bool = True):
         self.generator.zero_grad()
         self.discriminator.zero_grad()
 
-    def forward(self, z):
-        generated_images = self.generator(z)
+    def forward(self, z, labels=None):
+        generated_images = self.generator(z) if labels is None else self.generator(z, labels)
         discriminator_output = self.discriminator(generated_images)
         return generated_images, discriminator_output
 

@@ -457,6 +457,105 @@ def consistency_loss(logits_x, logits_a, n_real: int, w_real: float, w_fake: flo
     return ConsistencyLossFn.apply(logits_x, logits_a, int(n_real), w_real, w_fake)
 
 
+# ---- class conditioning (include/vitgan_hip.h: vg_draw_labels, vg_class_add, vg_class_grad, vg_gan_loss_cond)
+_LOSS_KINDS = {"ns": 0, "hinge": 1, "wasserstein": 2}
+_LOSS_ROLES = {"d_real": 0, "d_fake": 1, "g": 2, 0: 0, 1: 1, 2: 2}
+
+
+def check_labels(labels, n: int, K: int, what: str, device=None) -> torch.Tensor:
+    """``labels`` as the kernels read them - a contiguous int32 [n] tensor - after the host-side checks the wrappers owe their callers:
+    an integer dtype, the shape, the device and every value in [0, K).  It reads the values, so it synchronises; the kernels clamp
+    on their own and never index with a bad label, so ``GanEngine.step`` does without it."""
+    if not torch.is_tensor(labels) or labels.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8, torch.uint8):
+        raise ValueError(f"{what}: labels must be an integer tensor, got {getattr(labels, 'dtype', type(labels))!r}")
+    if labels.dim() != 1 or labels.shape[0] != n:
+        raise ValueError(f"{what}: labels must have shape [{n}], got {tuple(labels.shape)}")
+    if device is not None and labels.device != device:
+        raise ValueError(f"{what}: labels must be on {device}, got {labels.device}")
+    if not 1 <= int(K) <= 16:
+        raise ValueError(f"{what}: the number of classes must be in [1, 16], got {K!r}")
+    if n and (int(labels.min()) < 0 or int(labels.max()) >= K):
+        raise ValueError(f"{what}: labels must be in [0, {K}), got values in [{int(labels.min())}, {int(labels.max())}]")
+    return labels.detach().to(torch.int32).contiguous()
+
+
+class ConditionalGanLossFn(torch.autograd.Function):
+    """The label-selected loss D(x, y) = D(x)[y] on a K-way head: one launch computes the mean loss and the gradient of every logit
+    (+0 off the label), so the backward only scales what the forward saved."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, kind, role):
+        lg = logits.detach().float().contiguous()
+        n, Kc = lg.shape
+        dl, sel = torch.empty_like(lg), torch.empty(n, dtype=torch.float32, device=lg.device)
+        out = torch.empty(1, dtype=torch.float32, device=lg.device)
+        _lib.check(_lib.lib().vg_gan_loss_cond(_p(lg), _p(labels), _p(dl), _p(sel), _p(out), n, Kc, kind, role, 1.0, _st()), "vg_gan_loss_cond")
+        ctx.save_for_backward(dl)
+        ctx.dt = logits.dtype
+        ctx.mark_non_differentiable(sel)
+        return out[0], sel
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout, _dsel):
+        (dl,) = ctx.saved_tensors
+        return (dl * dout).to(ctx.dt), None, None, None
+
+
+def conditional_gan_loss(logits, labels, kind="ns", role="d_real", return_selected: bool = False):
+    """The GAN loss of ``kind`` ("ns", "hinge", "wasserstein") in ``role`` ("d_real" / 0, "d_fake" / 1, "g" / 2) on the label-selected
+    logits s_i = logits[i, labels[i]] of a [n, Kc] head: the mean over the n samples, differentiable in ``logits``.  ``labels``: an
+    integer tensor [n] on the logits' device, every value in [0, Kc) (checked here: this call synchronises).  ``return_selected``
+    also returns s (not differentiable)."""
+    _need_cuda(logits, "conditional_gan_loss")
+    if logits.dim() != 2:
+        raise ValueError("conditional_gan_loss: logits is a [n, Kc] tensor")
+    if kind not in _LOSS_KINDS or role not in _LOSS_ROLES:
+        raise ValueError(f"conditional_gan_loss: kind must be one of {sorted(_LOSS_KINDS)} and role one of d_real, d_fake, g")
+    y = check_labels(labels, logits.shape[0], logits.shape[1], "conditional_gan_loss", logits.device)
+    loss, sel = ConditionalGanLossFn.apply(logits, y, _LOSS_KINDS[kind], _LOSS_ROLES[role])
+    return (loss, sel) if return_selected else loss
+
+
+def draw_labels(n: int, K: int, seed: int, site: int, step: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
+    """``n`` class labels uniform over [0, K), int32 on the device: a pure function of (seed, site, step[0], index) - ``step``: a cuda
+    int32 counter (its device is the result's), or None with ``device``."""
+    if step is not None and (not step.is_cuda or step.dtype != torch.int32):
+        raise ValueError("draw_labels: step is the device step counter, a cuda int32 tensor")
+    if n < 1 or not 1 <= int(K) <= 16:
+        raise ValueError(f"draw_labels: n >= 1 and 1 <= K <= 16, got n={n!r}, K={K!r}")
+    dev = step.device if step is not None else torch.device("cuda" if device is None else device)
+    out = torch.empty(n, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().vg_draw_labels(_p(out), n, int(K), int(seed) & 0xFFFFFFFFFFFFFFFF, int(site), _p(step), _st()), "vg_draw_labels")
+    return out
+
+
+def class_add(wmod, table, labels):
+    """wmod [B, N] + table[labels] ([K, N]) in bf16 with fp32 addition (vg_class_add, out of place here): a new bf16 tensor."""
+    _need_cuda(wmod, "class_add")
+    if wmod.dim() != 2 or table.dim() != 2 or table.shape[1] != wmod.shape[1] or wmod.shape[1] % 8:
+        raise ValueError("class_add: wmod [B, N] and table [K, N] with N % 8 == 0")
+    y = check_labels(labels, wmod.shape[0], table.shape[0], "class_add", wmod.device)
+    out, tb = _bf(wmod).clone(), _bf(table)
+    _lib.check(_lib.lib().vg_class_add(_p(out), _p(tb), _p(y), out.shape[0], out.shape[1], tb.shape[0], _st()), "vg_class_add")
+    return out
+
+
+def class_grad(dw, labels, K: int, out: Optional[torch.Tensor] = None):
+    """The class table's gradient [K, N] of dw [B, N] fp32: row k = the sum of the rows of class k in ascending order (vg_class_grad).
+    ``out``: an fp32 [K, N] tensor to ACCUMULATE into (returned); None = a fresh tensor, overwritten."""
+    _need_cuda(dw, "class_grad")
+    if dw.dim() != 2 or dw.shape[1] % 4:
+        raise ValueError("class_grad: dw is [B, N] with N % 4 == 0")
+    y = check_labels(labels, dw.shape[0], K, "class_grad", dw.device)
+    d = _f32(dw)
+    if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (K, d.shape[1]) or not out.is_contiguous() or out.device != d.device):
+        raise ValueError(f"class_grad: out is a contiguous fp32 [{K}, {d.shape[1]}] tensor on the gradient's device")
+    res = torch.empty(K, d.shape[1], dtype=torch.float32, device=d.device) if out is None else out
+    _lib.check(_lib.lib().vg_class_grad(_p(d), _p(y), _p(res), d.shape[0], d.shape[1], int(K), int(out is not None), _st()), "vg_class_grad")
+    return res
+
+
 def _spectral_one(W, u, sigma0):
     """A one-matrix SpectralState holding (u, sigma0) for the fp32 matrix W [N, K] (a contiguous cuda tensor)."""
     from .spectral import SpectralState

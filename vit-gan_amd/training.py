@@ -165,11 +165,16 @@ def get_data_loader(c: Config):
     return DataLoader(ds, batch_size=c.batch_size, shuffle=True, num_workers=4, drop_last=True)
 
 
-class SyntheticLoader:
-    """``steps`` batches of uniform [-1,1] images (the range of Normalize(0.5, 0.5)) generated on the device."""
+class MissingLabelsError(ValueError):
+    """a conditional run was given a data loader without labels: the caller's error, raised out of ``train_model``"""
 
-    def __init__(self, c: Config, steps: int, device: torch.device, seed: int = 1234):
-        self.c, self.steps, self.device = c, steps, device
+
+class SyntheticLoader:
+    """``steps`` batches of uniform [-1,1] images (the range of Normalize(0.5, 0.5)) generated on the device.  ``labels=K > 0``: every
+    batch comes with int64 labels uniform over [0, K) from the same generator (0, the default: ``None`` in their place)."""
+
+    def __init__(self, c: Config, steps: int, device: torch.device, seed: int = 1234, labels: int = 0):
+        self.c, self.steps, self.device, self.labels = c, steps, device, int(labels)
         self.gen = torch.Generator(device=device).manual_seed(seed)
 
     def __len__(self) -> int:
@@ -179,17 +184,19 @@ class SyntheticLoader:
         c = self.c
         for _ in range(self.steps):
             x = torch.rand(c.batch_size, c.input_channels, c.image_size, c.image_size, device=self.device, generator=self.gen)
-            yield x * 2 - 1, None
+            y = torch.randint(0, self.labels, (c.batch_size,), device=self.device, generator=self.gen) if self.labels else None
+            yield x * 2 - 1, y
 
 
-def trainable_config(c: Config) -> Config:
+def trainable_config(c: Config, conditional: bool = False) -> Config:
     """The configuration ``train_model`` builds ``ViTGAN`` from: a 1-logit discriminator (the executable loss, SURVEY 8
     row a12) and a generator that can produce an image - the reference's default "v2" tail raises, so it is
-    replaced by the SLN/SIREN network (row-token layout at 32x32, patch grid beyond)."""
+    replaced by the SLN/SIREN network (row-token layout at 32x32, patch grid beyond).  ``conditional``: ``classes_count`` stays -
+    the K-way head is the conditional discriminator."""
     kind = c.generator_kind
     if kind == "v2":
         kind = "sln_siren" if c.image_size <= 32 else "sln_siren_patch"
-    return c.model_copy(update={"classes_count": 1, "generator_kind": kind})
+    return c.model_copy(update={"generator_kind": kind} if conditional else {"classes_count": 1, "generator_kind": kind})
 
 
 def discriminator_state(gan_state: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -206,7 +213,7 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                 diversity_weight: float = 0.0, instance_noise: float = 0.0, gp_weight: float = 0.0, diffaug: str = "",
                 ema_decay: float = 0.0, ema_start: int = 0, spectral_norm: str = "", bcr=(0.0, 0.0), bcr_aug: str = "",
                 aug_p: Optional[float] = None, ada_target: float = 0.0, ada_interval: int = 4, ada_kimg: float = 500.0,
-                r1_gamma: float = 0.0, r1_interval: int = 1):
+                r1_gamma: float = 0.0, r1_interval: int = 1, conditional: bool = False):
     """``loss``: "ns" (default: the executable v1 loss), "hinge", or "wasserstein" - the critic losses of the reference's
     unreached step (training.py:67-125); ``clip_d`` / ``clip_g``: its clip_grad_norm_ limits (5.0 / 0.5 there);
     ``diversity_weight``: its diversity term (0.1 there); ``instance_noise``: sigma of the noise on D's inputs (0.1
@@ -232,7 +239,12 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     carries the probability in force and the overfitting signal r_t of the last update.
     ``r1_gamma`` / ``r1_interval``: the zero-centred R1 penalty on real images and its lazy-regularisation interval
     (``GanEngine(r1_gamma=..., r1_interval=...)``; the reference has none).  When it is on, every epoch's line also carries the last
-    computed unweighted penalty."""
+    computed unweighted penalty.
+    ``conditional``: class-conditional training (``GanEngine(n_classes=...)``; the reference has none that runs) with
+    ``classes_count`` classes (at most 16): the loader's labels go to the step - a loader that yields ``None`` in their place, like the
+    default ``SyntheticLoader`` without ``labels=K``, is an error; when no loader is given the synthetic one draws labels itself -
+    and image i of every sample grid is of class ``i % classes_count``.  The checkpoints then also hold
+    ``generator.class_embedding.weight``."""
     global _log_file
     from .ops import parse_aug_policy, parse_bcr_weights
     parse_aug_policy(diffaug)  # a bad policy string is the caller's error whatever the machine: before the device check
@@ -253,6 +265,12 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     if int(ema_start) != ema_start or ema_start < 0:
         raise ValueError(f"ema_start must be a non-negative integer, got {ema_start!r}")
     c = Config() if not config else Config(**config)
+    conditional = bool(conditional)
+    K = int(c.classes_count) if conditional else 0
+    if conditional and not 1 <= K <= 16:
+        raise ValueError(f"conditional: classes_count must be in [1, 16] (the width of the head kernels), got {c.classes_count!r}")
+    if conditional and (float(gp_weight) != 0.0 or float(r1_gamma) > 0.0):
+        raise ValueError("conditional: the gradient penalties (gp_weight, r1_gamma) are not built for the label-selected logit; switch them off")
     if not torch.cuda.is_available():
         raise RuntimeError("train_model needs an MI355X: the HIP engine has no CPU path")
     dev = torch.device(device)
@@ -261,13 +279,13 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     if save_artifacts:
         dirs.construct()
         _log_file = os.path.join(dirs.save, "training.log")
-    gan = ViTGAN(trainable_config(c)).to(dev).train()  # modules.ViTGAN(c).to(device); gan.train(), training.py:145,148
+    gan = ViTGAN(trainable_config(c, conditional), conditional).to(dev).train()  # modules.ViTGAN(c).to(device); gan.train(), training.py:145,148
     D, G = gan.discriminator, gan.generator
     eng = GanEngine(D, G, batch=c.batch_size, loss=loss, lr_d=c.discriminator_learning_rate, lr_g=c.generator_learning_rate,
                     weight_decay=1e-3, seed=seed, clip_d=clip_d, clip_g=clip_g, diversity_weight=diversity_weight,
                     instance_noise=instance_noise, gp_weight=gp_weight, diffaug=diffaug, ema_decay=ema_decay, ema_start=ema_start,
                     spectral_norm=spectral_norm, bcr=bcr, bcr_aug=bcr_aug, aug_p=aug_p, ada_target=ada_target, ada_interval=ada_interval,
-                    ada_kimg=ada_kimg, r1_gamma=r1_gamma, r1_interval=r1_interval)
+                    ada_kimg=ada_kimg, r1_gamma=r1_gamma, r1_interval=r1_interval, n_classes=K)
 
     def gan_checkpoint():  # gan.state_dict(), the discriminator's normalised matrices as the network applies them
         sd = gan.state_dict()
@@ -278,14 +296,16 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     G_ema: Optional[nn.Module] = None
     gan_ema: Optional[nn.Module] = None
     if eng.ema_g is not None:  # the averaged generator as a module of its own: same constructor arguments, eval mode, never trained
-        G_ema = generator_from_config(trainable_config(c)).to(dev).eval()
+        G_ema = generator_from_config(trainable_config(c, conditional), K).to(dev).eval()
         gan_ema = nn.Module()  # what fid_fn receives: .generator = the averaged network, .discriminator = D
         gan_ema.generator, gan_ema.discriminator = G_ema, D
 
     def refresh_ema():
         if G_ema is not None:
             G_ema.load_state_dict(eng.ema_state_dict(), strict=True)
-    loader = data_loader if data_loader is not None else SyntheticLoader(c, steps_per_epoch, dev)
+    loader = data_loader if data_loader is not None else SyntheticLoader(c, steps_per_epoch, dev, labels=K)
+    # the fixed sample grid of a conditional run: image i is of class i % K
+    grid_labels = (torch.arange(c.batch_size, device=dev) % K).to(torch.int32) if conditional else None
     epochs = c.epochs if max_epochs is None else min(c.epochs, max_epochs)
 
     def construct_noise():  # the v1 generator's latent, gan.py:231-232 (the v2 noise is image-shaped, training.py:35-42)
@@ -297,12 +317,12 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
         if G_ema is not None:  # from the averaged weights
             refresh_ema()
             with torch.no_grad():
-                samples = G_ema(noise).detach().float().cpu() * 0.5 + 0.5
+                samples = G_ema(noise, grid_labels).detach().float().cpu() * 0.5 + 0.5
         else:
             was = G.training
             G.eval()
             with torch.no_grad():
-                samples = G(noise).detach().float().cpu() * 0.5 + 0.5
+                samples = G(noise, grid_labels).detach().float().cpu() * 0.5 + 0.5
             G.train(was)
         save_images(os.path.join(dirs.images, f"samples_epoch_{label}.png"), samples, c.batch_size)
 
@@ -328,6 +348,8 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
         if eng.spec is not None:
             log(f"Spectral normalisation of the discriminator: set '{spectral_norm}', {eng.spec.n} matrices; checkpoints hold the EFFECTIVE "
                 "weights sigma0 W / sigma (discriminator_raw.pth: the raw weights for a resumed run)")
+        if conditional:
+            log(f"Class-conditional training: {K} classes, label-selected discriminator logit, class-modulated generator")
         if eng.r1:
             log(f"R1 penalty on real images: gamma {eng.r1_gamma:g}, every {eng.r1_interval} step(s) with weight {0.5 * eng.r1_gamma * eng.r1_interval:g}")
         for epoch in range(epochs):
@@ -336,10 +358,12 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                 save_images(os.path.join(dirs.noise, f"noise_epoch_{epoch}.png"), noise_as_image(noise), c.batch_size)
             save_samples(epoch, noise)
             losses = None
-            for i, (real_images, _) in enumerate(loader):
+            for i, (real_images, real_labels) in enumerate(loader):
                 if i == 0 and save_artifacts:
                     save_images(os.path.join(dirs.input, f"input_epoch_{epoch}.png"), real_images, c.batch_size)
-                losses = eng.step(real_images.to(dev))
+                if conditional and real_labels is None:
+                    raise MissingLabelsError("conditional: the data loader yields no labels (SyntheticLoader draws them with labels=classes_count)")
+                losses = eng.step(real_images.to(dev), labels=real_labels.to(dev)) if conditional else eng.step(real_images.to(dev))
             if losses is None:
                 raise RuntimeError("the data loader produced no batch")
             d_real, d_fake, g = losses.tolist()  # the only host sync of the epoch (training.py:228)
@@ -371,6 +395,9 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
         log(f"{ke} raised!")
     except _lib.HipError as e:  # a failed launch / rejected kernel arguments is never a "successful" run
         log(f"HIP engine error: {e}\n{traceback.format_exc()}")
+        fatal = e
+    except MissingLabelsError as e:
+        log(f"{e}")
         fatal = e
     except Exception as e:  # the reference logs and carries on to `finally` (training.py:250-251)
         log(f"Exception: {e}\n{traceback.format_exc()}")
