@@ -409,6 +409,48 @@ int vg_adamw_ema_step(float* p, const float* g, float* m, float* v, void* shadow
  * elsewhere (the sharded update of the generator's mapping Linear). */
 int vg_ema_update(float* ema, const float* p, long long n, float ema_decay, int ema_start, int step, const int* step_dev,
                   void* stream);
+/* The learning rates on the device (additive to ABI 9).  The reference meant to schedule its rates (src/v2/training.py:15 imports
+ * ReduceLROnPlateau, :215-216 hold the commented scheduler steps) and never did, so this header is the definition.
+ *
+ * vg_lr_schedule: ONE launch of one workgroup, thread 0 = slot 0 (the discriminator, schedule *d), thread 1 = slot 1 (the generator, *g).
+ * With t = max(step_dev[0], 1) - the device step counter as vg_zero_tick left it, 1 on the first step; a counter below 1 counts as 1 -
+ * and per slot (base, kind, warmup, total, final_ratio), the factor is f = f_w f_d:
+ *   f_w = t / warmup                      for 1 <= t <= warmup (so exactly 1 at t = warmup), and exactly 1 otherwise (warmup == 0 too)
+ *   f_d = 1                               exactly, while t <= warmup and for kind == VG_LR_CONSTANT (total is then not read)
+ *   f_d = final_ratio                     exactly, once t >= total
+ *   else, s = (t - warmup) / (total - warmup):
+ *     VG_LR_LINEAR   f_d = 1 - (1 - final_ratio) s
+ *     VG_LR_COSINE   f_d = final_ratio + (1 - final_ratio) 0.5 (1 + cos(pi s))
+ *   lr_out[slot] = (float)((double)base * f * (double)scale_dev[slot])
+ * every exact case an explicit branch, everything in fp64 (not contracted) with ONE rounding to fp32 at the end: an fp64 evaluation
+ * elsewhere agrees to one fp32 ulp, and where f and the scale are exactly 1 the result is base bit for bit.  A slot reads its own
+ * scale only.  scale_dev, lr_out: two floats each on the device.  Plain stores, no atomics, no LDS.  The schedules are passed by
+ * value: the pointers are host pointers, read before the call returns.
+ * Returns -1: a null pointer (step_dev is required);  -2: kind out of range, warmup < 0, total <= warmup for a decaying kind,
+ * final_ratio outside [0, 1] or NaN, base not finite and positive - all before any launch.
+ *
+ * vg_adamw_step_dlr / vg_adamw_ema_step_dlr: vg_adamw_step / vg_adamw_ema_step with the rate read on the device, lr = lr_dev[0] (one
+ * uniform load per thread; a launch behind vg_lr_schedule on the same stream sees the rate it wrote), in the place of the float: a
+ * captured hipGraph then replays with a fresh rate.  The update expressions are the same code: given lr_dev[0] equal to the float, p, m,
+ * v, shadow_bf16 and ema come out bit for bit as the float forms write them.  Errors as there, lr_dev == NULL is -1. */
+#define VG_LR_CONSTANT 0
+#define VG_LR_LINEAR 1
+#define VG_LR_COSINE 2
+typedef struct VgLrSched {
+  float base;        /* the rate the factor multiplies: finite, > 0 */
+  int kind;          /* VG_LR_* */
+  int warmup;        /* steps of linear warm-up, >= 0 */
+  int total;         /* step from which the factor is final_ratio; > warmup for a decaying kind */
+  float final_ratio; /* in [0, 1] */
+} VgLrSched;
+int vg_lr_schedule(const VgLrSched* d, const VgLrSched* g, const int* step_dev, const float* scale_dev /*[2]*/, float* lr_out /*[2]*/,
+                   void* stream);
+int vg_adamw_step_dlr(float* p, const float* g, float* m, float* v, void* shadow_bf16, long long n,
+                      const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, int step,
+                      const int* step_dev, float gscale, void* stream);
+int vg_adamw_ema_step_dlr(float* p, const float* g, float* m, float* v, void* shadow_bf16, float* ema, long long n,
+                          const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, int step, const int* step_dev,
+                          float gscale, float ema_decay, int ema_start, void* stream);
 /* diversity_loss of the reference's unreached generator step (src/v2/utils.py:147-152; training.py:73-74 adds 0.1 x it
  * to the generator loss): loss_out[0] = sum_{i,j} |x_i - x_j|_1 / (B (B-1)) over images bf16 [B, D]; when d_images is
  * not NULL, d_images (bf16 [B, D]) += weight * d loss / d images.  scratch: ceil(D/16) floats.  B <= 1024. */

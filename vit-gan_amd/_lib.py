@@ -70,6 +70,10 @@ class VgSpectralDesc(C.Structure):
                 + [(n, c_int) for n in ("blk_a", "blk_b", "blk_c", "reserved")])
 
 
+class VgLrSched(C.Structure):
+    _fields_ = [("base", c_float), ("kind", c_int), ("warmup", c_int), ("total", c_int), ("final_ratio", c_float)]
+
+
 P = c_void_p
 _SIGNATURES = {
     "vg_abi_version": (c_int, []),
@@ -135,6 +139,9 @@ _SIGNATURES = {
     "vg_bcr_loss": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_float, P]),
     "vg_adamw_step": (c_int, [P, P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_float, c_int, P, c_float, P]),
     "vg_adamw_ema_step": (c_int, [P, P, P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_float, c_int, P, c_float, c_float, c_int, P]),
+    "vg_adamw_step_dlr": (c_int, [P, P, P, P, P, c_ll, P, c_float, c_float, c_float, c_float, c_int, P, c_float, P]),
+    "vg_adamw_ema_step_dlr": (c_int, [P, P, P, P, P, P, c_ll, P, c_float, c_float, c_float, c_float, c_int, P, c_float, c_float, c_int, P]),
+    "vg_lr_schedule": (c_int, [C.POINTER(VgLrSched), C.POINTER(VgLrSched), P, P, P, P]),
     "vg_ema_update": (c_int, [P, P, c_ll, c_float, c_int, c_int, P, P]),
     "vg_diversity_loss": (c_int, [P, P, P, P, c_int, c_int, c_float, P]),
     "vg_grad_clip": (c_int, [P, c_ll, c_float, c_float, P, P]),

@@ -388,6 +388,23 @@ extern "C" int vg_adamw_ema_step(float* p, const float* g, float* m, float* v, v
   return vg_adamw_ema_launch(p, g, m, v, (bf16*)shadow_bf16, ema, n, lr, beta1, beta2, eps, weight_decay, step, step_dev, gscale, ema_decay,
                              ema_start, (hipStream_t)stream);
 }
+// ---- device-resident learning rate: AdamW reading lr_dev[0], and the schedule controller that writes it (elementwise.hip) ----
+extern "C" int vg_adamw_step_dlr(float* p, const float* g, float* m, float* v, void* shadow_bf16, long long n, const float* lr_dev, float beta1,
+                                 float beta2, float eps, float weight_decay, int step, const int* step_dev, float gscale, void* stream) {
+  if (!p || !g || !m || !v || !shadow_bf16 || !lr_dev || n < 1 || (step < 1 && !step_dev)) return -1;
+  return vg_adamw_dlr_launch(p, g, m, v, (bf16*)shadow_bf16, n, lr_dev, beta1, beta2, eps, weight_decay, step, step_dev, gscale,
+                             (hipStream_t)stream);
+}
+extern "C" int vg_adamw_ema_step_dlr(float* p, const float* g, float* m, float* v, void* shadow_bf16, float* ema, long long n,
+                                     const float* lr_dev, float beta1, float beta2, float eps, float weight_decay, int step,
+                                     const int* step_dev, float gscale, float ema_decay, int ema_start, void* stream) {
+  if (!p || !g || !m || !v || !shadow_bf16 || !ema || !lr_dev || n < 1 || (step < 1 && !step_dev)) return -1;
+  return vg_adamw_ema_dlr_launch(p, g, m, v, (bf16*)shadow_bf16, ema, n, lr_dev, beta1, beta2, eps, weight_decay, step, step_dev, gscale,
+                                 ema_decay, ema_start, (hipStream_t)stream);
+}
+extern "C" int vg_lr_schedule(const VgLrSched* d, const VgLrSched* g, const int* step_dev, const float* scale_dev, float* lr_out, void* stream) {
+  return vg_lr_schedule_launch(d, g, step_dev, scale_dev, lr_out, (hipStream_t)stream);
+}
 extern "C" int vg_ema_update(float* ema, const float* p, long long n, float ema_decay, int ema_start, int step, const int* step_dev,
                              void* stream) {
   if (!ema || !p || n < 1 || (step < 1 && !step_dev)) return -1;

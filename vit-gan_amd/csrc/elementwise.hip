@@ -1,6 +1,7 @@
 // Patchify / un-patchify, CLS/positional bookkeeping, classifier head, GAN losses, fused AdamW
 // and the casts around them.  All memory-bound, coalesced, deterministic (no float atomics).
 #include "vg_common.h"
+#include "../../include/vitgan_hip.h"  // VgLrSched, VG_LR_*
 
 // ---- patchify: NCHW image -> [B*NP, C*P*P] bf16 rows in (c, py, px) order ----------------------
 // (the memory order of conv1.weight[e], src/v2/modules.py:70-72, so the conv is one NT GEMM)
@@ -500,6 +501,35 @@ __global__ __launch_bounds__(256) void vg_ada_update_kernel(const float* __restr
   }
 }
 
+// ---- learning-rate schedule: the controller of the two rates (include/vitgan_hip.h, vg_lr_schedule) ----
+// One workgroup, thread 0 = the discriminator's slot, thread 1 = the generator's.  t = step[0] as vg_zero_tick left it (1 on the first
+// step; anything below 1 counts as 1).  f = f_w f_d, every exact case an explicit branch; all of it in fp64 and rounded to fp32 ONCE, so
+// an fp64 restatement off the device agrees to one fp32 ulp whatever cosine it uses (here cospi: no range reduction to trust).  A slot
+// reads its own scale only.  Plain stores.
+__device__ __forceinline__ float vg_lr_now(const VgLrSched s, int t, const float scale) {
+#pragma clang fp contract(off)
+  if (t < 1) t = 1;
+  double f = 1.0;
+  if (t <= s.warmup) {
+    if (t < s.warmup) f = (double)t / (double)s.warmup;
+  } else if (s.kind != VG_LR_CONSTANT) {
+    const double fin = (double)s.final_ratio;
+    if (t >= s.total) {
+      f = fin;
+    } else {
+      const double x = (double)(t - s.warmup) / (double)(s.total - s.warmup);
+      f = s.kind == VG_LR_LINEAR ? 1.0 - (1.0 - fin) * x : fin + (1.0 - fin) * 0.5 * (1.0 + cospi(x));
+    }
+  }
+  return (float)((double)s.base * f * (double)scale);
+}
+__global__ __launch_bounds__(64) void vg_lr_schedule_kernel(VgLrSched d, VgLrSched g, const int* __restrict__ step,
+                                                            const float* __restrict__ scale, float* __restrict__ lr_out) {
+  if (threadIdx.x > 1) return;
+  const int t = step[0];
+  lr_out[threadIdx.x] = vg_lr_now(threadIdx.x == 0 ? d : g, t, scale[threadIdx.x]);
+}
+
 // ---- torch.nn.utils.clip_grad_norm_ over a flat gradient buffer (src/v2/training.py:78,104) -------------------------
 // Two deterministic stages: per-workgroup sums of squares, then every workgroup folds the partials in the same fixed
 // order, derives coef = min(1, max_norm / (gscale*|g| + 1e-6)) and scales its slice in place.
@@ -605,17 +635,19 @@ struct VgAdamwArgs {
   float lr, b1, b2, eps, wd, bc1, bc2_sqrt, gscale;
   const int* step_dev;
 };
-// The update of four adjacent elements, the ONE copy of the arithmetic that vg_adamw_kernel and vg_adamw_ema_kernel share (their p, m, v
-// and shadow agree bit for bit).  Returns the updated weights; they, the moments and the shadow are stored here.
+// The update of four adjacent elements, the ONE copy of the arithmetic that every AdamW kernel shares (their p, m, v and shadow agree
+// bit for bit).  ``lr`` is the caller's: the kernel argument a.lr, or for the _dlr kernels the float the schedule controller left on
+// the device.  Returns the updated weights; they, the moments and the shadow are stored here.
 __device__ __forceinline__ f32x4 vg_adamw_update4(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                  float* __restrict__ v, bf16* __restrict__ shadow, long long i4, const VgAdamwArgs& a) {
+                                                  float* __restrict__ v, bf16* __restrict__ shadow, long long i4, const VgAdamwArgs& a,
+                                                  const float lr) {
   float bc1 = a.bc1, bc2_sqrt = a.bc2_sqrt;
   if (a.step_dev) {  // step counter kept on the device so a captured hipGraph replays correctly
     const float t = (float)a.step_dev[0];
     bc1 = 1.f - __powf(a.b1, t);
     bc2_sqrt = sqrtf(1.f - __powf(a.b2, t));
   }
-  const float lr = a.lr, b1 = a.b1, b2 = a.b2, eps = a.eps, wd = a.wd, gscale = a.gscale;
+  const float b1 = a.b1, b2 = a.b2, eps = a.eps, wd = a.wd, gscale = a.gscale;
   f32x4 pv = *(f32x4*)(p + i4), gv = *(const f32x4*)(g + i4), mv = *(f32x4*)(m + i4), vv = *(f32x4*)(v + i4);
   bf16x4 sh;
 #pragma unroll
@@ -635,7 +667,15 @@ __global__ __launch_bounds__(256) void vg_adamw_kernel(float* __restrict__ p, co
                                                        float* __restrict__ v, bf16* __restrict__ shadow, long long n, VgAdamwArgs a) {
   const long long i4 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
   if (i4 >= n) return;
-  vg_adamw_update4(p, g, m, v, shadow, i4, a);
+  vg_adamw_update4(p, g, m, v, shadow, i4, a, a.lr);
+}
+// the same update with the rate read from the device (one uniform load; a.lr is not read): what a captured step replays with a fresh rate
+__global__ __launch_bounds__(256) void vg_adamw_dlr_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, bf16* __restrict__ shadow, long long n, VgAdamwArgs a,
+                                                           const float* __restrict__ lr_dev) {
+  const long long i4 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i4 >= n) return;
+  vg_adamw_update4(p, g, m, v, shadow, i4, a, lr_dev[0]);
 }
 // ---- exponential moving average of the weights (the generator's sample / FID weights) ------------
 // t <= max(1, start): e = p (the average follows the weights through the warm-up; the first step ALWAYS copies, so e's old content -
@@ -658,7 +698,16 @@ __global__ __launch_bounds__(256) void vg_adamw_ema_kernel(float* __restrict__ p
                                                            long long n, VgAdamwArgs a, float decay, int start, int step) {
   const long long i4 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
   if (i4 >= n) return;
-  const f32x4 p1 = vg_adamw_update4(p, g, m, v, shadow, i4, a);
+  const f32x4 p1 = vg_adamw_update4(p, g, m, v, shadow, i4, a, a.lr);
+  vg_ema_update4(ema, p1, i4, decay, start, step, a.step_dev);
+}
+__global__ __launch_bounds__(256) void vg_adamw_ema_dlr_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                               float* __restrict__ v, bf16* __restrict__ shadow, float* __restrict__ ema,
+                                                               long long n, VgAdamwArgs a, float decay, int start, int step,
+                                                               const float* __restrict__ lr_dev) {
+  const long long i4 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i4 >= n) return;
+  const f32x4 p1 = vg_adamw_update4(p, g, m, v, shadow, i4, a, lr_dev[0]);
   vg_ema_update4(ema, p1, i4, decay, start, step, a.step_dev);
 }
 __global__ __launch_bounds__(256) void vg_ema_kernel(float* __restrict__ ema, const float* __restrict__ p, long long n, float decay, int start,
@@ -966,6 +1015,33 @@ int vg_adamw_ema_launch(float* p, const float* g, float* m, float* v, bf16* shad
   if (!(decay >= 0.f && decay < 1.f) || start < 0) return -2;
   hipLaunchKernelGGL(vg_adamw_ema_kernel, dim3(nblk(n / 4)), dim3(256), 0, st, p, g, m, v, shadow, ema, n,
                      vg_adamw_args(lr, b1, b2, eps, wd, step, step_dev, gscale), decay, start, step);
+  return (int)hipGetLastError();
+}
+int vg_adamw_dlr_launch(float* p, const float* g, float* m, float* v, bf16* shadow, long long n, const float* lr_dev, float b1, float b2,
+                        float eps, float wd, int step, const int* step_dev, float gscale, hipStream_t st) {
+  if (n & 3) return -3;
+  hipLaunchKernelGGL(vg_adamw_dlr_kernel, dim3(nblk(n / 4)), dim3(256), 0, st, p, g, m, v, shadow, n,
+                     vg_adamw_args(0.f, b1, b2, eps, wd, step, step_dev, gscale), lr_dev);
+  return (int)hipGetLastError();
+}
+int vg_adamw_ema_dlr_launch(float* p, const float* g, float* m, float* v, bf16* shadow, float* ema, long long n, const float* lr_dev, float b1,
+                            float b2, float eps, float wd, int step, const int* step_dev, float gscale, float decay, int start, hipStream_t st) {
+  if (n & 3) return -3;
+  if (!(decay >= 0.f && decay < 1.f) || start < 0) return -2;
+  hipLaunchKernelGGL(vg_adamw_ema_dlr_kernel, dim3(nblk(n / 4)), dim3(256), 0, st, p, g, m, v, shadow, ema, n,
+                     vg_adamw_args(0.f, b1, b2, eps, wd, step, step_dev, gscale), decay, start, step, lr_dev);
+  return (int)hipGetLastError();
+}
+static bool vg_lr_sched_ok(const VgLrSched& s) {
+  if (s.kind < VG_LR_CONSTANT || s.kind > VG_LR_COSINE || s.warmup < 0) return false;
+  if (s.kind != VG_LR_CONSTANT && s.total <= s.warmup) return false;
+  if (!(s.final_ratio >= 0.f && s.final_ratio <= 1.f)) return false;
+  return s.base > 0.f && s.base <= 3.402823466e+38f;  // finite and positive (a NaN fails both)
+}
+int vg_lr_schedule_launch(const VgLrSched* d, const VgLrSched* g, const int* step_dev, const float* scale_dev, float* lr_out, hipStream_t st) {
+  if (!d || !g || !step_dev || !scale_dev || !lr_out) return -1;
+  if (!vg_lr_sched_ok(*d) || !vg_lr_sched_ok(*g)) return -2;
+  hipLaunchKernelGGL(vg_lr_schedule_kernel, dim3(1), dim3(64), 0, st, *d, *g, step_dev, scale_dev, lr_out);
   return (int)hipGetLastError();
 }
 int vg_ema_launch(float* ema, const float* p, long long n, float decay, int start, int step, const int* step_dev, hipStream_t st) {

@@ -94,6 +94,15 @@ int vg_adamw_launch(float* p, const float* g, float* m, float* v, bf16* shadow, 
                     float eps, float wd, int step, const int* step_dev, float gscale, hipStream_t st);
 int vg_adamw_ema_launch(float* p, const float* g, float* m, float* v, bf16* shadow, float* ema, long long n, float lr, float b1, float b2,
                         float eps, float wd, int step, const int* step_dev, float gscale, float decay, int start, hipStream_t st);
+// the same two with the rate read on the device (lr_dev[0], one uniform load): p, m, v, shadow and average bit-equal to the forms above
+// given the same float
+int vg_adamw_dlr_launch(float* p, const float* g, float* m, float* v, bf16* shadow, long long n, const float* lr_dev, float b1, float b2,
+                        float eps, float wd, int step, const int* step_dev, float gscale, hipStream_t st);
+int vg_adamw_ema_dlr_launch(float* p, const float* g, float* m, float* v, bf16* shadow, float* ema, long long n, const float* lr_dev, float b1,
+                            float b2, float eps, float wd, int step, const int* step_dev, float gscale, float decay, int start, hipStream_t st);
+// controller of the two learning rates (slot 0 = D, 1 = G; VgLrSched of include/vitgan_hip.h): one workgroup, fp64, rounded once
+struct VgLrSched;
+int vg_lr_schedule_launch(const VgLrSched* d, const VgLrSched* g, const int* step_dev, const float* scale_dev, float* lr_out, hipStream_t st);
 int vg_ema_launch(float* ema, const float* p, long long n, float decay, int start, int step, const int* step_dev, hipStream_t st);
 int vg_cast_f32_bf16_launch(const float* src, bf16* dst, long long n, hipStream_t st);
 int vg_slab_reduce_launch(const float* slab, long long stride, int nslab, float* dst, long long n, int accumulate, hipStream_t st);

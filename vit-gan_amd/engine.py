@@ -54,7 +54,8 @@ class GanEngine:
                  exchange_single_rank: bool = False, dense_top_block: bool = False, gp_autograd: bool = False, diffaug: str = "",
                  ema_decay: float = 0.0, ema_start: int = 0, spectral_norm: str = "", bcr=(0.0, 0.0), bcr_aug: str = "",
                  aug_p: Optional[float] = None, ada_target: float = 0.0, ada_interval: int = 4, ada_kimg: float = 500.0,
-                 r1_gamma: float = 0.0, r1_interval: int = 1, n_classes: int = 0):
+                 r1_gamma: float = 0.0, r1_interval: int = 1, n_classes: int = 0,
+                 lr_schedule: str = "", lr_warmup: int = 0, lr_total: int = 0, lr_final: float = 0.0):
         """concurrent_wgrad: the discriminator's weight gradients on a side stream beside its input gradients.  Off by default
         since the persistent GEMMs (csrc/gemm_wr.hip, gemm_tn.hip: their workgroups hold the CUs for a whole launch) - the
         side stream measured 6.70 against 6.67 ms/step.
@@ -185,7 +186,20 @@ class GanEngine:
         step is launch for launch the plain one - a Kc-way head is then B Kc independent samples, as before.  Not with ``gp_weight``
         / ``r1_gamma`` (the penalty call seeds its first backward with ones over all Kc logits and folds that into its second-order
         head: a label-selected seed is a follow-up), ``two_stream``, or a process group of more than one rank (the staged exchange of
-        the generator's gradient treats the tail of the flat buffer as final after stage 1; the table is final after stage L+1)."""
+        the generator's gradient treats the tail of the flat buffer as final after stage 1; the table is final after stage L+1).
+        lr_schedule / lr_warmup / lr_total / lr_final: a learning-rate schedule evaluated ON THE DEVICE (the reference imports
+        ReduceLROnPlateau and never steps it, training.py:15,215-216): "constant", "linear" or "cosine", one shape for both networks,
+        each on its own base rate ``lr_d`` / ``lr_g``.  With t the device step counter (1 on the first step) the rate of step t is
+        base * f(t) * multiplier: f rises as t / lr_warmup over the first ``lr_warmup`` steps, is 1 at t = lr_warmup, then falls -
+        linearly, or along half a cosine - to ``lr_final`` at t = ``lr_total`` and stays there ("constant": stays 1; ``lr_warmup > 0``
+        with ``lr_schedule=""`` means "constant" with warm-up).  ONE launch of two threads, vg_lr_schedule, right behind vg_zero_tick,
+        writes both rates into ``lr_now`` in fp64 rounded once; every AdamW call of the step is then the _dlr form
+        (vg_adamw_step_dlr / vg_adamw_ema_step_dlr, the sharded pieces included), which reads its network's rate there - so a captured
+        step replays with a fresh rate and a resumed run continues its schedule from the restored counter.  ``lr`` reads the pair in
+        force; ``set_lr_scale(d=, g=)`` writes the multipliers (1 at construction; what a plateau rule drives), ``state_dict()`` carries
+        them and the four options.  Default ("" and no warm-up): no buffer, the host floats ``hyp["lr_d"]`` / ``hyp["lr_g"]`` as kernel
+        arguments, and the step is launch for launch and bit for bit the plain one.  With a schedule on, ``hyp["lr_*"]`` are the base
+        rates, read when a step is enqueued (captured).  Goes with every other option and both schedules of the step."""
         self._check_options(discriminator, generator, dict(locals()))
         self._carve()
         self._attach()
@@ -201,6 +215,15 @@ class GanEngine:
         self.bcr = self.bcr_w != (0.0, 0.0)
         self.r1_gamma, self.r1_interval = ops.parse_r1_options(o["r1_gamma"], o["r1_interval"], o["gp_weight"])
         self.r1 = self.r1_gamma > 0.0
+        self.lr_opts = ops.parse_lr_schedule(o["lr_schedule"], o["lr_warmup"], o["lr_total"], o["lr_final"])  # None = host floats
+        if self.lr_opts is not None:
+            for name in ("lr_d", "lr_g"):  # (what vg_lr_schedule refuses as a base rate)
+                try:
+                    ok = 0.0 < float(o[name]) < float("inf")
+                except (TypeError, ValueError):
+                    ok = False
+                if not ok:
+                    raise ValueError(f"lr_schedule: the base rate {name} must be positive and finite, got {o[name]!r}")
         if self.bcr_policy and self.aug:
             raise ValueError("bcr_aug: with diffaug on, diffaug's own transform T_1 is the consistency partner; leave bcr_aug empty")
         if self.bcr_policy and not self.bcr:
@@ -376,6 +399,12 @@ class GanEngine:
         self.m_g, self.v_g = torch.zeros_like(fg.flat), torch.zeros_like(fg.flat)
         # the generator's averaged weights (a copy of the master until the first step, which copies again: see ema_decay)
         self.ema_g: Optional[torch.Tensor] = fg.flat.detach().clone() if self.ema_decay > 0.0 else None
+        # the scheduled rates: the multipliers (training state, written by set_lr_scale) and what vg_lr_schedule writes each step
+        self.lr_scale: Optional[torch.Tensor] = None
+        self.lr_now: Optional[torch.Tensor] = None
+        if self.lr_opts is not None:
+            self.lr_scale, self.lr_now = torch.ones(2, dtype=torch.float32, device=dev), f32(2)
+            self.lr_slot = (self.lr_now[0:1], self.lr_now[1:2])  # slot 0 = D, 1 = G: the _dlr calls' lr_dev
         # ---- the views: what each pass reads and writes, chosen here once
         halves = lambda t: (t[:B], t[B:2 * B])  # noqa: E731
         self.fake = self.imgs[B:]
@@ -559,31 +588,40 @@ class GanEngine:
         """(master, gradient, m, v, shadow, average or None, elements) of [lo, hi) of a network's flat buffers: AdamW's operands"""
         return tuple(None if t is None else t[lo:hi] for t in (fp.flat, fp.grad, m, v, fp.shadow, ema)) + (hi - lo,)
 
-    def _adamw_range(self, r, lr, st) -> None:
-        """AdamW on one range (``_range``) - with the weights' moving average in the same pass when the range carries one."""
+    def _lr_tick(self, st) -> None:
+        """Both networks' rates of this step from the counter vg_zero_tick has just advanced (one launch); nothing without a schedule."""
+        if self.lr_opts is not None:
+            d, g = (ops.lr_sched_struct(self.hyp[k], *self.lr_opts) for k in ("lr_d", "lr_g"))
+            _call("vg_lr_schedule", C.byref(d), C.byref(g), _p(self.step_t), _p(self.lr_scale), _p(self.lr_now), st)
+
+    def _adamw_range(self, r, slot: int, st) -> None:
+        """AdamW on one range (``_range``) of network ``slot`` (0 = D, 1 = G) - with the weights' moving average in the same pass when
+        the range carries one; the rate is the host float, or with a schedule on the slot's float on the device (the _dlr calls)."""
         *bufs, ema, n = r
         if n <= 0:
             return
         h = self.hyp
+        dlr = "" if self.lr_opts is None else "_dlr"
+        lr = _p(self.lr_slot[slot]) if dlr else h["lr_g" if slot else "lr_d"]
         tail = (n, lr, h["b1"], h["b2"], h["eps"], h["wd"], 0, _p(self.step_t), 1.0 / self.world)
         if ema is None:
-            _call("vg_adamw_step", *map(_p, bufs), *tail, st)
+            _call("vg_adamw_step" + dlr, *map(_p, bufs), *tail, st)
         else:
-            _call("vg_adamw_ema_step", *map(_p, bufs), _p(ema), *tail, self.ema_decay, self._ema_from, st)
+            _call("vg_adamw_ema_step" + dlr, *map(_p, bufs), _p(ema), *tail, self.ema_decay, self._ema_from, st)
 
-    def _adamw(self, r, lr, st, clip=None, slot=0) -> None:
-        """A whole network's optimizer step: the clipping (on the exchanged, global gradient, like clip_grad_norm_ before
-        optimizer.step()), then AdamW on the whole range."""
+    def _adamw(self, r, slot: int, st, clip=None) -> None:
+        """A whole network's optimizer step (``slot``: 0 = D, 1 = G): the clipping (on the exchanged, global gradient, like
+        clip_grad_norm_ before optimizer.step()), then AdamW on the whole range."""
         if clip is not None:
             _call("vg_grad_clip", _p(r[1]), r[-1], 1.0 / self.world, float(clip), _p(self.clip_slot[slot]), st)
-        self._adamw_range(r, lr, st)
+        self._adamw_range(r, slot, st)
 
     def _adamw_g_sharded(self, st) -> None:
         """The generator's AdamW with the mapping Linear sharded: the whole buffer but that layer as usual, of the layer this rank's
         share only; then the updated fp32 master shares to every rank and the layer's bf16 shadow cast from them there (the GEMMs of
         every rank read the whole shadow; gathering the master, not the shadow, keeps every rank's master current)."""
         for r in self.r_g_pieces:  # below the layer, this rank's share of it (its average comes from the gathered master), above it
-            self._adamw_range(r, self.hyp["lr_g"], st)
+            self._adamw_range(r, 1, st)
         w0, w1 = self._map_range()
         self.sync.all_gather_range(self.gen._flat.flat, w0, w1)
         self.sync.wait()
@@ -638,6 +676,38 @@ class GanEngine:
         """r_t = E[sign(D(real))] over the window of the controller's last update (synchronises: for logging)."""
         return float(self._need_ada("ada_rt")[3])
 
+    @property
+    def lr(self):
+        """``(lr_d, lr_g)`` now in force (synchronises: for logging): with a schedule on, what the last step's AdamW read
+        ((0, 0) until this engine has run a step); without one, the host floats."""
+        if self.lr_opts is None:
+            return float(self.hyp["lr_d"]), float(self.hyp["lr_g"])
+        d, g = self.lr_now.tolist()
+        return d, g
+
+    @property
+    def lr_scales(self):
+        """The two device multipliers ``(d, g)`` (synchronises: for logging)."""
+        d, g = self._need(self.lr_scale, "lr_scales: this engine runs no learning-rate schedule (built without lr_schedule / lr_warmup)").tolist()
+        return d, g
+
+    def set_lr_scale(self, d: Optional[float] = None, g: Optional[float] = None) -> None:
+        """Write the device multipliers of the scheduled rates (None leaves one alone): the step after the call runs at
+        base * f(t) * multiplier.  The write goes to a buffer the step reads, outside the hipGraph like the step's inputs, so a
+        captured step needs no new capture.  Under data parallelism the caller sets the SAME value on every rank (nothing exchanges
+        the multipliers; the schedule itself is a function of the counter and needs no exchange)."""
+        scale = self._need(self.lr_scale, "set_lr_scale: this engine runs no learning-rate schedule (built without lr_schedule / lr_warmup)")
+        for i, v in ((0, d), (1, g)):
+            if v is None:
+                continue
+            try:
+                ok = 0.0 <= float(v) < float("inf")
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f"set_lr_scale: a multiplier is a finite, non-negative number, got {v!r}")
+            scale[i:i + 1].fill_(float(v))
+
     def _need_ada(self, what: str) -> torch.Tensor:
         return self._need(self.ada_state, f"{what}: this engine holds no augmentation probability (built without aug_p / ada_target)")
 
@@ -667,6 +737,7 @@ class GanEngine:
         fd, fg = self.vit._flat, self.gen._flat
         noisy = self.inst_sigma > 0.0
         _call("vg_zero_tick", _p(fd.grad), fd.total, _p(self.step_t), st0)
+        self._lr_tick(st0)
         self.grad2.zero_()
         s1.wait_stream(s0)
         # chain 1 (side stream): G forward, then D on the fake batch (weight gradients into grad2)
@@ -685,7 +756,7 @@ class GanEngine:
         self._d_backward(nd_a, B, self.ws_d, self.dlg_half[0], 1, None, st0, exchange=False)
         s0.wait_stream(s1)
         fd.grad.add_(self.grad2)  # the two passes accumulate into one .grad in the reference (training.py:184,194)
-        self._adamw(self.r_d, self.hyp["lr_d"], st0, self.clip_d, 0)
+        self._adamw(self.r_d, 0, st0, self.clip_d)
         fg.grad.zero_()
         # generator's pass through the updated D: two half-batches side by side (no weight gradients, nothing shared)
         h = B // 2
@@ -703,7 +774,7 @@ class GanEngine:
         s0.wait_stream(s1)
         self._diversity(st0)
         _call("vg_gen_backward", C.byref(ng), B, _p(self.ws_g), _p(self.dfake), st0)
-        self._adamw(self.r_g, self.hyp["lr_g"], st0, self.clip_g, 1)
+        self._adamw(self.r_g, 1, st0, self.clip_g)
 
     def _inputs(self, real: torch.Tensor, labels=None, fake_labels=None) -> None:
         """The step's inputs, ONE launch in front of the step proper (and outside its hipGraph, so it reads the caller's tensor
@@ -768,6 +839,7 @@ class GanEngine:
         fd, fg = self.vit._flat, self.gen._flat
         # gan.discriminator.zero_grad() (training.py:177) and the device step counter += 1, one launch
         _call("vg_zero_tick", _p(fd.grad), fd.total, _p(self.step_t), st)
+        self._lr_tick(st)
         self._g_forward(ng, st)
         if self.inst_sigma > 0.0:
             self._instance_noise(self.noise_parts[0])
@@ -803,7 +875,7 @@ class GanEngine:
         self.sync.wait()
         if self.spec is not None:  # dL/dW_eff -> dL/dW on the exchanged total of both passes and the penalty (the map is linear)
             self.spec.project(fd.grad, fd.flat, st)
-        self._adamw(self.r_d, self.hyp["lr_d"], st, self.clip_d, 0)
+        self._adamw(self.r_d, 0, st, self.clip_d)
         if self.spec is not None:  # one power iteration on the updated master; AdamW's plain cast of the normalised ranges is overwritten
             self.spec.update(fd.flat, fd.shadow, True, st)
         fg.grad.zero_()            # gan.generator.zero_grad(), training.py:199
@@ -821,19 +893,21 @@ class GanEngine:
         if self.shard_map:
             self._adamw_g_sharded(st)
         else:
-            self._adamw(self.r_g, self.hyp["lr_g"], st, self.clip_g, 1)
+            self._adamw(self.r_g, 1, st, self.clip_g)
 
     # ------------------------------------------------------------------------------------------
     def _optional_state(self):
         """THE table of training state an option adds: (key, tensor or None when the option is off, options key, options getter).  It
         drives ``_state_tensors`` (what the graph warm-up must put back), ``state_dict`` and ``load_state_dict``: an option's state is
-        one entry here.  (bCR and R1 hold no state, only options; the average is saved without options.)"""
+        one entry here.  (bCR and R1 hold no state, only options; the average is saved without options; the learning-rate schedule's
+        state is its two multipliers - the rates themselves are rewritten by every step.)"""
         spec = self.spec is not None
         return (("spectral_state", self.spec.state if spec else None, "spectral_norm", lambda: self.spectral_norm if spec else None),
                 (None, None, "bcr", self._bcr_options),
                 (None, None, "r1", self._r1_options),
                 (None, None, "n_classes", lambda: self.n_classes or None),
                 ("ada_state", self.ada_state, "ada", self._ada_options),
+                ("lr_scale", self.lr_scale, "lr", lambda: self.lr_opts),
                 ("ema_g", self.ema_g, None, None))
 
     def _state_tensors(self):
@@ -848,6 +922,7 @@ class GanEngine:
         (a fresh optimizer, which is what the reference has after a restart: it saves no optimizer state,
         training.py:218-226,262-263).  The generator's moving average needs no code here: a plain refresh leaves it alone, and a
         cleared step counter makes the next step's kernel copy the updated weights into it - the average restarts with the optimizer.
+        A learning-rate schedule restarts with the counter as well (its warm-up runs again); the multipliers stay as they are.
         With ``spectral_norm`` a plain refresh keeps the normalisation (the scaled cast from the stored sigma); ``reset_optimizer``
         measures it again: sigma0 = sigma_max of the current weights, so the network is the plain one at that point."""
         if reset_optimizer and self.spec is not None:
@@ -964,7 +1039,9 @@ class GanEngine:
         spectral-normalisation state follows the same rule: missing under ``strict`` raises, with ``strict=False`` it is measured
         again from the current weights.  Consistency regularisation has no state; the saved ``bcr`` options must equal this engine's under
         ``strict``, and so must the saved ``r1`` options (the lazy schedule continues from the restored ``steps``).  The augmentation probability and its controller (``aug_p`` / ``ada_target``) follow bCR's rule for the options, and
-        their state is restored whenever both sides hold one."""
+        their state is restored whenever both sides hold one.  The learning-rate schedule's options (``"lr"``) are compared under ``strict``
+        in the same way; its multipliers are restored whenever both sides hold them, so a resumed run continues its schedule from the
+        restored counter at the restored multipliers."""
         if sd.get("format_version") != self.STATE_FORMAT:
             raise ValueError(f"engine state format {sd.get('format_version')!r}, this engine reads format {self.STATE_FORMAT}")
         names = ("m_d", "v_d", "m_g", "v_g", "step_t")
@@ -991,6 +1068,10 @@ class GanEngine:
         if strict and saved_r1 != self._r1_options():
             raise ValueError(f"engine state was saved with the R1 penalty (r1_gamma, r1_interval) = {saved_r1!r}, this engine has "
                              f"{self._r1_options()!r} (strict=False loads it all the same: R1 holds no training state)")
+        saved_lr = None if sd.get("lr") is None else tuple(sd["lr"])
+        if strict and saved_lr != self.lr_opts:
+            raise ValueError(f"engine state was saved with the learning-rate schedule (kind, warmup, total, final) = {saved_lr!r}, this engine "
+                             f"has {self.lr_opts!r} (strict=False loads the multipliers all the same when both sides hold them)")
         has_ema = sd.get("ema_g") is not None
         if strict and has_ema != (self.ema_g is not None):
             raise ValueError("engine state has no ema_g but this engine keeps a moving average (strict=False restarts it)" if not has_ema

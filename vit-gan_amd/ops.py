@@ -420,6 +420,61 @@ def r1_due(step_index: int, interval: int) -> bool:
     return (int(step_index) - 1) % int(interval) == 0
 
 
+LR_KINDS = {"constant": 0, "linear": 1, "cosine": 2}  # VG_LR_* of include/vitgan_hip.h
+
+
+def parse_lr_schedule(kind, warmup, total, final):
+    """``(kind, warmup, total, final)`` of the learning-rate schedule, checked as GanEngine and train_model both state them, or None when
+    no schedule is asked for (``kind=""`` and ``warmup=0``: the rates stay host floats).  kind: "" | "constant" | "linear" | "cosine" -
+    "" with a warm-up means "constant"; warmup: a non-negative integer, the steps of linear warm-up; total: a non-negative integer, the
+    step from which the factor is ``final`` - a decaying kind needs total > warmup; final: a number in [0, 1].  A constant schedule
+    reads neither total nor final: they come back as 0 and 0.0, so two such runs carry the same options."""
+    if not isinstance(kind, str) or (kind and kind not in LR_KINDS):
+        raise ValueError(f"lr_schedule must be one of '', {', '.join(repr(k) for k in LR_KINDS)}, got {kind!r}")
+    for name, v in (("lr_warmup", warmup), ("lr_total", total)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 2 ** 31:
+            raise ValueError(f"{name} must be a non-negative integer (steps), got {v!r}")
+    try:
+        fin = float(final)
+    except (TypeError, ValueError):
+        raise ValueError(f"lr_final must be a number in [0, 1], got {final!r}") from None
+    if not 0.0 <= fin <= 1.0:
+        raise ValueError(f"lr_final must be a number in [0, 1] (the factor from lr_total on), got {final!r}")
+    if not kind and warmup == 0:
+        if total != 0 or fin != 0.0:
+            raise ValueError(f"lr_total={total!r} / lr_final={final!r} without a schedule would do nothing; name one in lr_schedule")
+        return None
+    kind = kind or "constant"
+    if kind == "constant":
+        return kind, int(warmup), 0, 0.0
+    if total <= warmup:
+        raise ValueError(f"lr_schedule={kind!r}: the decay runs from step lr_warmup to step lr_total and needs lr_total > lr_warmup, "
+                         f"got lr_total={total!r}, lr_warmup={warmup!r}")
+    return kind, int(warmup), int(total), fin
+
+
+def lr_sched_struct(base, kind, warmup, total, final) -> "_lib.VgLrSched":
+    """One slot's VgLrSched from a base rate and a parsed schedule (``parse_lr_schedule``'s tuple; the kind by name or number)."""
+    return _lib.VgLrSched(float(base), LR_KINDS.get(kind, kind), int(warmup), int(total), float(final))
+
+
+def lr_schedule(step: torch.Tensor, d, g, scale: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The two learning rates in force at the device step counter ``step`` (a cuda int32 tensor; a value below 1 counts as 1), one
+    vg_lr_schedule launch: ``d`` / ``g`` = (base, kind, warmup, total, final) of slot 0 (the discriminator) and slot 1 (the generator),
+    ``scale``: the two device multipliers (fp32 [2]; None = ones), ``out``: fp32 [2] to write (returned; None = a fresh tensor).
+    Every argument the kernel would misread is refused by the C call (HipError, argument validation)."""
+    if not torch.is_tensor(step) or not step.is_cuda or step.dtype != torch.int32 or step.numel() < 1:
+        raise ValueError("lr_schedule: step is the device step counter, a cuda int32 tensor")
+    for name, t in (("scale", scale), ("out", out)):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32 or t.numel() != 2 or not t.is_contiguous() or t.device != step.device):
+            raise ValueError(f"lr_schedule: {name} is a contiguous fp32 tensor of two elements on the counter's device")
+    scale = torch.ones(2, dtype=torch.float32, device=step.device) if scale is None else scale
+    out = torch.empty(2, dtype=torch.float32, device=step.device) if out is None else out
+    sd, sg = lr_sched_struct(*d), lr_sched_struct(*g)
+    _lib.check(_lib.lib().vg_lr_schedule(C.byref(sd), C.byref(sg), _p(step), _p(scale), _p(out), _st()), "vg_lr_schedule")
+    return out
+
+
 class ConsistencyLossFn(torch.autograd.Function):
     """Balanced consistency regularisation between D(x) and D(T(x)) (include/vitgan_hip.h, vg_bcr_loss): one launch computes both segment
     means and both gradients, so the backward only scales what the forward saved."""

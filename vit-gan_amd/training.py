@@ -34,7 +34,7 @@ import os
 import struct
 import traceback
 import zlib
-from typing import Any, Callable, Dict, Iterable, Optional, Union
+from typing import Any, Callable, Dict, Iterable, Optional, Tuple, Union
 
 import torch
 from torch import nn
@@ -165,6 +165,43 @@ def get_data_loader(c: Config):
     return DataLoader(ds, batch_size=c.batch_size, shuffle=True, num_workers=4, drop_last=True)
 
 
+class Plateau:
+    """``torch.optim.lr_scheduler.ReduceLROnPlateau(mode="min", factor, patience)`` with its defaults (relative threshold 1e-4, no
+    cooldown) as a host-side rule: ``step(metric)`` says whether the rates are to be reduced now."""
+
+    def __init__(self, factor: float, patience: int, threshold: float = 1e-4):
+        self.factor, self.patience, self.threshold = factor, patience, threshold
+        self.best, self.bad = float("inf"), 0
+
+    def step(self, metric: float) -> bool:
+        if metric < self.best * (1.0 - self.threshold):
+            self.best, self.bad = metric, 0
+        else:
+            self.bad += 1  # (a NaN score is a bad epoch, as in torch)
+        if self.bad > self.patience:
+            self.bad = 0
+            return True
+        return False
+
+
+def parse_lr_plateau(lr_plateau, fid_fn) -> Optional[Plateau]:
+    """``(factor, patience)`` of ``train_model(lr_plateau=...)`` as a ``Plateau`` (None = off); host only."""
+    if lr_plateau is None:
+        return None
+    try:
+        factor, patience = lr_plateau
+        factor = float(factor)
+    except (TypeError, ValueError):
+        raise ValueError(f"lr_plateau must be a pair (factor, patience), got {lr_plateau!r}") from None
+    if not 0.0 < factor < 1.0:
+        raise ValueError(f"lr_plateau: the factor must be in (0, 1), got {lr_plateau[0]!r}")
+    if isinstance(patience, bool) or not isinstance(patience, int) or patience < 0:
+        raise ValueError(f"lr_plateau: the patience must be a non-negative integer (epochs), got {patience!r}")
+    if fid_fn is None:
+        raise ValueError("lr_plateau: the plateau rule watches the FID hook's score; pass fid_fn")
+    return Plateau(factor, patience)
+
+
 class MissingLabelsError(ValueError):
     """a conditional run was given a data loader without labels: the caller's error, raised out of ``train_model``"""
 
@@ -213,7 +250,9 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                 diversity_weight: float = 0.0, instance_noise: float = 0.0, gp_weight: float = 0.0, diffaug: str = "",
                 ema_decay: float = 0.0, ema_start: int = 0, spectral_norm: str = "", bcr=(0.0, 0.0), bcr_aug: str = "",
                 aug_p: Optional[float] = None, ada_target: float = 0.0, ada_interval: int = 4, ada_kimg: float = 500.0,
-                r1_gamma: float = 0.0, r1_interval: int = 1, conditional: bool = False):
+                r1_gamma: float = 0.0, r1_interval: int = 1, conditional: bool = False,
+                lr_schedule: str = "", lr_warmup: int = 0, lr_total: Optional[int] = None, lr_final: float = 0.0,
+                lr_plateau: Optional[Tuple[float, int]] = None):
     """``loss``: "ns" (default: the executable v1 loss), "hinge", or "wasserstein" - the critic losses of the reference's
     unreached step (training.py:67-125); ``clip_d`` / ``clip_g``: its clip_grad_norm_ limits (5.0 / 0.5 there);
     ``diversity_weight``: its diversity term (0.1 there); ``instance_noise``: sigma of the noise on D's inputs (0.1
@@ -244,7 +283,16 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     ``classes_count`` classes (at most 16): the loader's labels go to the step - a loader that yields ``None`` in their place, like the
     default ``SyntheticLoader`` without ``labels=K``, is an error; when no loader is given the synthetic one draws labels itself -
     and image i of every sample grid is of class ``i % classes_count``.  The checkpoints then also hold
-    ``generator.class_embedding.weight``."""
+    ``generator.class_embedding.weight``.
+    ``lr_schedule`` / ``lr_warmup`` / ``lr_total`` / ``lr_final``: a learning-rate schedule evaluated on the device
+    (``GanEngine(lr_schedule=...)``: "constant", "linear" or "cosine" with ``lr_warmup`` steps of linear warm-up, falling to ``lr_final``
+    times the base rate at step ``lr_total``); ``lr_total=None`` means the whole run, ``epochs * len(loader)`` steps.  When it is on, a
+    header line of ``training.log`` states the schedule and every epoch's line carries the two rates in force.
+    ``lr_plateau``: ``(factor, patience)``, the reference's intended ``ReduceLROnPlateau(mode="min")`` on the FID hook
+    (src/v2/training.py:15,215-216; torch's default relative threshold 1e-4, no cooldown, no floor): when ``fid_fn``'s score has not
+    improved for more than ``patience`` epochs, both rates' multipliers are multiplied by ``factor``
+    (``GanEngine.set_lr_scale``).  It needs ``fid_fn``, and it switches the device-resident rates on (``lr_schedule=""`` then means
+    "constant")."""
     global _log_file
     from .ops import parse_aug_policy, parse_bcr_weights
     parse_aug_policy(diffaug)  # a bad policy string is the caller's error whatever the machine: before the device check
@@ -260,6 +308,7 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     parse_ada_options(aug_p, ada_target, ada_interval, ada_kimg, parse_aug_policy(diffaug), loss)
     from .ops import parse_r1_options
     parse_r1_options(r1_gamma, r1_interval, gp_weight)
+    plateau = parse_lr_plateau(lr_plateau, fid_fn)
     if not 0.0 <= float(ema_decay) < 1.0:
         raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
     if int(ema_start) != ema_start or ema_start < 0:
@@ -271,6 +320,15 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
         raise ValueError(f"conditional: classes_count must be in [1, 16] (the width of the head kernels), got {c.classes_count!r}")
     if conditional and (float(gp_weight) != 0.0 or float(r1_gamma) > 0.0):
         raise ValueError("conditional: the gradient penalties (gp_weight, r1_gamma) are not built for the label-selected logit; switch them off")
+    epochs = c.epochs if max_epochs is None else min(c.epochs, max_epochs)
+    # the schedule's argument errors are the caller's whatever the machine: before the device check (None = the whole run)
+    from .ops import parse_lr_schedule
+    if plateau is not None and not lr_schedule and not lr_warmup:
+        lr_schedule = "constant"  # the multipliers live with the device-resident rates
+    if lr_total is None:
+        per_epoch = len(data_loader) if data_loader is not None else steps_per_epoch
+        lr_total = epochs * per_epoch if (lr_schedule or lr_warmup) else 0
+    lr_opts = parse_lr_schedule(lr_schedule, lr_warmup, lr_total, lr_final)
     if not torch.cuda.is_available():
         raise RuntimeError("train_model needs an MI355X: the HIP engine has no CPU path")
     dev = torch.device(device)
@@ -285,7 +343,8 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                     weight_decay=1e-3, seed=seed, clip_d=clip_d, clip_g=clip_g, diversity_weight=diversity_weight,
                     instance_noise=instance_noise, gp_weight=gp_weight, diffaug=diffaug, ema_decay=ema_decay, ema_start=ema_start,
                     spectral_norm=spectral_norm, bcr=bcr, bcr_aug=bcr_aug, aug_p=aug_p, ada_target=ada_target, ada_interval=ada_interval,
-                    ada_kimg=ada_kimg, r1_gamma=r1_gamma, r1_interval=r1_interval, n_classes=K)
+                    ada_kimg=ada_kimg, r1_gamma=r1_gamma, r1_interval=r1_interval, n_classes=K,
+                    lr_schedule=lr_schedule, lr_warmup=lr_warmup, lr_total=lr_total, lr_final=lr_final)
 
     def gan_checkpoint():  # gan.state_dict(), the discriminator's normalised matrices as the network applies them
         sd = gan.state_dict()
@@ -306,7 +365,6 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     loader = data_loader if data_loader is not None else SyntheticLoader(c, steps_per_epoch, dev, labels=K)
     # the fixed sample grid of a conditional run: image i is of class i % K
     grid_labels = (torch.arange(c.batch_size, device=dev) % K).to(torch.int32) if conditional else None
-    epochs = c.epochs if max_epochs is None else min(c.epochs, max_epochs)
 
     def construct_noise():  # the v1 generator's latent, gan.py:231-232 (the v2 noise is image-shaped, training.py:35-42)
         return torch.randn(c.batch_size, G.latent, device=dev)
@@ -352,6 +410,11 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
             log(f"Class-conditional training: {K} classes, label-selected discriminator logit, class-modulated generator")
         if eng.r1:
             log(f"R1 penalty on real images: gamma {eng.r1_gamma:g}, every {eng.r1_interval} step(s) with weight {0.5 * eng.r1_gamma * eng.r1_interval:g}")
+        if lr_opts is not None:
+            kind, warm, total, fin = lr_opts
+            log(f"Learning-rate schedule: {kind}, {warm} warm-up step(s)" + (f", to {fin:g} x base at step {total}" if kind != "constant" else "")
+                + f"; base rates D {eng.hyp['lr_d']:g}, G {eng.hyp['lr_g']:g}"
+                + (f"; on a plateau of the FID (patience {plateau.patience}) both x {plateau.factor:g}" if plateau is not None else ""))
         for epoch in range(epochs):
             noise = construct_noise()
             if save_artifacts:
@@ -388,6 +451,12 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                 cr += f" | ada_p: {eng.ada_p:.6f}, ada_rt: {eng.ada_rt:.4f}"
             if eng.r1:
                 cr += f" | R1: {float(eng.r1_loss):.6f}"
+            if eng.lr_opts is not None:  # the rates this epoch's last step ran at
+                cr += " | lr_d: {:.9e}, lr_g: {:.9e}".format(*eng.lr)
+            if plateau is not None and plateau.step(fid_score):  # takes effect from the next step on
+                sd_, sg_ = eng.lr_scales
+                eng.set_lr_scale(d=sd_ * plateau.factor, g=sg_ * plateau.factor)
+                cr += f" | FID plateau: rate multipliers now {sd_ * plateau.factor:g}, {sg_ * plateau.factor:g}"
             log(f"Epoch [{epoch}/{epochs}] | Disc Loss: {d_real + d_fake:.8f}, Gen Loss: {g:.4f} | FID: {fid_score:.4f}{cr}")
             if save_artifacts:
                 save_figures(dirs.save, disc_losses=disc_losses, gen_losses=gen_losses, fid_scores=fid_scores)
