@@ -15,14 +15,12 @@
 // group t):   W1(0) | W1(1) W2(0) | W1(2) W2(1) | ... | W1(11) W2(10) | W2(11)        W1(t): 2 stages [64 n][192 k]: hidden
 // columns 64 t .. 64 t + 63 over k halves; W2(t): 2 stages [384 n][32 k]: fc2's k-steps 2 t, 2 t + 1.
 #include "vg_chain.h"
+#include "vg_tile.h"
 #include <type_traits>
 
 #pragma clang fp contract(off)
 
 namespace {
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 constexpr int CH_NS = 6;                       // ring slots
 constexpr int CH_RING = CH_NS * VG_CH_STAGE;   // 147 456 B
 #ifndef CH_QN_
@@ -104,13 +102,13 @@ __global__ __launch_bounds__(512) void vg_chain_fwd_kernel(const VgChainMlpArgs 
   __shared__ __attribute__((aligned(1024))) unsigned char smem[CH_RING + CH_PAR + (((CH_DBG & 64) && !FRONT) ? 8 * 104 * 8 : 0)];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const unsigned sbase = (unsigned)(unsigned long)(lptr_t)smem;
+  const unsigned sbase = (unsigned)(unsigned long)(vg_lptr_t)smem;
   const unsigned lane16 = (unsigned)lane * 16u;
   constexpr int S = VG_CH_MLP_STAGES + (FRONT ? VG_CH_FRONT_STAGES : 0);
   const int upw = a.upw;  // 16-row units (= active waves) of a workgroup tile
   const int ntiles = (a.units + upw - 1) / upw;
   const int g = lane >> 4, li = lane & 15;
-  const int cg = ((g & 1) << 4) + ((g & 2) << 2);  // first of the lane's 8 consecutive columns inside a tile pair, after the swap
+  const int cg = vg_pair_col(g);  // first of the lane's 8 consecutive columns inside a tile pair, after the swap
 
   // kernel arguments, read once (an s_load in the middle of the stream would sit in the counted lgkmcnt queue)
   const char* img = (const char*)a.img;
@@ -143,7 +141,7 @@ __global__ __launch_bounds__(512) void vg_chain_fwd_kernel(const VgChainMlpArgs 
       unsigned char* d = smem + (s % CH_NS) * VG_CH_STAGE + 3072 * wid;
 #pragma unroll
       for (int i = 0; i < 3; ++i)
-        __builtin_amdgcn_global_load_lds((gptr_t)(src + 1024 * i + lane16), (lptr_t)(d + 1024 * i), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((vg_gptr_t)(src + 1024 * i + lane16), (vg_lptr_t)(d + 1024 * i), 16, 0, 0);
     };
     // The first Linear's A operand: rows of xn (FRONT: of the attention output) as 12 fragments, k order natural (16 B per lane and
     // k-step); requested before the ring's first stages so that the first counted wait covers them.  FRONT: the epilogue behind
@@ -271,7 +269,7 @@ __global__ __launch_bounds__(512) void vg_chain_fwd_kernel(const VgChainMlpArgs 
       asm volatile("" : "+v"(ln));
       asm volatile("" : "+s"(resp), "+s"(Yp), "+s"(Ynp), "+s"(meanp), "+s"(rstdp));
       const int eg = ln >> 4;
-      const int ecg = ((eg & 1) << 4) + ((eg & 2) << 2);
+      const int ecg = vg_pair_col(eg);
       const int erow = (a.upw * tile + wid) * 16 + (ln & 15);
       const unsigned char* par = smem + CH_RING;
       const unsigned dthr = a.drop_thresh, dkey = vg_drop_key(key_host, a.drop_step);
@@ -293,13 +291,11 @@ __global__ __launch_bounds__(512) void vg_chain_fwd_kernel(const VgChainMlpArgs 
         const u32x4 rc = rv[p % RB];
         if (p + RB < 12) rv[p % RB] = ld_res(p + RB);
         const f32x4 bA = *(const f32x4*)(par + par_bias + 4 * c0), bB = *(const f32x4*)(par + par_bias + 4 * c0 + 16);
+        f32x4 lo, hi;
+        vg_pair_swap(acc[2 * p], acc[2 * p + 1], lo, hi);
         float v[8];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[2 * p][r]), __float_as_uint(acc[2 * p + 1][r]), false, false);
-          v[r] = __uint_as_float(sw[0]) + bA[r];
-          v[r + 4] = __uint_as_float(sw[1]) + bB[r];
-        }
+        for (int r = 0; r < 4; ++r) { v[r] = lo[r] + bA[r]; v[r + 4] = hi[r] + bB[r]; }
         if (dthr) {
           const unsigned i4 = ((unsigned)erow * drm * (unsigned)VG_CH_E + (unsigned)c0) >> 2;
           const unsigned w0 = vg_drop_word(dkey, i4), w1 = vg_drop_word(dkey, i4 + 1);
@@ -481,7 +477,7 @@ __global__ __launch_bounds__(256) void vg_chain_pack_kernel(const bf16* __restri
   if (korder == VG_CH_KNAT) {
     v = *(const bf16x8*)(src + 8 * g);
   } else if (korder == VG_CH_KS) {
-    v = *(const bf16x8*)(src + ((g & 1) << 4) + ((g & 2) << 2));
+    v = *(const bf16x8*)(src + vg_pair_col(g));
   } else {
     const bf16x4 lo = *(const bf16x4*)(src + 4 * g), hi = *(const bf16x4*)(src + 16 + 4 * g);
     v = (bf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};

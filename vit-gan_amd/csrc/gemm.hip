@@ -8,18 +8,9 @@
 // ring at every step.  What bounds the family is the L2 -> LDS staging rate (~10 TB/s chip-wide):
 // FLOP/s follow flop per staged byte, i.e. the tile size.
 //
-// The MFMA is issued "swapped": its A operand carries the GEMM's n index and its B operand the
-// m index, so a lane's 4 accumulator registers are 4 CONSECUTIVE n of one output row m; the epilogue pairs
-// n-tiles with v_permlane16_swap and stores 16 B (bf16) / 32 B (fp32) per lane straight from registers.
-//
-// Operand images in LDS:
-//   row form  [rows][32 k]  (64-B rows): 16-B chunk c of row r lives at chunk c ^ F[(r>>2)&3],
-//             F = {0,2,3,1}: the four 16-lane groups of a ds_read_b128 then each cover all 16
-//             slots of a 256-B bank row (conflict-free).
-//   tr  form  [32 k][128 cols]  (256-B rows): 16-B chunk c of row k lives at c ^ (2*sigma(k)),
-//             sigma(k) = (k&3) | ((k>>3)&1)<<2; fragments by two ds_read_b64_tr_b16, whose 32-lane
-//             halves then touch all 64 banks exactly once.
-#include "vg_gemm.h"
+// The operand images in LDS (row form, tr form), the swapped MFMA and the lane's place in a tile are defined in vg_tile.h,
+// the register epilogue of a slot in vg_epilogue.h.
+#include "vg_epilogue.h"
 #include <stdlib.h>
 
 #define BM (64 * WM)   // WM wave-rows: 2 -> 128 x 128 tile (256 threads), 4 -> 256 x 128 tile (512 threads)
@@ -45,18 +36,7 @@
 #define B_TILE_BYTES (BN * BK * 2)
 #define STAGE_BYTES (A_TILE_BYTES + B_TILE_BYTES)
 
-__device__ __forceinline__ int tr_sigma(int kk) { return (kk & 3) | (((kk >> 3) & 1) << 2); }
-
-// ---- global -> LDS, direct (global_load_lds_dwordx4: 64 lanes x 16 B = 1 KiB per wave-instruction) ----
-// The LDS destination of one instruction is wave-uniform base + lane*16, so the tile images are
-// lane-linear per 1-KiB piece and the XOR swizzle is applied to the per-lane SOURCE address
-// (cdna_hip_programming.md rule 21).  A tile is 16 pieces; wave w issues pieces w, w+4, w+8, w+12.
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-// row-form chunk swizzle: {0,2,3,1}[(r>>2)&3]
-__device__ __forceinline__ int row_f(int r) { return (0x78 >> (2 * ((r >> 2) & 3))) & 3; }
-
+// ---- global -> LDS, direct (LDS-DMA; the images and their swizzles: vg_tile.h) ----
 // PIECES 1-KiB pieces per tile (8 per 128 rows/cols), dealt round-robin to the NW waves.
 // Addressing is split into a wave-UNIFORM base (tile origin at the current k, kept in SGPRs and advanced by one
 // scalar add per k-step) and a per-lane 32-bit byte offset per piece that never changes: in the steady state a
@@ -77,7 +57,7 @@ struct Stager {
     if (!TR) {
       constexpr int LPR = 4;
       const int rl = (64 / LPR) * j + lane / LPR;
-      return ((lane & (LPR - 1)) ^ row_f(rl)) << 3;
+      return ((lane & (LPR - 1)) ^ vg_row_swz(rl)) << 3;
     }
     return 4 * (j % 8) + (lane >> 4);
   }
@@ -96,7 +76,7 @@ struct Stager {
       } else {    // piece = 4 k-rows x 256 B of one 128-column sub-tile (8 pieces per sub-tile)
         const int sub = j / 8;
         const int kk = lane_k(j, lane);
-        const int c = (lane & 15) ^ (2 * tr_sigma(kk));
+        const int c = (lane & 15) ^ (2 * vg_tr_sigma(kk));
         const int col = min(idx0 + 128 * sub + (c << 3), idx_end - 8);
         voff[i] = ((unsigned)kk * (unsigned)ld + (unsigned)col) * 2u;
       }
@@ -106,7 +86,7 @@ struct Stager {
   __device__ __forceinline__ void issue(unsigned char* tile, int wid) {
 #pragma unroll
     for (int i = 0; i < PER; ++i)
-      __builtin_amdgcn_global_load_lds((gptr_t)(base + voff[i]), (lptr_t)(tile + 1024 * (wid + NW * i)), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((vg_gptr_t)(base + voff[i]), (vg_lptr_t)(tile + 1024 * (wid + NW * i)), 16, 0, 0);
     base += step_bytes;
     k_cur += BK;
   }
@@ -116,7 +96,7 @@ struct Stager {
     for (int i = 0; i < PER; ++i) {
       const int j = wid + NW * i;
       const void* p = (k_cur + lane_k(j, lane) < k_end) ? (const void*)(base + voff[i]) : zeros;
-      __builtin_amdgcn_global_load_lds((gptr_t)p, (lptr_t)(tile + 1024 * j), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((vg_gptr_t)p, (vg_lptr_t)(tile + 1024 * j), 16, 0, 0);
     }
     base += step_bytes;
     k_cur += BK;
@@ -136,19 +116,13 @@ struct FragAddr {
   __device__ __forceinline__ void setup(int tile_off, int w0, int lane) {
     const int g = lane >> 4, li = lane & 15;
     if (!TR) {
-      a[0] = tile_off + (w0 + li) * 64 + ((g ^ row_f(w0 + li)) << 4);   // fragment i at + 1024 * i
+      a[0] = tile_off + (w0 + li) * 64 + ((g ^ vg_row_swz(w0 + li)) << 4);   // fragment i at + 1024 * i
     } else {
-      const int q = li >> 2, p = li & 3, sw = 2 * (q | ((g & 1) << 2)), kk0 = 8 * g + q;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int i0 = w0 + 16 * i, c8 = ((i0 & 127) >> 2) + p;
-        a[i] = tile_off + (i0 >> 7) * 8192 + kk0 * 256 + ((((c8 >> 1) ^ sw)) << 4) + ((c8 & 1) << 3);  // hi half at + 1024
-      }
+      for (int i = 0; i < 4; ++i) a[i] = tile_off + vg_tr_frag_off(w0 + 16 * i, lane);  // hi half at + 1024
     }
   }
 };
-__device__ __forceinline__ bf16x8 as_frag(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
-__device__ __forceinline__ bf16x8 as_frag(u32x2 lo, u32x2 hi) { return __builtin_bit_cast(bf16x8, (u32x4){lo[0], lo[1], hi[0], hi[1]}); }
 
 #define VG_RD128_4(o0, o1, o2, o3, ad) \
   "ds_read_b128 %" #o0 ", %" #ad "\n\tds_read_b128 %" #o1 ", %" #ad " offset:1024\n\t" \
@@ -162,16 +136,16 @@ __device__ __forceinline__ void load_frags_asm(unsigned sb, const FragAddr<A_TR>
     asm volatile(VG_RD128_4(0, 1, 2, 3, 8) VG_RD128_4(4, 5, 6, 7, 9) "s_waitcnt lgkmcnt(0)"
                  : "=&v"(m0), "=&v"(m1), "=&v"(m2), "=&v"(m3), "=&v"(n0), "=&v"(n1), "=&v"(n2), "=&v"(n3)
                  : "v"(sb + fa.a[0]), "v"(sb + fb.a[0]) : "memory");
-    fm[0] = as_frag(m0); fm[1] = as_frag(m1); fm[2] = as_frag(m2); fm[3] = as_frag(m3);
-    fn[0] = as_frag(n0); fn[1] = as_frag(n1); fn[2] = as_frag(n2); fn[3] = as_frag(n3);
+    fm[0] = vg_frag(m0); fm[1] = vg_frag(m1); fm[2] = vg_frag(m2); fm[3] = vg_frag(m3);
+    fn[0] = vg_frag(n0); fn[1] = vg_frag(n1); fn[2] = vg_frag(n2); fn[3] = vg_frag(n3);
   } else if constexpr (!A_TR && B_TR) {
     u32x4 m0, m1, m2, m3;
     u32x2 l0, h0, l1, h1, l2, h2, l3, h3;
     asm volatile(VG_RD128_4(0, 1, 2, 3, 12) VG_RDTR_2(4, 5, 13) VG_RDTR_2(6, 7, 14) VG_RDTR_2(8, 9, 15) VG_RDTR_2(10, 11, 16) "s_waitcnt lgkmcnt(0)"
                  : "=&v"(m0), "=&v"(m1), "=&v"(m2), "=&v"(m3), "=&v"(l0), "=&v"(h0), "=&v"(l1), "=&v"(h1), "=&v"(l2), "=&v"(h2), "=&v"(l3), "=&v"(h3)
                  : "v"(sb + fa.a[0]), "v"(sb + fb.a[0]), "v"(sb + fb.a[1]), "v"(sb + fb.a[2]), "v"(sb + fb.a[3]) : "memory");
-    fm[0] = as_frag(m0); fm[1] = as_frag(m1); fm[2] = as_frag(m2); fm[3] = as_frag(m3);
-    fn[0] = as_frag(l0, h0); fn[1] = as_frag(l1, h1); fn[2] = as_frag(l2, h2); fn[3] = as_frag(l3, h3);
+    fm[0] = vg_frag(m0); fm[1] = vg_frag(m1); fm[2] = vg_frag(m2); fm[3] = vg_frag(m3);
+    fn[0] = vg_frag(l0, h0); fn[1] = vg_frag(l1, h1); fn[2] = vg_frag(l2, h2); fn[3] = vg_frag(l3, h3);
   } else {
     static_assert(A_TR && B_TR, "operand forms: NT, NN, TN");
     u32x2 al0, ah0, al1, ah1, al2, ah2, al3, ah3, l0, h0, l1, h1, l2, h2, l3, h3;
@@ -181,17 +155,9 @@ __device__ __forceinline__ void load_frags_asm(unsigned sb, const FragAddr<A_TR>
                    "=&v"(l0), "=&v"(h0), "=&v"(l1), "=&v"(h1), "=&v"(l2), "=&v"(h2), "=&v"(l3), "=&v"(h3)
                  : "v"(sb + fa.a[0]), "v"(sb + fa.a[1]), "v"(sb + fa.a[2]), "v"(sb + fa.a[3]),
                    "v"(sb + fb.a[0]), "v"(sb + fb.a[1]), "v"(sb + fb.a[2]), "v"(sb + fb.a[3]) : "memory");
-    fm[0] = as_frag(al0, ah0); fm[1] = as_frag(al1, ah1); fm[2] = as_frag(al2, ah2); fm[3] = as_frag(al3, ah3);
-    fn[0] = as_frag(l0, h0); fn[1] = as_frag(l1, h1); fn[2] = as_frag(l2, h2); fn[3] = as_frag(l3, h3);
+    fm[0] = vg_frag(al0, ah0); fm[1] = vg_frag(al1, ah1); fm[2] = vg_frag(al2, ah2); fm[3] = vg_frag(al3, ah3);
+    fn[0] = vg_frag(l0, h0); fn[1] = vg_frag(l1, h1); fn[2] = vg_frag(l2, h2); fn[3] = vg_frag(l3, h3);
   }
-}
-
-template <int ACT>
-__device__ __forceinline__ float apply_act(float scale, float v) {
-  if (ACT == VG_ACT_GELU) return vg_gelu(v);
-  if (ACT == VG_ACT_SIN) return __sinf(scale * v);
-  if (ACT == VG_ACT_TANH) return vg_tanh(v);
-  return v;
 }
 
 // FEAT: epilogue features COMPILED IN (each still tests its runtime pointer); the launcher picks the
@@ -225,14 +191,7 @@ __global__ __launch_bounds__(128 * WM, (vg_gemm_waves<MODE, WM, ACT, FEAT>())) v
   constexpr int SMEM_BYTES = NSTAGE * STAGE_BYTES;
   __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM_BYTES];
 
-  // XCD-aware block order: blocks b, b+8, ... share an XCD (L2); give each XCD a contiguous
-  // run of tiles so the n-tiles of one m-panel hit the same L2 (bijective for any grid size).
-  int wg;
-  {
-    const int nwg = gridDim.x, orig = blockIdx.x, xcd = orig & 7;
-    const int q = nwg >> 3, r = nwg & 7;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-  }
+  const int wg = vg_xcd_order(blockIdx.x, gridDim.x);
   const int bid_first = wg * grp.tpw;
   const int bid_end = min(bid_first + grp.tpw, grp.total);
   const int tid = threadIdx.x, lane = tid & 63;
@@ -243,26 +202,6 @@ __global__ __launch_bounds__(128 * WM, (vg_gemm_waves<MODE, WM, ACT, FEAT>())) v
 #pragma unroll
   for (int i = 0; i < 8; ++i) ones[i] = (bf16)1.0f;
 
-  // tile -> (problem, origin, K slice)
-  struct Tile { int pi, m0, n0, tn, split, k_begin, k_end; };
-  auto locate = [&](int bid) {
-    Tile t;
-    t.pi = 0;
-#pragma unroll
-    for (int i = 1; i < VG_MAX_GROUP; ++i)
-      if (i < grp.n && bid >= grp.p[i].tile_start) t.pi = i;
-    const VgGemmProb& Q = grp.p[t.pi];
-    const int local = bid - Q.tile_start;
-    const int tiles_mn = Q.tiles_m * Q.tiles_n;
-    t.split = local / tiles_mn;
-    const int r = local - t.split * tiles_mn;
-    const int tm = r / Q.tiles_n;
-    t.tn = r - tm * Q.tiles_n;
-    t.m0 = tm * BM; t.n0 = t.tn * BN;
-    t.k_begin = t.split * Q.k_per_split;
-    t.k_end = min(Q.K, t.k_begin + Q.k_per_split);
-    return t;
-  };
   Stager<A_TR, 4 * WM, NW> sa;
   Stager<B_TR, 8, NW> sb;
   // stages are issued strictly in order (prologue, then one per k-step), so the stagers keep a running k
@@ -278,7 +217,7 @@ __global__ __launch_bounds__(128 * WM, (vg_gemm_waves<MODE, WM, ACT, FEAT>())) v
     }                                                                                                    \
   } while (0)
   // row form indexes rows (m or n) against M/N; tr form indexes columns against M/N.
-  auto prime = [&](const Tile& t) {  // stagers at the tile's origin + the DMA of its first NSTAGE-1 stages
+  auto prime = [&](const VgTile& t) {  // stagers at the tile's origin + the DMA of its first NSTAGE-1 stages
     const VgGemmProb& Q = grp.p[t.pi];
     // lane-derived address parts are recomputed per tile from an opaque copy of the lane id: hoisted out of the tile loop
     // they would be spilled around it, and a spill reload drags a compiler `s_waitcnt vmcnt(0)` into the seam
@@ -289,32 +228,28 @@ __global__ __launch_bounds__(128 * WM, (vg_gemm_waves<MODE, WM, ACT, FEAT>())) v
     const int n = (t.k_end - t.k_begin + BK - 1) / BK;
     for (int s = 0; s < NSTAGE - 1 && s < n; ++s) ISSUE(s, t.k_end);
   };
-  const unsigned smem_base = (unsigned)(unsigned long)(lptr_t)smem;
+  const unsigned smem_base = (unsigned)(unsigned long)(vg_lptr_t)smem;
   FragAddr<A_TR> fra;
   FragAddr<B_TR> frb;
   fra.setup(0, wm * 64, lane);
   frb.setup(A_TILE_BYTES, wn * 64, lane);
   constexpr int DPS = (4 * WM + 8) / NW;  // LDS-DMA instructions per wave per stage: 4 (WM=2) or 3 (WM=4)
 
-  Tile cur = locate(bid_first);
+  VgTile cur = vg_locate(grp, bid_first, BM, BN);  // tile -> (problem, origin, K slice)
   prime(cur);
   bool landed = false;  // the prologue stages of `cur` were retired by the previous tile's epilogue wait
   for (int bid = bid_first; bid < bid_end; ++bid) {
   const VgGemmProb& P = grp.p[cur.pi];
   // epilogue operands, read from kernarg memory up front (overlaps the DMA latency)
+  const VgEpi epi = vg_epi_of(P);  // (unused, and removed by the compiler, in the TN form)
   const int eM = P.M, eN = P.N;
-  bf16* const eC = P.C; const int eldc = P.ldc;
-  bf16* const eC2 = P.C2; const int eldc2 = P.ldc2; const int ec2g = P.c2_gelu_grad;
   float* const eCf = P.Cf; const int eldcf = P.ldcf; const long long ecfs = P.cf_split_stride;
   const float* const ebias = P.bias;
   const bf16* const eres = P.res; const int eldr = P.ldr;
   const float* const eresf = P.resf; const int eper = P.res_period;
   const bf16* const eZ = P.Z; const int eldz = P.ldz;
   const float* const eZf = P.Zf; const int eldzf = P.ldzf;
-  const float ascale = P.act_scale;
-  const int epre = P.pre_f32, rip = P.row_in_per, rop = P.row_out_per, roo = P.row_out_off;
-  const unsigned dthr = P.drop_thresh, dkey = vg_drop_key(P.drop_key, P.drop_step); const float dscale = P.drop_scale; const int dpost = P.drop_post;
-  const int drm = P.drop_row_mul > 1 ? P.drop_row_mul : 1;
+  const int rip = P.row_in_per, rop = P.row_out_per, roo = P.row_out_off;
   const int m0 = cur.m0, n0 = cur.n0, split = cur.split, k_end = cur.k_end;
   const int nsteps = (k_end - cur.k_begin + BK - 1) / BK;
 
@@ -354,9 +289,9 @@ __global__ __launch_bounds__(128 * WM, (vg_gemm_waves<MODE, WM, ACT, FEAT>())) v
   }
   // ---- seam: next tile's first stages go out before this tile's epilogue ----------------------
   const bool has_next = bid + 1 < bid_end;
-  Tile nxt = cur;
+  VgTile nxt = cur;
   if (has_next) {
-    nxt = locate(bid + 1);
+    nxt = vg_locate(grp, bid + 1, BM, BN);
     asm volatile("s_barrier" ::: "memory");  // every wave has finished its fragment reads of the last step (WAR on the ring)
     prime(nxt);
   }
@@ -379,19 +314,15 @@ __global__ __launch_bounds__(128 * WM, (vg_gemm_waves<MODE, WM, ACT, FEAT>())) v
     }
   }
   // ---- epilogue: registers only ---------------------------------------------------------------
-  // A lane holds, per (n-tile, m-tile), 4 consecutive n of row li.  v_permlane16_swap between the even and the
-  // odd n-tile of a pair hands every lane 8 CONSECUTIVE n of one tile (even lane-groups keep the even tile,
-  // odd lane-groups the odd one), so each lane loads/stores 16 B (bf16) or 32 B (fp32) per slot with no trip
-  // through LDS (the LDS transpose of the first version cost ~1.5k LDS cycles per workgroup and stalled the
-  // co-resident workgroup's main loop).  8 slots per lane: q = 2*mt + pair.
-  constexpr bool NEED_ZBF = (ACT == VG_ACT_MUL_GELU_GRAD || ACT == VG_ACT_MUL_TANH_GRAD || ACT == VG_ACT_MUL_Z || ACT == VG_ACT_MUL_Z8);
-  constexpr bool Z8 = (ACT == VG_ACT_MUL_Z8);
-  constexpr bool NEED_ZF = (ACT == VG_ACT_MUL_COS);
+  // vg_pair_swap (vg_tile.h) hands every lane 8 consecutive n of one row per pair of n-tiles: 16 B (bf16) or 32 B (fp32)
+  // per slot with no trip through LDS (the LDS transpose of the first version cost ~1.5k LDS cycles per workgroup and
+  // stalled the co-resident workgroup's main loop).  8 slots per lane: q = 2*mt + pair.
+  constexpr bool NEED_ZBF = vg_act_needs_zbf(ACT), Z8 = vg_act_z8(ACT), NEED_ZF = vg_act_needs_zf(ACT);
   constexpr bool HAS_RES = (FEAT & F_RES) != 0, HAS_RESF = (FEAT & F_RESF) != 0, HAS_REMAP = (FEAT & F_REMAP) != 0;
   constexpr bool HAS_C2 = (FEAT & F_C2) != 0, HAS_PREF32 = (FEAT & F_PREF32) != 0, HAS_DROP = (FEAT & F_DROP) != 0;
   constexpr bool PRE_BF = NEED_ZBF || HAS_RES, PRE_F = NEED_ZF || HAS_RESF;
   const int mrow0 = m0 + wm * 64 + li;                               // slot (mt, .) covers row mrow0 + 16*mt
-  const int ncol0 = n0 + wn * 64 + ((g & 1) << 4) + ((g & 2) << 2);  // slot (., pair) covers columns ncol0 + 32*pair .. +7
+  const int ncol0 = n0 + wn * 64 + vg_pair_col(g);                    // slot (., pair) covers columns ncol0 + 32*pair .. +7
   auto out_row = [&](int m) -> int {
     if (HAS_REMAP && rip > 0) return (m / rip) * rop + roo + (m % rip);
     return m;
@@ -415,8 +346,8 @@ __global__ __launch_bounds__(128 * WM, (vg_gemm_waves<MODE, WM, ACT, FEAT>())) v
   constexpr int NG = HAS_DROP ? 4 : 2, GS = 8 / NG;  // slot groups; the dropout epilogue (hash temporaries) takes quarters
 #pragma unroll
   for (int hf = 0; hf < NG; ++hf) {
-  bf16x8 pre_bf[PRE_BF ? GS : 1];
-  f32x4 pre_f0[PRE_F ? GS : 1], pre_f1[PRE_F ? GS : 1];
+  bf16x8 pre_bf[PRE_BF ? GS : 1] = {};
+  f32x4 pre_f0[PRE_F ? GS : 1] = {}, pre_f1[PRE_F ? GS : 1] = {};
   if (MODE != VG_TN && (PRE_BF || PRE_F)) {
 #pragma unroll
     for (int qq = 0; qq < GS; ++qq) {
@@ -451,15 +382,8 @@ __global__ __launch_bounds__(128 * WM, (vg_gemm_waves<MODE, WM, ACT, FEAT>())) v
       const int q = GS * hf + qq;
       const int mt = q >> 1, pr = q & 1;
       const int m = mrow0 + 16 * mt, n = ncol0 + 32 * pr;
-      const f32x4 te = acc[2 * pr][mt], to = acc[2 * pr + 1][mt];
       f32x4 lo, hi;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {  // rows 1,3 of the even tile's register <-> rows 0,2 of the odd tile's
-        const unsigned ue = __float_as_uint(te[r]), uo = __float_as_uint(to[r]);
-        const auto sw = __builtin_amdgcn_permlane16_swap(ue, uo, false, false);
-        lo[r] = __uint_as_float(sw[0]);
-        hi[r] = __uint_as_float(sw[1]);
-      }
+      vg_pair_swap(acc[2 * pr][mt], acc[2 * pr + 1][mt], lo, hi);
       const bool ncol_ok = n < eN;
       if (m >= eM || !ncol_ok) continue;
       if (MODE == VG_TN) {
@@ -470,84 +394,8 @@ __global__ __launch_bounds__(128 * WM, (vg_gemm_waves<MODE, WM, ACT, FEAT>())) v
         continue;
       }
       float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      const int mo = out_row(m);
-      if (HAS_PREF32 && epre) {
-        float* dst = eCf + (unsigned)(mo * eldcf + n);
-        *(f32x4*)dst = (f32x4){v[0], v[1], v[2], v[3]};
-        *(f32x4*)(dst + 4) = (f32x4){v[4], v[5], v[6], v[7]};
-      }
-      float gact[8];  // GELU: activation and derivative share one exp / rcp / polynomial
-      if (ACT == VG_ACT_GELU) {
-        float gd[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) vg_gelu_both(v[r], gact[r], gd[r]);
-        if (HAS_C2 && eC2) {
-          if (ec2g == 2) {
-            const u32x2 c8 = {vg_g8_pack4(gd[0], gd[1], gd[2], gd[3]), vg_g8_pack4(gd[4], gd[5], gd[6], gd[7])};
-            *(u32x2*)((unsigned char*)eC2 + (unsigned)(mo * eldc2 + n)) = c8;
-          } else {
-            bf16x8 o;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) o[r] = vg_f2bf(ec2g ? gd[r] : v[r]);
-            *(bf16x8*)(eC2 + (unsigned)(mo * eldc2 + n)) = o;
-          }
-        }
-      } else if (HAS_C2 && eC2) {
-        bf16x8 o;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) o[r] = vg_f2bf(v[r]);
-        *(bf16x8*)(eC2 + (unsigned)(mo * eldc2 + n)) = o;
-      }
-      if (Z8) {
-        union { bf16x8 b; u32x4 u; } cv; cv.b = pre_bf[PRE_BF ? qq : 0];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { v[r] *= vg_g8_value(cv.u[0], r); v[r + 4] *= vg_g8_value(cv.u[1], r); }
-      } else if (NEED_ZBF) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-          const float zv = vg_bf2f(pre_bf[PRE_BF ? qq : 0][r]);
-          v[r] *= (ACT == VG_ACT_MUL_GELU_GRAD) ? vg_gelu_grad(zv) : ((ACT == VG_ACT_MUL_Z) ? zv : (1.f - zv * zv));
-        }
-      } else if (NEED_ZF) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          v[r] *= ascale * __cosf(ascale * pre_f0[PRE_F ? qq : 0][r]);
-          v[r + 4] *= ascale * __cosf(ascale * pre_f1[PRE_F ? qq : 0][r]);
-        }
-      } else if (ACT == VG_ACT_GELU) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = gact[r];
-      } else if (ACT != VG_ACT_NONE) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = apply_act<ACT>(ascale, v[r]);
-      }
-      unsigned dw0 = 0, dw1 = 0;
-      if (HAS_DROP && dthr) {
-        const unsigned i4 = (unsigned)(mo * drm * eN + n) >> 2;
-        dw0 = vg_drop_word(dkey, i4); dw1 = vg_drop_word(dkey, i4 + 1);
-        if (!dpost) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) { v[r] *= vg_drop_factor(dw0, r, dthr, dscale); v[r + 4] *= vg_drop_factor(dw1, r, dthr, dscale); }
-        }
-      }
-      if (HAS_RES && !NEED_ZBF && eres) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] += vg_bf2f(pre_bf[PRE_BF ? qq : 0][r]);
-      }
-      if (HAS_RESF && !NEED_ZF && eresf) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { v[r] += pre_f0[PRE_F ? qq : 0][r]; v[r + 4] += pre_f1[PRE_F ? qq : 0][r]; }
-      }
-      if (HAS_DROP && dthr && dpost) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { v[r] *= vg_drop_factor(dw0, r, dthr, dscale); v[r + 4] *= vg_drop_factor(dw1, r, dthr, dscale); }
-      }
-      if (eC) {
-        bf16x8 o;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) o[r] = vg_f2bf(v[r]);
-        *(bf16x8*)(eC + (unsigned)(mo * eldc + n)) = o;
-      }
+      vg_epi_slot<ACT, HAS_C2, HAS_PREF32, HAS_DROP, HAS_RES, HAS_RESF>(epi, v, pre_bf[PRE_BF ? qq : 0], pre_f0[PRE_F ? qq : 0], pre_f1[PRE_F ? qq : 0],
+                                                                        out_row(m), n);
     }
   }
   }  // slot groups
@@ -626,15 +474,9 @@ int vg_gemm_launch(VgGemmProb* probs, int n, int mode, hipStream_t stream) {
     if (p.act == VG_ACT_MUL_Z8 && (!p.Z || (p.ldz & 7))) return -3;
     p.tiles_m = (p.M + bm - 1) / bm;
     p.tiles_n = (p.N + BN - 1) / BN;
-    int splits = (mode == VG_TN) ? (p.splits > 0 ? p.splits : 1) : 1;
-    int ksteps = (p.K + BK - 1) / BK;
-    int per = (ksteps + splits - 1) / splits;
-    p.k_per_split = per * BK;
-    splits = (ksteps + per - 1) / per;  // drop empty slices
-    p.splits = splits;
-    if (p.cf_accumulate && (mode != VG_TN || splits != 1)) return -4;  // accumulation needs a single writer per element
-    p.tile_start = total;
-    total += p.tiles_m * p.tiles_n * splits;
+    if (mode != VG_TN) p.splits = 1;  // only weight gradients are split over k
+    vg_plan_splits(p, BK, &total);
+    if (p.cf_accumulate && (mode != VG_TN || p.splits != 1)) return -4;  // accumulation needs a single writer per element
     grp.p[i] = p;
   }
   // Tiles per workgroup (see the kernel's header comment).  Measured on the C2 step (round 2, one MI355X): one tile per

@@ -23,6 +23,7 @@
 // the unfused pair had at its HBM round trip - and are re-read row-wise, 16 lanes per row, by the LayerNorm code of norm.hip:
 // every global access of the epilogue is then a whole 768-byte row in 16-byte pieces.
 #include "vg_row.h"
+#include "vg_tile.h"
 #include <type_traits>
 #include <stdlib.h>
 
@@ -33,9 +34,6 @@
 #pragma clang fp contract(off)
 
 namespace {
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 #ifndef RW_MAXMT_
 #define RW_MAXMT_ 9
 #endif
@@ -64,9 +62,6 @@ template <int N> struct RwCfg {
   static_assert(HM * 16 * TSF <= RING, "fp32 half tile must fit the ring");
   static_assert(BODY + GAM <= 160 * 1024, "LDS");
 };
-
-// row-form chunk swizzle of gemm.hip: 16-B chunk c of row r lives at position c ^ {0,2,3,1}[(r>>2)&3]
-__device__ __host__ __forceinline__ int rw_row_f(int r) { return (0x78 >> (2 * ((r >> 2) & 3))) & 3; }
 
 __device__ __forceinline__ void rw_wait_vm(int n) {  // n is wave-uniform (scalar branch)
   switch (n) {
@@ -111,7 +106,7 @@ __global__ __launch_bounds__(512, 2) void vg_gemm_row_kernel(const VgRowArgs a) 
   const int u0 = (int)((long long)blockIdx.x * a.units / a.nwg), u1 = (int)((long long)(blockIdx.x + 1) * a.units / a.nwg);
   if (u0 >= u1) return;  // never: the launcher keeps nwg <= units
   const int nsteps = a.K >> 5;
-  const unsigned sbase = (unsigned)(unsigned long)(lptr_t)smem;
+  const unsigned sbase = (unsigned)(unsigned long)(vg_lptr_t)smem;
   const long long a8 = (long long)128 * a.lda * 2;  // bytes from piece 0 to piece 8
 
   // N = 512, forward: gamma / beta live behind the ring too - 64 registers of them on top of 4 chunks of residual, modulation and row values
@@ -136,13 +131,13 @@ __global__ __launch_bounds__(512, 2) void vg_gemm_row_kernel(const VgRowArgs a) 
     int lnm = lane;
     asm volatile("" : "+v"(lnm));
     // fragment addresses inside a stage: W rows 48 wid + 16 nt + li, A rows 16 mt + li; the swizzle only sees li
-    const unsigned fsw = (unsigned)((((lnm >> 4) ^ rw_row_f(lnm & 15))) << 4);
+    const unsigned fsw = (unsigned)((((lnm >> 4) ^ vg_row_swz(lnm & 15))) << 4);
     const unsigned fw = sbase + (unsigned)((16 * NT * wid + (lnm & 15)) * 64) + fsw;  // n-tile nt at + 1024 nt
     const unsigned fa = sbase + (unsigned)(RW_WIMG + (lnm & 15) * 64) + fsw;        // m-tile mt at + 1024 mt
     // LDS-DMA lane offsets: W pieces are contiguous; an A piece is 16 rows x 64 B, position lane&3 of row lane>>2 holds
     // chunk (lane&3) ^ f(row)
     const unsigned offW = (unsigned)lnm * 16u;
-    const unsigned offA = ((unsigned)(lnm >> 2) * (unsigned)a.lda + (unsigned)(((lnm & 3) ^ rw_row_f(lnm >> 2)) << 3)) * 2u;
+    const unsigned offA = ((unsigned)(lnm >> 2) * (unsigned)a.lda + (unsigned)(((lnm & 3) ^ vg_row_swz(lnm >> 2)) << 3)) * 2u;
     const int pps = NT + (wid < MT ? 1 : 0) + ((MT == 9 && wid == 0) ? 1 : 0);  // LDS-DMA pieces of this wave per stage
     const char* wptr = (const char*)a.Wp + 1024 * wid;
     const char* aptr = (const char*)a.A + ((long long)(m0 + 16 * wid) * a.lda) * 2;
@@ -157,9 +152,9 @@ __global__ __launch_bounds__(512, 2) void vg_gemm_row_kernel(const VgRowArgs a) 
 #endif
 #pragma unroll
       for (int i = 0; i < NT; ++i)  // piece wid + 8 i of the W stage's 8 NT contiguous 1-KiB pieces
-        __builtin_amdgcn_global_load_lds((gptr_t)(wsrc + 8192 * i + offW), (lptr_t)(d + 8192 * i), 16, 0, 0);
-      if (wid < MT) __builtin_amdgcn_global_load_lds((gptr_t)(asrc + offA), (lptr_t)(d + RW_WIMG), 16, 0, 0);
-      if (MT == 9 && wid == 0) __builtin_amdgcn_global_load_lds((gptr_t)(asrc + a8 + offA), (lptr_t)(d + RW_WIMG + 8192), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((vg_gptr_t)(wsrc + 8192 * i + offW), (vg_lptr_t)(d + 8192 * i), 16, 0, 0);
+      if (wid < MT) __builtin_amdgcn_global_load_lds((vg_gptr_t)(asrc + offA), (vg_lptr_t)(d + RW_WIMG), 16, 0, 0);
+      if (MT == 9 && wid == 0) __builtin_amdgcn_global_load_lds((vg_gptr_t)(asrc + a8 + offA), (vg_lptr_t)(d + RW_WIMG + 8192), 16, 0, 0);
       wptr += RW_WIMG; aptr += 64;
     };
     struct Frags { u32x4 w[NT]; u32x4 m[MT]; };
@@ -636,7 +631,7 @@ __global__ __launch_bounds__(256) void vg_pack_rows_kernel(const VgPackJobs J) {
   if (q >= J.n) return;
   const VgPackDesc& D = J.d[q];
   const int s = (int)(t / (NW * 4)), rem = (int)(t - (long long)s * (NW * 4));
-  const int n = rem >> 2, pc = rem & 3, c = pc ^ rw_row_f(n), k = 32 * s + 8 * c;
+  const int n = rem >> 2, pc = rem & 3, c = pc ^ vg_row_swz(n), k = 32 * s + 8 * c;
   const bf16* src = J.src + (long long)blockIdx.y * J.src_stride + D.src_off;
   bf16* dst = J.dst + (long long)blockIdx.y * J.dst_stride + D.dst_off + t * 8;
   bf16x8 v;

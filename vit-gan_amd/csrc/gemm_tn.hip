@@ -9,56 +9,37 @@
 // flight), two waves per SIMD; the fragment reads of stage s+1 (20 ds_read_b64_tr_b16 per wave) are issued before the 24
 // MFMAs of stage s and waited for after them - no wave ever waits for LDS latency, and the co-resident wave covers the
 // barrier and the DMA issue.  Split-K slabs, the bias-gradient column sums (ones x dY fragments on the MFMA pipe) and the
-// grouped launch are those of the tiled kernel.
-#include "vg_gemm.h"
+// grouped launch are those of the tiled kernel; the tr-form images and the tile numbering are vg_tile.h's.
+#include "vg_tile.h"
 #include <stdlib.h>
 
 namespace {
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 constexpr int TN_NSLOT = 4;
-// stage = [dY: 32 k x 128 m][X: 32 k x (BN / 128) x 128 n], 8 KiB each, tr form (gemm.hip): 32 KiB (NT = 6) or 40 KiB (NT = 8: the
+// stage = [dY: 32 k x 128 m][X: 32 k x (BN / 128) x 128 n], 8 KiB each, tr form: 32 KiB (NT = 6) or 40 KiB (NT = 8: the
 // ring is then all 160 KiB of the CU)
 template <int NT> constexpr int tn_stage() { return 8192 * (1 + NT / 2); }
-
-__device__ __forceinline__ int tn_sigma(int kk) { return (kk & 3) | (((kk >> 3) & 1) << 2); }
-__device__ __forceinline__ bf16x8 tn_frag(u32x2 lo, u32x2 hi) { return __builtin_bit_cast(bf16x8, (u32x4){lo[0], lo[1], hi[0], hi[1]}); }
 }  // namespace
 
 template <int NT>
 __global__ __launch_bounds__(512, 2) void vg_gemm_tn384_kernel(const VgGemmGroup grp) {
   constexpr int TN_STAGE = tn_stage<NT>(), BN = 64 * NT, NB = NT / 2, PPS = 1 + NB;  // X images, pieces per wave and stage
   __shared__ __attribute__((aligned(16))) unsigned char smem[TN_NSLOT * TN_STAGE];
-  int bid;
-  {  // XCD-aware block order (gemm.hip): each XCD takes a contiguous run of tiles - the tiles of one K slice share its rows
-    const int nwg = gridDim.x, orig = blockIdx.x, xcd = orig & 7;
-    const int q = nwg >> 3, r = nwg & 7;
-    bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-  }
-  int pi = 0;
-#pragma unroll
-  for (int i = 1; i < VG_MAX_GROUP; ++i)
-    if (i < grp.n && bid >= grp.p[i].tile_start) pi = i;
-  const VgGemmProb& P = grp.p[pi];
-  const int local = bid - P.tile_start;
-  const int tiles_mn = P.tiles_m * P.tiles_n;
-  const int split = local / tiles_mn;
-  const int rr = local - split * tiles_mn;
-  const int tm = rr / P.tiles_n, tn = rr - tm * P.tiles_n;
-  const int m0 = tm * 128, n0 = tn * BN;
-  const int k_begin = split * P.k_per_split, k_end = min(P.K, k_begin + P.k_per_split);
-  const int nsteps = (k_end - k_begin) >> 5;
+  const int bid = vg_xcd_order(blockIdx.x, gridDim.x);
+  const VgTile t = vg_locate(grp, bid, 128, BN);
+  const VgGemmProb& P = grp.p[t.pi];
+  const int split = t.split, tn = t.tn, m0 = t.m0, n0 = t.n0, k_begin = t.k_begin;
+  const int nsteps = (t.k_end - k_begin) >> 5;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wid >> 2, wn = wid & 3;
-  const unsigned sbase = (unsigned)(unsigned long)(lptr_t)smem;
+  const unsigned sbase = (unsigned)(unsigned long)(vg_lptr_t)smem;
 
   // LDS-DMA: wave w moves piece w (k rows 4w .. 4w+3, 256 B each) of each of the stage's four 8-KiB images
   unsigned offA, offB;
   {
     const int kk = 4 * wid + (lane >> 4);
-    const int c = (lane & 15) ^ (2 * tn_sigma(kk));
+    const int c = (lane & 15) ^ (2 * vg_tr_sigma(kk));
     offA = ((unsigned)kk * (unsigned)P.lda + (unsigned)(m0 + c * 8)) * 2u;
     offB = ((unsigned)kk * (unsigned)P.ldb + (unsigned)(n0 + c * 8)) * 2u;
   }
@@ -69,8 +50,8 @@ __global__ __launch_bounds__(512, 2) void vg_gemm_tn384_kernel(const VgGemmGroup
   auto issue_piece = [&](int slot, int i) {
     asm volatile("" : "+s"(baseA), "+s"(baseB));
     unsigned char* dst = smem + slot * TN_STAGE + 1024 * wid + 8192 * i;
-    if (i == 0) __builtin_amdgcn_global_load_lds((gptr_t)(baseA + offA), (lptr_t)dst, 16, 0, 0);
-    else __builtin_amdgcn_global_load_lds((gptr_t)(baseB + offB + 256 * (i - 1)), (lptr_t)dst, 16, 0, 0);
+    if (i == 0) __builtin_amdgcn_global_load_lds((vg_gptr_t)(baseA + offA), (vg_lptr_t)dst, 16, 0, 0);
+    else __builtin_amdgcn_global_load_lds((vg_gptr_t)(baseB + offB + 256 * (i - 1)), (vg_lptr_t)dst, 16, 0, 0);
   };
   auto advance = [&]() { baseA += stepA; baseB += stepB; };
   auto issue = [&](int slot) {
@@ -79,24 +60,15 @@ __global__ __launch_bounds__(512, 2) void vg_gemm_tn384_kernel(const VgGemmGroup
     advance();
   };
 
-  // fragment addresses inside a stage (tr form: gemm.hip FragAddr<true>); second half of a fragment at + 1024.  16 columns
+  // fragment addresses inside a stage (vg_tr_frag_off; the dY image is image 0, the X images follow); second half of a fragment at + 1024.  16 columns
   // further on is chunk index + 2 BEFORE the XOR with the row's swizzle (an even number), i.e. address ^ (t << 5) as long as
   // the fragments stay inside one 128-column image: true of the four dY fragments and, at NT = 8 (128 columns per wave), of
   // the X fragments - one address register each instead of 4 + 8 (NT = 8 has none to spare: 128 accumulators, 96 fragment
   // registers).  NT = 6 (96 columns per wave) crosses images and keeps its six X addresses.
   unsigned adA0, adB[NT == 8 ? 1 : NT];
-  {
-    const int g = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3, sw = 2 * (q | ((g & 1) << 2)), kk0 = 8 * g + q;
-    {
-      const int c8 = ((64 * wm) >> 2) + p;
-      adA0 = sbase + (unsigned)(kk0 * 256 + (((c8 >> 1) ^ sw) << 4) + ((c8 & 1) << 3));
-    }
+  adA0 = sbase + vg_tr_frag_off(64 * wm, lane);
 #pragma unroll
-    for (int nt = 0; nt < (NT == 8 ? 1 : NT); ++nt) {
-      const int i0 = 16 * NT * wn + 16 * nt, c8 = ((i0 & 127) >> 2) + p;
-      adB[nt] = sbase + (unsigned)(8192 * (1 + (i0 >> 7)) + kk0 * 256 + (((c8 >> 1) ^ sw) << 4) + ((c8 & 1) << 3));
-    }
-  }
+  for (int nt = 0; nt < (NT == 8 ? 1 : NT); ++nt) adB[nt] = sbase + 8192 + vg_tr_frag_off(16 * NT * wn + 16 * nt, lane);
   struct Frags { u32x2 al[4], ah[4], bl[NT], bh[NT]; };
   auto read_frags = [&](Frags& f, int slot) {
     const unsigned so = (unsigned)(slot * TN_STAGE);  // a multiple of 8 KiB: commutes with the XOR of bits 5-7
@@ -178,10 +150,10 @@ __global__ __launch_bounds__(512, 2) void vg_gemm_tn384_kernel(const VgGemmGroup
     {
       bf16x8 fm[4];
 #pragma unroll
-      for (int mt = 0; mt < 4; ++mt) fm[mt] = tn_frag(cur.al[mt], cur.ah[mt]);
+      for (int mt = 0; mt < 4; ++mt) fm[mt] = vg_frag(cur.al[mt], cur.ah[mt]);
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
-        const bf16x8 fn = tn_frag(cur.bl[nt], cur.bh[nt]);
+        const bf16x8 fn = vg_frag(cur.bl[nt], cur.bh[nt]);
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) acc[nt][mt] = vg_mfma(fn, fm[mt], acc[nt][mt]);
       }
@@ -220,20 +192,14 @@ __global__ __launch_bounds__(512, 2) void vg_gemm_tn384_kernel(const VgGemmGroup
   }
   float* const Cf = P.Cf + (size_t)split * P.cf_split_stride;
   const int ldcf = P.ldcf;
-  const int ncol = n0 + wn * 16 * NT + ((g & 1) << 4) + ((g & 2) << 2);
+  const int ncol = n0 + wn * 16 * NT + vg_pair_col(g);
 #pragma unroll
   for (int mt = 0; mt < 4; ++mt) {
     const int m = m0 + wm * 64 + 16 * mt + li;
 #pragma unroll
     for (int pr = 0; pr < NT / 2; ++pr) {
-      const f32x4 te = acc[2 * pr][mt], to = acc[2 * pr + 1][mt];
       f32x4 lo, hi;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {  // rows 1,3 of the even tile's register <-> rows 0,2 of the odd tile's: 8 consecutive n per lane
-        const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(te[r]), __float_as_uint(to[r]), false, false);
-        lo[r] = __uint_as_float(sw[0]);
-        hi[r] = __uint_as_float(sw[1]);
-      }
+      vg_pair_swap(acc[2 * pr][mt], acc[2 * pr + 1][mt], lo, hi);  // 8 consecutive n per lane
       float* dst = Cf + (unsigned)(m * ldcf + ncol + 32 * pr);
       *(f32x4*)dst = lo;
       *(f32x4*)(dst + 4) = hi;
@@ -268,14 +234,7 @@ int vg_gemm_tn384_try(VgGemmProb* probs, int n, hipStream_t stream) {
     VgGemmProb& p = probs[i];
     p.tiles_m = p.M / 128;
     p.tiles_n = p.N / bn;
-    int splits = p.splits > 0 ? p.splits : 1;
-    const int ksteps = p.K / 32;
-    const int per = (ksteps + splits - 1) / splits;
-    p.k_per_split = per * 32;
-    splits = (ksteps + per - 1) / per;  // drop empty slices
-    p.splits = splits;
-    p.tile_start = total;
-    total += p.tiles_m * p.tiles_n * splits;
+    vg_plan_splits(p, 32, &total);
     grp.p[i] = p;
   }
   grp.total = total;

@@ -14,13 +14,13 @@
 //
 // Rows are dealt to the workgroups in units of 32 (a run = full 128-row tiles + one shorter tile), the n-tiles of one
 // run sit in one XCD so the A rows are fetched from HBM once.
-#include "vg_gemm.h"
+//
+// The tr-form W images, the fragment casts and the lane's place in a tile are those of vg_tile.h, the slot epilogue is
+// vg_epilogue.h.
+#include "vg_epilogue.h"
 #include <type_traits>
 
 namespace {
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 constexpr int WR_KS = 6;          // 64-deep stages per tile (K = 384)
 constexpr int WR_STAGE = 16384;   // 128 rows x 128 B
 constexpr int WR_NSLOT = 4;
@@ -34,11 +34,6 @@ struct VgWrArgs {
   int n_tiles;  // 128-column tiles
   int gpx;      // runs (row groups) per XCD
 };
-
-__device__ __forceinline__ bf16x8 wr_frag(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
-__device__ __forceinline__ bf16x8 wr_frag(u32x2 lo, u32x2 hi) { return __builtin_bit_cast(bf16x8, (u32x4){lo[0], lo[1], hi[0], hi[1]}); }
-__device__ __forceinline__ int wr_sigma(int kk) { return (kk & 3) | (((kk >> 3) & 1) << 2); }
-
 }  // namespace
 
 template <int WTR, int ACT, int FEAT>
@@ -54,7 +49,7 @@ __global__ __launch_bounds__(256, 2) void vg_gemm_wr_kernel(const VgWrArgs args)
   const int u0 = (int)((long long)run * args.units / nruns), u1 = (int)((long long)(run + 1) * args.units / nruns);
   if (u0 >= u1) return;
   const int n0 = ntile * 128;
-  const unsigned sbase = (unsigned)(unsigned long)(lptr_t)smem;
+  const unsigned sbase = (unsigned)(unsigned long)(vg_lptr_t)smem;
   const int eM = P.M, eN = P.N;
 
   // fragment read address inside a stage: row li (+16 per m-tile by immediate), 16-B chunk (g + 4 sub) ^ f(li)
@@ -69,7 +64,7 @@ __global__ __launch_bounds__(256, 2) void vg_gemm_wr_kernel(const VgWrArgs args)
     asm volatile("" : "+s"(base));
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_global_load_lds((gptr_t)(base + voff[i]), (lptr_t)(smem + slot * WR_STAGE + 1024 * (wid + 4 * i)), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((vg_gptr_t)(base + voff[i]), (vg_lptr_t)(smem + slot * WR_STAGE + 1024 * (wid + 4 * i)), 16, 0, 0);
   };
 
   // ---- A addressing (its first two stages are issued together with the second round of the W load below) ----------
@@ -119,8 +114,8 @@ __global__ __launch_bounds__(256, 2) void vg_gemm_wr_kernel(const VgWrArgs args)
                      : "=&v"(a), "=&v"(b), "=&v"(c), "=&v"(d)
                      : "v"(wa + s * WR_STAGE), "v"((wa + s * WR_STAGE) ^ 64u)
                      : "memory");
-        wf[0][2 * (s0 + s)] = wr_frag(a); wf[1][2 * (s0 + s)] = wr_frag(b);
-        wf[0][2 * (s0 + s) + 1] = wr_frag(c); wf[1][2 * (s0 + s) + 1] = wr_frag(d);
+        wf[0][2 * (s0 + s)] = vg_frag(a); wf[1][2 * (s0 + s)] = vg_frag(b);
+        wf[0][2 * (s0 + s) + 1] = vg_frag(c); wf[1][2 * (s0 + s) + 1] = vg_frag(d);
       }
       asm volatile("s_barrier" ::: "memory");
     }
@@ -131,18 +126,12 @@ __global__ __launch_bounds__(256, 2) void vg_gemm_wr_kernel(const VgWrArgs args)
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int j = wid + 4 * i, kk = 4 * j + (lane >> 4);
-      const int c = (lane & 15) ^ (2 * wr_sigma(kk));
+      const int c = (lane & 15) ^ (2 * vg_tr_sigma(kk));
       voffT[i] = ((unsigned)kk * (unsigned)P.ldb + (unsigned)min(n0 + c * 8, eN - 8)) * 2u;
     }
     unsigned ta[2];
-    {
-      const int g = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3, sw = 2 * (q | ((g & 1) << 2)), kk0 = 8 * g + q;
 #pragma unroll
-      for (int nt = 0; nt < 2; ++nt) {
-        const int c8 = ((32 * wid + 16 * nt) >> 2) + p;
-        ta[nt] = sbase + (unsigned)(kk0 * 256 + (((c8 >> 1) ^ sw) << 4) + ((c8 & 1) << 3));
-      }
-    }
+    for (int nt = 0; nt < 2; ++nt) ta[nt] = sbase + vg_tr_frag_off(32 * wid + 16 * nt, lane);
     const char* wb = (const char*)P.B;
     const long long kstep_bytes = (long long)32 * P.ldb * 2;
 #pragma unroll
@@ -154,7 +143,7 @@ __global__ __launch_bounds__(256, 2) void vg_gemm_wr_kernel(const VgWrArgs args)
         asm volatile("" : "+s"(base));
 #pragma unroll
         for (int i = 0; i < 2; ++i)
-          __builtin_amdgcn_global_load_lds((gptr_t)(base + voffT[i]), (lptr_t)(smem + s * 8192 + 1024 * (wid + 4 * i)), 16, 0, 0);
+          __builtin_amdgcn_global_load_lds((vg_gptr_t)(base + voffT[i]), (vg_lptr_t)(smem + s * 8192 + 1024 * (wid + 4 * i)), 16, 0, 0);
       }
       if (round == 1) issue_a01();  // the second round fills 32 KiB (slots 0, 1): A's first stages ride on the same wait
       asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
@@ -166,8 +155,8 @@ __global__ __launch_bounds__(256, 2) void vg_gemm_wr_kernel(const VgWrArgs args)
                      : "=&v"(l0), "=&v"(h0), "=&v"(l1), "=&v"(h1)
                      : "v"(ta[0] + s * 8192), "v"(ta[1] + s * 8192)
                      : "memory");
-        wf[0][s0 + s] = wr_frag(l0, h0);
-        wf[1][s0 + s] = wr_frag(l1, h1);
+        wf[0][s0 + s] = vg_frag(l0, h0);
+        wf[1][s0 + s] = vg_frag(l1, h1);
       }
       asm volatile("s_barrier" ::: "memory");
     }
@@ -175,13 +164,12 @@ __global__ __launch_bounds__(256, 2) void vg_gemm_wr_kernel(const VgWrArgs args)
 
   // ---- epilogue operands, read from kernarg memory once -----------------------------------------------------------
   constexpr bool HAS_RES = (FEAT & WF_RES) != 0, HAS_C2 = (FEAT & WF_C2) != 0, HAS_DROP = (FEAT & WF_DROP) != 0;
-  constexpr bool NEED_Z = (ACT == VG_ACT_MUL_Z || ACT == VG_ACT_MUL_Z8), Z8 = (ACT == VG_ACT_MUL_Z8);
-  bf16* const eC = P.C; const int eldc = P.ldc;
-  bf16* const eC2 = P.C2; const int eldc2 = P.ldc2; const int ec2g = P.c2_gelu_grad;
+  constexpr bool NEED_Z = vg_act_needs_zbf(ACT), Z8 = vg_act_z8(ACT);
+  VgEpi epi = vg_epi_of(P);
+  epi.drop_post = 0;                    // the launcher refuses dropout behind the addends,
+  __builtin_assume(epi.C != nullptr);   // and a problem without a bf16 result: every slot stores C (the seam wait counts on it)
   const float* const ebias = P.bias;
   const bf16* const eres = NEED_Z ? P.Z : P.res; const int eldr = NEED_Z ? P.ldz : P.ldr;
-  const unsigned dthr = P.drop_thresh, dkey = vg_drop_key(P.drop_key, P.drop_step); const float dscale = P.drop_scale;
-  const int drm = P.drop_row_mul > 1 ? P.drop_row_mul : 1;
 
   // ---- A pipeline: stages 0, 1 are in slots 2, 3 (landed with the W load), stage 2 goes to slot 0 now ---------------
   issue4(stage_src(m_begin, 2), voffA, 0);
@@ -262,8 +250,8 @@ __global__ __launch_bounds__(256, 2) void vg_gemm_wr_kernel(const VgWrArgs args)
     __builtin_amdgcn_s_setprio(0);
     asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");  // the last MFMAs' results, before the VALU reads them
 
-    // ---- epilogue: a lane holds, per (n-tile, m-tile), 4 consecutive n of row li; v_permlane16_swap between the two n-tiles
-    // gives it 8 consecutive n of one tile -> 16-byte loads / stores straight from registers, MT slots per lane
+    // ---- epilogue: vg_pair_swap between the wave's two n-tiles gives a lane 8 consecutive n of one row -> 16-byte loads /
+    // stores straight from registers, MT slots per lane
     int ln = lane;
     asm volatile("" : "+v"(ln));  // addresses are recomputed per tile (hoisted they would be live across the main loop)
     const int g = ln >> 4, li = ln & 15;
@@ -275,12 +263,13 @@ __global__ __launch_bounds__(256, 2) void vg_gemm_wr_kernel(const VgWrArgs args)
         for (int mt = 0; mt < MT; ++mt) acc[nt][mt] += b4;
       }
     }
-    const int ncol = n0 + 32 * wid + ((g & 1) << 4) + ((g & 2) << 2);
+    const int ncol = n0 + 32 * wid + vg_pair_col(g);
     constexpr int GS = (MT % 4 == 0) ? 4 : 2;  // slot groups: a group's loads all precede its first store
 #pragma unroll
     for (int h = 0; h < MT / GS; ++h) {
-      bf16x8 pre[(HAS_RES || NEED_Z) ? GS : 1];
-      if (HAS_RES || NEED_Z) {
+      constexpr bool PRE = HAS_RES || NEED_Z;
+      bf16x8 pre[PRE ? GS : 1] = {};
+      if (PRE) {
 #pragma unroll
         for (int qq = 0; qq < GS; ++qq) {
           const int m = m0 + 16 * (GS * h + qq) + li;
@@ -298,64 +287,11 @@ __global__ __launch_bounds__(256, 2) void vg_gemm_wr_kernel(const VgWrArgs args)
       for (int qq = 0; qq < GS; ++qq) {
         const int mt = GS * h + qq;
         const int m = m0 + 16 * mt + li;
-        const f32x4 te = acc[0][mt], to = acc[1][mt];
-        float v[8];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {  // rows 1,3 of the even tile's register <-> rows 0,2 of the odd tile's
-          const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(te[r]), __float_as_uint(to[r]), false, false);
-          v[r] = __uint_as_float(sw[0]);
-          v[r + 4] = __uint_as_float(sw[1]);
-        }
+        f32x4 lo, hi;
+        vg_pair_swap(acc[0][mt], acc[1][mt], lo, hi);
         if (m >= eM) continue;
-        if (ACT == VG_ACT_GELU) {
-          float ga[8], gd[8];
-#pragma unroll
-          for (int r = 0; r < 8; ++r) vg_gelu_both(v[r], ga[r], gd[r]);
-          if (HAS_C2 && eC2) {
-            if (ec2g == 2) {
-              const u32x2 c8 = {vg_g8_pack4(gd[0], gd[1], gd[2], gd[3]), vg_g8_pack4(gd[4], gd[5], gd[6], gd[7])};
-              *(u32x2*)((unsigned char*)eC2 + (unsigned)(m * eldc2 + ncol)) = c8;
-            } else {
-              bf16x8 o;
-#pragma unroll
-              for (int r = 0; r < 8; ++r) o[r] = vg_f2bf(ec2g ? gd[r] : v[r]);
-              *(bf16x8*)(eC2 + (unsigned)(m * eldc2 + ncol)) = o;
-            }
-          }
-#pragma unroll
-          for (int r = 0; r < 8; ++r) v[r] = ga[r];
-        } else if (HAS_C2 && eC2) {
-          bf16x8 o;
-#pragma unroll
-          for (int r = 0; r < 8; ++r) o[r] = vg_f2bf(v[r]);
-          *(bf16x8*)(eC2 + (unsigned)(m * eldc2 + ncol)) = o;
-        }
-        if (ACT == VG_ACT_TANH) {  // the classifier's fc1 (modules.py:196-197)
-#pragma unroll
-          for (int r = 0; r < 8; ++r) v[r] = vg_tanh(v[r]);
-        }
-        if (Z8) {
-          union { bf16x8 b; u32x4 u; } cv; cv.b = pre[qq];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) { v[r] *= vg_g8_value(cv.u[0], r); v[r + 4] *= vg_g8_value(cv.u[1], r); }
-        } else if (NEED_Z) {
-#pragma unroll
-          for (int r = 0; r < 8; ++r) v[r] *= vg_bf2f(pre[qq][r]);
-        }
-        if (HAS_DROP && dthr) {
-          const unsigned i4 = (unsigned)(m * drm * eN + ncol) >> 2;
-          const unsigned dw0 = vg_drop_word(dkey, i4), dw1 = vg_drop_word(dkey, i4 + 1);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) { v[r] *= vg_drop_factor(dw0, r, dthr, dscale); v[r + 4] *= vg_drop_factor(dw1, r, dthr, dscale); }
-        }
-        if (HAS_RES && !NEED_Z && eres) {
-#pragma unroll
-          for (int r = 0; r < 8; ++r) v[r] += vg_bf2f(pre[qq][r]);
-        }
-        bf16x8 o;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) o[r] = vg_f2bf(v[r]);
-        *(bf16x8*)(eC + (unsigned)(m * eldc + ncol)) = o;
+        float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        vg_epi_slot<ACT, HAS_C2, false, HAS_DROP, HAS_RES, false>(epi, v, pre[PRE ? qq : 0], (f32x4){}, (f32x4){}, m, ncol);
       }
     }
   };
