@@ -7,6 +7,7 @@ bit for bit; one dropped, doubled or misplaced product changes an integer by at 
 on whatever device the tensors live on: tests/test_exact_probes_cpu.py checks the generators and the checkers themselves.
 """
 import itertools
+import math
 
 import torch
 
@@ -298,6 +299,189 @@ class AttnProbe:
         assert spread <= 256, f"|dO.(V_a - V_b)| reaches {spread} > 256: dS would not survive its bf16 packing"
         dS = self.backward(1.0)[3]
         assert torch.equal(dS, dS.to(BF).double()), "dS not exact in bf16"
+
+    def check_fp8_preconditions(self):
+        """the fp8 (OCP e4m3) kernels quantise Q and K for the scores and 256 p and V for P.V: every one of those values
+        survives the round trip through e4m3 here, so every fp8 product and fp32 sum is exact and the mode-0 expectations
+        hold bit for bit"""
+        assert_e4m3_exact(self.Q, "Q")
+        assert_e4m3_exact(self.K, "K")
+        assert_e4m3_exact(self.V, "V")
+        assert_e4m3_exact(256.0 * self.P(), "256 p")
+
+
+def e4m3(x):
+    """x (any float dtype) rounded to OCP e4m3 and back, in x's dtype"""
+    return x.float().to(torch.float8_e4m3fn).float().to(x.dtype)
+
+
+def assert_e4m3_exact(x, what):
+    bad = e4m3(x) != x
+    if bool(bad.any()):
+        idx = tuple(int(i) for i in bad.nonzero()[0])
+        raise AssertionError(f"{what}: {float(x[idx])!r} at {idx} does not survive the round trip through e4m3")
+
+
+def assert_lse(got, m, logt, what):
+    """LSE of a saturated probe: exactly m (fp32, as fp64) where the query has one maximum (log t = 0), m + log t within
+    one fp32 ulp on a t-way tie"""
+    got = got.detach().double().cpu()
+    want = m + logt
+    ulp = torch.pow(2.0, torch.floor(torch.log2(want.abs())) - 23)
+    bad = torch.where(logt == 0, got != want, ~((got - want).abs() <= ulp))
+    n = int(bad.sum())
+    if n:
+        i = tuple(int(v) for v in bad.nonzero()[0])
+        raise AssertionError(f"{what}: {n} LSE values wrong; first at {i}: got {float(got[i])!r} want {float(want[i])!r}")
+
+
+def assert_bitwise_or_slack(got, want64, slack, what):
+    """got == rne(want) bit for bit wherever want is nonzero; where want is exactly 0, |got| <= slack (elementwise, fp64;
+    slack 0 demands an exact zero)"""
+    got64 = got.detach().double().cpu()
+    want = rne(want64, got.dtype).double()
+    assert got64.shape == want.shape, (what, tuple(got64.shape), tuple(want.shape))
+    bad = torch.where(want64 != 0, got64 != want, ~(got64.abs() <= slack))
+    n = int(bad.sum())
+    if n:
+        idx = tuple(int(i) for i in bad.nonzero()[0])
+        raise AssertionError(f"{what}: {n} of {bad.numel()} elements differ; first at {idx}: got {float(got64[idx])!r} "
+                             f"want {float(want64[idx])!r} (slack {float(slack[idx]) if torch.is_tensor(slack) else slack!r})")
+
+
+# ------------------------------------------------------------------------- saturated softmax of L2-distance scores
+DO_NZ = 8  # expected nonzeros of a dO row in an L2Probe (see its docstring)
+class L2Probe:
+    """the saturated-softmax probe of the L2-distance kernels, scores = +|q - k| * scale (mode 1 of csrc/attention.hip).
+
+    Key k carries c (e_a + e_b + e_c + e_d) on a distinct 4-subset of the head dims and query q carries -K[pi(q)], so
+    |q|^2 = |k|^2 = 4 c^2 and q . k_target = -4 c^2: the kernel's qn + kn - 2 qk is 16 c^2 and its root exactly 4 c.  A key
+    sharing j <= 3 dims with the target is at c sqrt(8 + 2 j) <= c sqrt(14), (4 - sqrt(14)) c scale below the maximum.
+    kind: 'perm'  O[q] = V[pi(q)], dS = 0, so dQ = dK = 0
+          'tie2' / 'tie4'  the keys `ties` share one code (query 0 always carries it): P = 1/t on them, dK nonzero on the
+          tied keys; q - k is the same vector for every tied key of a query and sum_k dS = 0, so dQ = 0.
+    There is no 'sum' kind (a query at equal distance from two distinct codes would need 20 c^2 to be a square): a nonzero
+    dQ is covered by the element-wise budget of tests/attn_modes_ref.py.  Everything is fp64 and exact.  dO is sparse (about
+    do_nonzeros of the HE entries of a row are +-1): dK on a tied key is 2 c colsum(W) = sum_q (dP - delta) / t, which a dense
+    dO pushes past the 8 significant bits of bf16."""
+
+    def __init__(self, B, H, S, HE, kind="perm", ties=None, seed=0, code=CODE, vlim=3, dolim=1, do_nonzeros=DO_NZ):
+        assert S >= 1 and HE >= 8
+        self.B, self.H, self.S, self.HE, self.kind, self.code = B, H, S, HE, kind, float(code)
+        g = gen(seed * 7919 + S * 131 + HE + 5)
+        Q = torch.zeros(B, H, S, HE, dtype=torch.float64)
+        K = torch.zeros(B, H, S, HE, dtype=torch.float64)
+        keys = torch.arange(S)
+        self.designed = torch.zeros(B, H, S, S, dtype=torch.bool)  # [b, h, q, k]: key k is one of query q's maxima by design
+        tied = kind in ("tie2", "tie4") and S >= len(ties)
+        for b in range(B):
+            for h in range(H):
+                sub = self._subsets(S, HE, g)
+                if tied:
+                    sub[list(ties[1:])] = sub[ties[0]].clone()
+                K[b, h, keys.unsqueeze(1), sub] = self.code
+                pi = torch.randperm(S, generator=g)
+                Q[b, h] = -K[b, h, pi]
+                self.designed[b, h, keys, pi] = True
+                if tied:
+                    Q[b, h, 0] = -K[b, h, ties[0]]
+                    on_tie = [q for q in range(S) if q == 0 or int(pi[q]) in ties]
+                    self.designed[b, h, on_tie] = False
+                    for q in on_tie:
+                        self.designed[b, h, q, list(ties)] = True
+        self.V = counting((B, H, S, HE), g, -vlim, vlim)
+        self.dO = counting((B, H, S, HE), g, -dolim, dolim, min(1.0, do_nonzeros / HE))
+        self.Q, self.K = Q, K
+        self.qkv = torch.cat([self.flat(t) for t in (Q, K, self.V)], 1)
+
+    @staticmethod
+    def _subsets(S, HE, g):
+        """S distinct sorted 4-subsets of range(HE), [S, 4]"""
+        seen, rows = set(), []
+        while len(rows) < S:
+            cand = torch.rand(2 * S + 8, HE, generator=g).argsort(-1)[:, :4].sort(-1).values
+            for r in cand.tolist():
+                if tuple(r) not in seen and len(rows) < S:
+                    seen.add(tuple(r))
+                    rows.append(r)
+        return torch.tensor(rows)
+
+    flat = AttnProbe.flat
+
+    # ---- exact consequences
+    def dist2(self):
+        """|q - k|^2 as the kernel forms it, qn + kn - 2 qk: exact integers (fp64), [B, H, q, k]"""
+        qn = (self.Q * self.Q).sum(-1, keepdim=True)
+        kn = (self.K * self.K).sum(-1).unsqueeze(-2)
+        return qn + kn - 2.0 * (self.Q @ self.K.transpose(-1, -2))
+
+    def P(self):
+        d = self.dist2()
+        top = d == d.amax(-1, keepdim=True)
+        return top.double() / top.sum(-1, keepdim=True)
+
+    def forward(self):
+        return self.P() @ self.V
+
+    def backward(self, scale):
+        """dQ, dK, dV and W = dS / dist, with dS = P (dP - delta) scale: dQ = rowsum(W) q - W K, dK = colsum(W) k - W^T Q"""
+        P = self.P()
+        O = P @ self.V
+        dV = P.transpose(-1, -2) @ self.dO
+        dP = self.dO @ self.V.transpose(-1, -2)
+        D = (self.dO * O).sum(-1, keepdim=True)
+        dist = self.dist2().sqrt()
+        W = torch.where(dist > 0, P * (dP - D) * scale / dist.clamp_min(1e-300), torch.zeros_like(dist))
+        dQ = W.sum(-1, keepdim=True) * self.Q - W @ self.K
+        dK = W.sum(-2).unsqueeze(-1) * self.K - W.transpose(-1, -2) @ self.Q
+        return dQ, dK, dV, W
+
+    def zero_slack(self, scale):
+        """what an exactly-zero element of dQ and of dK may hold instead, [B, H, S, HE] each.  The kernel keeps rowsum(W) and
+        colsum(W) in fp32, and on a tie its p = exp(m - lse) carries the rounding of lse = m + log t: at m = 4 c scale = 2048
+        one fp32 ulp is 2^-12, relative to p.  That factor multiplies one operand element (q_d or k_d: c on the row's code, 0
+        off it), so the element is off by at most 2^-12 sum |W| |q_d|; with W = 0 (every 'perm' row) or off the code the
+        bound is 0."""
+        W = self.backward(scale)[3].abs()
+        ulp = 2.0 ** (math.floor(math.log2(4 * self.code * scale)) - 23)
+        return ulp * W.sum(-1, keepdim=True) * self.Q.abs(), ulp * W.sum(-2).unsqueeze(-1) * self.K.abs()
+
+    def lse_exact(self, scale, queries=slice(None)):
+        """fp32(4 c) * fp32(scale), the kernel's fp32 product (as fp64), and log t of each query's tie"""
+        m = torch.tensor(4 * self.code, dtype=torch.float32) * torch.tensor(scale, dtype=torch.float32)
+        d = self.dist2()[:, :, queries]
+        top = d.amax(-1)
+        assert bool((top == 16 * self.code ** 2).all()), "every query's maximum is (4 c)^2"
+        return m.double(), torch.log((d == top.unsqueeze(-1)).sum(-1).double())
+
+    def check_preconditions(self, scales, bwd_scale=None):
+        """every query's largest squared distance is 16 c^2, reached at exactly the designed keys; every other distance is
+        far enough below 4 c that its exp underflows to 0 in fp32 at each scale; every squared distance is exact in fp32; and
+        (bwd_scale given) O, W, dQ and dK are exact in bf16"""
+        c = self.code
+        d = self.dist2()
+        assert float(d.max()) < EXACT_LIMIT * c * c and torch.equal(d, d.float().double()), "qn + kn - 2 qk not exact in fp32"
+        top = d.amax(-1, keepdim=True)
+        assert bool((top == 16 * c * c).all()), "a query's largest distance is not 4 c"
+        rest = torch.where(d == top, torch.full_like(d, -1.0), d).amax(-1)
+        has = rest >= 0
+        assert float(rest.max()) <= 14 * c * c
+        for scale in scales:
+            if bool(has.any()):
+                gap = float(((4 * c - rest[has].sqrt()) * scale).min())
+                assert gap >= MIN_GAP, f"score gap {gap} < {MIN_GAP} at scale {scale}"
+        wrong = (d == top) != self.designed
+        if bool(wrong.any()):
+            b, h, q, k = (int(v) for v in wrong.nonzero()[0])
+            raise AssertionError(f"query {q} of head ({b}, {h}): key {k} is {'not ' if self.designed[b, h, q, k] else ''}"
+                                 f"a maximum, against the design")
+        O = self.forward()
+        assert torch.equal(O, O.to(BF).double()), "O not exact in bf16"
+        if bwd_scale is not None:
+            dQ, dK, dV, W = self.backward(bwd_scale)
+            for t, name in ((W, "W"), (dQ, "dQ"), (dK, "dK"), (dV, "dV")):
+                assert torch.equal(t, t.to(BF).double()), f"{name} not exact in bf16"
+            assert float(dQ.abs().max()) == 0.0, "dQ is zero by construction"
 
 
 # ---------------------------------------------------------------------------------- which GEMM kernel a shape reaches
