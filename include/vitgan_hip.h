@@ -266,6 +266,33 @@ int vg_zero_tick(float* g, long long n, int* step_dev, void* stream);
 int vg_step_inputs(const float* real, void* imgs_bf16, long long n_img, float* z, long long n_z,
                    unsigned long long seed, const int* step_dev, void* stream);
 
+/* A device-resident dataset (the reference feeds CIFAR-10 through a host DataLoader; the rule below has no counterpart there, so this
+ * header is its definition): the step draws, decodes and labels its own real batch, keyed on the device step counter.  ONE launch, one
+ * workgroup per output image.  images: uint8 on the device, [N, C, IH, IH] (layout 0) or [N, IH, IH, C] (layout 1); labels (nullable):
+ * int32 [N]; lut: bf16 [C, 256], the decode table; imgs: bf16 [B, C, IH, IH].  All index arithmetic is uint32 (N < 2^31).
+ * Which image.  s = step_dev[0] (the counter as vg_step_inputs reads it, BEFORE vg_zero_tick: 0 on the first step);
+ *   nb = N / (B world) whole global batches per epoch (the remainder is dropped, like drop_last);  epoch = s / nb,  j = s % nb;
+ *   image n of rank `rank` sits at position p = (j world + rank) B + n of the epoch;  its index is idx = perm_epoch(p) with flags bit 0
+ *   (shuffle), else idx = p.
+ * perm_epoch: a keyed bijection of [0, N), no table and no state - a 4-round Feistel network on 2k bits with cycle walking.
+ *   k = max(1, ceil(bitlength(N - 1) / 2)),  m = 2^k - 1.  One pass on x: L = x >> k, R = x & m; for r = 0..3:
+ *   (L, R) <- (R, L ^ (h(key_r, R) & m));  x = (L << k) | R.  Starting from x = p the pass is repeated while x >= N (it ends: it walks
+ *   the cycle of a bijection of [0, 2^2k) that contains p < N).  h is the counter hash defined for vg_diffaug_fwd below,
+ *   key_r = h(ke, r + 1),  ke = h(h(Kp, 0), epoch),  Kp = the (seed, site 4) key defined there.  N = 1 gives 0.
+ * Flip.  With flags bit 1 the image at position p is mirrored left to right iff h(h(h(Kf, 0), epoch), p) >> 31, Kf = the (seed, site 5)
+ *   key: keyed on the position of the visit, so ranks and epochs draw independently.
+ * Pixels.  imgs[n, c, y, x] = lut[c][images[idx, ...]], the source read at (c, y, x') or (y, x', c) by layout, x' = IH - 1 - x when
+ *   flipped.  With lut[c][v] = bf16(((float(v) / 255) - mean[c]) / std[c]) in fp32 this is ToTensor + Normalize + the bf16 cast of
+ *   vg_step_inputs, bit for bit.  labels_out[n] = labels[idx] and index_out[n] = idx are written when the pointers are given.
+ * The source image and the table are staged in LDS with 16-byte loads; every thread emits runs of 8 pixels as one 16-byte store.
+ * Returns, all before any launch:  -1: null images / lut / imgs / step_dev, labels_out without labels, or N, C, IH or B < 1;  -2: world < 1, rank outside
+ * [0, world), layout not 0 / 1, flags outside [0, 3], N < B world or N >= 2^31;  -3: IH IH % 8 != 0, C IH IH % 16 != 0, C > 4, one image
+ * plus the table above 160 KiB of LDS, or images / lut / imgs not 16-byte aligned. */
+int vg_dataset_fetch(const unsigned char* images, const int* labels /*nullable*/, long long N, int C, int IH, int layout,
+                     const void* lut /*bf16 [C, 256]*/, void* imgs /*bf16 [B, C, IH, IH]*/, int* labels_out /*nullable*/,
+                     int* index_out /*nullable*/, int B, int rank, int world, int flags, unsigned long long seed,
+                     const int* step_dev, void* stream);
+
 /* Differentiable augmentation of the discriminator's input (DiffAugment: color, translation, cutout; the reference has none, so this
  * header is its definition) and its adjoint.  x, y, dy, dx bf16 [B, C, IH, IH] (x and y, dy and dx must not overlap); fp32 arithmetic.
  * Per image n:  T = cutout o translation o contrast o saturation o brightness,  members switched by `policy` (bit 0 the three color

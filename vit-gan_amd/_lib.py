@@ -129,6 +129,7 @@ _SIGNATURES = {
     "vg_attention_bwd_bwd": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
     "vg_zero_tick": (c_int, [P, c_ll, P, P]),
     "vg_step_inputs": (c_int, [P, P, c_ll, P, c_ll, C.c_ulonglong, P, P]),
+    "vg_dataset_fetch": (c_int, [P, P, c_ll, c_int, c_int, c_int, P, P, P, P, c_int, c_int, c_int, c_int, C.c_ulonglong, P, P]),
     "vg_diffaug_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, C.c_ulonglong, c_int, P, P]),
     "vg_diffaug_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, C.c_ulonglong, c_int, P, P]),
     "vg_diffaug_p_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, C.c_ulonglong, c_int, P, P, P]),

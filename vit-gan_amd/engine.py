@@ -25,6 +25,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib, flat, ops
+from .data import DeviceDataset, data_seed
 from .dist import GradSync, backward_pieces, world_size
 from .generator import SirenGenerator
 from .modules import ViTDiscriminator, VisionTransformer
@@ -55,7 +56,8 @@ class GanEngine:
                  ema_decay: float = 0.0, ema_start: int = 0, spectral_norm: str = "", bcr=(0.0, 0.0), bcr_aug: str = "",
                  aug_p: Optional[float] = None, ada_target: float = 0.0, ada_interval: int = 4, ada_kimg: float = 500.0,
                  r1_gamma: float = 0.0, r1_interval: int = 1, n_classes: int = 0,
-                 lr_schedule: str = "", lr_warmup: int = 0, lr_total: int = 0, lr_final: float = 0.0):
+                 lr_schedule: str = "", lr_warmup: int = 0, lr_total: int = 0, lr_final: float = 0.0,
+                 dataset: Optional[DeviceDataset] = None):
         """concurrent_wgrad: the discriminator's weight gradients on a side stream beside its input gradients.  Off by default
         since the persistent GEMMs (csrc/gemm_wr.hip, gemm_tn.hip: their workgroups hold the CUs for a whole launch) - the
         side stream measured 6.70 against 6.67 ms/step.
@@ -199,7 +201,18 @@ class GanEngine:
         force; ``set_lr_scale(d=, g=)`` writes the multipliers (1 at construction; what a plateau rule drives), ``state_dict()`` carries
         them and the four options.  Default ("" and no warm-up): no buffer, the host floats ``hyp["lr_d"]`` / ``hyp["lr_g"]`` as kernel
         arguments, and the step is launch for launch and bit for bit the plain one.  With a schedule on, ``hyp["lr_*"]`` are the base
-        rates, read when a step is enqueued (captured).  Goes with every other option and both schedules of the step."""
+        rates, read when a step is enqueued (captured).  Goes with every other option and both schedules of the step.
+        dataset: a ``DeviceDataset`` (data.py) - the step fetches its own real batch.  ONE vg_dataset_fetch at the HEAD of the step, in
+        front of vg_zero_tick and inside the captured graph, writes ``imgs[:B]``, the real labels and ``batch_indices`` from the device
+        step counter (the image at position p of epoch e is ``perm_e(p)``, a keyed bijection: include/vitgan_hip.h), followed there by
+        the launches that draw z and the fake labels - they read the counter as before.  ``step()`` then takes no ``real`` / ``labels``
+        (passing them raises; ``z`` / ``fake_labels`` stay the caller's under ``external_noise``), a replay needs no launch from the host,
+        and ``run(n)`` replays n steps.  The data seed is derived from ``seed`` WITHOUT the rank: all ranks walk one permutation and
+        rank r of a world of w reads batch ``j w + r`` of it (``rank`` / ``world`` from the process group).  The position is a function of
+        the counter ``state_dict()`` carries, so a resumed run continues the epoch where it stopped; the state records (N, B, world,
+        shuffle, flip, data seed) and ``load_state_dict`` refuses another.  The set must match the discriminator's geometry, carry
+        labels iff ``n_classes > 0`` (their values are not read on the host; the kernels clamp) and hold one global batch.  None
+        (default): no buffer, no call, and the step is launch for launch and bit for bit the host-fed one."""
         self._check_options(discriminator, generator, dict(locals()))
         self._carve()
         self._attach()
@@ -316,6 +329,18 @@ class GanEngine:
         self.div_w, self.inst_sigma = float(o["diversity_weight"]), float(o["instance_noise"])
         self.pg, self._single_rank = pg, o["exchange_single_rank"]
         self._want_ctx, self._use_graph = bool(o["concurrent_wgrad"]), bool(o["use_graph"])
+        self.dataset = ds = o["dataset"]
+        if ds is not None:
+            if not isinstance(ds, DeviceDataset):
+                raise TypeError(f"dataset must be a DeviceDataset, got {type(ds).__name__}")
+            if (ds.C, ds.IH) != (d.C, d.IH):
+                raise ValueError(f"dataset: its images are {ds.C} x {ds.IH} x {ds.IH}, the discriminator takes {d.C} x {d.IH} x {d.IH}")
+            if (ds.labels is not None) != self.cond:
+                raise ValueError(f"dataset: labels go with a class-conditional engine and only with one - the dataset "
+                                 f"{'has' if ds.labels is not None else 'has no'} labels, n_classes={K}")
+            if len(ds) < self.B * world:
+                raise ValueError(f"dataset: {len(ds)} images are fewer than one global batch of {self.B} x {world} rank(s)")
+            self.data_seed, self._data_world = data_seed(self.seed), world
 
     def _carve(self) -> None:
         """Constructor, part 2: the device check, the exchange, every buffer the step owns - and every SUB-RANGE the step addresses as a
@@ -393,6 +418,11 @@ class GanEngine:
             self.selected = f32(2 * B)
             self.sel_half = (self.selected[:B], self.selected[B:])
         self.losses = f32(3)  # d_real, d_fake, g
+        self.batch_indices: Optional[torch.Tensor] = None
+        if self.dataset is not None:  # the set moves to this device once and stays uint8; the last fetch's indices for inspection
+            self.dataset.to(dev)
+            self.batch_indices = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.real_dst = self.imgs[:B]
         self.step_t = torch.zeros(1, dtype=torch.int32, device=dev)
         fd, fg = vit._flat, generator._flat
         self.m_d, self.v_d = torch.zeros_like(fd.flat), torch.zeros_like(fd.flat)
@@ -723,6 +753,10 @@ class GanEngine:
     def _r1_options(self):
         return None if not self.r1 else (self.r1_gamma, self.r1_interval)
 
+    def _dataset_options(self):
+        ds = self.dataset
+        return None if ds is None else (ds.N, self.B, self._data_world, ds.shuffle, ds.flip, self.data_seed)
+
     def _bcr_options(self):
         return None if not self.bcr else (self.bcr_w[0], self.bcr_w[1], self.bcr_policy)
 
@@ -736,6 +770,7 @@ class GanEngine:
         (nd_a, nd_b, nd_c, nd_d), ng = self._nets()
         fd, fg = self.vit._flat, self.gen._flat
         noisy = self.inst_sigma > 0.0
+        self._fetch(st0)
         _call("vg_zero_tick", _p(fd.grad), fd.total, _p(self.step_t), st0)
         self._lr_tick(st0)
         self.grad2.zero_()
@@ -776,10 +811,15 @@ class GanEngine:
         _call("vg_gen_backward", C.byref(ng), B, _p(self.ws_g), _p(self.dfake), st0)
         self._adamw(self.r_g, 1, st0, self.clip_g)
 
-    def _inputs(self, real: torch.Tensor, labels=None, fake_labels=None) -> None:
+    def _inputs(self, real: Optional[torch.Tensor], labels=None, fake_labels=None) -> None:
         """The step's inputs, ONE launch in front of the step proper (and outside its hipGraph, so it reads the caller's tensor
         directly - no staging copy): imgs[:B] = bf16(real), and unless the caller supplies it, the latent batch z ~ N(0, 1)
-        (construct_noise(), training.py:35-42 / gan.py:231-232), counter-based on (seed, rank, steps done so far)."""
+        (construct_noise(), training.py:35-42 / gan.py:231-232), counter-based on (seed, rank, steps done so far).  With a dataset
+        the step fetches its own batch and draws z itself (``_fetch``): only the caller's fake labels are copied here."""
+        if self.dataset is not None:
+            if fake_labels is not None:
+                self.fake_labels.copy_(fake_labels)
+            return
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         # the kernel dereferences the caller's pointer with 16-byte loads on THIS engine's device: anything else (another GPU's
         # tensor, an unaligned view) goes through torch's copy, which handles it
@@ -796,6 +836,19 @@ class GanEngine:
             if fake_labels is not None:
                 self.fake_labels.copy_(fake_labels)
             else:
+                _call("vg_draw_labels", _p(self.fake_labels), self.B, self.n_classes, self._aug_seed, 3, _p(self.step_t), st)
+
+    def _fetch(self, st) -> None:
+        """The head of a step with a dataset, inside what the hipGraph captures: the real batch (images, labels, indices) from the device
+        step counter, then z and the fake labels as ``_inputs`` draws them - the counter is still the one ``_inputs`` would read."""
+        ds = self.dataset
+        if ds is None:
+            return
+        _call("vg_dataset_fetch", _p(ds.images), _p(ds.labels), ds.N, ds.C, ds.IH, ds.layout, _p(ds.lut_bf16), _p(self.real_dst),
+              _p(self.real_labels), _p(self.batch_indices), self.B, self.sync.rank, self.world, ds.flags, self.data_seed, _p(self.step_t), st)
+        if not self.external_noise:
+            _call("vg_step_inputs", None, None, 0, _p(self.z), self.z.numel(), self._noise_seed, _p(self.step_t), st)
+            if self.cond:
                 _call("vg_draw_labels", _p(self.fake_labels), self.B, self.n_classes, self._aug_seed, 3, _p(self.step_t), st)
 
     def _penalty(self, st) -> None:
@@ -837,6 +890,7 @@ class GanEngine:
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         (nd, nd_b, nd_c), ng = self._nets()
         fd, fg = self.vit._flat, self.gen._flat
+        self._fetch(st)
         # gan.discriminator.zero_grad() (training.py:177) and the device step counter += 1, one launch
         _call("vg_zero_tick", _p(fd.grad), fd.total, _p(self.step_t), st)
         self._lr_tick(st)
@@ -906,6 +960,7 @@ class GanEngine:
                 (None, None, "bcr", self._bcr_options),
                 (None, None, "r1", self._r1_options),
                 (None, None, "n_classes", lambda: self.n_classes or None),
+                (None, None, "dataset", self._dataset_options),
                 ("ada_state", self.ada_state, "ada", self._ada_options),
                 ("lr_scale", self.lr_scale, "lr", lambda: self.lr_opts),
                 ("ema_g", self.ema_g, None, None))
@@ -935,6 +990,8 @@ class GanEngine:
             # the latent noise is keyed on the device step counter just cleared: move to a fresh stream, keyed on the steps this
             # engine has really done, so a restarted run does not replay the first run's latent sequence
             self._noise_seed = (self._noise_seed * 0x9E3779B97F4A7C15 + 0xD1B54A32D192ED03 * (self.steps + 1)) & 0xFFFFFFFFFFFFFFFF
+            if self.dataset is not None:  # the seed is an argument of a captured node there (``_fetch``): capture again.  The cleared
+                self._graphs = {}         # counter also puts the dataset back to position 0 of epoch 0
 
     # ------------------------------------------------------------------------------------------ averaged generator, sampling
     def _need_ema(self, what: str) -> torch.Tensor:
@@ -1041,7 +1098,9 @@ class GanEngine:
         ``strict``, and so must the saved ``r1`` options (the lazy schedule continues from the restored ``steps``).  The augmentation probability and its controller (``aug_p`` / ``ada_target``) follow bCR's rule for the options, and
         their state is restored whenever both sides hold one.  The learning-rate schedule's options (``"lr"``) are compared under ``strict``
         in the same way; its multipliers are restored whenever both sides hold them, so a resumed run continues its schedule from the
-        restored counter at the restored multipliers."""
+        restored counter at the restored multipliers.  A dataset holds no state of its own - the position in the epoch is a function
+        of the counter - but the saved ``dataset`` options (N, B, world, shuffle, flip, data seed) must equal this engine's, strict or
+        not: with others the restored counter would point into another epoch."""
         if sd.get("format_version") != self.STATE_FORMAT:
             raise ValueError(f"engine state format {sd.get('format_version')!r}, this engine reads format {self.STATE_FORMAT}")
         names = ("m_d", "v_d", "m_g", "v_g", "step_t")
@@ -1064,6 +1123,10 @@ class GanEngine:
                              f"{self._ada_options()!r} (strict=False loads the probability all the same when both sides hold one)")
         if int(sd.get("n_classes") or 0) != self.n_classes:  # (strict or not: the generator's buffers differ in size)
             raise ValueError(f"engine state was saved with n_classes={int(sd.get('n_classes') or 0)}, this engine has n_classes={self.n_classes}")
+        saved_ds = None if sd.get("dataset") is None else tuple(sd["dataset"])
+        if saved_ds != self._dataset_options():  # (strict or not: the position in the epoch is a function of these and the counter)
+            raise ValueError(f"engine state was saved with the dataset (N, B, world, shuffle, flip, data seed) = {saved_ds!r}, this engine has "
+                             f"{self._dataset_options()!r}: the restored counter would not continue the same epoch")
         saved_r1 = None if sd.get("r1") is None else tuple(sd["r1"])
         if strict and saved_r1 != self._r1_options():
             raise ValueError(f"engine state was saved with the R1 penalty (r1_gamma, r1_interval) = {saved_r1!r}, this engine has "
@@ -1085,6 +1148,8 @@ class GanEngine:
         with torch.no_grad():
             for dst, src, _ in pairs:
                 dst.copy_(src.reshape(dst.shape))
+        if self.dataset is not None and int(sd["noise_seed"]) & 0xFFFFFFFFFFFFFFFF != self._noise_seed:
+            self._graphs = {}  # the latent stream's seed is an argument of a captured node there (``_fetch``): capture again
         self.steps, self._noise_seed = int(sd["steps"]), int(sd["noise_seed"]) & 0xFFFFFFFFFFFFFFFF
         if self.ema_g is not None:
             self._ema_loads += 1
@@ -1097,21 +1162,25 @@ class GanEngine:
             self.spec.measure(self.vit._flat.flat)
         self.sync_from_modules()
 
-    def step(self, real: torch.Tensor, z: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
+    def step(self, real: Optional[torch.Tensor] = None, z: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
              fake_labels: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Run one G/D step on ``real`` [B,C,IH,IW] (cuda).  Returns the device tensor
         [loss_d_real, loss_d_fake, loss_g] of this step without synchronising.  ``z`` [B, Z]: the latent batch, required
         iff the engine was built with ``external_noise=True``.  ``labels`` [B]: the classes of ``real``, an integer cuda tensor,
         required iff the engine is class-conditional; ``fake_labels`` [B]: the classes the generator is asked for, required together
         with ``z`` and drawn on the device otherwise.  The values are not read on the host (no synchronisation): the kernels clamp
-        a label into [0, n_classes) before they use it."""
-        if real.shape[0] != self.B or not real.is_cuda:
+        a label into [0, n_classes) before they use it.  An engine built with ``dataset`` fetches ``real`` and ``labels`` itself:
+        passing either raises."""
+        if self.dataset is not None:
+            if real is not None or labels is not None:
+                raise ValueError("this engine fetches its real batch from its dataset: call step() without real and labels")
+        elif real is None or real.shape[0] != self.B or not real.is_cuda:
             raise ValueError("real must be a cuda tensor with the engine's batch size")
         if (z is not None) != self.external_noise:
             raise ValueError("pass z exactly when the engine was built with external_noise=True")
         if not (self.vit._flat.aliased() and self.gen._flat.aliased()):
             raise RuntimeError("module parameters were re-allocated; rebuild the GanEngine")
-        if (labels is not None) != self.cond:
+        if self.dataset is None and (labels is not None) != self.cond:
             raise ValueError(f"pass labels exactly when the engine is class-conditional (n_classes={self.n_classes})")
         if (fake_labels is not None) != (self.cond and self.external_noise):
             raise ValueError("pass fake_labels exactly when a class-conditional engine was built with external_noise=True")
@@ -1169,3 +1238,39 @@ class GanEngine:
         self._inputs(real, labels, fake_labels)
         self._graphs[due].replay()
         return self.losses
+
+    # ------------------------------------------------------------------------------------------ the device-resident dataset
+    def _need_dataset(self, what: str) -> DeviceDataset:
+        if self.dataset is None:
+            raise RuntimeError(f"{what}: this engine has no dataset (built without dataset=)")
+        return self.dataset
+
+    def run(self, n: int) -> torch.Tensor:
+        """``n`` steps of an engine with a dataset, nothing synchronised; returns ``losses`` (the last step's).  Every step is the R1-due
+        or the plain launch list as in ``step()``; once a kind is captured its steps are bare replays.  Not with ``external_noise``
+        (every step would need the caller's z)."""
+        self._need_dataset("run()")
+        if self.external_noise:
+            raise ValueError("run(): an engine built with external_noise=True takes z with every step; call step(z=...)")
+        if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+            raise ValueError(f"run(): n must be a non-negative integer, got {n!r}")
+        if not (self.vit._flat.aliased() and self.gen._flat.aliased()):
+            raise RuntimeError("module parameters were re-allocated; rebuild the GanEngine")
+        for _ in range(n):
+            due = self.r1 and ops.r1_due(self.steps + 1, self.r1_interval)
+            if self._use_graph and due in self._graphs:
+                self.steps += 1
+                self._graphs[due].replay()
+            else:
+                self.step()
+        return self.losses
+
+    @property
+    def steps_per_epoch(self) -> int:
+        """Whole global batches per epoch of the dataset."""
+        return self._need_dataset("steps_per_epoch").steps_per_epoch(self.B, self._data_world)
+
+    @property
+    def epoch(self) -> int:
+        """The epoch the NEXT step fetches from, from the device step counter (synchronises: for logging)."""
+        return int(self.step_t.item()) // self.steps_per_epoch

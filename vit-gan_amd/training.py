@@ -41,6 +41,7 @@ from torch import nn
 
 from . import _lib
 from .config import Config
+from .data import DeviceDataset
 from .engine import GanEngine
 from .modules import ViTGAN, generator_from_config
 
@@ -252,7 +253,7 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                 aug_p: Optional[float] = None, ada_target: float = 0.0, ada_interval: int = 4, ada_kimg: float = 500.0,
                 r1_gamma: float = 0.0, r1_interval: int = 1, conditional: bool = False,
                 lr_schedule: str = "", lr_warmup: int = 0, lr_total: Optional[int] = None, lr_final: float = 0.0,
-                lr_plateau: Optional[Tuple[float, int]] = None):
+                lr_plateau: Optional[Tuple[float, int]] = None, dataset: Optional[DeviceDataset] = None):
     """``loss``: "ns" (default: the executable v1 loss), "hinge", or "wasserstein" - the critic losses of the reference's
     unreached step (training.py:67-125); ``clip_d`` / ``clip_g``: its clip_grad_norm_ limits (5.0 / 0.5 there);
     ``diversity_weight``: its diversity term (0.1 there); ``instance_noise``: sigma of the noise on D's inputs (0.1
@@ -292,8 +293,17 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     (src/v2/training.py:15,215-216; torch's default relative threshold 1e-4, no cooldown, no floor): when ``fid_fn``'s score has not
     improved for more than ``patience`` epochs, both rates' multipliers are multiplied by ``factor``
     (``GanEngine.set_lr_scale``).  It needs ``fid_fn``, and it switches the device-resident rates on (``lr_schedule=""`` then means
-    "constant")."""
+    "constant").
+    ``dataset``: a ``DeviceDataset`` (data.py) instead of ``data_loader`` (giving both is an error): the set lives on the device and
+    every step fetches its own batch (``GanEngine(dataset=...)``).  An epoch is then ``dataset.steps_per_epoch(batch_size)`` steps, and
+    ``input_epoch_<e>.png`` shows the batch the epoch's first step trains on, decoded on the host side from the same rule
+    (``dataset.decode(dataset.indices(...), dataset.flips(...))``).  A conditional run takes the set's labels."""
     global _log_file
+    if dataset is not None:  # the caller's errors whatever the machine: before the device check
+        if data_loader is not None:
+            raise ValueError("dataset: the step fetches its own batches from the dataset; pass either dataset or data_loader, not both")
+        if not isinstance(dataset, DeviceDataset):
+            raise TypeError(f"dataset must be a DeviceDataset, got {type(dataset).__name__}")
     from .ops import parse_aug_policy, parse_bcr_weights
     parse_aug_policy(diffaug)  # a bad policy string is the caller's error whatever the machine: before the device check
     bcr_on = parse_bcr_weights(bcr) != (0.0, 0.0)
@@ -325,6 +335,14 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     from .ops import parse_lr_schedule
     if plateau is not None and not lr_schedule and not lr_warmup:
         lr_schedule = "constant"  # the multipliers live with the device-resident rates
+    if dataset is not None:
+        if (dataset.C, dataset.IH) != (c.input_channels, c.image_size):
+            raise ValueError(f"dataset: its images are {dataset.C} x {dataset.IH} x {dataset.IH}, the configuration says "
+                             f"{c.input_channels} x {c.image_size} x {c.image_size}")
+        if (dataset.labels is not None) != conditional:
+            raise ValueError("dataset: a conditional run needs a dataset with labels, an unconditional one a dataset without them "
+                             f"(conditional={conditional}, labels {'present' if dataset.labels is not None else 'absent'})")
+        steps_per_epoch = dataset.steps_per_epoch(c.batch_size)  # ValueError: fewer images than one batch
     if lr_total is None:
         per_epoch = len(data_loader) if data_loader is not None else steps_per_epoch
         lr_total = epochs * per_epoch if (lr_schedule or lr_warmup) else 0
@@ -344,7 +362,7 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                     instance_noise=instance_noise, gp_weight=gp_weight, diffaug=diffaug, ema_decay=ema_decay, ema_start=ema_start,
                     spectral_norm=spectral_norm, bcr=bcr, bcr_aug=bcr_aug, aug_p=aug_p, ada_target=ada_target, ada_interval=ada_interval,
                     ada_kimg=ada_kimg, r1_gamma=r1_gamma, r1_interval=r1_interval, n_classes=K,
-                    lr_schedule=lr_schedule, lr_warmup=lr_warmup, lr_total=lr_total, lr_final=lr_final)
+                    lr_schedule=lr_schedule, lr_warmup=lr_warmup, lr_total=lr_total, lr_final=lr_final, dataset=dataset)
 
     def gan_checkpoint():  # gan.state_dict(), the discriminator's normalised matrices as the network applies them
         sd = gan.state_dict()
@@ -363,6 +381,16 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
         if G_ema is not None:
             G_ema.load_state_dict(eng.ema_state_dict(), strict=True)
     loader = data_loader if data_loader is not None else SyntheticLoader(c, steps_per_epoch, dev, labels=K)
+
+    def dataset_epoch():  # the steps of one epoch: the engine fetches; the first one carries the batch it will train on, for the input grid
+        for i in range(steps_per_epoch):
+            first = None
+            if i == 0 and save_artifacts:
+                at = (eng.steps, c.batch_size, eng.sync.rank, eng.world, eng.data_seed)
+                first = dataset.decode(dataset.indices(*at), dataset.flips(*at))
+            yield first, None
+    if dataset is not None:
+        loader = None
     # the fixed sample grid of a conditional run: image i is of class i % K
     grid_labels = (torch.arange(c.batch_size, device=dev) % K).to(torch.int32) if conditional else None
 
@@ -421,9 +449,12 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                 save_images(os.path.join(dirs.noise, f"noise_epoch_{epoch}.png"), noise_as_image(noise), c.batch_size)
             save_samples(epoch, noise)
             losses = None
-            for i, (real_images, real_labels) in enumerate(loader):
+            for i, (real_images, real_labels) in enumerate(loader if dataset is None else dataset_epoch()):
                 if i == 0 and save_artifacts:
                     save_images(os.path.join(dirs.input, f"input_epoch_{epoch}.png"), real_images, c.batch_size)
+                if dataset is not None:
+                    losses = eng.step()
+                    continue
                 if conditional and real_labels is None:
                     raise MissingLabelsError("conditional: the data loader yields no labels (SyntheticLoader draws them with labels=classes_count)")
                 losses = eng.step(real_images.to(dev), labels=real_labels.to(dev)) if conditional else eng.step(real_images.to(dev))
