@@ -528,6 +528,22 @@ int vg_spectral_update(const float* W, void* shadow_bf16, long long total, float
 int vg_spectral_project(float* G, const float* W, long long total, const float* state, long long state_floats, float* scratch,
                         long long scratch_floats, const VgSpectralDesc* table_host, const VgSpectralDesc* table_dev, int n, void* stream);
 
+/* ABI v9 (additive).  Streaming moments of feature vectors, the accumulator of the Frechet distance (metrics.hip); fp64 throughout.
+ *
+ * vg_moments_update: feats fp32 [n, d] with row stride ld (floats);  sum[j] += sum_i x_ij;  gram[j][k] += sum_i x_ij x_ik.
+ * Every x is widened to fp64 exactly, every product and addition is fp64 on v_mfma_f64_16x16x4_f64: per output element one chain
+ *   acc = gram[j][k];  for i = 0 .. n-1 in groups of 4 rows:  acc = mfma(x_i.j, x_i.k, acc)
+ * so integer-valued features below 2^53 in sum come out exact, and otherwise the error is an fp64 dot product's.  One wave owns each
+ * 16 x 16 tile of the upper triangle and walks the rows in order; there are no atomics: two runs are bit-equal, two updates equal one
+ * update of the concatenation whenever the first n is a multiple of 4 (and always for exactly representable sums).  gram comes out
+ * symmetric bit for bit (off-diagonal tiles are stored twice); the caller starts sum and gram from zeros and only passes them back in.
+ * Rows past n in the last group of 4 count as exact zeros.  d % 16 == 0, 16 <= d <= 2048, n >= 1, ld >= d.
+ * vg_moments_finish: mean = sum / n;  cov = (gram - n mean (x) mean) / (n - 1), the one-pass formula (torchmetrics' own), each
+ * operation rounded once; n >= 2.  Elementwise - here so that a caller of this ABI has the whole accumulator.
+ * Errors, before any launch: -1 a NULL pointer, n < 1 (finish: n < 2); -2 d or ld outside the above. */
+int vg_moments_update(const float* feats, long long ld, int n, int d, double* sum /*[d]*/, double* gram /*[d, d]*/, void* stream);
+int vg_moments_finish(const double* sum, const double* gram, long long n, int d, double* mean /*[d]*/, double* cov /*[d, d]*/, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Whole-network passes (what the nn.Modules call: one C call per forward / backward)
  * ---------------------------------------------------------------------------------------- */
@@ -596,6 +612,12 @@ typedef struct VgVitNet {
  * backward needs; one ws per in-flight forward. */
 int vg_vit_forward(const VgVitNet* net, int B, const void* img, int img_is_bf16, void* ws,
                    float* logits, void* stream);
+/* ABI v9 (additive).  vg_vit_forward with identical arguments and side effects - the same launches in the same order, logits bit-equal,
+ * ws valid for a following vg_vit_backward - that additionally writes feats fp32 [B, E]: the tensor the classifier's fc1 reads,
+ * vit.norm(x)[:, 0, :] (modules.py:195,236), as the forward holds it (bf16, widened: every value is a bf16), on the pruned-tail path and
+ * with dense_top alike.  The feature network of the Frechet distance (vg_moments_update below).  -1: a NULL pointer or B < 1. */
+int vg_vit_features(const VgVitNet* net, int B, const void* img, int img_is_bf16, void* ws, float* logits, float* feats /*[B, E]*/,
+                    void* stream);
 /* dlogits fp32 [B,Kc].  d_img bf16 [B,C,IH,IH] or NULL.  want_wgrad: accumulate into net->G
  * (G += dL/dP); 0 skips every weight-gradient kernel (generator pass through D, training.py:204-210). */
 int vg_vit_backward(const VgVitNet* net, int B, void* ws, const float* dlogits, void* d_img,

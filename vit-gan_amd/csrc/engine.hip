@@ -416,7 +416,7 @@ struct VitPass {
   VitBlock blk(int l) const { return vit_block(w, lay, net, sh, l); }
   int begin(const VgVitNet* net_, int B, void* ws, void* stream, const PenWs* pen_, int want_wgrad_);
   int lin_ln_fwd(bool row, const struct LinLn& j) const, dgrad_ln_bwd(bool row, const struct DgradLn& j, int step = FP_BOTH) const;
-  int forward(const void* img, int img_is_bf16, float* logits), backward(const float* dlogits, void* d_img, int stage_begin, int stage_end);
+  int forward(const void* img, int img_is_bf16, float* logits, float* feats = nullptr), backward(const float* dlogits, void* d_img, int stage_begin, int stage_end);
   int bwd_head(const float* dlogits), bwd_block(int l), bwd_wgrad(int la, int nb), bwd_embed(void* d_img);  // the backward's stages
   int pen_first_backward() const, pen_tangent_backward();                                                // the penalty's passes 2 and 4
 };
@@ -502,7 +502,7 @@ static int block_pair_splits(const VitShape& sh, bool pruned) {
   return pick_splits(pruned ? qkv + all : 2 * all, sh.M, VIT_SPLIT_CAP / 2);
 }
 
-int VitPass::forward(const void* img, int img_is_bf16, float* logits) {
+int VitPass::forward(const void* img, int img_is_bf16, float* logits, float* feats) {
   const VgVitDims& d = net->d;
   const int B = sh.B, E = sh.E, S = sh.S, M = sh.M, rE = sh.rE;
 
@@ -562,6 +562,9 @@ int VitPass::forward(const void* img, int img_is_bf16, float* logits) {
   if (!tail) VG_TRY(vg_ln_fwd_launch(blk(sh.L - 1).x_next, (long long)S * E, P + lay.lnf_w, P + lay.lnf_b, w.hcls, E, w.meanf, w.rstdf, B, E, 1e-5f, st));
   VG_TRY(lin_fwd(w.hcls, E, Pb + lay.hw1, P + lay.hb1, w.th, B, E, VG_ACT_TANH, 0.f, nullptr, nullptr, nullptr, st));
   VG_TRY(vg_head_fc2_launch(w.th, P + lay.hw2, P + lay.hb2, logits, B, E, sh.Kc, st));
+  // vg_vit_features: what the classifier's fc1 just read, norm(x)[:, 0, :], widened to fp32 (metrics.hip) - behind the head, so the
+  // launches that make the logits are those of vg_vit_forward, in its order
+  if (feats) VG_TRY(vg_widen_bf16_f32_launch(w.hcls, feats, (long long)B * E, st));
   return 0;
 }
 extern "C" int vg_vit_forward(const VgVitNet* net, int B, const void* img, int img_is_bf16, void* ws, float* logits,
@@ -570,6 +573,13 @@ extern "C" int vg_vit_forward(const VgVitNet* net, int B, const void* img, int i
   VitPass c;
   VG_TRY(c.begin(net, B, ws, stream, nullptr, 0));
   return c.forward(img, img_is_bf16, logits);
+}
+extern "C" int vg_vit_features(const VgVitNet* net, int B, const void* img, int img_is_bf16, void* ws, float* logits, float* feats,
+                               void* stream) {
+  if (!net || !img || !ws || !logits || !feats || B < 1) return -1;
+  VitPass c;
+  VG_TRY(c.begin(net, B, ws, stream, nullptr, 0));
+  return c.forward(img, img_is_bf16, logits, feats);
 }
 
 // Backward stages: 0 = classifier head + final LN, 1..L = encoder blocks L-1 .. 0, L+1 = patch embedding.

@@ -105,6 +105,7 @@ struct VgLrSched;
 int vg_lr_schedule_launch(const VgLrSched* d, const VgLrSched* g, const int* step_dev, const float* scale_dev, float* lr_out, hipStream_t st);
 int vg_ema_launch(float* ema, const float* p, long long n, float decay, int start, int step, const int* step_dev, hipStream_t st);
 int vg_cast_f32_bf16_launch(const float* src, bf16* dst, long long n, hipStream_t st);
+int vg_widen_bf16_f32_launch(const bf16* src, float* dst, long long n, hipStream_t st);  // metrics.hip
 int vg_slab_reduce_launch(const float* slab, long long stride, int nslab, float* dst, long long n, int accumulate, hipStream_t st);
 // two folds of the same shape in one launch (the two blocks of a paired weight-gradient launch)
 int vg_slab_reduce2_launch(const float* slab0, const float* slab1, long long stride, int nslab, float* dst0, float* dst1, long long n, int accumulate,

@@ -335,6 +335,30 @@ class VisionTransformer(nn.Module):
             return _VitF32Fn.apply(self, x, self.norm.weight, p)
         return _VitFn.apply(self, x, self.norm.weight, p)
 
+    def features(self, x, dense_top: bool = False):
+        """``(logits, feats)`` of an inference pass (dropout 0, no autograd): ``vg_vit_features``, the fused forward that also hands out
+        fp32 [B, E] ``feats`` = ``self.norm(x)[:, 0, :]``, the tensor the classifier's fc1 reads.  What metrics.py's frozen feature
+        network runs, here on the module's live parameters."""
+        if not x.is_cuda:
+            raise RuntimeError("VisionTransformer.features: the HIP engine needs cuda tensors; there is no CPU fallback")
+        if self._precision != "bf16":
+            raise ValueError("features is built on the bf16 engine; set precision = 'bf16' for it")
+        if not self._flat.aliased():
+            self._flat.named = dict(self.named_parameters())
+            self._flat.rebuild()
+        self._flat.refresh_shadow()
+        if x.dtype not in (torch.float32, torch.bfloat16):
+            x = x.float()
+        xin, B = x.detach().contiguous(), x.shape[0]
+        ws = torch.empty(self._ws_bytes(B), dtype=torch.uint8, device=x.device)
+        logits = torch.empty(B, self._dims.Kc, dtype=torch.float32, device=x.device)
+        feats = torch.empty(B, self._dims.E, dtype=torch.float32, device=x.device)
+        net = self._net(need_grad=False)
+        net.dense_top = int(dense_top)
+        _lib.check(_lib.lib().vg_vit_features(C.byref(net), B, xin.data_ptr(), int(xin.dtype == torch.bfloat16), ws.data_ptr(),
+                                              logits.data_ptr(), feats.data_ptr(), _stream()), "vg_vit_features")
+        return logits, feats
+
     def composed_forward(self, x):
         """The same network through the per-operator HIP path (ops.py) and torch's nn.Dropout modules."""
         h = self.embedding(x)

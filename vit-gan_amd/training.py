@@ -22,7 +22,8 @@ Substitutions (documented in DESIGN.md):
     batches, e.g. the reference's own DataLoader) or get synthetic uniform [-1,1] batches, the range of its
     ``Normalize(0.5, 0.5)``;
   * FID needs Inception weights that cannot be fetched offline (utils.py:155-175): pass ``fid_fn(gan, epoch) -> float``
-    to enable it; without it the score is NaN and no "best" checkpoint is written;
+    to enable it, or ``fid="random-vit"`` for the Frechet distance on a frozen random ViT (metrics.py; it ranks a run's epochs, it is
+    not the published FID); without either the score is NaN and no "best" checkpoint is written;
   * the generator is the v1 SLN/SIREN network (the v2 ``ViTGenerator`` tail raises) and the loss is
     BCE-with-logits on a 1-logit discriminator (the v2 ``criterion`` call raises).
 """
@@ -46,6 +47,8 @@ from .engine import GanEngine
 from .modules import ViTGAN, generator_from_config
 
 START_TIME = datetime.datetime.now()
+FID_KINDS = ("", "random-vit")  # train_model(fid=...)
+FID_SEED = 0                    # of the random feature net and of the evaluation's latents
 
 
 class RunDirs:
@@ -253,7 +256,8 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                 aug_p: Optional[float] = None, ada_target: float = 0.0, ada_interval: int = 4, ada_kimg: float = 500.0,
                 r1_gamma: float = 0.0, r1_interval: int = 1, conditional: bool = False,
                 lr_schedule: str = "", lr_warmup: int = 0, lr_total: Optional[int] = None, lr_final: float = 0.0,
-                lr_plateau: Optional[Tuple[float, int]] = None, dataset: Optional[DeviceDataset] = None):
+                lr_plateau: Optional[Tuple[float, int]] = None, dataset: Optional[DeviceDataset] = None,
+                fid: str = "", fid_samples: int = 10000):
     """``loss``: "ns" (default: the executable v1 loss), "hinge", or "wasserstein" - the critic losses of the reference's
     unreached step (training.py:67-125); ``clip_d`` / ``clip_g``: its clip_grad_norm_ limits (5.0 / 0.5 there);
     ``diversity_weight``: its diversity term (0.1 there); ``instance_noise``: sigma of the noise on D's inputs (0.1
@@ -292,13 +296,28 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     ``lr_plateau``: ``(factor, patience)``, the reference's intended ``ReduceLROnPlateau(mode="min")`` on the FID hook
     (src/v2/training.py:15,215-216; torch's default relative threshold 1e-4, no cooldown, no floor): when ``fid_fn``'s score has not
     improved for more than ``patience`` epochs, both rates' multipliers are multiplied by ``factor``
-    (``GanEngine.set_lr_scale``).  It needs ``fid_fn``, and it switches the device-resident rates on (``lr_schedule=""`` then means
+    (``GanEngine.set_lr_scale``).  It needs ``fid_fn`` (or ``fid=``), and it switches the device-resident rates on (``lr_schedule=""`` then means
     "constant").
     ``dataset``: a ``DeviceDataset`` (data.py) instead of ``data_loader`` (giving both is an error): the set lives on the device and
     every step fetches its own batch (``GanEngine(dataset=...)``).  An epoch is then ``dataset.steps_per_epoch(batch_size)`` steps, and
     ``input_epoch_<e>.png`` shows the batch the epoch's first step trains on, decoded on the host side from the same rule
-    (``dataset.decode(dataset.indices(...), dataset.flips(...))``).  A conditional run takes the set's labels."""
+    (``dataset.decode(dataset.indices(...), dataset.flips(...))``).  A conditional run takes the set's labels.
+    ``fid`` / ``fid_samples``: ``fid="random-vit"`` (and no ``fid_fn``) builds the FID hook itself: ``metrics.FrechetDistance`` on a
+    fixed-seed randomly initialised, frozen ViT of the model's own geometry, ``fid_samples`` generated images per evaluation from fixed
+    latents, scored on the averaged generator when ``ema_decay`` is on.  The real statistics come from ``dataset`` (all N images) or
+    else from one pass over the loader before the first step; they are written to ``real_stats.npz`` in the run's directory, and a
+    header line of ``training.log`` names the feature net, its seed, n_real and n_fake.  With it the epoch line's ``FID:`` is a number,
+    the best-FID checkpoints are written and ``lr_plateau`` needs no ``fid_fn``.  The score ranks the epochs of a run; it is NOT
+    comparable with published FID numbers (those need Inception weights: pass them as a callable).  The hook NEVER
+    defaults to the discriminator being trained - features that move with training would make the curve meaningless; a user who hands
+    ``FrechetDistance`` the live ``D`` gets a copy frozen at that moment.  ``fid=""`` (default): everything as before, ``FID: nan``."""
     global _log_file
+    if fid not in FID_KINDS:
+        raise ValueError(f"fid must be one of {FID_KINDS}, got {fid!r}")
+    if fid and fid_fn is not None:
+        raise ValueError("fid: the trainer builds the FID hook itself; pass either fid or fid_fn, not both")
+    if fid and (isinstance(fid_samples, bool) or not isinstance(fid_samples, int) or fid_samples < 2):
+        raise ValueError(f"fid_samples must be an integer >= 2, got {fid_samples!r}")
     if dataset is not None:  # the caller's errors whatever the machine: before the device check
         if data_loader is not None:
             raise ValueError("dataset: the step fetches its own batches from the dataset; pass either dataset or data_loader, not both")
@@ -318,7 +337,7 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     parse_ada_options(aug_p, ada_target, ada_interval, ada_kimg, parse_aug_policy(diffaug), loss)
     from .ops import parse_r1_options
     parse_r1_options(r1_gamma, r1_interval, gp_weight)
-    plateau = parse_lr_plateau(lr_plateau, fid_fn)
+    plateau = parse_lr_plateau(lr_plateau, fid_fn if fid_fn is not None else (fid or None))
     if not 0.0 <= float(ema_decay) < 1.0:
         raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
     if int(ema_start) != ema_start or ema_start < 0:
@@ -381,6 +400,10 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
         if G_ema is not None:
             G_ema.load_state_dict(eng.ema_state_dict(), strict=True)
     loader = data_loader if data_loader is not None else SyntheticLoader(c, steps_per_epoch, dev, labels=K)
+    fid_eval = None
+    if fid:  # the hook the trainer builds: a frozen random ViT of the model's geometry, never the discriminator in training
+        from .metrics import FrechetDistance
+        fid_eval = FrechetDistance.random_vit(trainable_config(c, conditional), seed=FID_SEED, n_fake=fid_samples, latent_seed=FID_SEED)
 
     def dataset_epoch():  # the steps of one epoch: the engine fetches; the first one carries the batch it will train on, for the input grid
         for i in range(steps_per_epoch):
@@ -443,6 +466,13 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
             log(f"Learning-rate schedule: {kind}, {warm} warm-up step(s)" + (f", to {fin:g} x base at step {total}" if kind != "constant" else "")
                 + f"; base rates D {eng.hyp['lr_d']:g}, G {eng.hyp['lr_g']:g}"
                 + (f"; on a plateau of the FID (patience {plateau.patience}) both x {plateau.factor:g}" if plateau is not None else ""))
+        if fid_eval is not None:  # before the first step: the real statistics (every image of the set, or one pass over the loader)
+            fid_eval.fit_real(dataset if dataset is not None else loader)
+            if save_artifacts:
+                fid_eval.save_real(os.path.join(dirs.save, "real_stats.npz"))
+            log(f"Frechet distance: feature net {fid_eval.tag}, latent seed {fid_eval.seed}, n_real {fid_eval.real['n']}, "
+                f"n_fake {fid_eval.n_fake}; real statistics in real_stats.npz; not comparable with published FID")
+            fid_fn = fid_eval
         for epoch in range(epochs):
             noise = construct_noise()
             if save_artifacts:
@@ -466,7 +496,8 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
             history.append((d_real + d_fake, g))
             if fid_fn is not None:
                 refresh_ema()
-            fid_score = float(fid_fn(gan if gan_ema is None else gan_ema, epoch)) if fid_fn is not None else float("nan")
+            scored = gan if (gan_ema is None or getattr(fid_fn, "ema", True) is False) else gan_ema
+            fid_score = float(fid_fn(scored, epoch)) if fid_fn is not None else float("nan")
             fid_scores.append(fid_score)
             if fid_score < best_fid:
                 best_fid = fid_score
@@ -526,4 +557,6 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     if G_ema is not None:
         refresh_ema()
         out["generator_ema"] = G_ema
+    if fid_eval is not None:
+        out["fid"] = fid_eval
     return out
