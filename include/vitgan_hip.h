@@ -490,6 +490,56 @@ int vg_diversity_loss(const void* images, void* d_images, float* loss_out, float
 int vg_grad_clip(float* g, long long n, float gscale, float max_norm, float* scratch, void* stream);
 int vg_cast_f32_bf16(const float* src, void* dst_bf16, long long n, void* stream);
 
+/* The kernels at the two ends of the networks, one by one (additive to ABI 9; csrc/elementwise.hip, tests/test_ends_gpu.py): the
+ * launches that vg_vit_forward / vg_vit_backward* / vg_gen_* make around the encoder blocks, exposed so that each is held to its own
+ * contract.  Every entry refuses a NULL pointer (-1) and a shape its kernel cannot take (-3) on the host, before any launch; the
+ * entries that carry a dropout mask take (p, seed, site, step_dev) as vg_dropout_apply does and refuse p outside [0, 1) (-1).
+ *
+ * vg_head_fwd:  logits[b, k] = sum_e t[b, e] W2[k, e] + b2[k]   (t bf16 [B, E], the tanh output of the classifier's fc1; W2 fp32 [Kc, E];
+ *   fp32 accumulation).  B, E, Kc >= 1.
+ * vg_head_bwd:  dz[b, e] = bf16((sum_k dlogits[b, k] W2[k, e]) (1 - t[b, e]^2)), the gradient at fc1's pre-activation, and with
+ *   want_wgrad the gradients of fc2.  Returns 1, 0 or a negative code (a hipError_t comes back negated):
+ *     1  (want_wgrad, Kc <= 16 and part != NULL): ONE launch; part, fp32
+ *        [vg_head_bwd_parts(B)][vg_head_bwd_part_width(E, Kc)], receives per 32 rows b one partial row
+ *        dW2 (Kc E: sum_b dlogits[b, k] t[b, e]) | db1 (E: sum_b of the ROUNDED dz) | db2 (Kc: sum_b dlogits[b, k]),
+ *        to be folded with vg_colsum_f32; dW2 and db2 are not touched (they may be NULL).
+ *     0  (Kc > 16, or part == NULL): the separate kernels; with want_wgrad dW2 [Kc, E] and db2 [Kc] are ACCUMULATED into (+=), and db1
+ *        is the caller's column sum of dz (vg_colsum_bf16).  want_wgrad = 0 (any Kc, returns 0): dz only, the same bits.
+ * vg_batch_sum:  out[s, e] = sum_b g[b S + s, e]   (g bf16 [B S, E], out fp32 [S, E], fixed order).  E % 64 == 0.
+ * vg_embed_small_grads:  d_cls[e] += tok_sum[0, e];  d_pos[s - 1, e] += tok_sum[s, e] and d_bias[e] += sum_{s >= 1} tok_sum[s, e] for
+ *   s = 1 .. S - 1   (tok_sum fp32 [S, E], the output of vg_batch_sum; d_pos is [(S - 1), E]).  S >= 2.
+ * vg_take_rows:  out[b n_take + j, :] = in[b S + first + j, :]   (bf16).  E % 8 == 0, 0 <= first, first + n_take <= S.
+ * vg_scatter_cls:  g[b S, :] = src[b, :], every other row of g [B S, E] = 0; with gm != NULL and p > 0 also gm = what vg_dropout_apply
+ *   with the same (p, seed, site, step_dev) makes of the whole of g (p = 0: gm is not written).  vg_scatter_cls_pair: two sources
+ *   into two tensors, no mask.  E % 8 == 0.
+ * vg_fill_cls:  x[b S, e] = bf16(cls[e] mask / keep), the mask of element (b S) E + e of the [B S, E] tensor; no other row is written.
+ * vg_patchify:  A[(b G + gy) G + gx, (c P + py) P + px] = bf16(img[b, c, gy P + py, gx P + px]), G = IH / P  (img fp32, or bf16 with
+ *   img_is_bf16).  vg_unpatchify: its inverse on bf16.  IH % P == 0.
+ * vg_slab_reduce:  dst[i] (+)= sum_s slab[s stride + i] for i < n, the slices added in slice order.  n % 4 == 0, nslab >= 1, and with more
+ *   than one slice stride >= n, stride % 4 == 0.  vg_slab_reduce_pair: two folds of one shape in one launch.
+ * vg_sin_grad:  dz[i] = bf16(dy[i] w0 cos(w0 z[i]))   (dy bf16, z fp32; the hardware cosine).  n % 4 == 0.
+ * vg_add_table:  x[r, :] = bf16(x[r, :] + table[r % period, :]) in place (x bf16 [rows, E], table fp32 [period, E]).  E % 4 == 0. */
+int vg_head_fwd(const void* t, const float* W2, const float* b2, float* logits, int B, int E, int Kc, void* stream);
+int vg_head_bwd_parts(int B);               /* host only */
+int vg_head_bwd_part_width(int E, int Kc);  /* host only */
+int vg_head_bwd(const float* dlogits, const float* W2, const void* t, void* dz, float* dW2, float* db2, float* part, int B, int E, int Kc,
+                int want_wgrad, void* stream);
+int vg_batch_sum(const void* g, float* out, int B, int S, int E, void* stream);
+int vg_embed_small_grads(const float* tok_sum, float* d_cls, float* d_pos, float* d_bias, int S, int E, void* stream);
+int vg_take_rows(const void* in, void* out, int B, int S, int first, int n_take, int E, void* stream);
+int vg_scatter_cls(const void* src, void* g, void* gm, int B, int S, int E, float p, unsigned long long seed, int site,
+                   const unsigned* step_dev, void* stream);
+int vg_scatter_cls_pair(const void* src_a, void* dst_a, const void* src_b, void* dst_b, int B, int S, int E, void* stream);
+int vg_fill_cls(void* x, const float* cls, int B, int S, int E, float p, unsigned long long seed, int site, const unsigned* step_dev,
+                void* stream);
+int vg_patchify(const void* img, int img_is_bf16, void* A, int B, int C, int IH, int P, void* stream);
+int vg_unpatchify(const void* dA, void* d_img, int B, int C, int IH, int P, void* stream);
+int vg_slab_reduce(const float* slab, long long stride, int nslab, float* dst, long long n, int accumulate, void* stream);
+int vg_slab_reduce_pair(const float* slab0, const float* slab1, long long stride, int nslab, float* dst0, float* dst1, long long n,
+                        int accumulate, void* stream);
+int vg_sin_grad(const void* dy, const float* z, void* dz, long long n, float w0, void* stream);
+int vg_add_table(void* x, const float* table, long long rows, int E, int period, void* stream);
+
 /* Spectral normalisation of a set of weight matrices that live inside one flat parameter buffer (ViTGAN's form,
  * W_eff = sigma_max(W_init) W / sigma_max(W); one power iteration per step as torch.nn.utils.spectral_norm runs in training).
  * The GEMMs read the bf16 shadow only, so normalising is a scaled cast of the fp32 master into the shadow plus one linear

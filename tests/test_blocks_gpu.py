@@ -173,6 +173,65 @@ def test_vit_every_stage_against_the_model(case, B, dropout):
     _report(f"ViT {case} B={B} p={dropout}", worst)
 
 
+@pytest.mark.parametrize("dropout", [0.0, 0.1])
+@pytest.mark.parametrize("B", [5, 33])
+@pytest.mark.parametrize("Kc", [17, 40])
+def test_vit_head_stage_wider_than_16_classes_against_the_model(Kc, B, dropout):
+    """The head stage above 16 classes - vg_head_bwd_dz_kernel + vg_head_bwd_w2_kernel accumulating straight into G, db1 from
+    vg_colsum_bf16 - teacher-forced against bm.vit_head exactly as the classes = 10 cases above, on the smallest network the layout
+    takes; after stage 0 nothing of G outside the head and the final LayerNorm may have been touched, and want_wgrad = 0 leaves G
+    alone and hands down the same dL/dX[L] bits."""
+    import gpu_util as u
+    from weights import make_input, make_state
+    from oracle import bf16_model as bm, vit_oracle as vo
+    from vit_gan_amd import _lib, flat
+
+    d = vo.VitDims(channels=3, image=16, patch=4, embed=128, heads=4, layers=2, mlp_ratio=2, classes=Kc)
+    L, S, E = d.layers, d.seq, d.embed
+    st_np = make_state(vo.vit_param_shapes(d), 50 + Kc, "vit")
+    x = torch.from_numpy(make_input((B, 3, 16, 16), 51 + Kc, "uniform"))
+    dd = flat.vit_dims_struct(3, 16, 4, E, 4, L, 2, Kc)
+    lay, slots = flat.vit_layout(dd), flat.vit_slots(dd)
+    P = flat.pack(slots, lay.total, st_np, device="cuda")
+    Pb = P.to(torch.bfloat16)
+    wm = _lib.VgVitWsMap()
+    u.call("vg_vit_ws_map", C.byref(dd), B, C.byref(wm))
+    ws = torch.zeros(_lib.lib().vg_vit_ws_bytes(C.byref(dd), B), dtype=torch.uint8, device="cuda")
+    R = torch.from_numpy(make_input((B, Kc), 52 + Kc))
+    X, Rd = x.cuda(), R.cuda()
+
+    def cls_only(off):
+        full = torch.zeros(B, S, E)
+        full[:, 0] = _view(ws, off, (B, E), torch.bfloat16).float().cpu()
+        return full
+    got = {}
+    for want_wgrad in (1, 0):
+        G = torch.zeros_like(P)
+        net = _lib.VgVitNet(dd, P.data_ptr(), Pb.data_ptr(), G.data_ptr(), dropout, 4321, None, _lib.context(), 0, 0)
+        logits = torch.empty(B, Kc, device="cuda")
+        u.call("vg_vit_forward", C.byref(net), B, u.ptr(X), 0, u.ptr(ws), u.ptr(logits), u.stream())
+        u.call("vg_vit_backward_stages", C.byref(net), B, u.ptr(ws), u.ptr(Rd), None, want_wgrad, 0, 1, u.stream())
+        u.sync()
+        got[want_wgrad] = (logits.cpu(), cls_only(wm.xtop), cls_only(wm.dxtop), {k: v.clone() for k, v in flat.unpack(slots, G).items()})
+    logits, xtop, gtop, grads = got[1]
+    head_keys = [k for k in st_np if k.startswith(("vit.norm.", "vit.classifier."))]
+    assert len(head_keys) == 6
+    for k, v in grads.items():
+        if k not in head_keys:
+            assert int(torch.count_nonzero(v)) == 0, f"stage 0 touched grad {k}"
+    assert all(int(torch.count_nonzero(v)) == 0 for v in got[0][3].values()), "want_wgrad = 0 wrote a weight gradient"
+    assert torch.equal(got[0][0], logits) and torch.equal(got[0][2], gtop), "want_wgrad = 0 changed the logits or dL/dX[L]"
+    st = {k: torch.from_numpy(v).requires_grad_(True) for k, v in st_np.items()}
+    xin = _leaf(xtop)
+    out = bm.vit_head(st, bm.stored(xin))
+    worst = {"head: logits": _rel_err(logits, out)}
+    (out * R).sum().backward()
+    worst["head: dL/dX[L]"] = _rel_err(gtop, xin.grad)
+    for k in head_keys:
+        worst[f"head: grad {k}"] = _rel_err(grads[k], st[k].grad)
+    _report(f"ViT wide head Kc={Kc} B={B} p={dropout}", worst)
+
+
 @pytest.mark.parametrize("B,dropout,patch", [(3, 0.0, 0), (2, 0.2, 0), (2, 0.0, 4), (32, 0.2, 0)])
 def test_generator_every_stage_against_the_model(B, dropout, patch):
     import gpu_util as u

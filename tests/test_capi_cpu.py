@@ -64,6 +64,79 @@ def test_argument_validation_without_gpu():
     assert lib.vg_vit_penalty(C.byref(nog), 16, p16, p16, p16, 1.0, p16, p16, p16, None) == -1   # no gradient buffer to accumulate into
 
 
+def test_end_kernel_entries_refuse_on_the_host():
+    """The single-kernel entries of the networks' ends (vg_head_fwd .. vg_add_table): every null pointer is -1 and every shape the
+    kernel silently assumes is -3, from the launcher, before anything is launched (the dummy pointers are never dereferenced)."""
+    lib = _lib.lib()
+    p = C.c_void_p(4096)
+    assert lib.vg_head_bwd_parts(1) == 1 and lib.vg_head_bwd_parts(32) == 1 and lib.vg_head_bwd_parts(33) == 2 and lib.vg_head_bwd_parts(130) == 5
+    assert lib.vg_head_bwd_part_width(384, 10) == 11 * 384 + 10 and lib.vg_head_bwd_part_width(128, 1) == 257
+    # classifier head
+    for hole in range(4):
+        a = [p, p, p, p]
+        a[hole] = None
+        assert lib.vg_head_fwd(*a, 4, 128, 10, None) == -1, hole
+        assert lib.vg_head_bwd(*a, p, p, p, 4, 128, 10, 1, None) == -1, hole
+    for B, E, Kc in ((0, 128, 10), (4, 0, 10), (4, 128, 0), (-1, 128, 10), (1 << 30, 128, 8)):
+        assert lib.vg_head_fwd(p, p, p, p, B, E, Kc, None) == -3, (B, E, Kc)
+        assert lib.vg_head_bwd(p, p, p, p, p, p, p, B, E, Kc, 1, None) == -3, (B, E, Kc)
+    assert lib.vg_head_bwd(p, p, p, p, None, p, None, 4, 128, 10, 1, None) == -1   # forced separate kernels accumulate into dW2 ...
+    assert lib.vg_head_bwd(p, p, p, p, p, None, None, 4, 128, 10, 1, None) == -1   # ... and db2
+    assert lib.vg_head_bwd(p, p, p, p, None, None, p, 4, 128, 17, 1, None) == -1   # above 16 classes the partial rows are not used
+    # batch sum and the embedding's small gradients
+    assert lib.vg_batch_sum(None, p, 4, 5, 128, None) == -1 and lib.vg_batch_sum(p, None, 4, 5, 128, None) == -1
+    for B, S, E in ((0, 5, 128), (4, 0, 128), (4, 5, 0), (4, 5, 96), (4, 5, 32), (4, 5, 130)):
+        assert lib.vg_batch_sum(p, p, B, S, E, None) == -3, (B, S, E)
+    for hole in range(4):
+        a = [p, p, p, p]
+        a[hole] = None
+        assert lib.vg_embed_small_grads(*a, 5, 128, None) == -1, hole
+    for S, E in ((1, 128), (0, 128), (5, 0), (1 << 20, 1 << 12)):
+        assert lib.vg_embed_small_grads(p, p, p, p, S, E, None) == -3, (S, E)
+    # row movers
+    assert lib.vg_take_rows(None, p, 2, 5, 1, 4, 128, None) == -1 and lib.vg_take_rows(p, None, 2, 5, 1, 4, 128, None) == -1
+    for B, S, first, n, E in ((2, 5, 1, 4, 132), (2, 5, 1, 4, 4), (2, 5, 1, 5, 128), (2, 5, 5, 1, 128), (2, 5, -1, 2, 128), (2, 5, 0, 0, 128),
+                              (0, 5, 1, 4, 128), (2, 0, 0, 1, 128), (2, 5, 0x7FFFFFFF, 2, 128)):
+        assert lib.vg_take_rows(p, p, B, S, first, n, E, None) == -3, (B, S, first, n, E)
+    assert lib.vg_scatter_cls(None, p, None, 2, 5, 128, 0.0, 1, 0, None, None) == -1 and lib.vg_scatter_cls(p, None, None, 2, 5, 128, 0.0, 1, 0, None, None) == -1
+    assert lib.vg_scatter_cls(p, p, p, 2, 5, 128, 1.0, 1, 0, None, None) == -1 and lib.vg_scatter_cls(p, p, p, 2, 5, 128, -0.1, 1, 0, None, None) == -1
+    for hole in range(4):
+        a = [p, p, p, p]
+        a[hole] = None
+        assert lib.vg_scatter_cls_pair(*a, 2, 5, 128, None) == -1, hole
+    for B, S, E in ((0, 5, 128), (2, 0, 128), (2, 5, 0), (2, 5, 132), (2, 5, 4)):
+        assert lib.vg_scatter_cls(p, p, None, B, S, E, 0.0, 1, 0, None, None) == -3, (B, S, E)
+        assert lib.vg_scatter_cls_pair(p, p, p, p, B, S, E, None) == -3, (B, S, E)
+    assert lib.vg_fill_cls(None, p, 2, 5, 128, 0.0, 1, 0, None, None) == -1 and lib.vg_fill_cls(p, None, 2, 5, 128, 0.0, 1, 0, None, None) == -1
+    assert lib.vg_fill_cls(p, p, 2, 5, 128, 1.0, 1, 0, None, None) == -1
+    for B, S, E in ((0, 5, 128), (2, 0, 128), (2, 5, 0), (1 << 20, 5, 1 << 12)):
+        assert lib.vg_fill_cls(p, p, B, S, E, 0.1, 1, 0, None, None) == -3, (B, S, E)
+    # patchify and its inverse
+    assert lib.vg_patchify(None, 0, p, 1, 3, 32, 4, None) == -1 and lib.vg_patchify(p, 0, None, 1, 3, 32, 4, None) == -1
+    assert lib.vg_unpatchify(None, p, 1, 3, 32, 4, None) == -1 and lib.vg_unpatchify(p, None, 1, 3, 32, 4, None) == -1
+    for B, Cc, IH, Pp in ((1, 3, 30, 4), (1, 3, 32, 0), (0, 3, 32, 4), (1, 0, 32, 4), (1, 3, 0, 4), (1, 3, 8, 16)):
+        assert lib.vg_patchify(p, 0, p, B, Cc, IH, Pp, None) == -3, (B, Cc, IH, Pp)
+        assert lib.vg_unpatchify(p, p, B, Cc, IH, Pp, None) == -3, (B, Cc, IH, Pp)
+    # slab folds
+    assert lib.vg_slab_reduce(None, 8, 2, p, 8, 0, None) == -1 and lib.vg_slab_reduce(p, 8, 2, None, 8, 0, None) == -1
+    for hole in (0, 1, 4, 5):
+        a = [p, p, 8, 2, p, p, 8, 0]
+        a[hole] = None
+        assert lib.vg_slab_reduce_pair(*a, None) == -1, hole
+    for stride, nslab, n in ((8, 2, 6), (8, 2, 0), (8, 0, 8), (4, 2, 8), (10, 2, 8), (8, -1, 8)):
+        assert lib.vg_slab_reduce(p, stride, nslab, p, n, 0, None) == -3, (stride, nslab, n)
+        assert lib.vg_slab_reduce_pair(p, p, stride, nslab, p, p, n, 0, None) == -3, (stride, nslab, n)
+    # SIREN gradient and the position table
+    for hole in range(3):
+        a = [p, p, p]
+        a[hole] = None
+        assert lib.vg_sin_grad(*a, 8, 30.0, None) == -1, hole
+    assert lib.vg_sin_grad(p, p, p, 6, 30.0, None) == -3 and lib.vg_sin_grad(p, p, p, 0, 30.0, None) == -3
+    assert lib.vg_add_table(None, p, 5, 128, 5, None) == -1 and lib.vg_add_table(p, None, 5, 128, 5, None) == -1
+    for rows, E, period in ((5, 130, 5), (5, 128, 0), (0, 128, 5), (5, 0, 5), (5, 2, 5)):
+        assert lib.vg_add_table(p, p, rows, E, period, None) == -3, (rows, E, period)
+
+
 def test_unsupported_depths_are_rejected_not_overflowed():
     """the backward queues 3 folds per ViT block (2L+1 for the generator) into a 42-entry host array (+ 2 for the head and the final LayerNorm, + 2 for the SIREN biases) and uses
     one event pair per block; depths beyond that used to write past the array.  The layouts now refuse them."""

@@ -99,6 +99,76 @@ def test_vit_forward_backward_vs_oracle(name, batch):
         u.assert_close(g2[k], 2 * grads[k], 1e-3, f"accumulate {k}")
 
 
+def _dropout_masks(u, B, S, E, L, p, seed):
+    """the multipliers (mask / keep) of every dropout site of a ViT run with (p, seed), through vg_dropout_apply"""
+    keep = 256.0 / (256.0 - round(p * 256))
+
+    def mask(site):
+        ones = torch.ones(B, S, E, dtype=torch.bfloat16, device="cuda")
+        out = torch.empty_like(ones)
+        u.call("vg_dropout_apply", u.ptr(ones), u.ptr(out), ones.numel(), p, seed, site, None, u.stream())
+        u.sync()
+        return (out.float().cpu() > 0).float() * keep
+    masks = {"embed": mask(0)}
+    for l in range(L):
+        masks[("attn", l)], masks[("mlp", l)] = mask(1 + 2 * l), mask(2 + 2 * l)
+    return masks
+
+
+@pytest.mark.parametrize("dropout", [0.0, 0.1])
+@pytest.mark.parametrize("B", [5, 33])
+@pytest.mark.parametrize("Kc", [17, 40])
+def test_vit_head_wider_than_16_classes_vs_oracle(Kc, B, dropout):
+    """Above 16 classes (a CIFAR-100 discriminator has 100) the head's backward leaves its one-launch kernel for vg_head_bwd_dz_kernel +
+    vg_head_bwd_w2_kernel, which accumulate straight into G, and db1 comes from vg_colsum_bf16.  The smallest network the layout takes
+    (16 x 16 images, 4 x 4 patches, E 128, 2 blocks), forward and staged backward with want_wgrad 1 and 0, against the fp32 oracle
+    computed live (with the engine's own masks at dropout 0.1), at this file's tolerances."""
+    import gpu_util as u
+    from oracle import vit_oracle as vo
+    from vit_gan_amd import _lib, flat
+    from weights import make_input, make_state
+
+    d = vo.VitDims(channels=3, image=16, patch=4, embed=128, heads=4, layers=2, mlp_ratio=2, classes=Kc)
+    L, S, E = d.layers, d.seq, d.embed
+    st_np = make_state(vo.vit_param_shapes(d), 40 + Kc, "vit")
+    x = torch.from_numpy(make_input((B, 3, 16, 16), 41 + Kc, "uniform"))
+    seed = 777
+    masks = _dropout_masks(u, B, S, E, L, dropout, seed) if dropout > 0 else None
+    st = {k: torch.from_numpy(v).requires_grad_(True) for k, v in st_np.items()}
+    xr = x.clone().requires_grad_(True)
+    out = vo.vit_forward(st, xr, d, masks=masks)
+    R = torch.from_numpy(make_input(tuple(out.shape), 42 + Kc))
+    (out * R).sum().backward()
+
+    dd = flat.vit_dims_struct(3, 16, 4, E, 4, L, 2, Kc)
+    lay, slots = flat.vit_layout(dd), flat.vit_slots(dd)
+    P = flat.pack(slots, lay.total, st_np, device="cuda")
+    Pb, X, Rd = P.to(torch.bfloat16), x.cuda(), R.cuda()
+    ws = torch.empty(_lib.lib().vg_vit_ws_bytes(C.byref(dd), B), dtype=torch.uint8, device="cuda")
+    for want_wgrad in (1, 0):
+        G = torch.zeros_like(P)
+        net = _lib.VgVitNet(dd, P.data_ptr(), Pb.data_ptr(), G.data_ptr(), dropout, seed, None, _lib.context(), 0, 0)
+        logits = torch.empty(B, Kc, device="cuda")
+        dimg = torch.empty(B, 3, 16, 16, dtype=torch.bfloat16, device="cuda")
+        u.call("vg_vit_forward", C.byref(net), B, u.ptr(X), 0, u.ptr(ws), u.ptr(logits), u.stream())
+        for stage in range(L + 2):
+            u.call("vg_vit_backward_stages", C.byref(net), B, u.ptr(ws), u.ptr(Rd), u.ptr(dimg), want_wgrad, stage, stage + 1, u.stream())
+        u.sync()
+        what = f"want_wgrad {want_wgrad}: "
+        u.assert_close(logits, out, 2.0 ** -5, what + "logits")
+        u.assert_close(dimg, xr.grad, 2.0 ** -4, what + "d_img")
+        if not want_wgrad:
+            assert int(torch.count_nonzero(G)) == 0, "want_wgrad = 0 wrote a weight gradient"
+            continue
+        grads = flat.unpack(slots, G)
+        for k, p in st.items():
+            if k.endswith("keys.bias"):  # the exact gradient is zero (softmax is invariant to a key shift): rounding noise against its sibling
+                sib = float(st[k.replace("keys", "queries")].grad.abs().max())
+                assert float(grads[k].abs().max()) < 2.0 ** -4 * sib + 1e-4, k
+                continue
+            u.assert_close(grads[k], p.grad, 2.0 ** -4, what + f"grad {k}")
+
+
 @pytest.mark.parametrize("name", ["g1", "g1b3"])
 def test_gen_forward_backward_vs_oracle(name):
     import gpu_util as u

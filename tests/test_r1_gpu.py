@@ -57,16 +57,18 @@ def _disc(B, layers, geo):
         img = 64
     elif geo == "c2-10-classes":
         kw.update(classes_count=10)
+    elif geo == "c2-17-classes":
+        kw.update(classes_count=17)
     elif geo == "e128":
         kw.update(embeddings_dimension=128, attention_heads_count=4)
     torch.manual_seed(3)
     return ViTDiscriminator(Config(**kw)).cuda().train(), img
 
 
-@pytest.mark.parametrize("B,layers,geo", [(16, 2, "c2"), (8, 2, "c2"), (8, 2, "e128"), (16, 2, "c4"), (16, 2, "c2-10-classes")])
+@pytest.mark.parametrize("B,layers,geo", [(16, 2, "c2"), (8, 2, "c2"), (8, 2, "e128"), (16, 2, "c4"), (16, 2, "c2-10-classes"), (16, 2, "c2-17-classes")])
 def test_r1_c_call_matches_the_operator_set(B, layers, geo):
     """(16, c2): the fused full-row forms; (8, c2) and e128: the GEMM + LayerNorm pairs; c4: the N = 512 instantiation; 10 classes: the
-    head's second-order kernel with more than one logit.  Dropout off, weight 5.  Tolerances of the gradient penalty's own test: the
+    head's second-order kernel with more than one logit; 17 classes: the head's first backward on its separate dz kernel (Kc > 16).  Dropout off, weight 5.  Tolerances of the gradient penalty's own test: the
     penalty within 2^-7 relative + 1e-5, every tensor within 2^-6 max|ref| + 2^-10 max|whole buffer|."""
     D, img = _disc(B, layers, geo)
     fl = D.vit._flat
@@ -145,6 +147,45 @@ def test_r1_matches_the_float64_oracle(form):
         worst.append((u.assert_close(got[k], g.float(), 2.0 ** -4, f"d penalty / d {k}", floor=1e-5), k))
     print("skipped:", skipped, " largest deviations:", [(k, f"{v:.2e}") for v, k in sorted(worst, key=lambda t: -(t[0] or 0))[:5]])
     assert len(skipped) <= 2, skipped
+
+
+def test_r1_c_call_at_17_classes_matches_the_float64_oracle():
+    """Above 16 classes the seed of the input gradient, vg_head_bwd_launch(ones, ...), runs the head's separate dz kernel.  vg_vit_r1 on
+    the smallest network the layout takes (16 x 16 images, 4 x 4 patches, E 128, 2 blocks, B 8) against r1_ref.r1_oracle in float64, at
+    the tolerances of test_r1_matches_the_float64_oracle: penalty 2^-6 relative + 1e-4, gradients 2^-4 of max|ref| with floor 1e-5, a
+    reference that is round-off of an exact zero held to 2^-10 of max|whole reference buffer|, only fc2.bias without a gradient."""
+    import gpu_util as u
+    import r1_ref
+    from oracle import vit_oracle as vo
+    from vit_gan_amd.config import Config
+    from vit_gan_amd.modules import ViTDiscriminator
+    from weights import make_input, make_state
+    B = 8
+    d = vo.VitDims(channels=3, image=16, patch=4, embed=128, heads=4, layers=2, mlp_ratio=2, classes=17)
+    st_np = make_state(vo.vit_param_shapes(d), 61, "vit")
+    x = torch.from_numpy(make_input((B, 3, 16, 16), 62, "uniform")).to(torch.bfloat16).float()
+    ref_pen, ref = r1_ref.r1_oracle(st_np, d, x, torch.float64)
+    D = ViTDiscriminator(Config(attention_heads_count=4, classes_count=17, dropout_rate=0.0, embeddings_dimension=128, transformer_blocks_count=2,
+                                batch_size=B, image_size=16, patch_size=4))
+    D.load_state_dict({k: torch.from_numpy(v) for k, v in st_np.items()}, strict=True)
+    D = D.cuda().train()
+    fl = D.vit._flat
+    out, flat_grad = _r1_c_call(D, x.cuda(), 1.0)
+    pen = float(out)
+    got = {"vit." + k: flat_grad[off:off + int(torch.tensor(shape).prod())].view(shape) for k, (off, shape) in fl.slots.items()}
+    print(f"R1 at 17 classes: HIP {pen:.6f}  float64 oracle {ref_pen:.6f}")
+    assert ref_pen > 0 and abs(pen - ref_pen) < 2.0 ** -6 * ref_pen + 1e-4
+    assert set(got) == set(ref)
+    zero_floor = 2.0 ** -10 * max(float(g.abs().max()) for g in ref.values() if g is not None)
+    skipped = []
+    for k, g in ref.items():
+        if g is None:
+            skipped.append(k)
+        elif float(g.abs().max()) < 1e-7:
+            assert float(got[k].abs().max()) <= zero_floor, k
+        else:
+            u.assert_close(got[k], g.float(), 2.0 ** -4, f"d penalty / d {k}", floor=1e-5)
+    assert skipped == ["vit.classifier.fc2.bias"], skipped
 
 
 def test_r1_c_call_with_dropout_is_the_gradient_of_its_own_value():

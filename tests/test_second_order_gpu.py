@@ -352,7 +352,7 @@ def test_attention_double_backward_refuses_bad_shapes():
 
 
 # ------------------------------------------------------------------------------------------------- the penalty as one call
-@pytest.mark.parametrize("geo", ["c2", "c4", "e128", "c2-10-classes", "c2-mlp4"])
+@pytest.mark.parametrize("geo", ["c2", "c4", "e128", "c2-10-classes", "c2-17-classes", "c2-mlp4"])
 def test_penalty_c_call_against_the_float64_oracle(geo):
     """vg_vit_penalty against oracle.step_oracle.gradient_penalty over oracle.vit_oracle.vit_forward in float64 (B = 16, L = 2, dropout
     off; tests/test_second_order_ref_cpu.py checks that the oracle really runs in float64).  The weights are rounded to bf16 first, so
@@ -373,6 +373,9 @@ def test_penalty_c_call_against_the_float64_oracle(geo):
     elif geo == "c2-10-classes":
         kw.update(classes_count=10)
         dims.update(classes=10)
+    elif geo == "c2-17-classes":   # Kc > 16: vg_head_bwd_launch(ones, ...) leaves the one-launch kernel for vg_head_bwd_dz_kernel
+        kw.update(classes_count=17)
+        dims.update(classes=17)
     elif geo == "c2-mlp4":
         kw.update(mlp_ratio=4)
         dims.update(mlp_ratio=4)

@@ -147,6 +147,22 @@ _SIGNATURES = {
     "vg_diversity_loss": (c_int, [P, P, P, P, c_int, c_int, c_float, P]),
     "vg_grad_clip": (c_int, [P, c_ll, c_float, c_float, P, P]),
     "vg_cast_f32_bf16": (c_int, [P, P, c_ll, P]),
+    "vg_head_fwd": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
+    "vg_head_bwd_parts": (c_int, [c_int]),
+    "vg_head_bwd_part_width": (c_int, [c_int, c_int]),
+    "vg_head_bwd": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
+    "vg_batch_sum": (c_int, [P, P, c_int, c_int, c_int, P]),
+    "vg_embed_small_grads": (c_int, [P, P, P, P, c_int, c_int, P]),
+    "vg_take_rows": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
+    "vg_scatter_cls": (c_int, [P, P, P, c_int, c_int, c_int, c_float, C.c_ulonglong, c_int, P, P]),
+    "vg_scatter_cls_pair": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
+    "vg_fill_cls": (c_int, [P, P, c_int, c_int, c_int, c_float, C.c_ulonglong, c_int, P, P]),
+    "vg_patchify": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, P]),
+    "vg_unpatchify": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
+    "vg_slab_reduce": (c_int, [P, c_ll, c_int, P, c_ll, c_int, P]),
+    "vg_slab_reduce_pair": (c_int, [P, P, c_ll, c_int, P, P, c_ll, c_int, P]),
+    "vg_sin_grad": (c_int, [P, P, P, c_ll, c_float, P]),
+    "vg_add_table": (c_int, [P, P, c_ll, c_int, c_int, P]),
     "vg_spectral_plan": (c_int, [P, c_int, C.POINTER(c_ll), C.POINTER(c_ll)]),
     "vg_spectral_update": (c_int, [P, P, c_ll, P, c_ll, P, c_ll, P, P, c_int, c_int, P]),
     "vg_spectral_project": (c_int, [P, P, c_ll, P, c_ll, P, c_ll, P, P, c_int, P]),

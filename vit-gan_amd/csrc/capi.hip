@@ -120,12 +120,70 @@ extern "C" int vg_colsum_bf16(const void* X, long long ld, int R, int N, float* 
   if (!X || !part_ws || !dst) return -1;
   return vg_colsum_bf16_launch((const bf16*)X, ld, R, N, part_ws, dst, accumulate, (hipStream_t)stream);
 }
+// threshold, key and scale of dropout site `site` of (p, seed): the one derivation behind every single-operator entry that carries a mask
+struct CapiDrop { unsigned thr, key; float scale; };
+static inline CapiDrop capi_drop(float p, unsigned long long seed, int site) {
+  int t = (int)lrintf(p * 256.f); if (t > 255) t = 255;
+  return CapiDrop{(unsigned)t, vg_site_key(seed, site), t ? 256.f / (256.f - t) : 1.f};
+}
 extern "C" int vg_dropout_apply(const void* x, void* y, long long n, float p, unsigned long long seed, int site,
                                 const unsigned* step_dev, void* stream) {
   if (!x || !y || n < 1 || p < 0.f || p >= 1.f) return -1;
-  int t = (int)lrintf(p * 256.f); if (t > 255) t = 255;
-  return vg_dropout_apply_launch((const bf16*)x, (bf16*)y, n, (unsigned)t, vg_site_key(seed, site), t ? 256.f / (256.f - t) : 1.f,
-                                 step_dev, (hipStream_t)stream);
+  const CapiDrop d = capi_drop(p, seed, site);
+  return vg_dropout_apply_launch((const bf16*)x, (bf16*)y, n, d.thr, d.key, d.scale, step_dev, (hipStream_t)stream);
+}
+// ---- the kernels at the two ends of the networks, one by one (elementwise.hip; tests/test_ends_gpu.py).  Every null pointer and every
+// shape is refused by the launcher, before any launch; the mask-carrying entries refuse a probability outside [0, 1) here (-1).
+extern "C" int vg_head_fwd(const void* t, const float* W2, const float* b2, float* logits, int B, int E, int Kc, void* stream) {
+  return vg_head_fc2_launch((const bf16*)t, W2, b2, logits, B, E, Kc, (hipStream_t)stream);
+}
+// (vg_head_bwd_parts and vg_head_bwd_part_width are the launcher's own helpers, exported as they are: vg_kernels.h)
+extern "C" int vg_head_bwd(const float* dlogits, const float* W2, const void* t, void* dz, float* dW2, float* db2, float* part, int B, int E, int Kc,
+                           int want_wgrad, void* stream) {
+  return vg_head_bwd_launch(dlogits, W2, (const bf16*)t, (bf16*)dz, dW2, db2, B, E, Kc, want_wgrad, (hipStream_t)stream, part);
+}
+extern "C" int vg_batch_sum(const void* g, float* out, int B, int S, int E, void* stream) {
+  return vg_batch_sum_launch((const bf16*)g, out, B, S, E, (hipStream_t)stream);
+}
+extern "C" int vg_embed_small_grads(const float* tok_sum, float* d_cls, float* d_pos, float* d_bias, int S, int E, void* stream) {
+  return vg_embed_small_grads_launch(tok_sum, d_cls, d_pos, d_bias, S, E, (hipStream_t)stream);
+}
+extern "C" int vg_take_rows(const void* in, void* out, int B, int S, int first, int n_take, int E, void* stream) {
+  return vg_take_rows_launch((const bf16*)in, (bf16*)out, B, S, first, n_take, E, (hipStream_t)stream);
+}
+extern "C" int vg_scatter_cls(const void* src, void* g, void* gm, int B, int S, int E, float p, unsigned long long seed, int site,
+                              const unsigned* step_dev, void* stream) {
+  if (p < 0.f || p >= 1.f) return -1;
+  const CapiDrop d = capi_drop(p, seed, site);
+  return vg_scatter_cls_launch((const bf16*)src, (bf16*)g, B, S, E, (hipStream_t)stream, (bf16*)gm, d.thr, d.key, d.scale, step_dev);
+}
+extern "C" int vg_scatter_cls_pair(const void* src_a, void* dst_a, const void* src_b, void* dst_b, int B, int S, int E, void* stream) {
+  return vg_scatter_cls2_launch((const bf16*)src_a, (bf16*)dst_a, (const bf16*)src_b, (bf16*)dst_b, B, S, E, (hipStream_t)stream);
+}
+extern "C" int vg_fill_cls(void* x, const float* cls, int B, int S, int E, float p, unsigned long long seed, int site, const unsigned* step_dev,
+                           void* stream) {
+  if (p < 0.f || p >= 1.f) return -1;
+  const CapiDrop d = capi_drop(p, seed, site);
+  return vg_fill_cls_launch((bf16*)x, cls, B, S, E, d.thr, d.key, d.scale, step_dev, (hipStream_t)stream);
+}
+extern "C" int vg_patchify(const void* img, int img_is_bf16, void* A, int B, int C, int IH, int P, void* stream) {
+  return vg_patchify_launch(img, img_is_bf16, (bf16*)A, B, C, IH, P, (hipStream_t)stream);
+}
+extern "C" int vg_unpatchify(const void* dA, void* d_img, int B, int C, int IH, int P, void* stream) {
+  return vg_unpatchify_launch((const bf16*)dA, (bf16*)d_img, B, C, IH, P, (hipStream_t)stream);
+}
+extern "C" int vg_slab_reduce(const float* slab, long long stride, int nslab, float* dst, long long n, int accumulate, void* stream) {
+  return vg_slab_reduce_launch(slab, stride, nslab, dst, n, accumulate, (hipStream_t)stream);
+}
+extern "C" int vg_slab_reduce_pair(const float* slab0, const float* slab1, long long stride, int nslab, float* dst0, float* dst1, long long n,
+                                   int accumulate, void* stream) {
+  return vg_slab_reduce2_launch(slab0, slab1, stride, nslab, dst0, dst1, n, accumulate, (hipStream_t)stream);
+}
+extern "C" int vg_sin_grad(const void* dy, const float* z, void* dz, long long n, float w0, void* stream) {
+  return vg_sin_grad_launch((const bf16*)dy, z, (bf16*)dz, n, w0, (hipStream_t)stream);
+}
+extern "C" int vg_add_table(void* x, const float* table, long long rows, int E, int period, void* stream) {
+  return vg_add_table_launch((bf16*)x, table, rows, E, period, (hipStream_t)stream);
 }
 // ---- full-row Linear + LayerNorm (gemm_row.hip) ----
 extern "C" long long vg_row_pack_elems_e(int E, int K) { return (!vg_row_width_ok(E) || K < 32 || (K & 31)) ? -2 : (long long)E * K; }

@@ -778,6 +778,9 @@ __global__ __launch_bounds__(256) void vg_add_table_kernel(bf16* __restrict__ x,
 
 // --------------------------------------- launchers ---------------------------------------------
 static inline unsigned nblk(long long n, int per = 256) { return (unsigned)((n + per - 1) / per); }
+// The launchers below check on the host what their kernels assume without looking: -1 a null pointer, -3 a shape.  Nothing is
+// launched on a negative return.  VG_I32 is the largest element count a kernel that indexes with int can take.
+#define VG_I32 0x7FFFFFFFLL
 
 // ---- v1 overlapping-window tokeniser (src/v1/patch_encoder.py:54-73) ---------------------------------------------
 // images.unfold(2, W, stride).unfold(3, W, stride) has shape [B, C, n, n, W, W]; the reference then takes a FLAT view
@@ -842,19 +845,24 @@ int vg_unfold_tokens_bwd_launch(const bf16* dout, bf16* dimg, int B, int C, int 
   return (int)hipGetLastError();
 }
 int vg_patchify_launch(const void* img, int img_is_bf16, bf16* A, int B, int C, int IH, int P, hipStream_t st) {
-  if (IH % P) return -3;
+  if (!img || !A) return -1;
+  if (B < 1 || C < 1 || IH < 1 || P < 1 || IH % P) return -3;
   const long long total = (long long)B * C * IH * (IH / P);
   if (img_is_bf16) hipLaunchKernelGGL(vg_patchify_kernel<bf16>, dim3(nblk(total)), dim3(256), 0, st, (const bf16*)img, A, B, C, IH, P);
   else hipLaunchKernelGGL(vg_patchify_kernel<float>, dim3(nblk(total)), dim3(256), 0, st, (const float*)img, A, B, C, IH, P);
   return (int)hipGetLastError();
 }
 int vg_unpatchify_launch(const bf16* dA, bf16* dimg, int B, int C, int IH, int P, hipStream_t st) {
+  if (!dA || !dimg) return -1;
+  if (B < 1 || C < 1 || IH < 1 || P < 1 || IH % P) return -3;  // G = IH / P patches a side: a remainder would leave columns unwritten
   const long long total = (long long)B * C * IH * (IH / P);
   hipLaunchKernelGGL(vg_unpatchify_kernel, dim3(nblk(total)), dim3(256), 0, st, dA, dimg, B, C, IH, P);
   return (int)hipGetLastError();
 }
 int vg_fill_cls_launch(bf16* x, const float* cls, int B, int S, int E, unsigned dthr, unsigned dkey, float dscale, const unsigned* dstep,
                        hipStream_t st) {
+  if (!x || !cls) return -1;
+  if (B < 1 || S < 1 || E < 1 || (long long)B * E > VG_I32 || dthr > 255u) return -3;  // one thread per (b, e), an int index
   hipLaunchKernelGGL(vg_fill_cls_kernel, dim3(nblk((long long)B * E)), dim3(256), 0, st, x, cls, B, S, E, dthr, dkey, dscale, dstep);
   return (int)hipGetLastError();
 }
@@ -865,12 +873,16 @@ int vg_dropout_apply_launch(const bf16* x, bf16* y, long long n, unsigned dthr, 
   return (int)hipGetLastError();
 }
 int vg_take_rows_launch(const bf16* in, bf16* out, int B, int S, int first, int n_take, int E, hipStream_t st) {
+  if (!in || !out) return -1;
+  // 16-byte chunks of a row (E % 8), and the window [first, first + n_take) inside the S rows of an image
+  if (B < 1 || S < 1 || E < 8 || (E & 7) || first < 0 || n_take < 1 || (long long)first + n_take > S) return -3;
   hipLaunchKernelGGL(vg_take_rows_kernel, dim3(nblk((long long)B * n_take * (E / 8))), dim3(256), 0, st, in, out, B, S, first, n_take, E);
   return (int)hipGetLastError();
 }
 int vg_scatter_cls_launch(const bf16* src, bf16* g, int B, int S, int E, hipStream_t st, bf16* gm, unsigned dthr, unsigned dkey, float dscale,
                           const unsigned* dstep) {
-  if (E & 7) return -3;
+  if (!src || !g) return -1;
+  if (B < 1 || S < 1 || E < 8 || (E & 7) || dthr > 255u) return -3;
   hipLaunchKernelGGL(vg_scatter_cls_kernel, dim3(nblk((long long)B * S * (E / 8))), dim3(256), 0, st, src, g, B, S, E, (dthr ? gm : nullptr), dthr, dkey,
                      dscale, dstep);
   return (int)hipGetLastError();
@@ -889,30 +901,40 @@ __global__ __launch_bounds__(256) void vg_scatter_cls2_kernel(const bf16* __rest
   *(u32x4*)(dst_b + (size_t)r * E + 8 * c) = vb;
 }
 int vg_scatter_cls2_launch(const bf16* src_a, bf16* dst_a, const bf16* src_b, bf16* dst_b, int B, int S, int E, hipStream_t st) {
-  if ((E & 7) || !src_a || !dst_a || !src_b || !dst_b) return -3;
+  if (!src_a || !dst_a || !src_b || !dst_b) return -1;
+  if (B < 1 || S < 1 || E < 8 || (E & 7)) return -3;
   hipLaunchKernelGGL(vg_scatter_cls2_kernel, dim3(nblk((long long)B * S * (E / 8))), dim3(256), 0, st, src_a, dst_a, src_b, dst_b, B, S, E);
   return (int)hipGetLastError();
 }
 int vg_batch_sum_launch(const bf16* g, float* out, int B, int S, int E, hipStream_t st) {
-  if (E & 63) return -3;
+  if (!g || !out) return -1;
+  // a workgroup owns 64 columns of one token row; the grid is S * (E / 64)
+  if (B < 1 || S < 1 || E < 64 || (E & 63) || (long long)S * (E / 64) > VG_I32) return -3;
   hipLaunchKernelGGL(vg_batch_sum_kernel, dim3(S * (E / 64)), dim3(256), 0, st, g, out, B, S, E);
   return (int)hipGetLastError();
 }
 int vg_embed_small_grads_launch(const float* tok_sum, float* d_cls, float* d_pos, float* d_bias, int S, int E, hipStream_t st) {
+  if (!tok_sum || !d_cls || !d_pos || !d_bias) return -1;
+  if (S < 2 || E < 1 || (long long)S * E > VG_I32) return -3;  // row 0 is the CLS token, rows 1 .. S-1 the patches: at least one of them
   hipLaunchKernelGGL(vg_embed_small_grads_kernel, dim3(nblk((long long)S * E)), dim3(256), 0, st, tok_sum, d_cls, d_pos, d_bias, S, E);
   return (int)hipGetLastError();
 }
 int vg_head_fc2_launch(const bf16* t, const float* W2, const float* b2, float* logits, int B, int E, int Kc, hipStream_t st) {
+  if (!t || !W2 || !b2 || !logits) return -1;
+  if (B < 1 || E < 1 || Kc < 1 || (long long)B * Kc > VG_I32 / 4) return -3;  // one wave per (b, k), an int wave index
   hipLaunchKernelGGL(vg_head_fc2_kernel, dim3(nblk((long long)B * Kc, 4)), dim3(256), 0, st, t, W2, b2, logits, B, E, Kc);
   return (int)hipGetLastError();
 }
-int vg_head_bwd_parts(int B) { return (B + VG_HEAD_ROWS - 1) / VG_HEAD_ROWS; }
-int vg_head_bwd_part_width(int E, int Kc) { return (Kc + 1) * E + Kc; }
+extern "C" int vg_head_bwd_parts(int B) { return (B + VG_HEAD_ROWS - 1) / VG_HEAD_ROWS; }
+extern "C" int vg_head_bwd_part_width(int E, int Kc) { return (Kc + 1) * E + Kc; }
 // Kc <= 16: ONE launch; with `part` ([vg_head_bwd_parts(B)][vg_head_bwd_part_width(E, Kc)] floats) the gradients of W2, b1 and b2 are
 // left as partial rows for the caller's deferred fold and 1 is returned.  Otherwise (or part == nullptr with want_wgrad): the
 // separate kernels accumulate dW2 / db2 directly (db1 is then the caller's column sum) and 0 is returned.  < 0: -hipError.
 int vg_head_bwd_launch(const float* dlog, const float* W2, const bf16* t, bf16* dz, float* dW2, float* db2, int B, int E, int Kc,
                        int want_wgrad, hipStream_t st, float* part) {
+  if (!dlog || !W2 || !t || !dz) return -1;
+  if (B < 1 || E < 1 || Kc < 1 || (long long)B * E > VG_I32 || (long long)B * Kc > VG_I32 || (long long)Kc * (E + 1) > VG_I32 / 4) return -3;
+  if (want_wgrad && !(Kc <= VG_HEAD_KMAX && part) && (!dW2 || !db2)) return -1;  // the separate kernels accumulate into them
   if (Kc <= VG_HEAD_KMAX && (!want_wgrad || part)) {
     hipLaunchKernelGGL(vg_head_bwd_all_kernel, dim3((E + 63) / 64, vg_head_bwd_parts(B)), dim3(256), 0, st, dlog, W2, t, dz,
                        want_wgrad ? part : nullptr, B, E, Kc);
@@ -1055,25 +1077,33 @@ int vg_cast_f32_bf16_launch(const float* src, bf16* dst, long long n, hipStream_
   hipLaunchKernelGGL(vg_cast_f32_bf16_kernel, dim3(nblk(n / 4)), dim3(256), 0, st, src, dst, n);
   return (int)hipGetLastError();
 }
+// whole 16-byte vectors (n % 4, stride % 4), at least one slice, and slices that do not overlap (one slice: the stride is not read)
+static inline int vg_slab_shape_ok(long long stride, int nslab, long long n) {
+  return n >= 4 && !(n & 3) && nslab >= 1 && (nslab == 1 || (stride >= n && !(stride & 3)));
+}
 int vg_slab_reduce_launch(const float* slab, long long stride, int nslab, float* dst, long long n, int accumulate, hipStream_t st) {
-  if (n & 3) return -3;
+  if (!slab || !dst) return -1;
+  if (!vg_slab_shape_ok(stride, nslab, n)) return -3;
   hipLaunchKernelGGL(vg_slab_reduce_kernel, dim3(nblk(n / 4)), dim3(256), 0, st, slab, stride, nslab, dst, n, accumulate);
   return (int)hipGetLastError();
 }
 int vg_slab_reduce2_launch(const float* slab0, const float* slab1, long long stride, int nslab, float* dst0, float* dst1, long long n, int accumulate,
                            hipStream_t st) {
-  if (n & 3) return -3;
+  if (!slab0 || !slab1 || !dst0 || !dst1) return -1;
+  if (!vg_slab_shape_ok(stride, nslab, n)) return -3;
   hipLaunchKernelGGL(vg_slab_reduce2_kernel, dim3(nblk(n / 4), 2), dim3(256), 0, st, slab0, slab1, stride, nslab, dst0, dst1, n, accumulate);
   return (int)hipGetLastError();
 }
 int vg_add_table_launch(bf16* x, const float* table, long long rows, int E, int period, hipStream_t st) {
-  if ((E & 3) || period < 1) return -3;
+  if (!x || !table) return -1;
+  if (rows < 1 || E < 4 || (E & 3) || period < 1) return -3;  // four columns a thread, all in one row
   const long long n = rows * E;
   hipLaunchKernelGGL(vg_add_table_kernel, dim3(nblk(n / 4)), dim3(256), 0, st, x, table, n, E, period);
   return (int)hipGetLastError();
 }
 int vg_sin_grad_launch(const bf16* dy, const float* z, bf16* dz, long long n, float w0, hipStream_t st) {
-  if (n & 3) return -3;
+  if (!dy || !z || !dz) return -1;
+  if (n < 4 || (n & 3)) return -3;
   hipLaunchKernelGGL(vg_sin_grad_kernel, dim3(nblk(n / 4)), dim3(256), 0, st, dy, z, dz, n, w0);
   return (int)hipGetLastError();
 }

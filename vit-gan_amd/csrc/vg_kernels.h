@@ -61,8 +61,8 @@ int vg_batch_sum_launch(const bf16* g, float* out, int B, int S, int E, hipStrea
 int vg_embed_small_grads_launch(const float* tok_sum, float* d_cls, float* d_pos, float* d_bias, int S, int E, hipStream_t st);
 int vg_head_fc2_launch(const bf16* t, const float* W2, const float* b2, float* logits, int B, int E, int Kc, hipStream_t st);
 // one launch (returns 1: dW2 / db1 / db2 left as partial rows in `part` for a deferred fold) or the separate kernels (returns 0); < 0 error
-int vg_head_bwd_parts(int B);
-int vg_head_bwd_part_width(int E, int Kc);
+extern "C" int vg_head_bwd_parts(int B);                // (host only; exported as they are: include/vitgan_hip.h)
+extern "C" int vg_head_bwd_part_width(int E, int Kc);
 int vg_head_bwd_launch(const float* dlog, const float* W2, const bf16* t, bf16* dz, float* dW2, float* db2, int B, int E, int Kc,
                        int want_wgrad, hipStream_t st, float* part = nullptr);
 // start of a step: zero_grad + step counter; input cast + latent noise (elementwise.hip)
