@@ -16,50 +16,6 @@
 #include "vg_attn.h"
 #include "vg_kernels.h"
 
-// ---- fp8 (OCP e4m3) operands for the activation-side products (config C5: "fp8 MFMA attention") ------------------------
-// An fp8 16x16x32 fragment is 8 bytes per lane, element j of lane group g pairing with element j of the other operand's
-// lane group g exactly like the bf16 fragment's 8 elements - so a bf16 fragment converts element by element.
-typedef long fp8x8;
-__device__ __forceinline__ fp8x8 to_fp8(float a0, float a1, float a2, float a3, float a4, float a5, float a6, float a7) {
-  int lo = 0, hi = 0;
-  lo = __builtin_amdgcn_cvt_pk_fp8_f32(a0, a1, lo, false);
-  lo = __builtin_amdgcn_cvt_pk_fp8_f32(a2, a3, lo, true);
-  hi = __builtin_amdgcn_cvt_pk_fp8_f32(a4, a5, hi, false);
-  hi = __builtin_amdgcn_cvt_pk_fp8_f32(a6, a7, hi, true);
-  return (fp8x8)(((unsigned long)(unsigned)hi << 32) | (unsigned long)(unsigned)lo);
-}
-__device__ __forceinline__ fp8x8 to_fp8(bf16x8 v) {
-  return to_fp8(vg_bf2f(v[0]), vg_bf2f(v[1]), vg_bf2f(v[2]), vg_bf2f(v[3]), vg_bf2f(v[4]), vg_bf2f(v[5]), vg_bf2f(v[6]), vg_bf2f(v[7]));
-}
-__device__ __forceinline__ fp8x8 pack_pair_fp8(f32x4 a, f32x4 b, float mul) {  // same element order as pack_pair
-  return to_fp8(a[0] * mul, a[1] * mul, a[2] * mul, a[3] * mul, b[0] * mul, b[1] * mul, b[2] * mul, b[3] * mul);
-}
-__device__ __forceinline__ f32x4 vg_mfma_fp8(fp8x8 a, fp8x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a, b, c, 0, 0, 0); }
-// score product with either operand type (FP8: both operands rounded to e4m3; accumulation stays fp32)
-template <bool FP8>
-__device__ __forceinline__ f32x4 score_mfma(bf16x8 a, bf16x8 b, f32x4 c) {
-  if constexpr (FP8) return vg_mfma_fp8(to_fp8(a), to_fp8(b), c);
-  else return vg_mfma(a, b, c);
-}
-#define VG_P_FP8_SCALE 256.0f  // softmax numerators in (0, 1] are scaled into e4m3's normal range before the P.V product
-
-// squared L2 norm of every row of an LDS head image -> out[rows] (rows >= S are zero rows).  One thread per row.
-template <int HE>
-__device__ __forceinline__ void row_sqnorms(const unsigned char* img, float* out, int rows, int tid, int nthreads) {
-  for (int r = tid; r < rows; r += nthreads) {
-    float a = 0.f;
-#pragma unroll
-    for (int c = 0; c < HE / 8; ++c) {
-      const bf16x8 v = *(const bf16x8*)(img + lds_off<HE>(r, 8 * c));
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { const float f = vg_bf2f(v[j]); a += f * f; }
-    }
-    out[r] = a;
-  }
-}
-// v1 attention score (src/v1/attention.py:66-67): the Euclidean distance |q - k| from q.k and the squared norms
-__device__ __forceinline__ float l2_dist(float qk, float qn, float kn) { return sqrtf(fmaxf(qn + kn - 2.f * qk, 0.f)); }
-
 template <int HE, int NT, bool L2, bool FP8>
 __global__ __launch_bounds__(64 * NT) void vg_attn_fwd_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ o,
                                                               float* __restrict__ lse, int B, int S, int H, float scale,
@@ -73,17 +29,13 @@ __global__ __launch_bounds__(64 * NT) void vg_attn_fwd_kernel(const bf16* __rest
   if (!attn_block(B, H, b, h)) return;
   const int tid = threadIdx.x, lane = tid & 63, qt = tid >> 6;  // wave qt owns query rows 16*qt .. 16*qt+15
   const int g = lane >> 4, li = lane & 15;
-  const int E = H * HE;
-  const size_t ld = 3 * (size_t)E;
-  const bf16* qb = qkv + (size_t)b * S * ld + h * HE;
-  const bf16* kb = qb + E;
-  const bf16* vb = qb + 2 * E;
+  const attn_head hd = head_view(qkv, b, h, S, H, HE);
 
   bf16x8 qf[KS];  // this wave's queries straight from global (nobody else needs them)
 #pragma unroll
-  for (int ks = 0; ks < KS; ++ks) qf[ks] = gfrag(qb, ld, 16 * qt, ks, S, lane);
-  dma_head<HE, NT>(kl, kb, ld, S, RK, zeros, qt, lane);
-  dma_head<HE, NT>(vl, vb, ld, S, RP, zeros, (qt + 2) % NT, lane);
+  for (int ks = 0; ks < KS; ++ks) qf[ks] = gfrag(hd.q, hd.ld, 16 * qt, ks, S, lane);
+  dma_head<HE>(kl, hd.k, hd.ld, S, RK, zeros, qt, NT, lane);
+  dma_head<HE>(vl, hd.v, hd.ld, S, RP, zeros, (qt + 2) % NT, NT, lane);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   float qn = 0.f;
@@ -129,15 +81,14 @@ __global__ __launch_bounds__(64 * NT) void vg_attn_fwd_kernel(const bf16* __rest
     }
   l = group_sum(l);
   const float inv_l = 1.0f / l;
-  if (g == 0 && q < S) lse[((size_t)b * H + h) * S + q] = m + __logf(l);
+  if (g == 0 && q < S) lse[hd.offl + q] = m + __logf(l);
 
   f32x4 oa[DT];
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) oa[dt] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int u = 0; u < KP; ++u) {
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    const f32x4 hi = (2 * u + 1 < NT) ? sc[(2 * u + 1 < NT) ? 2 * u + 1 : 0] : zero;
+    const f32x4 hi = tile_or_zero<NT>(sc, 2 * u + 1);  // shared by the fp8 and the bf16 packing
     if constexpr (FP8) {
       const fp8x8 pf = pack_pair_fp8(sc[2 * u], hi, VG_P_FP8_SCALE);
 #pragma unroll
@@ -148,7 +99,7 @@ __global__ __launch_bounds__(64 * NT) void vg_attn_fwd_kernel(const bf16* __rest
       for (int dt = 0; dt < DT; ++dt) oa[dt] = vg_mfma(lfrag_tr<HE>(vl, u, 16 * dt, lane), pf, oa[dt]);
     }
   }
-  store_tiles<DT>(o + ((size_t)b * S + (q < S ? q : 0)) * E + h * HE, oa, FP8 ? inv_l * (1.0f / VG_P_FP8_SCALE) : inv_l, g, q < S);
+  store_tiles<DT>(hd.o_row(o, q < S ? q : 0), oa, FP8 ? inv_l * (1.0f / VG_P_FP8_SCALE) : inv_l, g, q < S);
 }
 
 // Backward.  Phase A works in the S^T orientation (lane = query) and yields dQ; phase B in the
@@ -156,15 +107,16 @@ __global__ __launch_bounds__(64 * NT) void vg_attn_fwd_kernel(const bf16* __rest
 // costs 2 x 75 extra MFMAs per head and removes every register transpose.
 // FP8: the score product is recomputed with the forward's e4m3 operands (so P matches the forward's lse exactly); every
 // product that carries a gradient operand (dP, dV, dQ, dK) stays bf16 - gradients need the range.
+// The arithmetic is bwd_phase_a / bwd_phase_b of vg_attn.h; the two kernels below are two stagings of those phases.
+// Four images: everything a head needs is staged ONCE (K, V, Q, dO images by LDS-DMA + lse and delta per query).  One load
+// phase, one compute phase, one store phase per workgroup; the co-resident workgroup overlaps them.
 template <int HE, int NT, bool L2, bool FP8>
 __global__ __launch_bounds__(64 * NT, 2) void vg_attn_bwd_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ o,
                                                          const bf16* __restrict__ d_o, const float* __restrict__ lse,
                                                          bf16* __restrict__ dqkv, int B, int S, int H, float scale,
                                                          const void* __restrict__ zeros) {
-  constexpr int KS = HE / 32, DT = HE / 16, KP = (NT + 1) / 2, RP = KP * 32;
+  constexpr int KS = HE / 32, KP = (NT + 1) / 2, RP = KP * 32;
   constexpr int IMG = RP * HE * 2;
-  // Everything a head needs is staged ONCE: K, V, Q, dO images (LDS-DMA) + lse and delta per query.  One load
-  // phase, one compute phase, one store phase per workgroup; the co-resident workgroup overlaps them.
   __shared__ __attribute__((aligned(16))) unsigned char sm[4 * IMG + (L2 ? 4 : 2) * RP * 4];
   unsigned char* lk = sm;
   unsigned char* lv = sm + IMG;
@@ -178,157 +130,42 @@ __global__ __launch_bounds__(64 * NT, 2) void vg_attn_bwd_kernel(const bf16* __r
   if (!attn_block(B, H, b, h)) return;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;  // wave wv owns query tile wv (phase A) / key tile wv (phase B)
   const int g = lane >> 4, li = lane & 15;
-  const int E = H * HE;
-  const size_t ld = 3 * (size_t)E;
-  const bf16* qb = qkv + (size_t)b * S * ld + h * HE;
-  const bf16* kb = qb + E;
-  const bf16* vb = qb + 2 * E;
-  const bf16* ob = o + (size_t)b * S * E + h * HE;
-  const bf16* dob = d_o + (size_t)b * S * E + h * HE;
-  const float* lb = lse + ((size_t)b * H + h) * S;
-  bf16* dqb = dqkv + (size_t)b * S * ld + h * HE;
-  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  const attn_head hd = head_view(qkv, b, h, S, H, HE);
+  const bf16* ob = hd.in_o(o);
+  const bf16* dob = hd.in_o(d_o);
+  const float* lb = hd.in_lse(lse);
+  const bwd_rows rw = {dl, ll, qn_l, kn_l};
 
   bf16x8 of[KS];  // O is only needed for delta: this wave's 16 query rows, straight from global
 #pragma unroll
-  for (int ks = 0; ks < KS; ++ks) of[ks] = gfrag(ob, (size_t)E, 16 * wv, ks, S, lane);
-  dma_head<HE, NT>(lk, kb, ld, S, RP, zeros, wv, lane);
-  dma_head<HE, NT>(lv, vb, ld, S, RP, zeros, (wv + 1) % NT, lane);
-  dma_head<HE, NT>(lq, qb, ld, S, RP, zeros, (wv + 2) % NT, lane);
-  dma_head<HE, NT>(ldo, dob, (size_t)E, S, RP, zeros, (wv + 3) % NT, lane);
+  for (int ks = 0; ks < KS; ++ks) of[ks] = gfrag(ob, (size_t)hd.E, 16 * wv, ks, S, lane);
+  dma_head<HE>(lk, hd.k, hd.ld, S, RP, zeros, wv, NT, lane);
+  dma_head<HE>(lv, hd.v, hd.ld, S, RP, zeros, (wv + 1) % NT, NT, lane);
+  dma_head<HE>(lq, hd.q, hd.ld, S, RP, zeros, (wv + 2) % NT, NT, lane);
+  dma_head<HE>(ldo, dob, (size_t)hd.E, S, RP, zeros, (wv + 3) % NT, NT, lane);
   for (int i = tid; i < RP; i += 64 * NT) ll[i] = (i < S) ? lb[i] : 0.f;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
   bf16x8 qf[KS], dof[KS];
-  {
-    float dpart = 0.f;
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      qf[ks] = lfrag_row<HE>(lq, 16 * wv, ks, lane);
-      dof[ks] = lfrag_row<HE>(ldo, 16 * wv, ks, lane);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) dpart += vg_bf2f(dof[ks][j]) * vg_bf2f(of[ks][j]);
-    }
-    const float delta = group_sum(dpart);
-    if (g == 0) dl[16 * wv + li] = delta;
+  for (int ks = 0; ks < KS; ++ks) {
+    qf[ks] = lfrag_row<HE>(lq, 16 * wv, ks, lane);
+    dof[ks] = lfrag_row<HE>(ldo, 16 * wv, ks, lane);
   }
+  const float delta = row_delta<KS>(dof, of);
+  if (g == 0) dl[16 * wv + li] = delta;
   if (L2) { row_sqnorms<HE>(lq, qn_l, RP, tid, 64 * NT); row_sqnorms<HE>(lk, kn_l, RP, tid, 64 * NT); }
   __syncthreads();
 
-  // ---------------- phase A: S^T orientation (lane = query) -> dQ ----------------------
-  {
-    const int qt = wv;
-    const int q = 16 * qt + li;
-    const float delta = dl[q];
-    const float lse_q = ll[q];
-    const float qn = L2 ? qn_l[q] : 0.f;
-    float wsum = 0.f;  // L2: sum_k W[q,k], W = dL/d dist / dist
-    f32x4 ds[NT];
+  bwd_phase_a<HE, NT, L2, FP8>(lk, lv, lq, qf, dof, rw, hd.in_qkv(dqkv), hd.ld, S, scale, wv, lane);
+  bf16x8 kf[KS], vf[KS];
 #pragma unroll
-    for (int kt = 0; kt < NT; ++kt) {
-      f32x4 st = zero, dpt = zero;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        st = score_mfma<FP8>(lfrag_row<HE>(lk, 16 * kt, ks, lane), qf[ks], st);
-        dpt = vg_mfma(lfrag_row<HE>(lv, 16 * kt, ks, lane), dof[ks], dpt);
-      }
-      f32x4 kn4 = zero;
-      if (L2) kn4 = *(const f32x4*)(kn_l + 16 * kt + 4 * g);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int key = 16 * kt + 4 * g + r;
-        const float raw = L2 ? l2_dist(st[r], qn, kn4[r]) : st[r];
-        const float p = (key < S && q < S) ? __expf(raw * scale - lse_q) : 0.f;
-        float dsv = p * (dpt[r] - delta) * scale;
-        if (L2) { dsv = raw > 0.f ? dsv / raw : 0.f; wsum += dsv; }  // d dist/dq = (q - k)/dist
-        ds[kt][r] = dsv;
-      }
-    }
-    if (L2) wsum = group_sum(wsum);
-    f32x4 dq[DT];
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) dq[dt] = zero;
-#pragma unroll
-    for (int u = 0; u < KP; ++u) {
-      const bf16x8 dsf = pack_pair(ds[2 * u], (2 * u + 1 < NT) ? ds[(2 * u + 1 < NT) ? 2 * u + 1 : 0] : zero);
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) dq[dt] = vg_mfma(lfrag_tr<HE>(lk, u, 16 * dt, lane), dsf, dq[dt]);
-    }
-    if (L2) {  // dQ = rowsum(W) q - W K
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        const bf16x4 qv = *(const bf16x4*)(lq + lds_off<HE>(q, 16 * dt + 4 * g));
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dq[dt][r] = wsum * vg_bf2f(qv[r]) - dq[dt][r];
-      }
-    }
-    store_tiles<DT>(dqb + (size_t)(q < S ? q : 0) * ld, dq, 1.0f, g, q < S);
+  for (int ks = 0; ks < KS; ++ks) {
+    kf[ks] = lfrag_row<HE>(lk, 16 * wv, ks, lane);
+    vf[ks] = lfrag_row<HE>(lv, 16 * wv, ks, lane);
   }
-  // ---------------- phase B: S orientation (lane = key) -> dK, dV ---------------------
-  {
-    const int kt = wv;
-    const int key = 16 * kt + li;
-    bf16x8 kf[KS], vf[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      kf[ks] = lfrag_row<HE>(lk, 16 * kt, ks, lane);
-      vf[ks] = lfrag_row<HE>(lv, 16 * kt, ks, lane);
-    }
-    f32x4 pr[NT], ds[NT];
-    const float kn = L2 ? kn_l[key] : 0.f;
-    float wsum = 0.f;  // L2: sum_q W[q,key]
-#pragma unroll
-    for (int qt = 0; qt < NT; ++qt) {
-      f32x4 s = zero, dp = zero;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        s = score_mfma<FP8>(lfrag_row<HE>(lq, 16 * qt, ks, lane), kf[ks], s);
-        dp = vg_mfma(lfrag_row<HE>(ldo, 16 * qt, ks, lane), vf[ks], dp);
-      }
-      const f32x4 lq4 = *(const f32x4*)(ll + 16 * qt + 4 * g);
-      const f32x4 dl4 = *(const f32x4*)(dl + 16 * qt + 4 * g);
-      f32x4 qn4 = zero;
-      if (L2) qn4 = *(const f32x4*)(qn_l + 16 * qt + 4 * g);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int q = 16 * qt + 4 * g + r;
-        const bool ok = (q < S) && (key < S);
-        const float raw = L2 ? l2_dist(s[r], qn4[r], kn) : s[r];
-        const float p = ok ? __expf(raw * scale - lq4[r]) : 0.f;
-        pr[qt][r] = p;
-        float dsv = p * (dp[r] - dl4[r]) * scale;
-        if (L2) { dsv = raw > 0.f ? dsv / raw : 0.f; wsum += dsv; }  // d dist/dk = (k - q)/dist
-        ds[qt][r] = dsv;
-      }
-    }
-    if (L2) wsum = group_sum(wsum);
-    f32x4 dv[DT], dk[DT];
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) { dv[dt] = zero; dk[dt] = zero; }
-#pragma unroll
-    for (int u = 0; u < KP; ++u) {
-      const int hi = (2 * u + 1 < NT) ? 2 * u + 1 : 0;
-      const bf16x8 pf = pack_pair(pr[2 * u], (2 * u + 1 < NT) ? pr[hi] : zero);
-      const bf16x8 dsf = pack_pair(ds[2 * u], (2 * u + 1 < NT) ? ds[hi] : zero);
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        dv[dt] = vg_mfma(lfrag_tr<HE>(ldo, u, 16 * dt, lane), pf, dv[dt]);
-        dk[dt] = vg_mfma(lfrag_tr<HE>(lq, u, 16 * dt, lane), dsf, dk[dt]);
-      }
-    }
-    if (L2) {  // dK = colsum(W) k - W^T Q
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        const bf16x4 kv = *(const bf16x4*)(lk + lds_off<HE>(key, 16 * dt + 4 * g));
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dk[dt][r] = wsum * vg_bf2f(kv[r]) - dk[dt][r];
-      }
-    }
-    bf16* rowp = dqb + (size_t)(key < S ? key : 0) * ld;
-    store_tiles<DT>(rowp + E, dk, 1.0f, g, key < S);
-    store_tiles<DT>(rowp + 2 * E, dv, 1.0f, g, key < S);
-  }
+  bwd_phase_b<HE, NT, L2, FP8>(lq, ldo, lk, kf, vf, rw, hd.in_qkv(dqkv), hd.ld, hd.E, S, scale, wv, lane);
 }
 
 // The same backward with TWO LDS images instead of four (dot-product scores, S > 32): phase A needs K and V whole and only this
@@ -337,7 +174,8 @@ __global__ __launch_bounds__(64 * NT, 2) void vg_attn_bwd_kernel(const bf16* __r
 // the phases.  37 KB instead of 74 KB of LDS per workgroup: four workgroups (20 waves) per CU instead of two, and it is the
 // co-resident workgroups that overlap one another's load / compute / store phases (the kernel is latency-bound: 4.0 TB/s of its
 // 205 MB at two workgroups per CU).  HBM bytes are unchanged (the fragment reads of the own rows hit L2 or are the first touch of
-// lines the second staging then finds there).  Arithmetic and operand values are those of vg_attn_bwd_kernel: results are bit-equal.
+// lines the second staging then finds there).  Results are bit-equal to vg_attn_bwd_kernel's because both kernels call the same two
+// phases on the same operand values (the phases produce the output tiles two at a time: 96 registers at five waves per SIMD).
 #ifndef VG_ATTN_BWD2_WPE
 #define VG_ATTN_BWD2_WPE 5  // waves per SIMD the register budget is set for: 5 = four 5-wave workgroups per CU (96 VGPRs)
 #endif
@@ -346,7 +184,7 @@ __global__ __launch_bounds__(64 * NT, VG_ATTN_BWD2_WPE) void vg_attn_bwd2_kernel
                                                                   const bf16* __restrict__ d_o, const float* __restrict__ lse,
                                                                   bf16* __restrict__ dqkv, int B, int S, int H, float scale,
                                                                   const void* __restrict__ zeros) {
-  constexpr int KS = HE / 32, DT = HE / 16, KP = (NT + 1) / 2, RP = KP * 32;
+  constexpr int KS = HE / 32, KP = (NT + 1) / 2, RP = KP * 32;
   constexpr int IMG = RP * HE * 2;
   __shared__ __attribute__((aligned(16))) unsigned char sm[2 * IMG + 2 * RP * 4];
   unsigned char* s0 = sm;        // K, then Q
@@ -357,77 +195,31 @@ __global__ __launch_bounds__(64 * NT, VG_ATTN_BWD2_WPE) void vg_attn_bwd2_kernel
   if (!attn_block(B, H, b, h)) return;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;  // wave wv owns query tile wv (phase A) / key tile wv (phase B)
   const int g = lane >> 4, li = lane & 15;
-  const int E = H * HE;
-  const size_t ld = 3 * (size_t)E;
-  const bf16* qb = qkv + (size_t)b * S * ld + h * HE;
-  const bf16* kb = qb + E;
-  const bf16* vb = qb + 2 * E;
-  const bf16* ob = o + (size_t)b * S * E + h * HE;
-  const bf16* dob = d_o + (size_t)b * S * E + h * HE;
-  const float* lb = lse + ((size_t)b * H + h) * S;
-  bf16* dqb = dqkv + (size_t)b * S * ld + h * HE;
-  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  const attn_head hd = head_view(qkv, b, h, S, H, HE);
+  const bf16* ob = hd.in_o(o);
+  const bf16* dob = hd.in_o(d_o);
+  const float* lb = hd.in_lse(lse);
+  const bwd_rows rw = {dl, ll, nullptr, nullptr};
 
-  dma_head<HE, NT>(s0, kb, ld, S, RP, zeros, wv, lane);
-  dma_head<HE, NT>(s1, vb, ld, S, RP, zeros, (wv + 1) % NT, lane);
+  dma_head<HE>(s0, hd.k, hd.ld, S, RP, zeros, wv, NT, lane);
+  dma_head<HE>(s1, hd.v, hd.ld, S, RP, zeros, (wv + 1) % NT, NT, lane);
   bf16x8 qf[KS], dof[KS];
   {
     bf16x8 of[KS];  // this wave's 16 query rows of O, Q, dO straight from global
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      of[ks] = gfrag(ob, (size_t)E, 16 * wv, ks, S, lane);
-      dof[ks] = gfrag(dob, (size_t)E, 16 * wv, ks, S, lane);
-      qf[ks] = gfrag(qb, ld, 16 * wv, ks, S, lane);
+      of[ks] = gfrag(ob, (size_t)hd.E, 16 * wv, ks, S, lane);
+      dof[ks] = gfrag(dob, (size_t)hd.E, 16 * wv, ks, S, lane);
+      qf[ks] = gfrag(hd.q, hd.ld, 16 * wv, ks, S, lane);
     }
     for (int i = tid; i < RP; i += 64 * NT) ll[i] = (i < S) ? lb[i] : 0.f;
-    float dpart = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) dpart += vg_bf2f(dof[ks][j]) * vg_bf2f(of[ks][j]);
-    }
-    const float delta = group_sum(dpart);
+    const float delta = row_delta<KS>(dof, of);
     if (g == 0) dl[16 * wv + li] = delta;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
-  // ---------------- phase A: S^T orientation (lane = query) -> dQ ----------------------
-  {
-    const int q = 16 * wv + li;
-    const float delta = dl[q];
-    const float lse_q = ll[q];
-    f32x4 ds[NT];
-#pragma unroll
-    for (int kt = 0; kt < NT; ++kt) {
-      f32x4 st = zero, dpt = zero;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        st = score_mfma<FP8>(lfrag_row<HE>(s0, 16 * kt, ks, lane), qf[ks], st);
-        dpt = vg_mfma(lfrag_row<HE>(s1, 16 * kt, ks, lane), dof[ks], dpt);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int key = 16 * kt + 4 * g + r;
-        const float p = (key < S && q < S) ? __expf(st[r] * scale - lse_q) : 0.f;
-        ds[kt][r] = p * (dpt[r] - delta) * scale;
-      }
-    }
-    bf16x8 dsf[KP];
-#pragma unroll
-    for (int u = 0; u < KP; ++u) dsf[u] = pack_pair(ds[2 * u], (2 * u + 1 < NT) ? ds[(2 * u + 1 < NT) ? 2 * u + 1 : 0] : zero);
-    bf16* rowq = dqb + (size_t)(q < S ? q : 0) * ld;
-#pragma unroll
-    for (int pp = 0; pp < DT / 2; ++pp) {  // two head-dim tiles (32 columns = one 16-byte store per lane) at a time: registers
-      f32x4 dq[2] = {zero, zero};
-#pragma unroll
-      for (int u = 0; u < KP; ++u) {
-        dq[0] = vg_mfma(lfrag_tr<HE>(s0, u, 32 * pp, lane), dsf[u], dq[0]);
-        dq[1] = vg_mfma(lfrag_tr<HE>(s0, u, 32 * pp + 16, lane), dsf[u], dq[1]);
-      }
-      store_tiles<2>(rowq + 32 * pp, dq, 1.0f, g, q < S);
-    }
-  }
+  bwd_phase_a<HE, NT, false, FP8>(s0, s1, nullptr, qf, dof, rw, hd.in_qkv(dqkv), hd.ld, S, scale, wv, lane);
   // this wave's key tile for phase B, before Q and dO take the images over
   bf16x8 kf[KS], vf[KS];
 #pragma unroll
@@ -436,55 +228,11 @@ __global__ __launch_bounds__(64 * NT, VG_ATTN_BWD2_WPE) void vg_attn_bwd2_kernel
     vf[ks] = lfrag_row<HE>(s1, 16 * wv, ks, lane);
   }
   __syncthreads();  // (waits for the LDS reads above: every wave is done with K and V)
-  dma_head<HE, NT>(s0, qb, ld, S, RP, zeros, wv, lane);
-  dma_head<HE, NT>(s1, dob, (size_t)E, S, RP, zeros, (wv + 1) % NT, lane);
+  dma_head<HE>(s0, hd.q, hd.ld, S, RP, zeros, wv, NT, lane);
+  dma_head<HE>(s1, dob, (size_t)hd.E, S, RP, zeros, (wv + 1) % NT, NT, lane);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  // ---------------- phase B: S orientation (lane = key) -> dK, dV ---------------------
-  {
-    const int key = 16 * wv + li;
-    f32x4 pr[NT], ds[NT];
-#pragma unroll
-    for (int qt = 0; qt < NT; ++qt) {
-      f32x4 s = zero, dp = zero;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        s = score_mfma<FP8>(lfrag_row<HE>(s0, 16 * qt, ks, lane), kf[ks], s);
-        dp = vg_mfma(lfrag_row<HE>(s1, 16 * qt, ks, lane), vf[ks], dp);
-      }
-      const f32x4 lq4 = *(const f32x4*)(ll + 16 * qt + 4 * g);
-      const f32x4 dl4 = *(const f32x4*)(dl + 16 * qt + 4 * g);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int q = 16 * qt + 4 * g + r;
-        const float p = ((q < S) && (key < S)) ? __expf(s[r] * scale - lq4[r]) : 0.f;
-        pr[qt][r] = p;
-        ds[qt][r] = p * (dp[r] - dl4[r]) * scale;
-      }
-    }
-    bf16x8 pf[KP], dsf[KP];
-#pragma unroll
-    for (int u = 0; u < KP; ++u) {
-      const int hi = (2 * u + 1 < NT) ? 2 * u + 1 : 0;
-      pf[u] = pack_pair(pr[2 * u], (2 * u + 1 < NT) ? pr[hi] : zero);
-      dsf[u] = pack_pair(ds[2 * u], (2 * u + 1 < NT) ? ds[hi] : zero);
-    }
-    bf16* rowp = dqb + (size_t)(key < S ? key : 0) * ld;
-#pragma unroll
-    for (int pp = 0; pp < DT / 2; ++pp) {
-      f32x4 dv[2] = {zero, zero}, dk[2] = {zero, zero};
-#pragma unroll
-      for (int u = 0; u < KP; ++u) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          dv[t] = vg_mfma(lfrag_tr<HE>(s1, u, 32 * pp + 16 * t, lane), pf[u], dv[t]);
-          dk[t] = vg_mfma(lfrag_tr<HE>(s0, u, 32 * pp + 16 * t, lane), dsf[u], dk[t]);
-        }
-      }
-      store_tiles<2>(rowp + E + 32 * pp, dk, 1.0f, g, key < S);
-      store_tiles<2>(rowp + 2 * E + 32 * pp, dv, 1.0f, g, key < S);
-    }
-  }
+  bwd_phase_b<HE, NT, false, FP8>(s0, s1, nullptr, kf, vf, rw, hd.in_qkv(dqkv), hd.ld, hd.E, S, scale, wv, lane);
 }
 
 // ---- the backward OF the attention backward (gradient penalty, src/v2/utils.py:124-144) on the MFMA pipe -------------------
@@ -520,6 +268,9 @@ __global__ __launch_bounds__(320, 2) void vg_attn_bwd_bwd2_kernel(const bf16* __
   if (!attn_block(B, H, b, h)) return;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int g = lane >> 4, li = lane & 15;
+  // The head's bases are spelled out here instead of taken from head_view (vg_attn.h), on measurement: with the view the scalar
+  // preamble comes out a few instructions different and every launch at the hot shape 0.3 - 0.8 us (of 123) longer, in every order of
+  // the libraries; with this text the instruction stream is the one it had before the shared header (profiles/attn_shared_phases.txt).
   const int E = H * HE;
   const size_t ld = 3 * (size_t)E;
   const bf16* qb = qkv + (size_t)b * S * ld + h * HE;
@@ -534,10 +285,10 @@ __global__ __launch_bounds__(320, 2) void vg_attn_bwd_bwd2_kernel(const bf16* __
   bf16* dqb = d_qkv + (size_t)b * S * ld + h * HE;
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 
-  dma_head<HE, NT>(i0, kb, ld, S, RP, zeros, wv, lane);
-  dma_head<HE, NT>(i1, vb, ld, S, RP, zeros, (wv + 1) % NT, lane);
-  dma_head<HE, NT>(i2, ukb, ld, S, RP, zeros, (wv + 2) % NT, lane);
-  dma_head<HE, NT>(i3, uvb, ld, S, RP, zeros, (wv + 3) % NT, lane);
+  dma_head<HE>(i0, kb, ld, S, RP, zeros, wv, NT, lane);
+  dma_head<HE>(i1, vb, ld, S, RP, zeros, (wv + 1) % NT, NT, lane);
+  dma_head<HE>(i2, ukb, ld, S, RP, zeros, (wv + 2) % NT, NT, lane);
+  dma_head<HE>(i3, uvb, ld, S, RP, zeros, (wv + 3) % NT, NT, lane);
   bf16x8 qf[KS], dof[KS], uqf[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
@@ -604,13 +355,11 @@ __global__ __launch_bounds__(320, 2) void vg_attn_bwd_bwd2_kernel(const bf16* __
       }
     bf16x8 pf[KP], hf[KP], dsf[KP], sgf[KP];
 #pragma unroll
-    for (int u = 0; u < KP; ++u) {
-      const bool two = 2 * u + 1 < NT;
-      const int hi = two ? 2 * u + 1 : 0;
-      pf[u] = pack_pair(Pm[2 * u], two ? Pm[hi] : zero);
-      hf[u] = pack_pair(Gm[2 * u], two ? Gm[hi] : zero);
-      dsf[u] = pack_pair(Dm[2 * u], two ? Dm[hi] : zero);
-      sgf[u] = pack_pair(Tm[2 * u], two ? Tm[hi] : zero);
+    for (int u = 0; u < KP; ++u) {  // pair by pair over the four sets: packing set after set costs 17 packed float operations and 0.5 us
+      pf[u] = pack_tiles_at<NT>(Pm, u);
+      hf[u] = pack_tiles_at<NT>(Gm, u);
+      dsf[u] = pack_tiles_at<NT>(Dm, u);
+      sgf[u] = pack_tiles_at<NT>(Tm, u);
     }
     bf16* rowo = ddob + (size_t)(q < S ? q : 0) * E;
     bf16* rowq = dqb + (size_t)(q < S ? q : 0) * ld;
@@ -641,9 +390,9 @@ __global__ __launch_bounds__(320, 2) void vg_attn_bwd_bwd2_kernel(const bf16* __
     uvf[ks] = lfrag_row<HE>(i3, 16 * wv, ks, lane);
   }
   __syncthreads();  // every wave is done with K, V, uK, uV (and delta / gam / pi of every query are in LDS)
-  dma_head<HE, NT>(i0, qb, ld, S, RP, zeros, wv, lane);
-  dma_head<HE, NT>(i1, dob, (size_t)E, S, RP, zeros, (wv + 1) % NT, lane);
-  dma_head<HE, NT>(i2, uqb, ld, S, RP, zeros, (wv + 2) % NT, lane);
+  dma_head<HE>(i0, qb, ld, S, RP, zeros, wv, NT, lane);
+  dma_head<HE>(i1, dob, (size_t)E, S, RP, zeros, (wv + 1) % NT, NT, lane);
+  dma_head<HE>(i2, uqb, ld, S, RP, zeros, (wv + 2) % NT, NT, lane);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   // ---------------- phase B: lane = key li of tile wv; queries 16 qt + 4 g + r -------------------------------------------
@@ -681,11 +430,9 @@ __global__ __launch_bounds__(320, 2) void vg_attn_bwd_bwd2_kernel(const bf16* __
     bf16x8 hf[KP], dsf[KP], sgf[KP];
 #pragma unroll
     for (int u = 0; u < KP; ++u) {
-      const bool two = 2 * u + 1 < NT;
-      const int hi = two ? 2 * u + 1 : 0;
-      hf[u] = pack_pair(Hm[2 * u], two ? Hm[hi] : zero);
-      dsf[u] = pack_pair(Dm[2 * u], two ? Dm[hi] : zero);
-      sgf[u] = pack_pair(Sm[2 * u], two ? Sm[hi] : zero);
+      hf[u] = pack_tiles_at<NT>(Hm, u);
+      dsf[u] = pack_tiles_at<NT>(Dm, u);
+      sgf[u] = pack_tiles_at<NT>(Sm, u);
     }
     bf16* rowp = dqb + (size_t)(key < S ? key : 0) * ld;
 #pragma unroll
@@ -706,8 +453,9 @@ __global__ __launch_bounds__(320, 2) void vg_attn_bwd_bwd2_kernel(const bf16* __
   }
 }
 
+// the 16-byte zero page every LDS-DMA staging reads its padded rows from (attention_long.hip's too); null if it cannot be resolved
 __device__ __attribute__((aligned(16))) unsigned int vg_attn_zero_page[4] = {0u, 0u, 0u, 0u};
-static const void* attn_zeros() {
+const void* vg_attn_zeros() {
   static void* zp = nullptr;  // one device per process
   if (!zp && hipGetSymbolAddress(&zp, HIP_SYMBOL(vg_attn_zero_page)) != hipSuccess) zp = nullptr;
   return zp;
@@ -715,7 +463,7 @@ static const void* attn_zeros() {
 
 template <int HE, int NT, int MODE>  // MODE: 0 dot-product bf16, 1 L2-distance scores, 2 dot-product with fp8 activation products
 static int launch_fwd(const bf16* qkv, bf16* o, float* lse, int B, int H, int S, float scale, hipStream_t st) {
-  const void* z = attn_zeros();
+  const void* z = vg_attn_zeros();
   if (!z) return -5;
   hipLaunchKernelGGL((vg_attn_fwd_kernel<HE, NT, MODE == 1, MODE == 2>), dim3(attn_grid(B, H)), dim3(64 * NT), 0, st, qkv, o, lse, B, S, H, scale, z);
   return (int)hipGetLastError();
@@ -723,15 +471,17 @@ static int launch_fwd(const bf16* qkv, bf16* o, float* lse, int B, int H, int S,
 template <int HE, int NT, int MODE>
 static int launch_bwd(const bf16* qkv, const bf16* o, const bf16* d_o, const float* lse, bf16* dqkv, int B, int H,
                       int S, float scale, hipStream_t st) {
-  const void* z = attn_zeros();
+  const void* z = vg_attn_zeros();
   if (!z) return -5;
 #ifndef VG_ATTN_BWD_4IMG  // A/B builds (make var DEFS=-DVG_ATTN_BWD_4IMG): the four-image kernel everywhere
-  if constexpr (MODE != 1 && NT == 5) {
-    hipLaunchKernelGGL((vg_attn_bwd2_kernel<HE, NT, MODE == 2>), dim3(attn_grid(B, H)), dim3(64 * NT), 0, st, qkv, o, d_o, lse, dqkv, B, S, H, scale, z);
-    return (int)hipGetLastError();
-  }
+  constexpr bool two_images = MODE != 1 && NT == 5;
+#else
+  constexpr bool two_images = false;
 #endif
-  hipLaunchKernelGGL((vg_attn_bwd_kernel<HE, NT, MODE == 1, MODE == 2>), dim3(attn_grid(B, H)), dim3(64 * NT), 0, st, qkv, o, d_o, lse, dqkv, B, S, H, scale, z);
+  if constexpr (two_images)  // only the kernel that is launched is instantiated
+    hipLaunchKernelGGL((vg_attn_bwd2_kernel<HE, NT, MODE == 2>), dim3(attn_grid(B, H)), dim3(64 * NT), 0, st, qkv, o, d_o, lse, dqkv, B, S, H, scale, z);
+  else
+    hipLaunchKernelGGL((vg_attn_bwd_kernel<HE, NT, MODE == 1, MODE == 2>), dim3(attn_grid(B, H)), dim3(64 * NT), 0, st, qkv, o, d_o, lse, dqkv, B, S, H, scale, z);
   return (int)hipGetLastError();
 }
 
@@ -750,10 +500,10 @@ static int launch_bwd(const bf16* qkv, const bf16* o, const bf16* d_o, const flo
     if (S < 1 || S > 80 || B < 1 || H < 1) return -2;                  \
     if (mode < 0 || mode > 2) return -4;                               \
     const bool small = (S <= 32);                                      \
-    if (HE == 96) VG_ATTN_BY_MODE(FN, 96, __VA_ARGS__);                \
-    if (HE == 64) VG_ATTN_BY_MODE(FN, 64, __VA_ARGS__);                \
-    if (HE == 32) VG_ATTN_BY_MODE(FN, 32, __VA_ARGS__);                \
-    return -3;                                                         \
+    return attn_by_head_dim(HE, [&](auto he) -> int {                  \
+      constexpr int HE_ = decltype(he)::value;                         \
+      VG_ATTN_BY_MODE(FN, HE_, __VA_ARGS__);                           \
+    });                                                                \
   } while (0)
 // 80 < S <= VG_ATTN_LONG_MAX_S with dot-product scores (mode 0): the streaming kernels of attention_long.hip; modes 1 and 2 stay S <= 80.
 int vg_attn_fwd_launch(const bf16* qkv, bf16* o, float* lse, int B, int H, int S, int HE, float scale, int mode, hipStream_t st) {
@@ -790,11 +540,10 @@ __global__ __launch_bounds__(64) void vg_attn_cls_fwd_kernel(const bf16* __restr
   const int lane = threadIdx.x;
   const int rr = lane / CPR, c = lane - rr * CPR;
   const bool act = rr < RPI;
-  const int E = H * HE;
-  const size_t ld = 3 * (size_t)E;
-  const bf16* qb = qkv + (size_t)b * S * ld + h * HE;
-  const bf16* kb = qb + E;
-  const bf16* vb = qb + 2 * E;
+  const attn_head hd = head_view(qkv, b, h, S, H, HE);
+  const int E = hd.E;
+  const size_t ld = hd.ld;
+  const bf16 *qb = hd.q, *kb = hd.k, *vb = hd.v;
   for (int d = lane; d < HE; d += 64) q0l[d] = vg_bf2f(qb[d]);
   __syncthreads();
   float qc[8];
@@ -872,12 +621,11 @@ __global__ __launch_bounds__(64) void vg_attn_cls_bwd_kernel(const bf16* __restr
   const int lane = threadIdx.x;
   const int rr = lane / CPR, c = lane - rr * CPR;
   const bool act = rr < RPI;
-  const int E = H * HE;
-  const size_t ld = 3 * (size_t)E;
-  const bf16* qb = qkv + (size_t)b * S * ld + h * HE;
-  const bf16* kb = qb + E;
-  const bf16* vb = qb + 2 * E;
-  bf16* dqb = dqkv + (size_t)b * S * ld + h * HE;
+  const attn_head hd = head_view(qkv, b, h, S, H, HE);
+  const int E = hd.E;
+  const size_t ld = hd.ld;
+  const bf16 *qb = hd.q, *kb = hd.k, *vb = hd.v;
+  bf16* dqb = hd.in_qkv(dqkv);
   const float lse0 = lse_cls[(size_t)b * H + h];
   float dpart = 0.f;  // delta = sum_d dO_0[d] O_0[d]
   for (int d = lane; d < HE; d += 64) {
@@ -958,32 +706,34 @@ __global__ __launch_bounds__(64) void vg_attn_cls_bwd_kernel(const bf16* __restr
 // 128-key instance (half the LDS of the 256-key one: twice the workgroups per CU), 128 < S <= VG_ATTN_LONG_MAX_S the 256-key one.
 int vg_attn_cls_fwd_launch(const bf16* qkv, bf16* o_cls, float* lse_cls, int B, int H, int S, int HE, float scale, hipStream_t st) {
   if (S < 1 || S > VG_ATTN_LONG_MAX_S || B < 1 || H < 1) return -2;
-#define VG_ACLS(HE_, K_) hipLaunchKernelGGL((vg_attn_cls_fwd_kernel<HE_, K_>), dim3(attn_grid(B, H)), dim3(64), 0, st, qkv, o_cls, lse_cls, B, S, H, scale)
-#define VG_ACLS_K(K_) if (HE == 96) VG_ACLS(96, K_); else if (HE == 64) VG_ACLS(64, K_); else if (HE == 32) VG_ACLS(32, K_); else return -3
-  if (S <= 128) { VG_ACLS_K(128); } else { VG_ACLS_K(256); }
-#undef VG_ACLS_K
-#undef VG_ACLS
-  return (int)hipGetLastError();
+  return attn_by_head_dim(HE, [&](auto he) {
+    constexpr int HE_ = decltype(he)::value;
+    const dim3 grid(attn_grid(B, H));
+    if (S <= 128) hipLaunchKernelGGL((vg_attn_cls_fwd_kernel<HE_, 128>), grid, dim3(64), 0, st, qkv, o_cls, lse_cls, B, S, H, scale);
+    else hipLaunchKernelGGL((vg_attn_cls_fwd_kernel<HE_, 256>), grid, dim3(64), 0, st, qkv, o_cls, lse_cls, B, S, H, scale);
+    return (int)hipGetLastError();
+  });
 }
 int vg_attn_cls_bwd_launch(const bf16* qkv, const bf16* o_cls, const bf16* do_cls, const float* lse_cls, bf16* dqkv, int B, int H, int S, int HE,
                            float scale, hipStream_t st) {
   if (S < 1 || S > VG_ATTN_LONG_MAX_S || B < 1 || H < 1) return -2;
-#define VG_ACLS(HE_, K_) hipLaunchKernelGGL((vg_attn_cls_bwd_kernel<HE_, K_>), dim3(attn_grid(B, H)), dim3(64), 0, st, qkv, o_cls, do_cls, lse_cls, dqkv, B, S, H, scale)
-#define VG_ACLS_K(K_) if (HE == 96) VG_ACLS(96, K_); else if (HE == 64) VG_ACLS(64, K_); else if (HE == 32) VG_ACLS(32, K_); else return -3
-  if (S <= 128) { VG_ACLS_K(128); } else { VG_ACLS_K(256); }
-#undef VG_ACLS_K
-#undef VG_ACLS
-  return (int)hipGetLastError();
+  return attn_by_head_dim(HE, [&](auto he) {
+    constexpr int HE_ = decltype(he)::value;
+    const dim3 grid(attn_grid(B, H));
+    if (S <= 128) hipLaunchKernelGGL((vg_attn_cls_bwd_kernel<HE_, 128>), grid, dim3(64), 0, st, qkv, o_cls, do_cls, lse_cls, dqkv, B, S, H, scale);
+    else hipLaunchKernelGGL((vg_attn_cls_bwd_kernel<HE_, 256>), grid, dim3(64), 0, st, qkv, o_cls, do_cls, lse_cls, dqkv, B, S, H, scale);
+    return (int)hipGetLastError();
+  });
 }
 
 // the second-order kernel above (S <= 80: padded to five 16-row tiles); -3: head dim not 32 / 64 / 96
 int vg_attn_bwd_bwd_mfma_launch(const bf16* qkv, const bf16* d_o, const float* lse, const bf16* uqkv, bf16* d_do, bf16* d_qkv, int B, int H,
                                 int S, int HE, float scale, hipStream_t st) {
   if (S < 1 || S > 80 || B < 1 || H < 1) return -2;
-  const void* z = attn_zeros();
+  const void* z = vg_attn_zeros();
   if (!z) return -5;
-#define VG_ABB2(HE_) hipLaunchKernelGGL((vg_attn_bwd_bwd2_kernel<HE_>), dim3(attn_grid(B, H)), dim3(320), 0, st, qkv, d_o, lse, uqkv, d_do, d_qkv, B, S, H, scale, z)
-  if (HE == 96) VG_ABB2(96); else if (HE == 64) VG_ABB2(64); else if (HE == 32) VG_ABB2(32); else return -3;
-#undef VG_ABB2
-  return (int)hipGetLastError();
+  return attn_by_head_dim(HE, [&](auto he) {
+    hipLaunchKernelGGL((vg_attn_bwd_bwd2_kernel<decltype(he)::value>), dim3(attn_grid(B, H)), dim3(320), 0, st, qkv, d_o, lse, uqkv, d_do, d_qkv, B, S, H, scale, z);
+    return (int)hipGetLastError();
+  });
 }

@@ -19,21 +19,6 @@
 
 #define VG_ATTN_LONG_WAVES 8  // at most; 512 threads, so the register budget is 256 per lane
 
-// rows [0, rows_alloc) x HE of one head into an LDS image: dma_head (vg_attn.h) with the wave count known at run time only
-template <int HE>
-__device__ __forceinline__ void dma_rows(unsigned char* img, const bf16* __restrict__ src, size_t ld, int S, int rows_alloc, const void* zeros,
-                                         int wave, int nw, int lane) {
-  constexpr int CPR = HE / 8;
-  const int pieces = rows_alloc * CPR / 64;  // rows_alloc is a multiple of 32: whole 1-KiB pieces at every head dim
-  for (int pc = wave; pc < pieces; pc += nw) {
-    const int ci = 64 * pc + lane;
-    const int r = ci / CPR, cp = ci - r * CPR;
-    const int c = swz_chunk<HE>(r, cp);
-    const void* p = (r < S) ? (const void*)(src + (size_t)r * ld + 8 * c) : zeros;
-    __builtin_amdgcn_global_load_lds((gptr_t)p, (lptr_t)(img + 1024 * pc), 16, 0, 0);
-  }
-}
-
 template <int HE>
 __global__ __launch_bounds__(64 * VG_ATTN_LONG_WAVES) void vg_attn_long_fwd_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ o,
                                                                                    float* __restrict__ lse, int B, int S, int H, float scale,
@@ -47,22 +32,18 @@ __global__ __launch_bounds__(64 * VG_ATTN_LONG_WAVES) void vg_attn_long_fwd_kern
   if (!attn_block(B, H, b, h)) return;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = blockDim.x >> 6;
   const int g = lane >> 4, li = lane & 15;
-  const int E = H * HE;
-  const size_t ld = 3 * (size_t)E;
-  const bf16* qb = qkv + (size_t)b * S * ld + h * HE;
-  const bf16* kb = qb + E;
-  const bf16* vb = qb + 2 * E;
+  const attn_head hd = head_view(qkv, b, h, S, H, HE);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 
-  dma_rows<HE>(kl, kb, ld, S, RP, zeros, wv, nw, lane);
-  dma_rows<HE>(vl, vb, ld, S, RP, zeros, wv, nw, lane);
+  dma_head<HE>(kl, hd.k, hd.ld, S, RP, zeros, wv, nw, lane);
+  dma_head<HE>(vl, hd.v, hd.ld, S, RP, zeros, wv, nw, lane);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
   for (int qt = wv; qt < NT; qt += nw) {
     bf16x8 qf[KS];  // this tile's queries straight from global (nobody else needs them)
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) qf[ks] = gfrag(qb, ld, 16 * qt, ks, S, lane);
+    for (int ks = 0; ks < KS; ++ks) qf[ks] = gfrag(hd.q, hd.ld, 16 * qt, ks, S, lane);
     const int q = 16 * qt + li;
     float m = -INFINITY;  // running max of query q (the same in its 4 lane groups)
     float l = 0.f;        // this lane's share of the running sum, in units of exp(m)
@@ -106,11 +87,13 @@ __global__ __launch_bounds__(64 * VG_ATTN_LONG_WAVES) void vg_attn_long_fwd_kern
       for (int dt = 0; dt < DT; ++dt) oa[dt] = vg_mfma(lfrag_tr<HE>(vl, u, 16 * dt, lane), pf, oa[dt] * alpha);
     }
     l = group_sum(l);
-    if (g == 0 && q < S) lse[((size_t)b * H + h) * S + q] = m + __logf(l);
-    store_tiles<DT>(o + ((size_t)b * S + (q < S ? q : 0)) * E + h * HE, oa, 1.0f / l, g, q < S);
+    if (g == 0 && q < S) lse[hd.offl + q] = m + __logf(l);
+    store_tiles<DT>(hd.o_row(o, q < S ? q : 0), oa, 1.0f / l, g, q < S);
   }
 }
 
+// The recompute tiles (bwd_tile_q / bwd_tile_k) and row_delta are those of the short backward (vg_attn.h); the loops around them
+// are this kernel's own: it streams the key (query) pairs and accumulates dQ (dK, dV) across them.
 template <int HE>
 __global__ __launch_bounds__(64 * VG_ATTN_LONG_WAVES) void vg_attn_long_bwd_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ o,
                                                                                    const bf16* __restrict__ d_o, const float* __restrict__ lse,
@@ -127,30 +110,25 @@ __global__ __launch_bounds__(64 * VG_ATTN_LONG_WAVES) void vg_attn_long_bwd_kern
   if (!attn_block(B, H, b, h)) return;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nw = blockDim.x >> 6;
   const int g = lane >> 4, li = lane & 15;
-  const int E = H * HE;
-  const size_t ld = 3 * (size_t)E;
-  const bf16* qb = qkv + (size_t)b * S * ld + h * HE;
-  const bf16* kb = qb + E;
-  const bf16* vb = qb + 2 * E;
-  const bf16* ob = o + (size_t)b * S * E + h * HE;
-  const bf16* dob = d_o + (size_t)b * S * E + h * HE;
-  const float* lb = lse + ((size_t)b * H + h) * S;
-  bf16* dqb = dqkv + (size_t)b * S * ld + h * HE;
+  const attn_head hd = head_view(qkv, b, h, S, H, HE);
+  const bf16* ob = hd.in_o(o);
+  const bf16* dob = hd.in_o(d_o);
+  const float* lb = hd.in_lse(lse);
+  bf16* dqb = hd.in_qkv(dqkv);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  float unused = 0.f;  // the L2 row sum of the tile functions: dot-product scores only here
 
-  dma_rows<HE>(s0, kb, ld, S, RP, zeros, wv, nw, lane);
-  dma_rows<HE>(s1, vb, ld, S, RP, zeros, wv, nw, lane);
+  dma_head<HE>(s0, hd.k, hd.ld, S, RP, zeros, wv, nw, lane);
+  dma_head<HE>(s1, hd.v, hd.ld, S, RP, zeros, wv, nw, lane);
   for (int i = tid; i < RP; i += 64 * nw) ll[i] = (i < S) ? lb[i] : 0.f;
   for (int t = wv; t < RP / 16; t += nw) {  // every 16-row tile of the image, the padded one included (gfrag reads zeros there)
-    float dpart = 0.f;
+    bf16x8 of[KS], df[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      const bf16x8 of = gfrag(ob, (size_t)E, 16 * t, ks, S, lane);
-      const bf16x8 df = gfrag(dob, (size_t)E, 16 * t, ks, S, lane);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) dpart += vg_bf2f(df[j]) * vg_bf2f(of[j]);
+      of[ks] = gfrag(ob, (size_t)hd.E, 16 * t, ks, S, lane);
+      df[ks] = gfrag(dob, (size_t)hd.E, 16 * t, ks, S, lane);
     }
-    const float delta = group_sum(dpart);
+    const float delta = row_delta<KS>(df, of);
     if (g == 0) dl[16 * t + li] = delta;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -161,8 +139,8 @@ __global__ __launch_bounds__(64 * VG_ATTN_LONG_WAVES) void vg_attn_long_bwd_kern
     bf16x8 qf[KS], dof[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      qf[ks] = gfrag(qb, ld, 16 * qt, ks, S, lane);
-      dof[ks] = gfrag(dob, (size_t)E, 16 * qt, ks, S, lane);
+      qf[ks] = gfrag(hd.q, hd.ld, 16 * qt, ks, S, lane);
+      dof[ks] = gfrag(dob, (size_t)hd.E, 16 * qt, ks, S, lane);
     }
     const int q = 16 * qt + li;
     const float delta = dl[q];
@@ -173,29 +151,17 @@ __global__ __launch_bounds__(64 * VG_ATTN_LONG_WAVES) void vg_attn_long_bwd_kern
     for (int u = 0; u < NPAIR; ++u) {
       f32x4 ds[2];
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        f32x4 st = zero, dpt = zero;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          st = vg_mfma(lfrag_row<HE>(s0, 32 * u + 16 * t, ks, lane), qf[ks], st);
-          dpt = vg_mfma(lfrag_row<HE>(s1, 32 * u + 16 * t, ks, lane), dof[ks], dpt);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int key = 32 * u + 16 * t + 4 * g + r;
-          const float p = (key < S && q < S) ? __expf(st[r] * scale - lse_q) : 0.f;
-          ds[t][r] = p * (dpt[r] - delta) * scale;
-        }
-      }
+      for (int t = 0; t < 2; ++t)
+        ds[t] = bwd_tile_q<HE, false, false>(s0, s1, 32 * u + 16 * t, qf, dof, lse_q, delta, 0.f, nullptr, q < S, S, scale, unused, lane);
       const bf16x8 dsf = pack_pair(ds[0], ds[1]);
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) dq[dt] = vg_mfma(lfrag_tr<HE>(s0, u, 16 * dt, lane), dsf, dq[dt]);
     }
-    store_tiles<DT>(dqb + (size_t)(q < S ? q : 0) * ld, dq, 1.0f, g, q < S);
+    store_tiles<DT>(dqb + (size_t)(q < S ? q : 0) * hd.ld, dq, 1.0f, g, q < S);
   }
   __syncthreads();  // every wave is done with K and V
-  dma_rows<HE>(s0, qb, ld, S, RP, zeros, wv, nw, lane);
-  dma_rows<HE>(s1, dob, (size_t)E, S, RP, zeros, wv, nw, lane);
+  dma_head<HE>(s0, hd.q, hd.ld, S, RP, zeros, wv, nw, lane);
+  dma_head<HE>(s1, dob, (size_t)hd.E, S, RP, zeros, wv, nw, lane);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
@@ -204,8 +170,8 @@ __global__ __launch_bounds__(64 * VG_ATTN_LONG_WAVES) void vg_attn_long_bwd_kern
     bf16x8 kf[KS], vf[KS];  // this tile's keys straight from global (L2: phase A's staging read the same rows)
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      kf[ks] = gfrag(kb, ld, 16 * kt, ks, S, lane);
-      vf[ks] = gfrag(vb, ld, 16 * kt, ks, S, lane);
+      kf[ks] = gfrag(hd.k, hd.ld, 16 * kt, ks, S, lane);
+      vf[ks] = gfrag(hd.v, hd.ld, 16 * kt, ks, S, lane);
     }
     const int key = 16 * kt + li;
     f32x4 dk[DT], dv[DT];
@@ -214,24 +180,8 @@ __global__ __launch_bounds__(64 * VG_ATTN_LONG_WAVES) void vg_attn_long_bwd_kern
     for (int u = 0; u < NPAIR; ++u) {
       f32x4 pr[2], ds[2];
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const int qt = 2 * u + t;
-        f32x4 s = zero, dp = zero;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          s = vg_mfma(lfrag_row<HE>(s0, 16 * qt, ks, lane), kf[ks], s);
-          dp = vg_mfma(lfrag_row<HE>(s1, 16 * qt, ks, lane), vf[ks], dp);
-        }
-        const f32x4 lq4 = *(const f32x4*)(ll + 16 * qt + 4 * g);
-        const f32x4 dl4 = *(const f32x4*)(dl + 16 * qt + 4 * g);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int q = 16 * qt + 4 * g + r;
-          const float p = ((q < S) && (key < S)) ? __expf(s[r] * scale - lq4[r]) : 0.f;
-          pr[t][r] = p;
-          ds[t][r] = p * (dp[r] - dl4[r]) * scale;
-        }
-      }
+      for (int t = 0; t < 2; ++t)
+        bwd_tile_k<HE, false, false>(s0, s1, 32 * u + 16 * t, kf, vf, ll, dl, nullptr, 0.f, key < S, S, scale, unused, lane, pr[t], ds[t]);
       const bf16x8 pf = pack_pair(pr[0], pr[1]);
       const bf16x8 dsf = pack_pair(ds[0], ds[1]);
 #pragma unroll
@@ -240,18 +190,12 @@ __global__ __launch_bounds__(64 * VG_ATTN_LONG_WAVES) void vg_attn_long_bwd_kern
         dk[dt] = vg_mfma(lfrag_tr<HE>(s0, u, 16 * dt, lane), dsf, dk[dt]);
       }
     }
-    bf16* rowp = dqb + (size_t)(key < S ? key : 0) * ld;
-    store_tiles<DT>(rowp + E, dk, 1.0f, g, key < S);
-    store_tiles<DT>(rowp + 2 * E, dv, 1.0f, g, key < S);
+    bf16* rowp = dqb + (size_t)(key < S ? key : 0) * hd.ld;
+    store_tiles<DT>(rowp + hd.E, dk, 1.0f, g, key < S);
+    store_tiles<DT>(rowp + 2 * hd.E, dv, 1.0f, g, key < S);
   }
 }
 
-__device__ __attribute__((aligned(16))) unsigned int vg_attn_long_zero_page[4] = {0u, 0u, 0u, 0u};
-static const void* long_zeros() {
-  static void* zp = nullptr;  // one device per process
-  if (!zp && hipGetSymbolAddress(&zp, HIP_SYMBOL(vg_attn_long_zero_page)) != hipSuccess) zp = nullptr;
-  return zp;
-}
 static inline int long_rows(int S) { return (S + 31) & ~31; }
 static inline int long_waves(int S) { const int nt = (S + 15) / 16; return nt < VG_ATTN_LONG_WAVES ? nt : VG_ATTN_LONG_WAVES; }
 static inline size_t long_fwd_lds(int S, int HE) { return (size_t)2 * long_rows(S) * HE * 2; }
@@ -261,7 +205,7 @@ static int long_allow_lds(const void* fn, size_t bytes) { return (int)hipFuncSet
 
 template <int HE>
 static int launch_long_fwd(const bf16* qkv, bf16* o, float* lse, int B, int H, int S, float scale, hipStream_t st) {
-  const void* z = long_zeros();
+  const void* z = vg_attn_zeros();
   if (!z) return -5;
   static const int lim = long_allow_lds((const void*)vg_attn_long_fwd_kernel<HE>, long_fwd_lds(VG_ATTN_LONG_MAX_S, HE));
   if (lim) return lim;
@@ -272,7 +216,7 @@ static int launch_long_fwd(const bf16* qkv, bf16* o, float* lse, int B, int H, i
 template <int HE>
 static int launch_long_bwd(const bf16* qkv, const bf16* o, const bf16* d_o, const float* lse, bf16* dqkv, int B, int H, int S, float scale,
                            hipStream_t st) {
-  const void* z = long_zeros();
+  const void* z = vg_attn_zeros();
   if (!z) return -5;
   static const int lim = long_allow_lds((const void*)vg_attn_long_bwd_kernel<HE>, long_bwd_lds(VG_ATTN_LONG_MAX_S, HE));
   if (lim) return lim;
@@ -285,16 +229,10 @@ static int launch_long_bwd(const bf16* qkv, const bf16* o, const bf16* d_o, cons
 // correct for any 1 <= S <= VG_ATTN_LONG_MAX_S.  -2: shape out of range, -3: head dim not 32 / 64 / 96.
 int vg_attn_long_fwd_launch(const bf16* qkv, bf16* o, float* lse, int B, int H, int S, int HE, float scale, hipStream_t st) {
   if (S < 1 || S > VG_ATTN_LONG_MAX_S || B < 1 || H < 1) return -2;
-  if (HE == 96) return launch_long_fwd<96>(qkv, o, lse, B, H, S, scale, st);
-  if (HE == 64) return launch_long_fwd<64>(qkv, o, lse, B, H, S, scale, st);
-  if (HE == 32) return launch_long_fwd<32>(qkv, o, lse, B, H, S, scale, st);
-  return -3;
+  return attn_by_head_dim(HE, [&](auto he) { return launch_long_fwd<decltype(he)::value>(qkv, o, lse, B, H, S, scale, st); });
 }
 int vg_attn_long_bwd_launch(const bf16* qkv, const bf16* o, const bf16* d_o, const float* lse, bf16* dqkv, int B, int H, int S, int HE,
                             float scale, hipStream_t st) {
   if (S < 1 || S > VG_ATTN_LONG_MAX_S || B < 1 || H < 1) return -2;
-  if (HE == 96) return launch_long_bwd<96>(qkv, o, d_o, lse, dqkv, B, H, S, scale, st);
-  if (HE == 64) return launch_long_bwd<64>(qkv, o, d_o, lse, dqkv, B, H, S, scale, st);
-  if (HE == 32) return launch_long_bwd<32>(qkv, o, d_o, lse, dqkv, B, H, S, scale, st);
-  return -3;
+  return attn_by_head_dim(HE, [&](auto he) { return launch_long_bwd<decltype(he)::value>(qkv, o, d_o, lse, dqkv, B, H, S, scale, st); });
 }

@@ -4,6 +4,8 @@
 // (the backward of dX = dY W is d(dY) = ddX W^T and dW = dY^T ddX).  They serve the penalty term only - a few launches per
 // step beside the fused passes - so the elementwise ones are written for clarity and determinism (fp32 math, no atomics); the
 // attention double backward, which was 18 % of the penalty step as fp32 FMA loops, runs on the MFMA pipe since round 3 (attention.hip).
+// Its comparison is the fp64 reference test (tests/test_second_order_gpu.py, every S from 1 to 80); the fp32 FMA form that used to
+// stay here behind a build flag lives in history, last at commit de5f7cd.
 #include "vg_common.h"
 // the MFMA form of the attention double backward lives with the attention kernels (attention.hip)
 int vg_attn_bwd_bwd_mfma_launch(const bf16* qkv, const bf16* d_o, const float* lse, const bf16* uqkv, bf16* d_do, bf16* d_qkv, int B, int H,
@@ -141,128 +143,11 @@ int vg_ln_bwd_bwd_launch(const bf16* u, const bf16* dy, const bf16* x, const flo
   return (int)hipGetLastError();
 }
 
-#ifdef VG_ABB_FMA
-// ---------------------------------------------------------------------------------------------------------------------
-// Attention backward's backward, round 2's form (A/B builds only: make var SRC=second_order DEFS=-DVG_ABB_FMA; the product runs
-// vg_attn_bwd_bwd2_kernel of attention.hip, 18 x faster, same formulas).  One workgroup per (image, head).  Forward: P = softmax(s Q K^T), O = P V.  Backward:
-//   dV = P^T dO ; dP = dO V^T ; delta_i = sum_j P_ij dP_ij ; dS = P (dP - delta) ; dQ = s dS K ; dK = s dS^T Q.
-// Given (uQ, uK, uV) = dL/d(dQ, dK, dV):
-//   G = s (uQ K^T + Q uK^T) ; gam_i = sum_j G_ij P_ij ; H = P (G - gam)                       [dL/d dP]
-//   Pi = dO uV^T + G (dP - delta) - gam dP ; pi_i = sum_j P_ij Pi_ij ; Sg = P (Pi - pi)       [dL/d S]
-//   d(dO) = P uV + H V ;  d(Q) = s (dS uK + Sg K) ;  d(K) = s (dS^T uQ + Sg^T Q) ;  d(V) = H^T dO.
-// LDS: the seven [S x HE] operands as bf16 (what they are in HBM) and four S x S matrices (P, A = dP - delta, G then Pi, H)
-// as fp32: 155 KB for S = 65, HE = 96 - one workgroup per CU.  Plain FMA loops (see the file header).
-template <int HE>
-__global__ __launch_bounds__(256) void vg_attn_bwd_bwd_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ d_o, const float* __restrict__ lse,
-                                                              const bf16* __restrict__ uqkv, bf16* __restrict__ d_do, bf16* __restrict__ d_qkv,
-                                                              int S, int H, float scale) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem2[];
-  const int SP = S;  // rows
-  bf16* Q = (bf16*)smem2; bf16* K = Q + SP * HE; bf16* V = K + SP * HE; bf16* DO = V + SP * HE;
-  bf16* UQ = DO + SP * HE; bf16* UK = UQ + SP * HE; bf16* UV = UK + SP * HE;
-  float* P = (float*)(UV + SP * HE);        // [S][S]
-  float* A = P + S * S;                     // dP, then dP - delta
-  float* G = A + S * S;                     // G, then Pi
-  float* Hm = G + S * S;                    // H
-  float* dl = Hm + S * S;                   // delta[S], later pi[S]
-  float* gm = dl + S;                       // gam[S]
-  const int b = blockIdx.x / H, h = blockIdx.x - b * H;
-  const int E = H * HE, tid = threadIdx.x, nt = blockDim.x;
-  const size_t ld = 3 * (size_t)E;
-  const bf16* qb = qkv + (size_t)b * S * ld + h * HE;
-  const bf16* ub = uqkv + (size_t)b * S * ld + h * HE;
-  const bf16* dob = d_o + (size_t)b * S * E + h * HE;
-  for (int i = tid; i < S * HE; i += nt) {
-    const int r = i / HE, d = i - r * HE;
-    Q[i] = qb[r * ld + d]; K[i] = qb[r * ld + E + d]; V[i] = qb[r * ld + 2 * E + d];
-    UQ[i] = ub[r * ld + d]; UK[i] = ub[r * ld + E + d]; UV[i] = ub[r * ld + 2 * E + d];
-    DO[i] = dob[(size_t)r * E + d];
-  }
-  __syncthreads();
-  const float* lb = lse + ((size_t)b * H + h) * S;
-  // pass 1: P, dP, G  (one (i, j) entry per thread step)
-  for (int e = tid; e < S * S; e += nt) {
-    const int i = e / S, j = e - i * S;
-    float s = 0.f, dp = 0.f, g = 0.f;
-    for (int d = 0; d < HE; ++d) {
-      const float q = vg_bf2f(Q[i * HE + d]), k = vg_bf2f(K[j * HE + d]);
-      s += q * k;
-      dp += vg_bf2f(DO[i * HE + d]) * vg_bf2f(V[j * HE + d]);
-      g += vg_bf2f(UQ[i * HE + d]) * k + q * vg_bf2f(UK[j * HE + d]);
-    }
-    P[e] = __expf(s * scale - lb[i]);
-    A[e] = dp;
-    G[e] = g * scale;
-  }
-  __syncthreads();
-  for (int i = tid; i < S; i += nt) {  // row sums: delta_i = sum_j P dP, gam_i = sum_j P G
-    float d = 0.f, gmm = 0.f;
-    for (int j = 0; j < S; ++j) { d += P[i * S + j] * A[i * S + j]; gmm += P[i * S + j] * G[i * S + j]; }
-    dl[i] = d; gm[i] = gmm;
-  }
-  __syncthreads();
-  // pass 2: H = P (G - gam);  Pi = dO uV^T + G (dP - delta) - gam dP;  A <- dP - delta,  G <- Pi
-  for (int e = tid; e < S * S; e += nt) {
-    const int i = e / S, j = e - i * S;
-    float t = 0.f;
-    for (int d = 0; d < HE; ++d) t += vg_bf2f(DO[i * HE + d]) * vg_bf2f(UV[j * HE + d]);
-    const float dp = A[e], a = dp - dl[i], g = G[e];
-    Hm[e] = P[e] * (g - gm[i]);
-    A[e] = a;
-    G[e] = t + g * a - gm[i] * dp;
-  }
-  __syncthreads();
-  for (int i = tid; i < S; i += nt) {  // pi_i = sum_j P Pi  (delta is no longer needed: overwrite)
-    float s = 0.f;
-    for (int j = 0; j < S; ++j) s += P[i * S + j] * G[i * S + j];
-    dl[i] = s;
-  }
-  __syncthreads();
-  // outputs.  dS = P A ;  Sg = P (Pi - pi)
-  bf16* ddo = d_do + (size_t)b * S * E + h * HE;
-  bf16* dq = d_qkv + (size_t)b * S * ld + h * HE;
-  for (int e = tid; e < S * HE; e += nt) {   // d(dO)_id = sum_j P_ij uV_jd + H_ij V_jd ;  d(Q)_id = s sum_j dS_ij uK_jd + Sg_ij K_jd
-    const int i = e / HE, d = e - i * HE;
-    float o1 = 0.f, o2 = 0.f;
-    for (int j = 0; j < S; ++j) {
-      const float p = P[i * S + j];
-      o1 += p * vg_bf2f(UV[j * HE + d]) + Hm[i * S + j] * vg_bf2f(V[j * HE + d]);
-      o2 += p * A[i * S + j] * vg_bf2f(UK[j * HE + d]) + p * (G[i * S + j] - dl[i]) * vg_bf2f(K[j * HE + d]);
-    }
-    ddo[(size_t)i * E + d] = vg_f2bf(o1);
-    dq[(size_t)i * ld + d] = vg_f2bf(o2 * scale);
-  }
-  for (int e = tid; e < S * HE; e += nt) {   // d(K)_jd = s sum_i dS_ij uQ_id + Sg_ij Q_id ;  d(V)_jd = sum_i H_ij dO_id
-    const int j = e / HE, d = e - j * HE;
-    float o1 = 0.f, o2 = 0.f;
-    for (int i = 0; i < S; ++i) {
-      const float p = P[i * S + j];
-      o1 += p * A[i * S + j] * vg_bf2f(UQ[i * HE + d]) + p * (G[i * S + j] - dl[i]) * vg_bf2f(Q[i * HE + d]);
-      o2 += Hm[i * S + j] * vg_bf2f(DO[i * HE + d]);
-    }
-    dq[(size_t)j * ld + E + d] = vg_f2bf(o1 * scale);
-    dq[(size_t)j * ld + 2 * E + d] = vg_f2bf(o2);
-  }
-}
-#endif
+// Attention backward's backward: the range check, then vg_attn_bwd_bwd2_kernel of attention.hip.
 int vg_attn_bwd_bwd_launch(const bf16* qkv, const bf16* d_o, const float* lse, const bf16* uqkv, bf16* d_do, bf16* d_qkv, int B, int H,
                            int S, int HE, float scale, hipStream_t st) {
   if (S < 1 || S > 80 || B < 1 || H < 1) return -2;
-#ifndef VG_ABB_FMA
-  return vg_attn_bwd_bwd_mfma_launch(qkv, d_o, lse, uqkv, d_do, d_qkv, B, H, S, HE, scale, st);  // attention.hip: on the MFMA pipe since round 3
-#else
-  const size_t lds = (size_t)7 * S * HE * 2 + (size_t)4 * S * S * 4 + (size_t)2 * S * 4;  // 155 KB at S = 65, HE = 96
-  if (lds > 160 * 1024) return -3;
-#define VG_ABB(HE_)                                                                                                           \
-  do {                                                                                                                        \
-    hipError_t e = hipFuncSetAttribute((const void*)vg_attn_bwd_bwd_kernel<HE_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    if (e != hipSuccess) return (int)e;                                                                                       \
-    hipLaunchKernelGGL((vg_attn_bwd_bwd_kernel<HE_>), dim3(B * H), dim3(256), lds, st, qkv, d_o, lse, uqkv, d_do, d_qkv, S, H, scale); \
-  } while (0)
-  if (HE == 96) VG_ABB(96); else if (HE == 64) VG_ABB(64); else if (HE == 32) VG_ABB(32); else return -3;
-#undef VG_ABB
-  return (int)hipGetLastError();
-#endif
+  return vg_attn_bwd_bwd_mfma_launch(qkv, d_o, lse, uqkv, d_do, d_qkv, B, H, S, HE, scale, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

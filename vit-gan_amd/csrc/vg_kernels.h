@@ -12,6 +12,7 @@ int vg_attn_bwd_launch(const bf16* qkv, const bf16* o, const bf16* d_o, const fl
 int vg_attn_long_fwd_launch(const bf16* qkv, bf16* o, float* lse, int B, int H, int S, int HE, float scale, hipStream_t st);
 int vg_attn_long_bwd_launch(const bf16* qkv, const bf16* o, const bf16* d_o, const float* lse, bf16* dqkv, int B, int H, int S, int HE,
                             float scale, hipStream_t st);
+const void* vg_attn_zeros();  // device address of the 16-byte zero page the attention stagings pad from (attention.hip); null on failure
 
 int vg_ln_fwd_launch(const bf16* x, long long xs, const float* gamma, const float* beta, bf16* y, long long ys,
                      float* mean, float* rstd, int R, int E, float eps, hipStream_t st);
