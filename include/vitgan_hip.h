@@ -190,7 +190,17 @@ int vg_colsum_bf16(const void* X, long long ld, int R, int N, float* part_ws, fl
 /* y = x * mask / keep for dropout site `site` of a network run with (p, seed): exactly the mask the fused
  * passes apply (element index = position in the row-major tensor; n % 4 == 0).  D sites: 0 embedding,
  * 1+2l attention branch, 2+2l MLP branch of block l; G sites: 100+2l, 101+2l.  Used by tests and by the
- * backward where no producer kernel can fuse the mask. */
+ * backward where no producer kernel can fuse the mask.
+ * The mask, which every masked entry of this header means by "as in vg_dropout_apply":
+ *   thr   = the fp32 product 256 p rounded to an integer, halves to even (lrintf), clamped to [0, 255]: p is quantised to 1/256,
+ *           thr = 0 is no dropout (y = x bitwise), and a p whose product rounds to 256 drops with thr = 255
+ *   scale = the fp32 quotient 256 / (256 - thr), exactly 1 at thr = 0
+ *   key   = the host key of (seed, site), mixed with the step counter: k = step_dev ? key ^ (step_dev[0] 0x9E3779B1 + 0x7F4A7C15) : key
+ *           (32-bit arithmetic modulo 2^32; key and the counter hash h are written out under vg_diffaug_fwd below).  A NULL step_dev
+ *           is not a counter of 0.
+ *   element e of the row-major tensor is kept iff byte (e & 3) of the word h(k, e >> 2) is >= thr, byte 0 the lowest
+ *   y[e]  = bf16(fp32(x[e]) * (kept ? scale : 0)): one fp32 product, rounded to nearest even
+ * Returns -1: null x / y, n < 1 or p outside [0, 1);  -3: n % 4 != 0 - all before any launch. */
 int vg_dropout_apply(const void* x, void* y, long long n, float p, unsigned long long seed, int site,
                      const unsigned* step_dev, void* stream);
 

@@ -6,33 +6,12 @@ conditional generator as ``oracle.gen_oracle.gen_forward`` on the extended laten
 import numpy as np
 import torch
 
-M32, M64 = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
+from drop_ref import M32, h, site_key  # noqa: F401  (the host key and the counter hash of the dropout masks)
 KINDS = ("ns", "hinge", "wasserstein")  # kind 0, 1, 2
 LABEL_SITE = 3                          # the fused step's draws: its augmentation seed, site 3
 
 
 # ---------------------------------------------------------------------------------------------------------------- the label hash
-def site_key(seed: int, site: int) -> int:
-    """key = fold(splitmix64(seed + 0x9E3779B97F4A7C15 (site + 1)))"""
-    z = (seed + 0x9E3779B97F4A7C15 * (site + 1)) & M64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
-    z ^= z >> 31
-    return (z ^ (z >> 32)) & M32
-
-
-def h(k, i):
-    """the counter hash, on numpy uint32 arrays (or scalars), modulo 2^32"""
-    with np.errstate(over="ignore"):
-        x = (np.asarray(i, dtype=np.uint32) * np.uint32(0x9E3779B1) + np.uint32(k)).astype(np.uint32)
-        x ^= x >> np.uint32(16)
-        x = (x * np.uint32(0x7FEB352D)).astype(np.uint32)
-        x ^= x >> np.uint32(15)
-        x = (x * np.uint32(0x846CA68B)).astype(np.uint32)
-        x ^= x >> np.uint32(16)
-    return x
-
-
 def launch_key(seed: int, site: int, step) -> int:
     """ks = h(step_dev ? key ^ (step 0x9E3779B1 + 0x7F4A7C15) : key, 0); ``step`` None = no device counter"""
     key = site_key(seed, site)

@@ -5,31 +5,10 @@ arithmetic modulo 2^32.  ``perm_epoch`` takes ``walk=False`` to plant the defect
 import numpy as np
 import torch
 
-M32, M64 = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
+from drop_ref import M32, h, site_key  # noqa: F401  (the host key and the counter hash of the dropout masks)
 SITE_PERM, SITE_FLIP = 4, 5
 SIZES = (1, 2, 3, 5, 16, 17, 50, 53, 1000, 4096, 4097, 50000, 65537, 2 ** 20)
 EPOCHS = (0, 1, 7, 12345)
-
-
-def site_key(seed: int, site: int) -> int:
-    """key = fold(splitmix64(seed + 0x9E3779B97F4A7C15 (site + 1)))"""
-    z = (seed + 0x9E3779B97F4A7C15 * (site + 1)) & M64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
-    z ^= z >> 31
-    return (z ^ (z >> 32)) & M32
-
-
-def h(k, i):
-    """the counter hash, on numpy uint32 arrays (or scalars), modulo 2^32"""
-    with np.errstate(over="ignore"):
-        x = (np.asarray(i, dtype=np.uint32) * np.uint32(0x9E3779B1) + np.asarray(k, dtype=np.uint32)).astype(np.uint32)
-        x ^= x >> np.uint32(16)
-        x = (x * np.uint32(0x7FEB352D)).astype(np.uint32)
-        x ^= x >> np.uint32(15)
-        x = (x * np.uint32(0x846CA68B)).astype(np.uint32)
-        x ^= x >> np.uint32(16)
-    return x
 
 
 def half_width(N: int) -> int:

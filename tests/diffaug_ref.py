@@ -14,42 +14,15 @@ Both return ``mag`` next to the value: the sum of the magnitudes of everything t
 import numpy as np
 import torch
 
-M32 = 0xFFFFFFFF
-M64 = 0xFFFFFFFFFFFFFFFF
+from drop_ref import h, site_key, step_mix  # noqa: F401  (the host key, the counter hash and the step mix of the dropout masks)
 
 
 # ------------------------------------------------------------------------------------------------------------- parameters
-def site_key(seed, site):
-    """fold(splitmix64(seed + 0x9E3779B97F4A7C15 (site + 1))) -> 32 bits"""
-    z = (int(seed) + 0x9E3779B97F4A7C15 * (int(site) + 1)) & M64
-    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
-    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
-    z ^= z >> 31
-    return (z ^ (z >> 32)) & M32
-
-
-def h(k, i):
-    """the counter hash of the dropout masks on uint32 values (held in uint64 arrays, reduced mod 2^32 after every product)"""
-    k = np.asarray(k, dtype=np.uint64)
-    i = np.asarray(i, dtype=np.uint64)
-    x = (i * np.uint64(0x9E3779B1) + k) & np.uint64(M32)
-    x ^= x >> np.uint64(16)
-    x = (x * np.uint64(0x7FEB352D)) & np.uint64(M32)
-    x ^= x >> np.uint64(15)
-    x = (x * np.uint64(0x846CA68B)) & np.uint64(M32)
-    x ^= x >> np.uint64(16)
-    return x
-
-
 def k24(seed, site, step, n, p):
     """the 24-bit value of parameter p for image n at step counter ``step`` (None: no device counter); step and n broadcast"""
-    key = np.uint64(site_key(seed, site))
-    if step is not None:
-        s = np.asarray(step, dtype=np.uint64)
-        key = key ^ ((s * np.uint64(0x9E3779B1) + np.uint64(0x7F4A7C15)) & np.uint64(M32))
-    ks = h(key, 0)
+    ks = h(step_mix(site_key(seed, site), step), 0)
     kn = h(ks, n)
-    return h(kn, p) >> np.uint64(8)
+    return h(kn, p).astype(np.uint64) >> np.uint64(8)
 
 
 def draw(seed, site, step, B, IH, policy):

@@ -37,6 +37,16 @@ def sync():
     torch.cuda.synchronize()
 
 
+def dropout_mask(shape, p, seed, site, step=None):
+    """vg_dropout_apply on bf16 ones of ``shape``, as fp32 on the host: 0 where dropped, bf16(256 / (256 - thr)) where kept.
+    step: None (no device counter) or a one-element 32-bit integer device tensor"""
+    ones = torch.ones(shape, dtype=BF, device="cuda")
+    out = torch.empty_like(ones)
+    call("vg_dropout_apply", ptr(ones), ptr(out), ones.numel(), p, seed, site, ptr(step), stream())
+    sync()
+    return out.float().cpu()
+
+
 def assert_close(got, ref, rel, what="", floor=1e-6):
     """max|got-ref| <= rel * max|ref|  (per-tensor tolerance)"""
     got = got.detach().float().cpu()

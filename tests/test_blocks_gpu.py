@@ -117,11 +117,7 @@ def test_vit_every_stage_against_the_model(case, B, dropout):
         keep = 256.0 / (256.0 - round(dropout * 256))
 
         def mask(site):
-            ones = torch.ones(B, S, E, dtype=torch.bfloat16, device="cuda")
-            out = torch.empty_like(ones)
-            u.call("vg_dropout_apply", u.ptr(ones), u.ptr(out), ones.numel(), dropout, seed, site, None, u.stream())
-            u.sync()
-            return (out.float().cpu() > 0).float() * keep
+            return (u.dropout_mask((B, S, E), dropout, seed, site) > 0).float() * keep
         masks["embed"] = mask(0)
         for l in range(L):
             masks[("attn", l)], masks[("mlp", l)] = mask(1 + 2 * l), mask(2 + 2 * l)
@@ -287,11 +283,7 @@ def test_generator_every_stage_against_the_model(B, dropout, patch):
         keep = 256.0 / (256.0 - round(dropout * 256))
 
         def mask(site):
-            ones = torch.ones(B, T, E, dtype=torch.bfloat16, device="cuda")
-            out = torch.empty_like(ones)
-            u.call("vg_dropout_apply", u.ptr(ones), u.ptr(out), ones.numel(), dropout, seed, site, None, u.stream())
-            u.sync()
-            return (out.float().cpu() > 0).float() * keep
+            return (u.dropout_mask((B, T, E), dropout, seed, site) > 0).float() * keep
         for l in range(L):
             masks[("attn", l)], masks[("mlp", l)] = mask(100 + 2 * l), mask(101 + 2 * l)
 

@@ -24,11 +24,7 @@ def _u():
 
 
 def _mask(u, M, p, seed, site):
-    ones = torch.ones(M, E, dtype=u.BF, device="cuda")
-    m = torch.empty_like(ones)
-    u.call("vg_dropout_apply", u.ptr(ones), u.ptr(m), M * E, p, seed, site, None, u.stream())
-    u.sync()
-    return m.float().cpu()
+    return u.dropout_mask((M, E), p, seed, site)
 
 
 def _gelu_grad(z):

@@ -9,11 +9,7 @@ pytestmark = pytest.mark.gpu
 
 
 def _mask(u, shape, p, seed, site):
-    ones = torch.ones(shape, dtype=torch.bfloat16, device="cuda")
-    out = torch.empty_like(ones)
-    u.call("vg_dropout_apply", u.ptr(ones), u.ptr(out), ones.numel(), p, seed, site, None, u.stream())
-    u.sync()
-    return out.float().cpu()
+    return u.dropout_mask(shape, p, seed, site)
 
 
 def _exact(m, p):
@@ -37,6 +33,51 @@ def test_mask_statistics_and_determinism():
     assert not torch.equal(m, _mask(u, n, p, 7, 4)) and not torch.equal(m, _mask(u, n, p, 8, 3))
     # columns and rows are both unbiased
     assert float((m > 0).float().mean(0).std()) < 0.02 and float((m > 0).float().mean(1).std()) < 0.03
+
+
+# ---- vg_dropout_apply against drop_ref, the mask restated from the header, bit for bit
+DROP_P = [0.0, 1 / 512, 3 / 512, 1 / 256, 0.5, 255 / 256, 0.9990000128746033]  # the last: fp32 0.999; thr 0, 0, 2, 1, 128, 255, 255 (clamped)
+DROP_SEED = [0, 1234, 2 ** 64 - 1]
+DROP_SITE = [0, 4, 101]
+DROP_N = [4, 8, 1020, 1024, 1028]  # a launch block covers 1024 elements: one vector short of, at and past its edge
+DROP_STEP = [None, 0, 1, 0xFFFFFFFF]  # NULL, and a device counter
+
+
+@pytest.mark.parametrize("i", range(len(DROP_P)))
+def test_dropout_apply_is_the_header_rule_bit_for_bit(i):
+    """y = bf16(fp32(x) * (kept ? scale : 0)) with the keep pattern and the fp32 scale of drop_ref.mask, on ones and on signed powers of
+    two (the fp32 product is exact, the one bf16 rounding remains); nothing behind element n is written; p = 0 copies the input bitwise;
+    a NULL step_dev is not a counter of 0.  Every p, seed and site appears; p = 0.5 keeps some and drops some at every n >= 8."""
+    import numpy as np
+    import drop_ref as R
+    import exact_util as X
+    import gpu_util as u
+    p, seed, site = DROP_P[i], DROP_SEED[i % 3], DROP_SITE[(i // 2) % 3]
+    outs = {}
+    for n in DROP_N:
+        e = torch.arange(n)
+        inputs = {"ones": torch.ones(n), "signed powers of two": torch.pow(2.0, ((e * 7) % 17 - 8).float()) * (1 - 2 * ((e // 3) % 2)).float()}
+        for step in DROP_STEP:
+            keep, scale = R.mask(p, seed, site, step, n)
+            if p == 0.5 and n >= 8:
+                assert 0 < int(keep.sum()) < n
+            factor = torch.from_numpy(np.where(keep, scale, np.float32(0.0)).astype(np.float32))
+            sd = None if step is None else torch.from_numpy(np.array([step], dtype=np.uint32).view(np.int32)).cuda()
+            for name, x in inputs.items():
+                what = f"p {p} seed {seed} site {site} n {n} step {step} input {name}"
+                xd = u.dev(x, u.BF)
+                buf = X.guarded(n // 4, 4, u.BF, "cuda", guard=8)
+                u.call("vg_dropout_apply", u.ptr(xd), u.ptr(buf), n, p, seed, site, u.ptr(sd), u.stream())
+                u.sync()
+                X.assert_guard(buf, n // 4, what)
+                X.assert_written(buf, n // 4, what)
+                y = buf[:n // 4].reshape(n).cpu()
+                X.assert_bitwise(y, (x * factor).to(u.BF), what)  # x and the product are exact in fp32: one rounding, to bf16
+                if p == 0.0:
+                    assert torch.equal(y.view(torch.int16), xd.cpu().view(torch.int16)), what + ": p = 0 must copy the input bitwise"
+                outs[(n, step, name)] = y
+    if p == 0.5:
+        assert not torch.equal(outs[(1024, None, "ones")], outs[(1024, 0, "ones")]), "the NULL mask must differ from the counter-0 mask"
 
 
 @pytest.mark.parametrize("B", [3, 32])  # 32: M = 2080 rows, the K = 384 Linears (dropout + residual epilogue included) run on csrc/gemm_wr.hip

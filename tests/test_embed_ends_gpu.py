@@ -81,13 +81,10 @@ def _run(geom, B, dropout, img_bf16):
     out["ln"] = (y.cpu(), mu.cpu(), rs.cpu())
     mask = None
     if dropout > 0:
-        ones = torch.ones(B, S, E, dtype=torch.bfloat16, device="cuda")
-        mo = torch.empty_like(ones)
-        u.call("vg_dropout_apply", u.ptr(ones), u.ptr(mo), ones.numel(), dropout, SEED, 0, None, u.stream())
-        u.sync()
+        mo = u.dropout_mask((B, S, E), dropout, SEED, 0)
         thr = round(dropout * 256)
         keep = torch.tensor(256.0, dtype=torch.float32) / torch.tensor(256.0 - thr, dtype=torch.float32)  # the kernels' fp32 scale
-        mask = (mo.float().cpu() > 0).float() * keep
+        mask = (mo > 0).float() * keep
     out["mask"] = mask
     # backward: the head and the block, then the embedding stage on its own - twice, then without weight gradients, then into a fresh buffer
     R = torch.from_numpy(make_input((B, d.classes), c["seed"] + 1)).cuda()

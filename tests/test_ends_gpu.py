@@ -369,7 +369,7 @@ def test_fill_cls():
             if p == 0.0:
                 X.assert_bitwise(got.contiguous(), cls64.float().to(BF).expand(B, E).contiguous(), what)
                 continue
-            mask = _dropout_of(torch.ones(B * S, E, dtype=BF, device="cuda"), p, 0, step).reshape(B, S, E)[:, 0].cpu()
+            mask = g.dropout_mask((B, S, E), p, SEED, 0, step)[:, 0]
             assert torch.equal(got == 0, mask == 0), what + ": zero pattern differs from vg_dropout_apply's"
             assert 0 < int((mask == 0).sum()) < mask.numel() or B * E < 64
             kept = mask != 0

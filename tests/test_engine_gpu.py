@@ -192,12 +192,9 @@ def _step_masks(u, eng, B, step):
     st = torch.tensor([step], dtype=torch.int32, device="cuda")
 
     def mask(shape, p, seed, site):
-        ones = torch.ones(shape, dtype=torch.bfloat16, device="cuda")
-        out = torch.empty_like(ones)
-        u.call("vg_dropout_apply", u.ptr(ones), u.ptr(out), ones.numel(), p, seed, site, u.ptr(st), u.stream())
-        u.sync()
+        out = u.dropout_mask(shape, p, seed, site, st)
         # bf16(keep-scale) -> the exact fp32 multiplier 256 / (256 - round(256 p)) the fused epilogues apply
-        return (out.float().cpu() > 0).float() * (256.0 / (256.0 - round(p * 256)))
+        return (out > 0).float() * (256.0 / (256.0 - round(p * 256)))
 
     def vit_masks(n_img, seed):
         m = {"embed": mask((n_img, S, d.E), eng.p_d, seed, 0)}

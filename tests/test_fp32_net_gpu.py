@@ -98,11 +98,7 @@ def _masks(u, B, S, E, L, p, seed):
     keep = torch.tensor(256.0 / (256.0 - round(p * 256)), dtype=torch.float32)
 
     def mask(site):
-        ones = torch.ones(B, S, E, dtype=torch.bfloat16, device="cuda")
-        out = torch.empty_like(ones)
-        u.call("vg_dropout_apply", u.ptr(ones), u.ptr(out), ones.numel(), p, seed, site, None, u.stream())
-        u.sync()
-        return (out.float().cpu() > 0).float() * keep
+        return (u.dropout_mask((B, S, E), p, seed, site) > 0).float() * keep
 
     m = {"embed": mask(0)}
     for l in range(L):

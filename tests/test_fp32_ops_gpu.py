@@ -80,12 +80,9 @@ def test_linear_f32_fwd_dropout_mask_is_the_engines():
     Y0, Y1 = torch.empty(M, N, device="cuda"), torch.empty(M, N, device="cuda")
     u.call("vg_linear_f32_fwd", u.ptr(X), u.ptr(W), None, None, u.ptr(Y0), None, M, N, K, 0, 0.0, 0, 0, None, u.stream())
     u.call("vg_linear_f32_fwd", u.ptr(X), u.ptr(W), None, None, u.ptr(Y1), None, M, N, K, 0, p, seed, site, None, u.stream())
-    ones = torch.ones(M, N, dtype=torch.bfloat16, device="cuda")
-    m = torch.empty_like(ones)
-    u.call("vg_dropout_apply", u.ptr(ones), u.ptr(m), ones.numel(), p, seed, site, None, u.stream())
-    u.sync()
+    m = u.dropout_mask((M, N), p, seed, site).cuda()
     keep = torch.tensor(256.0 / (256.0 - round(p * 256)), dtype=torch.float32)
-    mask = (m.float() > 0).float() * keep.cuda()
+    mask = (m > 0).float() * keep.cuda()
     assert 0.85 < float((m > 0).float().mean()) < 0.95
     assert torch.equal(Y1, Y0 * mask)
 

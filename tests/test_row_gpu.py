@@ -56,11 +56,7 @@ def _pack(u, W, K, transposed):
 
 
 def _mask(u, M, p, seed, site):
-    ones = torch.ones(M, E, dtype=u.BF, device="cuda")
-    m = torch.empty_like(ones)
-    u.call("vg_dropout_apply", u.ptr(ones), u.ptr(m), M * E, p, seed, site, None, u.stream())
-    u.sync()
-    return m.float().cpu()
+    return u.dropout_mask((M, E), p, seed, site)
 
 
 SHAPES = [(16, 384), (48, 768), (1040, 384), (2080, 1152), (2096, 768), (4160, 768), (16640, 384), (16640, 1152),

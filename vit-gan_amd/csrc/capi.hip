@@ -95,7 +95,7 @@ extern "C" int vg_layernorm_bwd(const void* dy, const void* x, const float* mean
                                 const void* gres, void* dx, float* part, int R, int E, void* stream) {
   if (!dy || !x || !mean || !rstd || !gamma || !dx || !part) return -1;
   return vg_ln_bwd_launch((const bf16*)dy, (const bf16*)x, mean, rstd, gamma, (const bf16*)gres, (bf16*)dx, part, R, E,
-                          nullptr, 0, 0, 1.f, nullptr, (hipStream_t)stream);
+                          nullptr, VgDrop(), (hipStream_t)stream);
 }
 extern "C" int vg_sln_fwd(const void* h, int h_bcast_rows, const void* w, const float* lw, const float* lb, const float* gs,
                           const float* bs, void* y, float* mean, float* rstd, int R, int E, float eps, void* stream) {
@@ -108,7 +108,7 @@ extern "C" int vg_sln_bwd(const void* dy, const void* h, int h_bcast_rows, const
                           float* dw_acc, int dw_accumulate, float* part, int R, int E, void* stream) {
   if (!dy || !h || !w || !mean || !rstd || !lw || !lb || !gs || !bs || !dh || !dw_acc || !part) return -1;
   return vg_sln_bwd_launch((const bf16*)dy, (const bf16*)h, h_bcast_rows, (const bf16*)w, mean, rstd, lw, lb, gs, bs,
-                           (const bf16*)gres, (bf16*)dh, dw_acc, dw_accumulate, part, R, E, nullptr, 0, 0, 1.f, nullptr, (hipStream_t)stream);
+                           (const bf16*)gres, (bf16*)dh, dw_acc, dw_accumulate, part, R, E, nullptr, VgDrop(), (hipStream_t)stream);
 }
 extern "C" int vg_colsum_f32(const float* part, int rows, int width, float* d0, int n0, float* d1, int n1, float* d2, int n2,
                              float* d3, int n3, int accumulate, void* stream) {
@@ -120,17 +120,11 @@ extern "C" int vg_colsum_bf16(const void* X, long long ld, int R, int N, float* 
   if (!X || !part_ws || !dst) return -1;
   return vg_colsum_bf16_launch((const bf16*)X, ld, R, N, part_ws, dst, accumulate, (hipStream_t)stream);
 }
-// threshold, key and scale of dropout site `site` of (p, seed): the one derivation behind every single-operator entry that carries a mask
-struct CapiDrop { unsigned thr, key; float scale; };
-static inline CapiDrop capi_drop(float p, unsigned long long seed, int site) {
-  int t = (int)lrintf(p * 256.f); if (t > 255) t = 255;
-  return CapiDrop{(unsigned)t, vg_site_key(seed, site), t ? 256.f / (256.f - t) : 1.f};
-}
+// (every entry that carries a mask makes its site with vg_drop_site, vg_common.h)
 extern "C" int vg_dropout_apply(const void* x, void* y, long long n, float p, unsigned long long seed, int site,
                                 const unsigned* step_dev, void* stream) {
-  if (!x || !y || n < 1 || p < 0.f || p >= 1.f) return -1;
-  const CapiDrop d = capi_drop(p, seed, site);
-  return vg_dropout_apply_launch((const bf16*)x, (bf16*)y, n, d.thr, d.key, d.scale, step_dev, (hipStream_t)stream);
+  if (!x || !y || n < 1 || !vg_drop_p_ok(p)) return -1;
+  return vg_dropout_apply_launch((const bf16*)x, (bf16*)y, n, vg_drop_site(p, seed, site, step_dev), (hipStream_t)stream);
 }
 // ---- the kernels at the two ends of the networks, one by one (elementwise.hip; tests/test_ends_gpu.py).  Every null pointer and every
 // shape is refused by the launcher, before any launch; the mask-carrying entries refuse a probability outside [0, 1) here (-1).
@@ -153,18 +147,16 @@ extern "C" int vg_take_rows(const void* in, void* out, int B, int S, int first, 
 }
 extern "C" int vg_scatter_cls(const void* src, void* g, void* gm, int B, int S, int E, float p, unsigned long long seed, int site,
                               const unsigned* step_dev, void* stream) {
-  if (p < 0.f || p >= 1.f) return -1;
-  const CapiDrop d = capi_drop(p, seed, site);
-  return vg_scatter_cls_launch((const bf16*)src, (bf16*)g, B, S, E, (hipStream_t)stream, (bf16*)gm, d.thr, d.key, d.scale, step_dev);
+  if (!vg_drop_p_ok(p)) return -1;
+  return vg_scatter_cls_launch((const bf16*)src, (bf16*)g, B, S, E, (hipStream_t)stream, (bf16*)gm, vg_drop_site(p, seed, site, step_dev));
 }
 extern "C" int vg_scatter_cls_pair(const void* src_a, void* dst_a, const void* src_b, void* dst_b, int B, int S, int E, void* stream) {
   return vg_scatter_cls2_launch((const bf16*)src_a, (bf16*)dst_a, (const bf16*)src_b, (bf16*)dst_b, B, S, E, (hipStream_t)stream);
 }
 extern "C" int vg_fill_cls(void* x, const float* cls, int B, int S, int E, float p, unsigned long long seed, int site, const unsigned* step_dev,
                            void* stream) {
-  if (p < 0.f || p >= 1.f) return -1;
-  const CapiDrop d = capi_drop(p, seed, site);
-  return vg_fill_cls_launch((bf16*)x, cls, B, S, E, d.thr, d.key, d.scale, step_dev, (hipStream_t)stream);
+  if (!vg_drop_p_ok(p)) return -1;
+  return vg_fill_cls_launch((bf16*)x, cls, B, S, E, vg_drop_site(p, seed, site, step_dev), (hipStream_t)stream);
 }
 extern "C" int vg_patchify(const void* img, int img_is_bf16, void* A, int B, int C, int IH, int P, void* stream) {
   return vg_patchify_launch(img, img_is_bf16, (bf16*)A, B, C, IH, P, (hipStream_t)stream);
@@ -201,23 +193,19 @@ extern "C" int vg_row_pack_weight(const void* W, int ld, int K, int transposed, 
   return vg_row_pack_weight_e(VG_ROW_N, W, ld, K, transposed, Wp, stream);
 }
 extern "C" int vg_row_parts(int M) { return vg_row_nwg(M); }
-static void row_drop(VgRowArgs& ra, float p, unsigned long long seed, int site, const unsigned* step_dev) {
-  int t = (int)lrintf(p * 256.f); if (t < 0) t = 0; if (t > 255) t = 255;
-  if (!t) return;
-  ra.drop_thresh = (unsigned)t; ra.drop_key = vg_site_key(seed, site); ra.drop_scale = 256.f / (256.f - t); ra.drop_step = step_dev;
-}
+// the row and chain launchers answer 1 = enqueued, 0 = not of the kernel's kind, < 0 = -hipError: as a return code
+static inline int row_status(int r) { return r > 0 ? 0 : (r < 0 ? -r : -3); }
 extern "C" int vg_linear_ln_fwd_e(int E, const void* A, const void* Wp, const float* bias, const void* res, void* Y, void* Yn, float* mean,
                                 float* rstd, const float* gamma, const float* beta, int M, int K, float eps, float drop_p,
                                 unsigned long long seed, int site, const unsigned* step_dev, void* stream) {
   if (!vg_row_width_ok(E)) return -3;
-  if (!A || !Wp || !Y || (Yn && (!mean || !rstd || !gamma || !beta)) || drop_p < 0.f || drop_p >= 1.f) return -1;
+  if (!A || !Wp || !Y || (Yn && (!mean || !rstd || !gamma || !beta)) || !vg_drop_p_ok(drop_p)) return -1;
   VgRowArgs ra = {};
   ra.N = E;
   ra.A = (const bf16*)A; ra.lda = K; ra.Wp = (const bf16*)Wp; ra.M = M; ra.K = K; ra.bias = bias; ra.res = (const bf16*)res;
   ra.Y = (bf16*)Y; ra.Yn = (bf16*)Yn; ra.mean_out = mean; ra.rstd_out = rstd; ra.gamma = gamma; ra.beta = beta; ra.eps = eps;
-  row_drop(ra, drop_p, seed, site, step_dev);
-  const int r = vg_gemm_row_launch(ra, VG_ROW_LNFWD, (hipStream_t)stream);
-  return r > 0 ? 0 : (r < 0 ? -r : -3);
+  ra.drop = vg_drop_site(drop_p, seed, site, step_dev);
+  return row_status(vg_gemm_row_launch(ra, VG_ROW_LNFWD, (hipStream_t)stream));
 }
 extern "C" int vg_linear_ln_fwd(const void* A, const void* Wp, const float* bias, const void* res, void* Y, void* Yn, float* mean,
                                 float* rstd, const float* gamma, const float* beta, int M, int K, float eps, float drop_p,
@@ -232,15 +220,13 @@ extern "C" int vg_encoder_mlp_fwd(const void* xn, const void* img, const float* 
                                   void* dcode, void* Y, void* Yn, float* mean, float* rstd, const float* gamma, const float* beta,
                                   int M, float eps, float drop_p, unsigned long long seed, int site, const unsigned* step_dev,
                                   void* stream) {
-  if (!xn || !img || !b1 || !b2 || !a1 || !dcode || !Y || (Yn && (!mean || !rstd || !gamma || !beta)) || drop_p < 0.f || drop_p >= 1.f) return -1;
+  if (!xn || !img || !b1 || !b2 || !a1 || !dcode || !Y || (Yn && (!mean || !rstd || !gamma || !beta)) || !vg_drop_p_ok(drop_p)) return -1;
   VgChainMlpArgs ca = {};
   ca.xn = (const bf16*)xn; ca.ldx = VG_CH_E; ca.img = (const bf16*)img; ca.b1 = b1; ca.b2 = b2; ca.res = (const bf16*)res;
   ca.a1 = (bf16*)a1; ca.z8 = (unsigned char*)dcode; ca.Y = (bf16*)Y; ca.Yn = (bf16*)Yn; ca.mean_out = mean; ca.rstd_out = rstd;
   ca.gamma = gamma; ca.beta = beta; ca.eps = eps; ca.M = M;
-  int t = (int)lrintf(drop_p * 256.f); if (t < 0) t = 0; if (t > 255) t = 255;
-  if (t) { ca.drop_thresh = (unsigned)t; ca.drop_key = vg_site_key(seed, site); ca.drop_scale = 256.f / (256.f - t); ca.drop_step = step_dev; }
-  const int r = vg_chain_mlp_fwd_launch(ca, (hipStream_t)stream);
-  return r > 0 ? 0 : (r < 0 ? -r : -3);
+  ca.drop = vg_drop_site(drop_p, seed, site, step_dev);
+  return row_status(vg_chain_mlp_fwd_launch(ca, (hipStream_t)stream));
 }
 extern "C" long long vg_encoder_post_attention_image_elems(void) { return (long long)(VG_CH_MLP_STAGES + VG_CH_FRONT_STAGES) * VG_CH_STAGE / 2; }
 extern "C" int vg_encoder_post_attention_pack(const void* Wo, const void* W1, const void* W2, void* img, void* stream) {
@@ -252,27 +238,22 @@ extern "C" int vg_encoder_post_attention_fwd(const void* ao, const void* x, cons
                                              float eps, float drop_p, unsigned long long seed, int site_attn, int site_mlp,
                                              const unsigned* step_dev, void* stream) {
   if (!ao || !x || !img || !b1 || !b2 || !gamma2 || !beta2 || !xmid || !xn2 || !mean2 || !rstd2 || !a1 || !dcode || !Y ||
-      (Yn && (!mean || !rstd || !gamma || !beta)) || drop_p < 0.f || drop_p >= 1.f)
+      (Yn && (!mean || !rstd || !gamma || !beta)) || !vg_drop_p_ok(drop_p))
     return -1;
   VgChainMlpArgs ca = {};
   ca.ao = (const bf16*)ao; ca.xin = (const bf16*)x; ca.ldx = VG_CH_E; ca.img = (const bf16*)img; ca.bo = bo; ca.b1 = b1; ca.b2 = b2;
   ca.gamma2 = gamma2; ca.beta2 = beta2; ca.xmid = (bf16*)xmid; ca.xn_out = (bf16*)xn2; ca.mean2 = mean2; ca.rstd2 = rstd2;
   ca.a1 = (bf16*)a1; ca.z8 = (unsigned char*)dcode; ca.Y = (bf16*)Y; ca.Yn = (bf16*)Yn; ca.mean_out = mean; ca.rstd_out = rstd;
   ca.gamma = gamma; ca.beta = beta; ca.eps = eps; ca.M = M;
-  int t = (int)lrintf(drop_p * 256.f); if (t < 0) t = 0; if (t > 255) t = 255;
-  if (t) {
-    ca.drop_thresh = (unsigned)t; ca.drop_key = vg_site_key(seed, site_mlp); ca.drop_key_a = vg_site_key(seed, site_attn);
-    ca.drop_scale = 256.f / (256.f - t); ca.drop_step = step_dev;
-  }
-  const int r = vg_chain_mlp_fwd_launch(ca, (hipStream_t)stream);
-  return r > 0 ? 0 : (r < 0 ? -r : -3);
+  ca.drop = vg_drop_site(drop_p, seed, site_mlp, step_dev); ca.drop_key_a = vg_site_key(seed, site_attn);
+  return row_status(vg_chain_mlp_fwd_launch(ca, (hipStream_t)stream));
 }
 extern "C" int vg_linear_sln_fwd_e(int E, const void* A, const void* Wp, const float* bias, const void* res, const float* resf, int res_period,
                                  void* Y, void* Yn, float* mean, float* rstd, const void* wmod, const float* lw, const float* lb,
                                  const float* gs, const float* bs, int M, int K, float eps, float drop_p, unsigned long long seed,
                                  int site, const unsigned* step_dev, void* stream) {
   if (!vg_row_width_ok(E)) return -3;
-  if (!A || !Wp || !Y || !Yn || !mean || !rstd || !wmod || !lw || !lb || !gs || !bs || drop_p < 0.f || drop_p >= 1.f) return -1;
+  if (!A || !Wp || !Y || !Yn || !mean || !rstd || !wmod || !lw || !lb || !gs || !bs || !vg_drop_p_ok(drop_p)) return -1;
   if (res && resf) return -1;
   VgRowArgs ra = {};
   ra.N = E;
@@ -280,9 +261,8 @@ extern "C" int vg_linear_sln_fwd_e(int E, const void* A, const void* Wp, const f
   ra.resf = resf; ra.res_period = res_period;
   ra.Y = (bf16*)Y; ra.Yn = (bf16*)Yn; ra.mean_out = mean; ra.rstd_out = rstd; ra.gamma = lw; ra.beta = lb; ra.eps = eps;
   ra.wmod = (const bf16*)wmod; ra.gs = gs; ra.bs = bs;
-  row_drop(ra, drop_p, seed, site, step_dev);
-  const int r = vg_gemm_row_launch(ra, VG_ROW_LNFWD, (hipStream_t)stream);
-  return r > 0 ? 0 : (r < 0 ? -r : -3);
+  ra.drop = vg_drop_site(drop_p, seed, site, step_dev);
+  return row_status(vg_gemm_row_launch(ra, VG_ROW_LNFWD, (hipStream_t)stream));
 }
 extern "C" int vg_linear_sln_fwd(const void* A, const void* Wp, const float* bias, const void* res, const float* resf, int res_period,
                                  void* Y, void* Yn, float* mean, float* rstd, const void* wmod, const float* lw, const float* lb,
@@ -296,17 +276,15 @@ extern "C" int vg_linear_dgrad_sln_bwd_e(int E, const void* dY, const void* WpT,
                                        float* part, int M, int K, float drop_p, unsigned long long seed, int site,
                                        const unsigned* step_dev, void* stream) {
   if (!vg_row_width_ok(E)) return -3;
-  if (!dY || !WpT || !h || !wmod || !mean || !rstd || !lw || !lb || !gs || !bs || !dh || !dw_acc || !part || drop_p < 0.f || drop_p >= 1.f)
+  if (!dY || !WpT || !h || !wmod || !mean || !rstd || !lw || !lb || !gs || !bs || !dh || !dw_acc || !part || !vg_drop_p_ok(drop_p))
     return -1;
   VgRowArgs ra = {};
   ra.N = E;
   ra.A = (const bf16*)dY; ra.lda = K; ra.Wp = (const bf16*)WpT; ra.M = M; ra.K = K; ra.x = (const bf16*)h; ra.x_period = h_bcast_rows;
   ra.mean = mean; ra.rstd = rstd; ra.gamma = lw; ra.lbias = lb; ra.gs = gs; ra.bs = bs; ra.wmod = (const bf16*)wmod;
   ra.gres = (const bf16*)gres; ra.dx = (bf16*)dh; ra.dxm = (bf16*)dhm; ra.dw_acc = dw_acc; ra.dw_accumulate = dw_accumulate; ra.part = part;
-  if (dhm) row_drop(ra, drop_p, seed, site, step_dev);
-  if (dhm && !ra.drop_thresh) { ra.drop_thresh = 0; ra.drop_scale = 1.f; }
-  const int r = vg_gemm_row_launch(ra, VG_ROW_LNBWD, (hipStream_t)stream);
-  return r > 0 ? 0 : (r < 0 ? -r : -3);
+  if (dhm) ra.drop = vg_drop_site(drop_p, seed, site, step_dev);
+  return row_status(vg_gemm_row_launch(ra, VG_ROW_LNBWD, (hipStream_t)stream));
 }
 extern "C" int vg_linear_dgrad_sln_bwd(const void* dY, const void* WpT, const void* h, int h_bcast_rows, const void* wmod,
                                        const float* mean, const float* rstd, const float* lw, const float* lb, const float* gs,
@@ -319,15 +297,13 @@ extern "C" int vg_linear_dgrad_ln_bwd_e(int E, const void* dY, const void* WpT, 
                                       const float* gamma, const void* gres, void* dx, void* dxm, float* part, int M, int K,
                                       float drop_p, unsigned long long seed, int site, const unsigned* step_dev, void* stream) {
   if (!vg_row_width_ok(E)) return -3;
-  if (!dY || !WpT || !x || !mean || !rstd || !gamma || !dx || !part || drop_p < 0.f || drop_p >= 1.f) return -1;
+  if (!dY || !WpT || !x || !mean || !rstd || !gamma || !dx || !part || !vg_drop_p_ok(drop_p)) return -1;
   VgRowArgs ra = {};
   ra.N = E;
   ra.A = (const bf16*)dY; ra.lda = K; ra.Wp = (const bf16*)WpT; ra.M = M; ra.K = K; ra.x = (const bf16*)x; ra.mean = mean; ra.rstd = rstd;
   ra.gamma = gamma; ra.gres = (const bf16*)gres; ra.dx = (bf16*)dx; ra.dxm = (bf16*)dxm; ra.part = part;
-  if (dxm) row_drop(ra, drop_p, seed, site, step_dev);
-  if (dxm && !ra.drop_thresh) { ra.drop_thresh = 0; ra.drop_scale = 1.f; }
-  const int r = vg_gemm_row_launch(ra, VG_ROW_LNBWD, (hipStream_t)stream);
-  return r > 0 ? 0 : (r < 0 ? -r : -3);
+  if (dxm) ra.drop = vg_drop_site(drop_p, seed, site, step_dev);
+  return row_status(vg_gemm_row_launch(ra, VG_ROW_LNBWD, (hipStream_t)stream));
 }
 extern "C" int vg_linear_dgrad_ln_bwd(const void* dY, const void* WpT, const void* x, const float* mean, const float* rstd,
                                       const float* gamma, const void* gres, void* dx, void* dxm, float* part, int M, int K,

@@ -272,8 +272,8 @@ __global__ __launch_bounds__(512) void vg_chain_fwd_kernel(const VgChainMlpArgs 
       const int ecg = vg_pair_col(eg);
       const int erow = (a.upw * tile + wid) * 16 + (ln & 15);
       const unsigned char* par = smem + CH_RING;
-      const unsigned dthr = a.drop_thresh, dkey = vg_drop_key(key_host, a.drop_step);
-      const float dscale = a.drop_scale;
+      const unsigned dthr = a.drop.thr, dkey = vg_drop_key(key_host, a.drop.step);
+      const float dscale = a.drop.scale;
       const unsigned drm = a.drop_row_mul > 1 ? (unsigned)a.drop_row_mul : 1u;
       u32x4 rv[RB];
       auto ld_res = [&](int p) {
@@ -431,7 +431,7 @@ __global__ __launch_bounds__(512) void vg_chain_fwd_kernel(const VgChainMlpArgs 
     // Y = res + drop(fc2 + b2) and the LayerNorm behind it (the next block's norm1); FRONT: the residual is the x_mid this lane
     // stored behind the out-projection (same addresses, same thread: program order makes it visible)
     if (active && !(CH_DBG & 128))
-      row_epi(std::false_type{}, std::integral_constant<int, 12>{}, acc2, A, CH_PAR_B2, CH_PAR_GAM, CH_PAR_BET, a.drop_key, FRONT ? (const bf16*)a.xmid : a.res, a.Y,
+      row_epi(std::false_type{}, std::integral_constant<int, 12>{}, acc2, A, CH_PAR_B2, CH_PAR_GAM, CH_PAR_BET, a.drop.key, FRONT ? (const bf16*)a.xmid : a.res, a.Y,
               a.Yn, a.mean_out, a.rstd_out);
     if ((CH_DBG & 64) && !FRONT) {
       const unsigned long long t3 = __builtin_readcyclecounter();

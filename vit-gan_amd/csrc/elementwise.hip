@@ -42,30 +42,29 @@ __global__ __launch_bounds__(256) void vg_unpatchify_kernel(const bf16* __restri
 
 // ---- CLS rows of the token matrix: x[b*S + 0, :] = dropout(cls) (the embedding dropout, modules.py:99) ----
 __global__ __launch_bounds__(256) void vg_fill_cls_kernel(bf16* __restrict__ x, const float* __restrict__ cls, int B, int S,
-                                                          int E, unsigned dthr, unsigned dkey0, float dscale, const unsigned* __restrict__ dstep) {
-  const unsigned dkey = vg_drop_key(dkey0, dstep);
+                                                          int E, VgDrop drop) {
+  const unsigned dkey = vg_drop_key(drop.key, drop.step);
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= B * E) return;
   const int b = i / E, e = i - b * E;
   float v = cls[e];
-  if (dthr) {
+  if (drop.thr) {
     const unsigned idx = (unsigned)(b * S) * (unsigned)E + (unsigned)e;
-    v *= vg_drop_factor(vg_drop_word(dkey, idx >> 2), idx & 3, dthr, dscale);
+    v *= vg_drop_factor(vg_drop_word(dkey, idx >> 2), idx & 3, drop.thr, drop.scale);
   }
   x[(size_t)b * S * E + e] = vg_f2bf(v);
 }
 // y[i] = x[i] * mask(i) / keep   (gradient of a dropout site where no producer kernel can fuse it; n % 4 == 0)
 __global__ __launch_bounds__(256) void vg_dropout_apply_kernel(const bf16* __restrict__ x, bf16* __restrict__ y, long long n,
-                                                               unsigned dthr, unsigned dkey0, float dscale,
-                                                               const unsigned* __restrict__ dstep) {
-  const unsigned dkey = vg_drop_key(dkey0, dstep);
+                                                               VgDrop drop) {
+  const unsigned dkey = vg_drop_key(drop.key, drop.step);
   const long long i4 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
   if (i4 >= n) return;
   const bf16x4 v = *(const bf16x4*)(x + i4);
   const unsigned wd = vg_drop_word(dkey, (unsigned)(i4 >> 2));
   bf16x4 o;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) o[j] = vg_f2bf(vg_bf2f(v[j]) * vg_drop_factor(wd, j, dthr, dscale));
+  for (int j = 0; j < 4; ++j) o[j] = vg_f2bf(vg_bf2f(v[j]) * vg_drop_factor(wd, j, drop.thr, drop.scale));
   *(bf16x4*)(y + i4) = o;
 }
 // ---- gather / scatter of row subsets ---------------------------------------------------------
@@ -82,8 +81,7 @@ __global__ __launch_bounds__(256) void vg_take_rows_kernel(const bf16* __restric
 }
 // g[(b*S + 0), :] = src[b, :], every other row of g = 0;  gm (nullable): g times the dropout mask of the [B*S, E] buffer
 __global__ __launch_bounds__(256) void vg_scatter_cls_kernel(const bf16* __restrict__ src, bf16* __restrict__ g, int B, int S,
-                                                             int E, bf16* __restrict__ gm, unsigned dthr, unsigned dkey0, float dscale,
-                                                             const unsigned* __restrict__ dstep) {
+                                                             int E, bf16* __restrict__ gm, VgDrop drop) {
   const int cpr = E / 8;
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= (long long)B * S * cpr) return;
@@ -95,7 +93,7 @@ __global__ __launch_bounds__(256) void vg_scatter_cls_kernel(const bf16* __restr
   *(u32x4*)(g + (size_t)r * E + 8 * c) = v;
   if (gm) {
     if (s == 0) {  // same index and arithmetic as vg_dropout_apply_kernel over the whole buffer
-      const unsigned dkey = vg_drop_key(dkey0, dstep);
+      const unsigned dkey = vg_drop_key(drop.key, drop.step);
       const long long i4 = (r * E + 8 * c) >> 2;
       const bf16x8 x = __builtin_bit_cast(bf16x8, v);
       bf16x8 o;
@@ -103,7 +101,7 @@ __global__ __launch_bounds__(256) void vg_scatter_cls_kernel(const bf16* __restr
       for (int h = 0; h < 2; ++h) {
         const unsigned wd = vg_drop_word(dkey, (unsigned)(i4 + h));
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[4 * h + j] = vg_f2bf(vg_bf2f(x[4 * h + j]) * vg_drop_factor(wd, j, dthr, dscale));
+        for (int j = 0; j < 4; ++j) o[4 * h + j] = vg_f2bf(vg_bf2f(x[4 * h + j]) * vg_drop_factor(wd, j, drop.thr, drop.scale));
       }
       v = __builtin_bit_cast(u32x4, o);
     }
@@ -859,17 +857,15 @@ int vg_unpatchify_launch(const bf16* dA, bf16* dimg, int B, int C, int IH, int P
   hipLaunchKernelGGL(vg_unpatchify_kernel, dim3(nblk(total)), dim3(256), 0, st, dA, dimg, B, C, IH, P);
   return (int)hipGetLastError();
 }
-int vg_fill_cls_launch(bf16* x, const float* cls, int B, int S, int E, unsigned dthr, unsigned dkey, float dscale, const unsigned* dstep,
-                       hipStream_t st) {
+int vg_fill_cls_launch(bf16* x, const float* cls, int B, int S, int E, VgDrop drop, hipStream_t st) {
   if (!x || !cls) return -1;
-  if (B < 1 || S < 1 || E < 1 || (long long)B * E > VG_I32 || dthr > 255u) return -3;  // one thread per (b, e), an int index
-  hipLaunchKernelGGL(vg_fill_cls_kernel, dim3(nblk((long long)B * E)), dim3(256), 0, st, x, cls, B, S, E, dthr, dkey, dscale, dstep);
+  if (B < 1 || S < 1 || E < 1 || (long long)B * E > VG_I32 || drop.thr > 255u) return -3;  // one thread per (b, e), an int index
+  hipLaunchKernelGGL(vg_fill_cls_kernel, dim3(nblk((long long)B * E)), dim3(256), 0, st, x, cls, B, S, E, drop);
   return (int)hipGetLastError();
 }
-int vg_dropout_apply_launch(const bf16* x, bf16* y, long long n, unsigned dthr, unsigned dkey, float dscale, const unsigned* dstep,
-                            hipStream_t st) {
+int vg_dropout_apply_launch(const bf16* x, bf16* y, long long n, VgDrop drop, hipStream_t st) {
   if (n & 3) return -3;
-  hipLaunchKernelGGL(vg_dropout_apply_kernel, dim3(nblk(n / 4)), dim3(256), 0, st, x, y, n, dthr, dkey, dscale, dstep);
+  hipLaunchKernelGGL(vg_dropout_apply_kernel, dim3(nblk(n / 4)), dim3(256), 0, st, x, y, n, drop);
   return (int)hipGetLastError();
 }
 int vg_take_rows_launch(const bf16* in, bf16* out, int B, int S, int first, int n_take, int E, hipStream_t st) {
@@ -879,12 +875,10 @@ int vg_take_rows_launch(const bf16* in, bf16* out, int B, int S, int first, int 
   hipLaunchKernelGGL(vg_take_rows_kernel, dim3(nblk((long long)B * n_take * (E / 8))), dim3(256), 0, st, in, out, B, S, first, n_take, E);
   return (int)hipGetLastError();
 }
-int vg_scatter_cls_launch(const bf16* src, bf16* g, int B, int S, int E, hipStream_t st, bf16* gm, unsigned dthr, unsigned dkey, float dscale,
-                          const unsigned* dstep) {
+int vg_scatter_cls_launch(const bf16* src, bf16* g, int B, int S, int E, hipStream_t st, bf16* gm, VgDrop drop) {
   if (!src || !g) return -1;
-  if (B < 1 || S < 1 || E < 8 || (E & 7) || dthr > 255u) return -3;
-  hipLaunchKernelGGL(vg_scatter_cls_kernel, dim3(nblk((long long)B * S * (E / 8))), dim3(256), 0, st, src, g, B, S, E, (dthr ? gm : nullptr), dthr, dkey,
-                     dscale, dstep);
+  if (B < 1 || S < 1 || E < 8 || (E & 7) || drop.thr > 255u) return -3;
+  hipLaunchKernelGGL(vg_scatter_cls_kernel, dim3(nblk((long long)B * S * (E / 8))), dim3(256), 0, st, src, g, B, S, E, (drop.thr ? gm : nullptr), drop);
   return (int)hipGetLastError();
 }
 __global__ __launch_bounds__(256) void vg_scatter_cls2_kernel(const bf16* __restrict__ src_a, bf16* __restrict__ dst_a, const bf16* __restrict__ src_b,

@@ -354,17 +354,17 @@ int vg_embed_fused_ok(int C, int IH, int P, int E) { return E == EM_E && P == 4 
   switch (C) { case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break; default: return -3; }
 
 int vg_embed_fwd_launch(const void* img, int img_is_bf16, const bf16* W, const float* bias, const float* pos, const float* cls, const float* gamma,
-                        const float* beta, bf16* Apatch, bf16* X, bf16* Xn, float* mean, float* rstd, int B, int C, int IH, float eps, unsigned dthr,
-                        unsigned dkey, float dscale, const unsigned* dstep, hipStream_t st) {
+                        const float* beta, bf16* Apatch, bf16* X, bf16* Xn, float* mean, float* rstd, int B, int C, int IH, float eps, VgDrop drop,
+                        hipStream_t st) {
   if (!vg_embed_fused_ok(C, IH, 4, EM_E) || B < 1) return -3;
   const long long M = (long long)B * ((IH / 4) * (IH / 4) + 1);
   if (M * EM_E >= (1LL << 31)) return -3;  // dropout indices and row arithmetic are 32-bit
   const int ntiles = (int)((M + 31) / 32), grid = ntiles < 512 ? ntiles : 512;
 #define EM_FWD(C_)                                                                                                                           \
   if (img_is_bf16) hipLaunchKernelGGL((vg_embed_fwd_kernel<bf16, C_>), dim3(grid), dim3(512), 0, st, (const bf16*)img, W, bias, pos, cls, gamma, \
-                                      beta, Apatch, X, Xn, mean, rstd, B, IH, eps, dthr, dkey, dscale, dstep);                              \
+                                      beta, Apatch, X, Xn, mean, rstd, B, IH, eps, drop.thr, drop.key, drop.scale, drop.step);              \
   else hipLaunchKernelGGL((vg_embed_fwd_kernel<float, C_>), dim3(grid), dim3(512), 0, st, (const float*)img, W, bias, pos, cls, gamma, beta,  \
-                          Apatch, X, Xn, mean, rstd, B, IH, eps, dthr, dkey, dscale, dstep)
+                          Apatch, X, Xn, mean, rstd, B, IH, eps, drop.thr, drop.key, drop.scale, drop.step)
   EM_BY_C(EM_FWD)
 #undef EM_FWD
   return (int)hipGetLastError();

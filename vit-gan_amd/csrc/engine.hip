@@ -139,18 +139,12 @@ static VgGemmProb mk(const bf16* A, int lda, const bf16* Bm, int ldb, int M, int
   p.A = A; p.lda = lda; p.B = Bm; p.ldb = ldb; p.M = M; p.N = N; p.K = K;
   return p;
 }
-static unsigned site_key(const Drop& d, int site) { return vg_site_key(d.seed, site); }
-static void set_drop(VgGemmProb& p, const Drop& d, int site, int post) {
-  if (!d.thr) return;
-  p.drop_thresh = d.thr; p.drop_key = site_key(d, site); p.drop_scale = d.scale; p.drop_post = post; p.drop_step = d.step;
-}
 // forward Linear: C = act(A W^T + b) (+res)
 static int lin_fwd(const bf16* A, int K, const bf16* W, const float* bias, bf16* C, int M, int N, int act, float ascale,
-                   const bf16* res, bf16* pre_bf16, float* pre_f32, hipStream_t st, const Drop* drop = nullptr, int site = 0,
-                   int c2_gelu_grad = 0) {
+                   const bf16* res, bf16* pre_bf16, float* pre_f32, hipStream_t st, VgDrop drop = VgDrop(), int c2_gelu_grad = 0) {
   VgGemmProb p = mk(A, K, W, K, M, N, K);
   p.c2_gelu_grad = c2_gelu_grad;
-  if (drop) set_drop(p, *drop, site, 0);
+  p.drop = drop;
   p.C = C; p.ldc = N; p.bias = bias; p.act = act; p.act_scale = ascale;
   p.res = res; p.ldr = N; p.C2 = pre_bf16; p.ldc2 = N;
   if (pre_f32) { p.pre_f32 = 1; p.Cf = pre_f32; p.ldcf = N; }
@@ -199,7 +193,7 @@ static int pick_splits384(long long tiles, int Krows, int cap) {
 // masked copy is asked for - and turns the launcher's answer into a return code (a problem the kernel does not take is an error here).
 static int row_launch(VgRowArgs ra, int N, const bf16* A, int K, const bf16* Wp, int M, int epi, const Drop& dr, int site, hipStream_t st) {
   ra.N = N; ra.A = A; ra.lda = K; ra.Wp = Wp; ra.M = M; ra.K = K;
-  if (epi == VG_ROW_LNFWD ? dr.thr != 0 : ra.dxm != nullptr) { ra.drop_thresh = dr.thr; ra.drop_key = site_key(dr, site); ra.drop_scale = dr.scale; ra.drop_step = dr.step; }
+  if (epi == VG_ROW_LNFWD ? dr.on() : ra.dxm != nullptr) ra.drop = dr.at(site);
   const int r = vg_gemm_row_launch(ra, epi, st);
   return r > 0 ? 0 : (r < 0 ? -r : -3);
 }
@@ -428,9 +422,9 @@ int VitPass::begin(const VgVitNet* net_, int B, void* ws, void* stream, const Pe
   sh = vit_shape(net->d, B);
   if (net->attn_fp8 && sh.S > VG_SHORT_MAX_S) return -3;  // the fp8 attention kernels are S <= 80
   carve_vit(sh, lay, ws, w);
-  dr = mk_drop(net->dropout_p, net->dropout_seed, net->dropout_step);  // sites: 0 embedding, 1+2l attention branch, 2+2l MLP branch
+  dr = Drop{net->dropout_p, net->dropout_seed, net->dropout_step};  // sites: 0 embedding, 1+2l attention branch, 2+2l MLP branch
   st = (hipStream_t)stream; sd = net->ctx ? ((VgCtx*)net->ctx)->side : st;
-  drop = dr.thr != 0; tail = !net->dense_top; tail_row = tail && sh.rown && !net->attn_fp8 && vg_row_nwg(B) > 0;
+  drop = dr.on(); tail = !net->dense_top; tail_row = tail && sh.rown && !net->attn_fp8 && vg_row_nwg(B) > 0;
   return 0;
 }
 
@@ -453,10 +447,10 @@ int VitPass::lin_ln_fwd(bool row, const LinLn& j) const {
   if (j.rows) {
     VgGemmProb p = mk(j.A, (int)j.lda, j.W, j.K, rows, E, j.K);
     p.C = j.Y; p.ldc = E; p.bias = j.bias; p.res = j.res; p.ldr = j.ldr ? (int)j.ldr : E;
-    set_drop(p, dr, j.site, 0); p.drop_row_mul = sh.S;
+    p.drop = dr.at(j.site); p.drop_row_mul = sh.S;
     VG_TRY(vg_gemm_launch(&p, 1, VG_NT, st));
   } else {
-    VG_TRY(lin_fwd(j.A, j.K, j.W, j.bias, j.Y, rows, E, VG_ACT_NONE, 0.f, j.res, nullptr, nullptr, st, &dr, j.site));
+    VG_TRY(lin_fwd(j.A, j.K, j.W, j.bias, j.Y, rows, E, VG_ACT_NONE, 0.f, j.res, nullptr, nullptr, st, dr.at(j.site)));
   }
   if (j.Yn) VG_TRY(vg_ln_fwd_launch(j.Y, E, j.gamma, j.beta, j.Yn, E, j.mean, j.rstd, rows, E, 1e-5f, st));
   return 0;
@@ -486,8 +480,7 @@ int VitPass::dgrad_ln_bwd(bool row, const DgradLn& j, int step) const {
   if ((step & FP_NORM) && j.inj) { VG_TRY(vg_add_bf16_launch(j.gres, j.inj, pen->tmp, sh.ME, st)); gres = pen->tmp; }
   if (step & FP_GEMM) VG_TRY(lin_dgrad(j.dy, j.W, j.dxn, rows, j.N, E, 0, nullptr, nullptr, 0.f, st));
   if (step & FP_NORM)
-    VG_TRY(vg_ln_bwd_launch(j.dxn, j.x, j.mean, j.rstd, j.gamma, gres, j.dx, j.part, rows, E, j.dxm, dr.thr, site_key(dr, j.site), dr.scale,
-                            dr.step, st, 1, drm));
+    VG_TRY(vg_ln_bwd_launch(j.dxn, j.x, j.mean, j.rstd, j.gamma, gres, j.dx, j.part, rows, E, j.dxm, dr.at(j.site), st, 1, drm));
   return 0;
 }
 // K slices per block of a PAIR of blocks' weight gradients: as many as keep the grouped launch at about one workgroup per CU.
@@ -511,15 +504,15 @@ int VitPass::forward(const void* img, int img_is_bf16, float* logits, float* fea
   const VitBlock b0 = blk(0);
   if (sh.emb_fused) {
     VG_TRY(vg_embed_fwd_launch(img, img_is_bf16, Pb + lay.conv_w, P + lay.conv_b, P + lay.pos, P + lay.cls, b0.P + lay.ln1_w, b0.P + lay.ln1_b,
-                               w.Apatch, b0.x, b0.xn1, b0.mean1, b0.rstd1, B, d.C, d.IH, 1e-5f, dr.thr, site_key(dr, 0), dr.scale, dr.step, st));
+                               w.Apatch, b0.x, b0.xn1, b0.mean1, b0.rstd1, B, d.C, d.IH, 1e-5f, dr.at(0), st));
   } else {
     VG_TRY(vg_patchify_launch(img, img_is_bf16, w.Apatch, B, d.C, d.IH, d.P, st));
     VgGemmProb p = mk(w.Apatch, sh.Kp, Pb + lay.conv_w, sh.Kp, sh.MP, E, sh.Kp);
     p.C = b0.x; p.ldc = E; p.bias = P + lay.conv_b; p.resf = P + lay.pos; p.res_period = sh.NP;
     p.row_in_per = sh.NP; p.row_out_per = S; p.row_out_off = 1;
-    set_drop(p, dr, 0, 1);
+    p.drop = dr.at(0); p.drop_post = 1;
     VG_TRY(vg_gemm_launch(&p, 1, VG_NT, st));
-    VG_TRY(vg_fill_cls_launch(b0.x, P + lay.cls, B, S, E, dr.thr, site_key(dr, 0), dr.scale, dr.step, st));
+    VG_TRY(vg_fill_cls_launch(b0.x, P + lay.cls, B, S, E, dr.at(0), st));
   }
   if (sh.rown) VG_TRY(vit_pack_weights(sh, lay, Pb, w.wpack, st));
   if (!sh.emb_fused)  // block 0's norm1; every later one comes with the fc2 of the block below
@@ -541,7 +534,7 @@ int VitPass::forward(const void* img, int img_is_bf16, float* logits, float* fea
       const long long SE = (long long)S * E;
       VG_TRY(lin_ln_fwd(tail_row, {cls_attn ? w.t_ao : b.ao, E, b.Pb + lay.wo, b.wp + sh.po_wo, b.P + lay.bo, b.x, w.t_xmid, w.t_xn2, w.t_mean2,
                                         w.t_rstd2, b.P + lay.ln2_w, b.P + lay.ln2_b, 1 + 2 * l, B, cls_attn ? E : SE, SE}));
-      VG_TRY(lin_fwd(w.t_xn2, E, b.Pb + lay.w1, b.P + lay.b1, w.t_a1, B, rE, VG_ACT_GELU, 0.f, nullptr, (bf16*)w.t_z1, nullptr, st, nullptr, 0, 2));
+      VG_TRY(lin_fwd(w.t_xn2, E, b.Pb + lay.w1, b.P + lay.b1, w.t_a1, B, rE, VG_ACT_GELU, 0.f, nullptr, (bf16*)w.t_z1, nullptr, st, VgDrop(), 2));
       VG_TRY(lin_ln_fwd(tail_row, {w.t_a1, rE, b.Pb + lay.w2, b.wp + sh.po_w2, b.P + lay.b2, w.t_xmid, w.t_xtop, w.hcls, w.meanf, w.rstdf,
                                         P + lay.lnf_w, P + lay.lnf_b, 2 + 2 * l, B, rE, 0}));
       continue;
@@ -551,7 +544,7 @@ int VitPass::forward(const void* img, int img_is_bf16, float* logits, float* fea
                                    b.P + lay.ln2_b, 1 + 2 * l, 0, 0, 0}));
     // z1 keeps gelu'(pre-activation), the only thing the backward needs of it, as one byte per element
     if (pen) VG_TRY(lin_fwd(b.xn2, E, b.Pb + lay.w1, b.P + lay.b1, b.a1, M, rE, VG_ACT_GELU, 0.f, nullptr, pen_block(*pen, sh, l).h, nullptr, st));
-    else VG_TRY(lin_fwd(b.xn2, E, b.Pb + lay.w1, b.P + lay.b1, b.a1, M, rE, VG_ACT_GELU, 0.f, nullptr, (bf16*)b.z1, nullptr, st, nullptr, 0, 2));
+    else VG_TRY(lin_fwd(b.xn2, E, b.Pb + lay.w1, b.P + lay.b1, b.a1, M, rE, VG_ACT_GELU, 0.f, nullptr, (bf16*)b.z1, nullptr, st, VgDrop(), 2));
     // X[l+1] = x_mid + drop(fc2(a1)) and the NEXT block's norm1 of it (the last block's output only feeds the CLS rows)
     const bool nx = l + 1 < sh.L;
     const VitBlock nb = nx ? blk(l + 1) : VitBlock{};
@@ -611,14 +604,14 @@ int VitPass::bwd_head(const float* dlogits) {
   VG_TRY(lin_dgrad(w.dzh, Pb + lay.hw1, w.dhcls, B, E, E, 0, nullptr, nullptr, 0.f, st));
   if (tail) {
     // dL/dX[L] on the CLS rows (it is zero elsewhere) and its masked copy for the top block's MLP dropout - the bits of rows b S of the full tensor
-    VG_TRY(vg_ln_bwd_launch(w.dhcls, w.t_xtop, w.meanf, w.rstdf, P + lay.lnf_w, nullptr, w.dxcls, w.part, B, E, drop ? w.t_gb2 : nullptr, dr.thr,
-                            site_key(dr, 2 + 2 * top), dr.scale, dr.step, st, 1, S));
+    VG_TRY(vg_ln_bwd_launch(w.dhcls, w.t_xtop, w.meanf, w.rstdf, P + lay.lnf_w, nullptr, w.dxcls, w.part, B, E, drop ? w.t_gb2 : nullptr,
+                            dr.at(2 + 2 * top), st, 1, S));
   } else {
     const VitWs::Set& ts = w.set[top & 1];
-    VG_TRY(vg_ln_bwd_launch(w.dhcls, blk(top).x_next, w.meanf, w.rstdf, P + lay.lnf_w, nullptr, w.dxcls, w.part, B, E, nullptr, 0, 0, 1.f, nullptr, st, S));
+    VG_TRY(vg_ln_bwd_launch(w.dhcls, blk(top).x_next, w.meanf, w.rstdf, P + lay.lnf_w, nullptr, w.dxcls, w.part, B, E, nullptr, VgDrop(), st, S));
     if (pen) VG_TRY(vg_add_bf16_launch(w.dxcls, pen->s_xcls, w.dxcls, (long long)B * E, st));
     // dL/dX[L]: the CLS rows, zero elsewhere - and its masked copy for the last block's MLP dropout, in the same launch
-    VG_TRY(vg_scatter_cls_launch(w.dxcls, ts.gin, B, S, E, st, drop ? ts.gm2 : nullptr, dr.thr, site_key(dr, 2 + 2 * top), dr.scale, dr.step));
+    VG_TRY(vg_scatter_cls_launch(w.dxcls, ts.gin, B, S, E, st, drop ? ts.gm2 : nullptr, dr.at(2 + 2 * top)));
   }
   if (want_wgrad)  // (the final LayerNorm's own partial count: B rows, standalone kernel; w.part is nobody else's)
     VG_TRY(vg_fold_push(folds, w.part, vg_ln_bwd_nparts(B), 3 * E, G + lay.lnf_w, E, G + lay.lnf_b, E, nullptr, E, nullptr, 0));
@@ -890,9 +883,9 @@ int VitPass::pen_first_backward() const {
   VG_TRY(vg_fill_f32_launch(q.ones, (long long)B * sh.Kc, 1.0f, st));
   { const int r = vg_head_bwd_launch(q.ones, P + lay.hw2, w.th, w.dzh, nullptr, nullptr, B, E, sh.Kc, 0, st); if (r < 0) return -r; }  // g_pre
   VG_TRY(lin_dgrad(w.dzh, Pb + lay.hw1, w.dhcls, B, E, E, 0, nullptr, nullptr, 0.f, st));                                             // g_c
-  VG_TRY(vg_ln_bwd_launch(w.dhcls, blk(top).x_next, w.meanf, w.rstdf, P + lay.lnf_w, nullptr, w.dxcls, w.part, B, E, nullptr, 0, 0, 1.f, nullptr, st, S));
+  VG_TRY(vg_ln_bwd_launch(w.dhcls, blk(top).x_next, w.meanf, w.rstdf, P + lay.lnf_w, nullptr, w.dxcls, w.part, B, E, nullptr, VgDrop(), st, S));
   const PenBlock pt = pen_block(q, sh, top);
-  VG_TRY(vg_scatter_cls_launch(w.dxcls, pt.gin, B, S, E, st, drop ? pt.gm2 : nullptr, dr.thr, site_key(dr, 2 + 2 * top), dr.scale, dr.step));
+  VG_TRY(vg_scatter_cls_launch(w.dxcls, pt.gin, B, S, E, st, drop ? pt.gm2 : nullptr, dr.at(2 + 2 * top)));
   for (int l = top; l >= 0; --l) {
     const VitBlock b = blk(l);
     const PenBlock p = pen_block(q, sh, l);
@@ -919,7 +912,7 @@ int VitPass::pen_tangent_backward() {
     VG_TRY(vg_fill_f32_launch((float*)q.u_x[0], sh.ME / 2, 0.0f, st));  // (a kernel, not hipMemsetAsync: see DESIGN 7 - the memset node of a captured graph was not ordered with its neighbours)
     VgGemmProb p = mk(q.u_dA, Kp, Pb + lay.conv_w, Kp, sh.MP, E, Kp);
     p.C = q.u_x[0]; p.ldc = E; p.row_in_per = sh.NP; p.row_out_per = S; p.row_out_off = 1;
-    set_drop(p, dr, 0, 1);
+    p.drop = dr.at(0); p.drop_post = 1;
     VG_TRY(vg_gemm_launch(&p, 1, VG_NT, st));
     const int splits = pick_splits(tiles128(E, Kp), sh.MP, EMB_SPLIT_CAP);
     VgGemmProb pw = wg(w.gp, E, q.u_dA, Kp, sh.MP, w.slab, (long long)E * Kp, splits);
@@ -950,7 +943,7 @@ int VitPass::pen_tangent_backward() {
     // dqkv = attention'(dao; qkv)
     VG_TRY(vg_attn_bwd_bwd_launch(b.qkv, p.dao, b.lse, q.u_dqkv, u_dao, p.s_qkv, B, sh.H, S, sh.HE, sh.scale, st));
     // dao = gb1 Wo ; gb1 = mask1 gmid  ->  u_gmid = u_gX + mask1 (u_dao Wo^T)
-    VG_TRY(lin_fwd(u_dao, E, b.Pb + lay.wo, nullptr, q.u_gmid, M, E, VG_ACT_NONE, 0.f, u_gx, nullptr, nullptr, st, &dr, 1 + 2 * l));
+    VG_TRY(lin_fwd(u_dao, E, b.Pb + lay.wo, nullptr, q.u_gmid, M, E, VG_ACT_NONE, 0.f, u_gx, nullptr, nullptr, st, dr.at(1 + 2 * l)));
     pr[npr++] = wg(gb1, E, u_dao, E, M, slab + lay.wo, lay.layer_weights, sp);
     // gmid = gin + LN2'(dxn2; x_mid)
     VG_TRY(vg_ln_bwd_bwd_launch(q.u_gmid, p.dxn2, b.xmid, b.mean2, b.rstd2, b.P + lay.ln2_w, u_dxn2, p.s_xmid, pb2, M, E, st));
@@ -961,7 +954,7 @@ int VitPass::pen_tangent_backward() {
     // dz1 = da1 gelu'(h)
     VG_TRY(vg_act2_launch(p.h, p.da1, q.u_dz1, u_da1, p.s_h, sh.MR, 1, 2, st));
     // da1 = gb2 W2 ; gb2 = mask2 gin  ->  u_gin = u_gmid + mask2 (u_da1 W2^T)
-    VG_TRY(lin_fwd(u_da1, rE, b.Pb + lay.w2, nullptr, u_up, M, E, VG_ACT_NONE, 0.f, q.u_gmid, nullptr, nullptr, st, &dr, 2 + 2 * l));
+    VG_TRY(lin_fwd(u_da1, rE, b.Pb + lay.w2, nullptr, u_up, M, E, VG_ACT_NONE, 0.f, q.u_gmid, nullptr, nullptr, st, dr.at(2 + 2 * l)));
     pr[npr++] = wg(gb2, E, u_da1, rE, M, slab + lay.w2, lay.layer_weights, sp);
     if (ps == 1 || l == L - 1) {  // the pair (or the odd block out) is complete
       VG_TRY(vg_gemm_launch(pr, npr, VG_TN, st));
@@ -1181,8 +1174,8 @@ int GenPass::begin(const VgGenNet* net_, int B, void* ws, void* stream) {
   VG_TRY(vg_gen_layout(&net->d, &lay));
   sh = gen_shape(net->d, B);
   carve_gen(net->d, sh, lay, ws, w);
-  dr = mk_drop(net->dropout_p, net->dropout_seed, net->dropout_step);  // sites: 100+2l after output_linear, 101+2l inside the MLP
-  drop = dr.thr != 0; st = (hipStream_t)stream;
+  dr = Drop{net->dropout_p, net->dropout_seed, net->dropout_step};  // sites: 100+2l after output_linear, 101+2l inside the MLP
+  drop = dr.on(); st = (hipStream_t)stream;
   return 0;
 }
 // the three parameters of a self-modulated LayerNorm: weight, bias, and the (gamma, beta) scalar pair
@@ -1215,7 +1208,7 @@ int GenPass::dgrad_sln_bwd(const DgradSln& j, int step) const {
   if (step & FP_GEMM) VG_TRY(lin_dgrad(j.dy, j.W, w.ds, sh.R, j.N, sh.E, 0, nullptr, nullptr, 0.f, st));
   if (step & FP_NORM)
     VG_TRY(vg_sln_bwd_launch(w.ds, j.h, j.hb, w.wmod, j.mean, j.rstd, j.n.w, j.n.b, j.n.s, j.n.s + 1, j.gres, j.dh, w.dw_acc, j.accumulate, j.part,
-                             sh.R, sh.E, j.dhm, dr.thr, site_key(dr, j.site), dr.scale, dr.step, st));
+                             sh.R, sh.E, j.dhm, dr.at(j.site), st));
   return 0;
 }
 
@@ -1265,12 +1258,12 @@ extern "C" int vg_gen_forward_cond(const VgGenNet* net, int B, const float* z, v
         VgGemmProb p = mk(b.cat, E, b.Pb + lay.wo, E, R, E, E);
         p.C = b.htmp; p.ldc = E; p.bias = b.P + lay.bo;
         if (l == 0) { p.resf = P + lay.emb; p.res_period = T; } else { p.res = b.h; p.ldr = E; }
-        set_drop(p, dr, 100 + 2 * l, 0);  // attention_dropout(msha(...)) + h, transformer.py:86
+        p.drop = dr.at(100 + 2 * l);  // attention_dropout(msha(...)) + h, transformer.py:86
         VG_TRY(vg_gemm_launch(&p, 1, VG_NT, st));
       }
       VG_TRY(vg_sln_fwd_launch(b.htmp, 0, w.wmod, sln2.w, sln2.b, sln2.s, sln2.s + 1, b.s2, b.mean2, b.rstd2, R, E, 1e-5f, st));
       VG_TRY(lin_fwd(b.s2, E, b.Pb + lay.wm, b.P + lay.bm, b.hout, R, E, VG_ACT_NONE, 0.f, b.htmp, nullptr, nullptr, st,
-                     &dr, 101 + 2 * l));  // Sequential(Linear, Dropout) + htmp, muilti_layer_perceptron.py:26-28
+                     dr.at(101 + 2 * l)));  // Sequential(Linear, Dropout) + htmp, muilti_layer_perceptron.py:26-28
     }
   }
   if (!sh.rown)

@@ -75,13 +75,12 @@ extern "C" int vg_vit_forward_f32(const VgVitNet* net, int B, const float* img, 
   const long long ME = (long long)M * E;
   F32Ws w; carve_f32(d, B, ws, w);
   const float* P = net->P;
-  const Drop dr = mk_drop(net->dropout_p, net->dropout_seed, net->dropout_step);  // sites: 0 embedding, 1+2l attention, 2+2l MLP
-  auto key = [&](int site) { return dr.thr ? vg_site_key(dr.seed, site) : 0u; };
+  const Drop dr = {net->dropout_p, net->dropout_seed, net->dropout_step};  // sites: 0 embedding, 1+2l attention, 2+2l MLP
 
   // patch embedding (modules.py:82-100): per-patch GEMM + bias, + pos_embedding, CLS row, dropout
   VG_TRY(vg_f32_patchify_launch(img, w.tiles, B, d.C, d.IH, d.P, 0, st));
-  VG_TRY(vg_f32_linear_fwd(w.tiles, P + lay.conv_w, P + lay.conv_b, nullptr, w.tok, nullptr, B * NP, E, Kp, VG_F32_ACT_NONE, 0, 0, 1.f, nullptr, st));
-  VG_TRY(vg_f32_embed_assemble_launch(w.tok, P + lay.pos, P + lay.cls, w.X, B, S, E, dr.thr, key(0), dr.scale, dr.step, st));
+  VG_TRY(vg_f32_linear_fwd(w.tiles, P + lay.conv_w, P + lay.conv_b, nullptr, w.tok, nullptr, B * NP, E, Kp, VG_F32_ACT_NONE, VgDrop(), st));
+  VG_TRY(vg_f32_embed_assemble_launch(w.tok, P + lay.pos, P + lay.cls, w.X, B, S, E, dr.at(0), st));
 
   const float scale = 1.0f / sqrtf((float)HE);
   for (int l = 0; l < d.L; ++l) {  // Encoder.forward (modules.py:178-183), pre-LN
@@ -90,21 +89,19 @@ extern "C" int vg_vit_forward_f32(const VgVitNet* net, int B, const float* img, 
     float *xmid = w.xmid + l * ME, *xn2 = w.xn2 + l * ME, *z1 = w.z1 + (long long)l * M * rE, *a1 = w.a1 + (long long)l * M * rE;
     VG_TRY(vg_f32_ln_fwd_launch(X, E, Pl + lay.ln1_w, Pl + lay.ln1_b, xn1, E, w.mean1 + (long long)l * M, w.rstd1 + (long long)l * M, M, E,
                                 1e-5f, st));
-    VG_TRY(vg_f32_linear_fwd(xn1, Pl + lay.wqkv, Pl + lay.bqkv, nullptr, qkv, nullptr, M, 3 * E, E, VG_F32_ACT_NONE, 0, 0, 1.f, nullptr, st));
+    VG_TRY(vg_f32_linear_fwd(xn1, Pl + lay.wqkv, Pl + lay.bqkv, nullptr, qkv, nullptr, M, 3 * E, E, VG_F32_ACT_NONE, VgDrop(), st));
     VG_TRY(vg_f32_attn_fwd_launch(qkv, ao, w.lse + (long long)l * B * d.H * S, B, d.H, S, HE, scale, st));
-    VG_TRY(vg_f32_linear_fwd(ao, Pl + lay.wo, Pl + lay.bo, X, xmid, nullptr, M, E, E, VG_F32_ACT_NONE, dr.thr, key(1 + 2 * l), dr.scale,
-                             dr.step, st));
+    VG_TRY(vg_f32_linear_fwd(ao, Pl + lay.wo, Pl + lay.bo, X, xmid, nullptr, M, E, E, VG_F32_ACT_NONE, dr.at(1 + 2 * l), st));
     VG_TRY(vg_f32_ln_fwd_launch(xmid, E, Pl + lay.ln2_w, Pl + lay.ln2_b, xn2, E, w.mean2 + (long long)l * M, w.rstd2 + (long long)l * M, M, E,
                                 1e-5f, st));
-    VG_TRY(vg_f32_linear_fwd(xn2, Pl + lay.w1, Pl + lay.b1, nullptr, a1, z1, M, rE, E, VG_F32_ACT_GELU, 0, 0, 1.f, nullptr, st));
-    VG_TRY(vg_f32_linear_fwd(a1, Pl + lay.w2, Pl + lay.b2, xmid, Xn, nullptr, M, E, rE, VG_F32_ACT_NONE, dr.thr, key(2 + 2 * l), dr.scale,
-                             dr.step, st));
+    VG_TRY(vg_f32_linear_fwd(xn2, Pl + lay.w1, Pl + lay.b1, nullptr, a1, z1, M, rE, E, VG_F32_ACT_GELU, VgDrop(), st));
+    VG_TRY(vg_f32_linear_fwd(a1, Pl + lay.w2, Pl + lay.b2, xmid, Xn, nullptr, M, E, rE, VG_F32_ACT_NONE, dr.at(2 + 2 * l), st));
   }
   // final LayerNorm on the CLS rows (the classifier reads x[:, 0], modules.py:195,236), Linear -> Tanh -> Linear
   const float* XL = w.X + (long long)d.L * ME;
   VG_TRY(vg_f32_ln_fwd_launch(XL, (long long)S * E, P + lay.lnf_w, P + lay.lnf_b, w.cn, E, w.meanf, w.rstdf, B, E, 1e-5f, st));
-  VG_TRY(vg_f32_linear_fwd(w.cn, P + lay.hw1, P + lay.hb1, nullptr, w.th, nullptr, B, E, E, VG_F32_ACT_TANH, 0, 0, 1.f, nullptr, st));
-  return vg_f32_linear_fwd(w.th, P + lay.hw2, P + lay.hb2, nullptr, logits, nullptr, B, d.Kc, E, VG_F32_ACT_NONE, 0, 0, 1.f, nullptr, st);
+  VG_TRY(vg_f32_linear_fwd(w.cn, P + lay.hw1, P + lay.hb1, nullptr, w.th, nullptr, B, E, E, VG_F32_ACT_TANH, VgDrop(), st));
+  return vg_f32_linear_fwd(w.th, P + lay.hw2, P + lay.hb2, nullptr, logits, nullptr, B, d.Kc, E, VG_F32_ACT_NONE, VgDrop(), st);
 }
 
 extern "C" int vg_vit_backward_f32(const VgVitNet* net, int B, void* ws, const float* dlogits, float* d_img, int want_wgrad, void* stream) {
@@ -119,8 +116,7 @@ extern "C" int vg_vit_backward_f32(const VgVitNet* net, int B, void* ws, const f
   F32Ws w; carve_f32(d, B, ws, w);
   const float* P = net->P;
   float* G = net->G;
-  const Drop dr = mk_drop(net->dropout_p, net->dropout_seed, net->dropout_step);
-  auto key = [&](int site) { return dr.thr ? vg_site_key(dr.seed, site) : 0u; };
+  const Drop dr = {net->dropout_p, net->dropout_seed, net->dropout_step};
   const bool wg = want_wgrad != 0;
 
   // classifier head
@@ -145,7 +141,7 @@ extern "C" int vg_vit_backward_f32(const VgVitNet* net, int B, void* ws, const f
     float* gnext = w.g[cur ^ 1];
     // MLP half: X[l+1] = xmid + drop2(fc2(gelu(fc1(norm2(xmid)))))
     const float* gm = g;
-    if (dr.thr) { VG_TRY(vg_f32_dropout_launch(g, w.gm, ME, dr.thr, key(2 + 2 * l), dr.scale, dr.step, st)); gm = w.gm; }
+    if (dr.on()) { VG_TRY(vg_f32_dropout_launch(g, w.gm, ME, dr.at(2 + 2 * l), st)); gm = w.gm; }
     if (wg) VG_TRY(vg_f32_linear_wgrad(gm, a1, Gl + lay.w2, Gl + lay.b2, w.slab, M, E, rE, st));
     VG_TRY(vg_f32_linear_dgrad(gm, Pl + lay.w2, z1, w.dz1, M, E, rE, VG_F32_MUL_GELU, st));
     if (wg) VG_TRY(vg_f32_linear_wgrad(w.dz1, xn2, Gl + lay.w1, Gl + lay.b1, w.slab, M, rE, E, st));
@@ -154,7 +150,7 @@ extern "C" int vg_vit_backward_f32(const VgVitNet* net, int B, void* ws, const f
                                 wg ? Gl + lay.ln2_w : nullptr, wg ? Gl + lay.ln2_b : nullptr, w.part, M, E, st));
     // attention half: xmid = X + drop1(out_projection(attention(norm1(X))))
     const float* ga = w.gmid;
-    if (dr.thr) { VG_TRY(vg_f32_dropout_launch(w.gmid, w.gm, ME, dr.thr, key(1 + 2 * l), dr.scale, dr.step, st)); ga = w.gm; }
+    if (dr.on()) { VG_TRY(vg_f32_dropout_launch(w.gmid, w.gm, ME, dr.at(1 + 2 * l), st)); ga = w.gm; }
     if (wg) VG_TRY(vg_f32_linear_wgrad(ga, ao, Gl + lay.wo, Gl + lay.bo, w.slab, M, E, E, st));
     VG_TRY(vg_f32_linear_dgrad(ga, Pl + lay.wo, nullptr, w.dao, M, E, E, VG_F32_ACT_NONE, st));
     VG_TRY(vg_f32_attn_bwd_launch(qkv, ao, w.dao, w.lse + (long long)l * B * d.H * S, w.dqkv, B, d.H, S, HE, scale, st));
@@ -165,7 +161,7 @@ extern "C" int vg_vit_backward_f32(const VgVitNet* net, int B, void* ws, const f
     cur ^= 1;
   }
   // patch embedding: dropout, CLS / pos sums over the batch, conv bias and weight, the image
-  VG_TRY(vg_f32_embed_grad_launch(w.g[cur], w.gm, w.gt, B, S, E, dr.thr, key(0), dr.scale, dr.step, st));
+  VG_TRY(vg_f32_embed_grad_launch(w.g[cur], w.gm, w.gt, B, S, E, dr.at(0), st));
   if (wg) {
     VG_TRY(vg_f32_colsum_launch(w.gm, (long long)S * E, B, w.part, G + lay.cls, E, G + lay.pos, NP * E, st));
     VG_TRY(vg_f32_linear_wgrad(w.gt, w.tiles, G + lay.conv_w, G + lay.conv_b, w.slab, B * NP, E, Kp, st));
@@ -181,10 +177,8 @@ extern "C" int vg_linear_f32_fwd(const float* X, const float* W, const float* bi
                                  int K, int act, float drop_p, unsigned long long seed, int site, const unsigned* step_dev, void* stream) {
   if (!X || !W || !Y) return -1;
   if (M < 1 || N < 1 || K < 1) return -2;
-  if (act < 0 || act > 2 || drop_p < 0.f || drop_p >= 1.f) return -4;
-  const Drop dr = mk_drop(drop_p, seed, step_dev);
-  return vg_f32_linear_fwd(X, W, bias, res, Y, Z, M, N, K, act, dr.thr, dr.thr ? vg_site_key(seed, site) : 0u, dr.scale, dr.step,
-                           (hipStream_t)stream);
+  if (act < 0 || act > 2 || !vg_drop_p_ok(drop_p)) return -4;
+  return vg_f32_linear_fwd(X, W, bias, res, Y, Z, M, N, K, act, vg_drop_site(drop_p, seed, site, step_dev), (hipStream_t)stream);
 }
 extern "C" int vg_linear_f32_dgrad(const float* dY, const float* W, const float* aux, float* dX, int M, int N, int K, int act, void* stream) {
   if (!dY || !W || !dX || (act != 0 && !aux)) return -1;

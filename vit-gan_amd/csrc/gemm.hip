@@ -513,7 +513,7 @@ int vg_gemm_launch(VgGemmProb* probs, int n, int mode, hipStream_t stream) {
     if (q.row_in_per > 0) feat |= F_REMAP;
     if (q.C2) feat |= F_C2;
     if (q.pre_f32) feat |= F_PREF32;
-    if (q.drop_thresh) feat |= F_DROP;
+    if (q.drop.thr) feat |= F_DROP;
   }
   if ((feat & F_DROP) && ((feat & (F_C2 | F_PREF32)) || mode != VG_NT)) return -4;
   if (mode == VG_NT) {

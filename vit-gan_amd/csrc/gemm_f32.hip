@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void vg_f32_gemm_kernel(const VgF32Gemm g) {
       c11[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, c11[q], 0, 0, 0);
     }
   }
-  const unsigned dkey = g.dthr ? vg_drop_key(g.dkey, g.dstep) : 0u;
+  const unsigned dkey = g.drop.thr ? vg_drop_key(g.drop.key, g.drop.step) : 0u;
   auto emit = [&](const f32x4& acc, int ti, int tj) {
     const int n = n0 + wn + 16 * tj + li;  // C/D map: col = lane & 15, row = 4 * (lane >> 4) + reg
     if (n >= g.N) return;
@@ -98,9 +98,9 @@ __global__ __launch_bounds__(256) void vg_f32_gemm_kernel(const VgF32Gemm g) {
         const float t = g.aux[(long long)m * g.ldaux + n];
         v *= 1.0f - t * t;
       }
-      if (g.dthr) {  // the element index of the row-major [M, N] output, as vg_dropout_apply counts it
+      if (g.drop.thr) {  // the element index of the row-major [M, N] output, as vg_dropout_apply counts it
         const unsigned idx = (unsigned)m * (unsigned)g.N + (unsigned)n;
-        v *= vg_drop_factor(vg_drop_word(dkey, idx >> 2), idx & 3, g.dthr, g.dscale);
+        v *= vg_drop_factor(vg_drop_word(dkey, idx >> 2), idx & 3, g.drop.thr, g.drop.scale);
       }
       if (g.res) v += g.res[(long long)m * g.ldr + n];
       g.C[(long long)m * g.ldc + n] = v;
@@ -129,14 +129,14 @@ static VgF32Gemm f32_prob() {
 }
 
 int vg_f32_linear_fwd(const float* X, const float* W, const float* bias, const float* res, float* Y, float* Z, int M, int N, int K, int act,
-                      unsigned dthr, unsigned dkey, float dscale, const unsigned* dstep, hipStream_t st) {
+                      VgDrop drop, hipStream_t st) {
   if (act < VG_F32_ACT_NONE || act > VG_F32_ACT_TANH) return -4;
   VgF32Gemm g = f32_prob();
   g.A = X; g.sam = K; g.sak = 1;   // A(m, k) = X[m][k]
   g.B = W; g.sbk = 1; g.sbn = K;   // B(k, n) = W[n][k]
   g.M = M; g.N = N; g.K = K; g.kchunk = K;
   g.C = Y; g.ldc = N; g.bias = bias; g.act = act; g.Z = Z; g.ldz = N; g.res = res; g.ldr = N;
-  g.dthr = dthr; g.dkey = dkey; g.dscale = dscale; g.dstep = dstep;
+  g.drop = drop;
   return vg_f32_gemm_launch(g, st);
 }
 
@@ -258,17 +258,16 @@ int vg_f32_ln_param_grads(const float* dy, const float* x, long long xs, const f
 // elementwise
 static inline unsigned nblk_f32(long long n) { return (unsigned)((n + 255) / 256); }
 
-__global__ __launch_bounds__(256) void vg_f32_dropout_kernel(const float* __restrict__ x, float* __restrict__ y, long long n, unsigned dthr,
-                                                             unsigned dkey0, float dscale, const unsigned* __restrict__ dstep) {
+__global__ __launch_bounds__(256) void vg_f32_dropout_kernel(const float* __restrict__ x, float* __restrict__ y, long long n, VgDrop drop) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const unsigned dkey = vg_drop_key(dkey0, dstep), idx = (unsigned)i;
-  y[i] = x[i] * vg_drop_factor(vg_drop_word(dkey, idx >> 2), idx & 3, dthr, dscale);
+  const unsigned dkey = vg_drop_key(drop.key, drop.step), idx = (unsigned)i;
+  y[i] = x[i] * vg_drop_factor(vg_drop_word(dkey, idx >> 2), idx & 3, drop.thr, drop.scale);
 }
-int vg_f32_dropout_launch(const float* x, float* y, long long n, unsigned dthr, unsigned dkey, float dscale, const unsigned* dstep, hipStream_t st) {
+int vg_f32_dropout_launch(const float* x, float* y, long long n, VgDrop drop, hipStream_t st) {
   if (!x || !y) return -1;
   if (n < 1) return -2;
-  hipLaunchKernelGGL(vg_f32_dropout_kernel, dim3(nblk_f32(n)), dim3(256), 0, st, x, y, n, dthr, dkey, dscale, dstep);
+  hipLaunchKernelGGL(vg_f32_dropout_kernel, dim3(nblk_f32(n)), dim3(256), 0, st, x, y, n, drop);
   return (int)hipGetLastError();
 }
 
@@ -309,22 +308,21 @@ __global__ __launch_bounds__(256) void vg_f32_embed_assemble_kernel(const float*
   }
   X[i] = v;
 }
-int vg_f32_embed_assemble_launch(const float* tok, const float* pos, const float* cls, float* X, int B, int S, int E, unsigned dthr,
-                                 unsigned dkey, float dscale, const unsigned* dstep, hipStream_t st) {
+int vg_f32_embed_assemble_launch(const float* tok, const float* pos, const float* cls, float* X, int B, int S, int E, VgDrop drop,
+                                 hipStream_t st) {
   const long long n = (long long)B * S * E;
-  hipLaunchKernelGGL(vg_f32_embed_assemble_kernel, dim3(nblk_f32(n)), dim3(256), 0, st, tok, pos, cls, X, B, S, E, dthr, dkey, dscale, dstep);
+  hipLaunchKernelGGL(vg_f32_embed_assemble_kernel, dim3(nblk_f32(n)), dim3(256), 0, st, tok, pos, cls, X, B, S, E, drop.thr, drop.key, drop.scale, drop.step);
   return (int)hipGetLastError();
 }
 
 __global__ __launch_bounds__(256) void vg_f32_embed_grad_kernel(const float* __restrict__ g, float* __restrict__ gm, float* __restrict__ gt,
-                                                                int B, int S, int E, unsigned dthr, unsigned dkey0, float dscale,
-                                                                const unsigned* __restrict__ dstep) {
+                                                                int B, int S, int E, VgDrop drop) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= (long long)B * S * E) return;
   float v = g[i];
-  if (dthr) {
+  if (drop.thr) {
     const unsigned idx = (unsigned)i;
-    v *= vg_drop_factor(vg_drop_word(vg_drop_key(dkey0, dstep), idx >> 2), idx & 3, dthr, dscale);
+    v *= vg_drop_factor(vg_drop_word(vg_drop_key(drop.key, drop.step), idx >> 2), idx & 3, drop.thr, drop.scale);
   }
   gm[i] = v;
   const int e = (int)(i % E);
@@ -333,9 +331,8 @@ __global__ __launch_bounds__(256) void vg_f32_embed_grad_kernel(const float* __r
   const long long b = row / S;
   if (s > 0) gt[(b * (S - 1) + s - 1) * E + e] = v;
 }
-int vg_f32_embed_grad_launch(const float* g, float* gm, float* gt, int B, int S, int E, unsigned dthr, unsigned dkey, float dscale,
-                             const unsigned* dstep, hipStream_t st) {
+int vg_f32_embed_grad_launch(const float* g, float* gm, float* gt, int B, int S, int E, VgDrop drop, hipStream_t st) {
   const long long n = (long long)B * S * E;
-  hipLaunchKernelGGL(vg_f32_embed_grad_kernel, dim3(nblk_f32(n)), dim3(256), 0, st, g, gm, gt, B, S, E, dthr, dkey, dscale, dstep);
+  hipLaunchKernelGGL(vg_f32_embed_grad_kernel, dim3(nblk_f32(n)), dim3(256), 0, st, g, gm, gt, B, S, E, drop);
   return (int)hipGetLastError();
 }

@@ -250,8 +250,8 @@ __global__ __launch_bounds__(512, 2) void vg_gemm_row_kernel(const VgRowArgs a) 
       // LNFWD keeps the sum in fp32 until the residual is added (ONE rounding, as the unfused epilogue had): fp32 tile rows of
       // 1552 B, 5 m-tiles (80 rows) at a time
       constexpr int HM = Cf::HM, NH = (MT + HM - 1) / HM;
-      const unsigned dthr = a.drop_thresh, dkey = vg_drop_key(a.drop_key, a.drop_step);
-      const float dscale = a.drop_scale;
+      const unsigned dthr = a.drop.thr, dkey = vg_drop_key(a.drop.key, a.drop.step);
+      const float dscale = a.drop.scale;
       const unsigned drm = a.drop_row_mul > 1 ? (unsigned)a.drop_row_mul : 1u;
       const size_t ldres = a.ldr > 0 ? (size_t)a.ldr : (size_t)RW_E;
       f32x4 b4[NT];
@@ -384,8 +384,8 @@ __global__ __launch_bounds__(512, 2) void vg_gemm_row_kernel(const VgRowArgs a) 
       constexpr int ROWS = 16 * MT, PASSES = (ROWS + RPP - 1) / RPP;
       typedef typename std::conditional<CH == 8, bf16x8, bf16x4>::type chunk_t;
       const int subl = ln % LPR, rgl = ln / LPR;
-      const unsigned dthr = a.drop_thresh, dkey = vg_drop_key(a.drop_key, a.drop_step);
-      const float dscale = a.drop_scale;
+      const unsigned dthr = a.drop.thr, dkey = vg_drop_key(a.drop.key, a.drop.step);
+      const float dscale = a.drop.scale;
       const unsigned drm = a.drop_row_mul > 1 ? (unsigned)a.drop_row_mul : 1u;
       auto zero_chunk = [] { chunk_t z; for (int j = 0; j < CH; ++j) z[j] = (bf16)0.f; return z; };
       auto row_sum = [&](float v) { v = rw_row16_sum(v); if (LPR == 32) v += __shfl_xor(v, 16, 64); return v; };

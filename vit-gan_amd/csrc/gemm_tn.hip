@@ -218,7 +218,7 @@ int vg_gemm_tn384_try(VgGemmProb* probs, int n, hipStream_t stream) {
     if (p.N % 384) w384 = false;
     if (p.N % 512) w512 = false;
     if ((p.lda & 7) || (p.ldb & 7) || (p.ldcf & 3) || !p.Cf || p.cf_accumulate || p.act != VG_ACT_NONE) return 0;
-    if (p.C || p.C2 || p.bias || p.res || p.resf || p.Z || p.Zf || p.row_in_per > 0 || p.drop_thresh) return 0;
+    if (p.C || p.C2 || p.bias || p.res || p.resf || p.Z || p.Zf || p.row_in_per > 0 || p.drop.thr) return 0;
     if ((long long)(p.M + 128) * p.ldcf >= (1LL << 31)) return 0;
     if ((long long)64 * (p.lda > p.ldb ? p.lda : p.ldb) * 2 >= (1LL << 31)) return 0;
   }

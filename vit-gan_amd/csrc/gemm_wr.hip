@@ -324,8 +324,8 @@ int vg_gemm_wr_try(const VgGemmProb& p, int mode, hipStream_t stream) {
   int feat = 0;
   if (p.res) feat |= WF_RES;
   if (p.C2) feat |= WF_C2;
-  if (p.drop_thresh) feat |= WF_DROP;
-  if (p.drop_thresh && p.drop_post) return 0;
+  if (p.drop.thr) feat |= WF_DROP;
+  if (p.drop.thr && p.drop_post) return 0;
   const int n_tiles = p.N / 128;
   if (n_tiles > 64) return 0;
   VgWrArgs a;

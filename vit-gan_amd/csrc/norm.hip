@@ -130,12 +130,11 @@ __global__ __launch_bounds__(256) void vg_ln_bwd_kernel(const bf16* __restrict__
                                                         const bf16* __restrict__ wmod, const float* __restrict__ gs,
                                                         const float* __restrict__ bs, float* __restrict__ dw_acc,
                                                         int dw_accumulate, int R, bf16* __restrict__ dxm,
-                                                        unsigned dthr, unsigned dkey0, float dscale,
-                                                        const unsigned* __restrict__ dstep, int drop_row_mul) {
+                                                        VgDrop drop, int drop_row_mul) {
   constexpr int E = NV * 128, CH = 128 / LPR, RPW = 64 / LPR;
   __shared__ float red[3][4][E];
   __shared__ float reds[4][2];
-  const unsigned dkey = vg_drop_key(dkey0, dstep);
+  const unsigned dkey = vg_drop_key(drop.key, drop.step);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int sub = lane % LPR, rg = lane / LPR;
   float gam[NV][CH];
@@ -222,7 +221,7 @@ __global__ __launch_bounds__(256) void vg_ln_bwd_kernel(const bf16* __restrict__
         for (int q = 0; q < CH / 4; ++q) {
           const unsigned wd = vg_drop_word(dkey, i4 + q);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) o[4 * q + j] = vg_f2bf(vg_bf2f(o[4 * q + j]) * vg_drop_factor(wd, j, dthr, dscale));
+          for (int j = 0; j < 4; ++j) o[4 * q + j] = vg_f2bf(vg_bf2f(o[4 * q + j]) * vg_drop_factor(wd, j, drop.thr, drop.scale));
         }
         if (ok) *(typename ChunkT<CH>::bt*)(dxm + (size_t)rr * E + c) = o;
       }
@@ -373,13 +372,13 @@ int vg_sln_fwd_launch(const bf16* h, int h_bcast_rows, const bf16* wmod, const f
 // one partial row per workgroup: 16 rows per workgroup pass, at most LN_MAX_PARTS workgroups (bandwidth-bound: wants many)
 int vg_ln_bwd_nparts(int R) { const int n = (R + 15) / 16; return n < LN_MAX_PARTS ? n : LN_MAX_PARTS; }
 int vg_ln_bwd_launch(const bf16* dy, const bf16* x, const float* mean, const float* rstd, const float* gamma,
-                     const bf16* gres, bf16* dx, float* part, int R, int E, bf16* dxm, unsigned dthr, unsigned dkey,
-                     float dscale, const unsigned* dstep, hipStream_t st, int x_row_step, int drop_row_mul) {
+                     const bf16* gres, bf16* dx, float* part, int R, int E, bf16* dxm, VgDrop drop,
+                     hipStream_t st, int x_row_step, int drop_row_mul) {
   if ((E & 127) || E > 1024 || R < 1 || x_row_step < 1 || drop_row_mul < 1) return -3;
   const int xb = x_row_step > 1 ? -x_row_step : 0;  // row r of the problem reads row x_row_step * r of x (the CLS rows of [B, S, E])
 #define LN_BWD(NV_) hipLaunchKernelGGL((vg_ln_bwd_kernel<false, NV_, LN_BWD_LPR>), dim3(vg_ln_bwd_nparts(R)), dim3(256), 0, st, dy, x, xb, mean, rstd, gamma, \
                      (const float*)nullptr, gres, dx, part, 3 * E, (const bf16*)nullptr, (const float*)nullptr,                                      \
-                     (const float*)nullptr, (float*)nullptr, 0, R, dxm, dthr, dkey, dscale, dstep, drop_row_mul)
+                     (const float*)nullptr, (float*)nullptr, 0, R, dxm, drop, drop_row_mul)
   NV_SWITCH(E, LN_BWD)
 #undef LN_BWD
   return (int)hipGetLastError();
@@ -387,10 +386,10 @@ int vg_ln_bwd_launch(const bf16* dy, const bf16* x, const float* mean, const flo
 int vg_sln_bwd_launch(const bf16* dy, const bf16* h, int h_bcast_rows, const bf16* wmod, const float* mean,
                       const float* rstd, const float* lw, const float* lb, const float* gs, const float* bs,
                       const bf16* gres, bf16* dh, float* dw_acc, int dw_accumulate, float* part, int R, int E,
-                      bf16* dhm, unsigned dthr, unsigned dkey, float dscale, const unsigned* dstep, hipStream_t st) {
+                      bf16* dhm, VgDrop drop, hipStream_t st) {
   if ((E & 127) || E > 1024 || R < 1) return -3;
 #define SLN_BWD(NV_) hipLaunchKernelGGL((vg_ln_bwd_kernel<true, NV_, SLN_BWD_LPR>), dim3(vg_ln_bwd_nparts(R)), dim3(256), 0, st, dy, h, h_bcast_rows, mean, \
-                     rstd, lw, lb, gres, dh, part, 3 * E + 64, wmod, gs, bs, dw_acc, dw_accumulate, R, dhm, dthr, dkey, dscale, dstep, 1)
+                     rstd, lw, lb, gres, dh, part, 3 * E + 64, wmod, gs, bs, dw_acc, dw_accumulate, R, dhm, drop, 1)
   NV_SWITCH(E, SLN_BWD)
 #undef SLN_BWD
   return (int)hipGetLastError();

@@ -29,10 +29,11 @@ struct VgChainMlpArgs {
   bf16* Y;                         // [M, 384] res + drop(fc2(a1))
   bf16* Yn; float* mean_out; float* rstd_out; const float* gamma; const float* beta; float eps;  // LayerNorm of Y (Yn nullable)
   int M, units, upw;               // units = M / 16; upw: units (active waves) per workgroup tile (both filled by the launcher)
-  unsigned drop_thresh, drop_key; float drop_scale; const unsigned* drop_step; int drop_row_mul;
+  VgDrop drop; int drop_row_mul;  // the MLP site: Y = res + drop(.)
   // ---- front: x_mid = xin + drop_a(ao Wo^T + bo);  xn_out = LayerNorm2(x_mid) feeds fc1 (ao != nullptr selects it; xn is then unused)
   const bf16* ao; const bf16* xin; const float* bo; const float* gamma2; const float* beta2;
-  bf16* xmid; bf16* xn_out; float* mean2; float* rstd2; unsigned drop_key_a;
+  bf16* xmid; bf16* xn_out; float* mean2; float* rstd2;
+  unsigned drop_key_a;            // host key of the attention site: both sites of one launch share thr, scale and step, so the second is a key
   unsigned long long* stamps;      // diagnostic builds only (CH_DBG & 64): [workgroup][wave][2 * stages + 2] s_memtime stamps
 };
 

@@ -118,6 +118,26 @@ __device__ __forceinline__ uint32_t vg_drop_key(uint32_t key, const unsigned* __
 __device__ __forceinline__ float vg_drop_factor(uint32_t word, int e, uint32_t thresh, float scale) {
   return (((word >> (8 * (e & 3))) & 0xFFu) >= thresh) ? scale : 0.f;
 }
+// One dropout site ready to launch: what every masked launcher, argument struct and kernel takes.  thr == 0 is "off"; a kernel
+// that writes a masked copy regardless then multiplies by scale, which is 1.
+struct VgDrop {
+  unsigned thr = 0, key = 0;       // round(256 p) in [0, 255]; host key of (seed, site)
+  float scale = 1.f;               // 256 / (256 - thr)
+  const unsigned* step = nullptr;  // device step counter mixed into the key by vg_drop_key (nullable)
+};
+// host key of (seed, site): splitmix64 folded to 32 bits (the engine's site numbering: include/vitgan_hip.h, vg_dropout_apply)
+static inline unsigned vg_site_key(unsigned long long seed, int site) {
+  unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(site + 1);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; z ^= z >> 31;
+  return (unsigned)(z ^ (z >> 32));
+}
+// the probabilities an entry point takes; what it answers to the others is its own (-1, or -4 from vg_linear_f32_fwd)
+static inline bool vg_drop_p_ok(float p) { return !(p < 0.f || p >= 1.f); }
+// THE derivation: p quantised to 1/256 (fp32 product, round half to even), clamped to [0, 255]
+static inline VgDrop vg_drop_site(float p, unsigned long long seed, int site, const unsigned* step) {
+  int t = (int)lrintf(p * 256.f); if (t < 0) t = 0; if (t > 255) t = 255;
+  VgDrop d; d.thr = (unsigned)t; d.key = vg_site_key(seed, site); d.scale = t ? 256.f / (256.f - (float)t) : 1.f; d.step = step; return d;
+}
 
 // Differentiable augmentation (augment.hip): the per-image parameters, a pure function of (key, step counter, image, parameter).
 //   ks = vg_drop_word(vg_drop_key(key, dstep), 0)      the launch's key: host key of (seed, site) mixed with the device step counter

@@ -39,7 +39,7 @@ __device__ __forceinline__ VgEpi vg_epi_of(const VgGemmProb& P) {
   e.N = P.N;
   // the key mixes in a counter loaded from device memory: named uniform here, it lives in a scalar register across the main
   // loop (gemm_wr.hip has no vector register to spare for it; gemm.hip does not need the hint and only its SGPR counts move)
-  e.drop_thresh = P.drop_thresh; e.drop_key = __builtin_amdgcn_readfirstlane(vg_drop_key(P.drop_key, P.drop_step)); e.drop_scale = P.drop_scale;
+  e.drop_thresh = P.drop.thr; e.drop_key = __builtin_amdgcn_readfirstlane(vg_drop_key(P.drop.key, P.drop.step)); e.drop_scale = P.drop.scale;
   e.drop_post = P.drop_post; e.drop_row_mul = P.drop_row_mul > 1 ? P.drop_row_mul : 1;
   return e;
 }

@@ -5,7 +5,7 @@
 
 // C[m][n] = sum_k A(m,k) B(k,n); A(m,k) = A[m*sam + k*sak], B(k,n) = B[k*sbk + n*sbn] (sak == 1 or sam == 1; sbn == 1 or sbk == 1).
 // Epilogue (forward forms): v = acc + bias[n]; act 1: Z[m][n] = v (nullable), v = gelu(v); act 2: v = tanh(v); v *= dropout factor of
-// element m * N + n (dthr != 0); v += res[m][n].  Input-gradient forms: act 3: v *= gelu'(aux[m][n]) (aux = pre-activation);
+// element m * N + n (drop.thr != 0); v += res[m][n].  Input-gradient forms: act 3: v *= gelu'(aux[m][n]) (aux = pre-activation);
 // act 4: v *= 1 - aux^2 (aux = tanh output).  c_split != 0 (split-K): K is cut into `splits` slices of kchunk (a multiple of 16);
 // slice z writes its own fp32 slab C + z * c_split with no epilogue, folded later in slice order.
 struct VgF32Gemm {
@@ -17,14 +17,14 @@ struct VgF32Gemm {
   const float* aux; long long ldaux;
   float* Z; long long ldz;
   const float* res; long long ldr;
-  unsigned dthr, dkey; float dscale; const unsigned* dstep;
+  VgDrop drop;
 };
 enum { VG_F32_ACT_NONE = 0, VG_F32_ACT_GELU = 1, VG_F32_ACT_TANH = 2, VG_F32_MUL_GELU = 3, VG_F32_MUL_TANH = 4 };
 int vg_f32_gemm_launch(const VgF32Gemm& g, hipStream_t st);
 
 // nn.Linear in its three forms over row-major operands: X [M,K], W [N,K], Y [M,N]
 int vg_f32_linear_fwd(const float* X, const float* W, const float* bias, const float* res, float* Y, float* Z, int M, int N, int K, int act,
-                      unsigned dthr, unsigned dkey, float dscale, const unsigned* dstep, hipStream_t st);
+                      VgDrop drop, hipStream_t st);
 int vg_f32_linear_dgrad(const float* dY, const float* W, const float* aux, float* dX, int M, int N, int K, int act, hipStream_t st);
 // dW [N,K] += dY^T X (split-K over M into slabs, folded in slice order); db [N] += column sums of dY (nullable)
 long long vg_f32_wgrad_slab_floats(int M, int N, int K);
@@ -39,7 +39,7 @@ int vg_f32_ln_param_grads(const float* dy, const float* x, long long xs, const f
                           float* part, int R, int E, hipStream_t st);
 
 // y = x * dropout mask over element indices [0, n) (the counter-based mask of vg_common.h)
-int vg_f32_dropout_launch(const float* x, float* y, long long n, unsigned dthr, unsigned dkey, float dscale, const unsigned* dstep, hipStream_t st);
+int vg_f32_dropout_launch(const float* x, float* y, long long n, VgDrop drop, hipStream_t st);
 
 // attention with dot-product scores: qkv [B*S, 3*H*HE], out [B*S, H*HE], lse [B,H,S]; HE in {32, 64, 96}, S <= 80
 int vg_f32_attn_fwd_launch(const float* qkv, float* out, float* lse, int B, int H, int S, int HE, float scale, hipStream_t st);
@@ -57,8 +57,7 @@ int vg_f32_ln_bwd_launch(const float* dy, const float* x, long long xs, const fl
 // patch embedding: img [B,C,IH,IH] <-> tiles [B*NP, C*P*P] (backward: d_img from d_tiles; every pixel lies in exactly one tile)
 int vg_f32_patchify_launch(const float* img, float* tiles, int B, int C, int IH, int P, int backward, hipStream_t st);
 // X[b*S + s] = mask * (s == 0 ? cls : tok[b*NP + s-1] + pos[s-1]), mask of element (b*S + s) * E + e
-int vg_f32_embed_assemble_launch(const float* tok, const float* pos, const float* cls, float* X, int B, int S, int E, unsigned dthr,
-                                 unsigned dkey, float dscale, const unsigned* dstep, hipStream_t st);
+int vg_f32_embed_assemble_launch(const float* tok, const float* pos, const float* cls, float* X, int B, int S, int E, VgDrop drop,
+                                 hipStream_t st);
 // gm = g * mask over [B*S, E]; gt[b*NP + p] = gm[b*S + 1 + p]
-int vg_f32_embed_grad_launch(const float* g, float* gm, float* gt, int B, int S, int E, unsigned dthr, unsigned dkey, float dscale,
-                             const unsigned* dstep, hipStream_t st);
+int vg_f32_embed_grad_launch(const float* g, float* gm, float* gt, int B, int S, int E, VgDrop drop, hipStream_t st);

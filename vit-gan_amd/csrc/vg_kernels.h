@@ -21,12 +21,12 @@ int vg_sln_fwd_launch(const bf16* h, int h_bcast_rows, const bf16* wmod, const f
                       hipStream_t st);
 int vg_ln_bwd_nparts(int R);
 int vg_ln_bwd_launch(const bf16* dy, const bf16* x, const float* mean, const float* rstd, const float* gamma,
-                     const bf16* gres, bf16* dx, float* part, int R, int E, bf16* dxm, unsigned dthr, unsigned dkey,
-                     float dscale, const unsigned* dstep, hipStream_t st, int x_row_step = 1, int drop_row_mul = 1);  // drop_row_mul: dxm's mask is that of row r * drop_row_mul of the full tensor
+                     const bf16* gres, bf16* dx, float* part, int R, int E, bf16* dxm, VgDrop drop,
+                     hipStream_t st, int x_row_step = 1, int drop_row_mul = 1);  // drop_row_mul: dxm's mask is that of row r * drop_row_mul of the full tensor
 int vg_sln_bwd_launch(const bf16* dy, const bf16* h, int h_bcast_rows, const bf16* wmod, const float* mean,
                       const float* rstd, const float* lw, const float* lb, const float* gs, const float* bs,
                       const bf16* gres, bf16* dh, float* dw_acc, int dw_accumulate, float* part, int R, int E,
-                      bf16* dhm, unsigned dthr, unsigned dkey, float dscale, const unsigned* dstep, hipStream_t st);
+                      bf16* dhm, VgDrop drop, hipStream_t st);
 int vg_colsum_f32_launch(const float* part, int rows, int width, float* d0, int n0, float* d1, int n1, float* d2, int n2,
                          float* d3, int n3, int accumulate, hipStream_t st);
 #include "vg_fold.h"
@@ -41,21 +41,18 @@ int vg_unpatchify_launch(const bf16* dA, bf16* dimg, int B, int C, int IH, int P
 // the patch embedding and its backward as one launch per side where vg_embed_fused_ok() (embed.hip): E = 384, 4 x 4 patches, C <= 4
 int vg_embed_fused_ok(int C, int IH, int P, int E);
 int vg_embed_fwd_launch(const void* img, int img_is_bf16, const bf16* W, const float* bias, const float* pos, const float* cls, const float* gamma,
-                        const float* beta, bf16* Apatch, bf16* X, bf16* Xn, float* mean, float* rstd, int B, int C, int IH, float eps, unsigned dthr,
-                        unsigned dkey, float dscale, const unsigned* dstep, hipStream_t st);
+                        const float* beta, bf16* Apatch, bf16* X, bf16* Xn, float* mean, float* rstd, int B, int C, int IH, float eps, VgDrop drop,
+                        hipStream_t st);
 int vg_embed_dimg_launch(const bf16* g, const bf16* W, bf16* dimg, int B, int C, int IH, hipStream_t st);
 int vg_embed_wgrad_launch(const bf16* g, const bf16* Apatch, float* slab, float* tok_sum, float* d_w, float* d_bias, float* d_pos, float* d_cls, int B,
                           int C, int IH, int splits, hipStream_t st);
 int vg_unfold_tokens_launch(const void* img, int img_is_bf16, bf16* out, int B, int C, int IH, int P, int overlap, hipStream_t st);
 int vg_unfold_tokens_bwd_launch(const bf16* dout, bf16* dimg, int B, int C, int IH, int P, int overlap, hipStream_t st);
-int vg_fill_cls_launch(bf16* x, const float* cls, int B, int S, int E, unsigned dthr, unsigned dkey, float dscale, const unsigned* dstep,
-                       hipStream_t st);
-int vg_dropout_apply_launch(const bf16* x, bf16* y, long long n, unsigned dthr, unsigned dkey, float dscale, const unsigned* dstep,
-                            hipStream_t st);
+int vg_fill_cls_launch(bf16* x, const float* cls, int B, int S, int E, VgDrop drop, hipStream_t st);
+int vg_dropout_apply_launch(const bf16* x, bf16* y, long long n, VgDrop drop, hipStream_t st);
 int vg_take_rows_launch(const bf16* in, bf16* out, int B, int S, int first, int n_take, int E, hipStream_t st);
-// gm (nullable): the same rows times the dropout mask of site key dkey over the [B*S, E] buffer (what vg_dropout_apply would make of g)
-int vg_scatter_cls_launch(const bf16* src, bf16* g, int B, int S, int E, hipStream_t st, bf16* gm = nullptr, unsigned dthr = 0, unsigned dkey = 0,
-                          float dscale = 1.f, const unsigned* dstep = nullptr);
+// gm (nullable): the same rows times the dropout mask of site `drop` over the [B*S, E] buffer (what vg_dropout_apply would make of g)
+int vg_scatter_cls_launch(const bf16* src, bf16* g, int B, int S, int E, hipStream_t st, bf16* gm = nullptr, VgDrop drop = VgDrop());
 // two compact [B, E] sources into the CLS rows of two zero-filled [B*S, E] tensors, one launch (the pruned tail of the top encoder block)
 int vg_scatter_cls2_launch(const bf16* src_a, bf16* dst_a, const bf16* src_b, bf16* dst_b, int B, int S, int E, hipStream_t st);
 int vg_batch_sum_launch(const bf16* g, float* out, int B, int S, int E, hipStream_t st);
@@ -113,13 +110,6 @@ int vg_slab_reduce2_launch(const float* slab0, const float* slab1, long long str
                            hipStream_t st);
 int vg_sin_grad_launch(const bf16* dy, const float* z, bf16* dz, long long n, float w0, hipStream_t st);
 
-// dropout key of (seed, site): splitmix64 folded to 32 bits (the engine's site numbering: include/vitgan_hip.h, vg_dropout_apply)
-static inline unsigned vg_site_key(unsigned long long seed, int site) {
-  unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(site + 1);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull; z = (z ^ (z >> 27)) * 0x94D049BB133111EBull; z ^= z >> 31;
-  return (unsigned)(z ^ (z >> 32));
-}
-
 // host helpers of the whole-network passes (engine.hip, engine_f32.hip): the workspace carver and the dropout of a call
 struct Carver {
   unsigned char* base; long long off;
@@ -129,11 +119,11 @@ struct Carver {
     return p;
   }
 };
-struct Drop { unsigned thr; float scale; unsigned long long seed; const unsigned* step; };
-static inline Drop mk_drop(float p, unsigned long long seed, const unsigned* step) {  // p quantised to 1/256
-  Drop d; int t = (int)lrintf(p * 256.f); if (t < 0) t = 0; if (t > 255) t = 255;
-  d.thr = (unsigned)t; d.scale = t ? 256.f / (256.f - (float)t) : 1.f; d.seed = seed; d.step = step; return d;
-}
+struct Drop {  // what a whole call knows; a launch takes at(site)
+  float p; unsigned long long seed; const unsigned* step;
+  VgDrop at(int site) const { return vg_drop_site(p, seed, site, step); }
+  bool on() const { return at(0).thr != 0; }
+};
 
 #define VG_TRY(expr)            \
   do {                          \

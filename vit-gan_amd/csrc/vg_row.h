@@ -45,7 +45,7 @@ struct VgRowArgs {
   int part_w;              // LNBWD: row stride of part (filled by the launcher: 3*384, or 3*384 + 64 with wmod)
   // ---- both -------------------------------------------------------------------------------------------------------
   const float* gamma;      // [384]
-  unsigned drop_thresh, drop_key; float drop_scale; const unsigned* drop_step;  // LNFWD: mask of drop(.); LNBWD: mask of dxm
+  VgDrop drop;            // LNFWD: mask of drop(.); LNBWD: mask of dxm
   int drop_row_mul;        // > 1: row m of this problem draws the mask bits of row m * drop_row_mul of a larger tensor (the CLS rows of [B*S, 384])
 };
 
