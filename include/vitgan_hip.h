@@ -604,6 +604,28 @@ int vg_spectral_project(float* G, const float* W, long long total, const float* 
 int vg_moments_update(const float* feats, long long ld, int n, int d, double* sum /*[d]*/, double* gram /*[d, d]*/, void* stream);
 int vg_moments_finish(const double* sum, const double* gram, long long n, int d, double* mean /*[d]*/, double* cov /*[d, d]*/, void* stream);
 
+/* ABI v9 (additive).  Arithmetic on PAIRS of feature vectors (pairwise.hip): what precision / recall / density / coverage and KID
+ * need beyond the moments.  Features fp32 [n, d] with a row stride in floats, widened exactly; every product and sum fp64 on
+ * v_mfma_f64_16x16x4_f64.  Squared Euclidean distances d2(q_i, c_j) = max((|q_i|^2 + |c_j|^2) - 2 q_i.c_j, 0), where the norms are
+ * the diagonal of the SAME product chain as the dots: bit-equal rows are at distance exactly 0.0.  Comparisons are inclusive.
+ * No n x n buffer exists: tiles live in registers, `ws` (vg_pair_ws_bytes(nq, nc, k) bytes, k = 0 where there is none) holds the norms
+ * and the per-column-split partials.  The split count depends on (nq, nc) only and partials are merged in split order, without
+ * atomics: two runs are bit-equal; rad2, count and min_d2 are also bit-identical under any permutation of the centre rows.
+ *
+ * vg_knn_radii:  rad2[i] = the k-th smallest of { d2(x_i, x_j) : j != i }, the self-exclusion BY INDEX (a duplicate row at another
+ *   index is a neighbour at 0.0).
+ * vg_ball_counts:  count[i] = #{ j : d2(q_i, c_j) <= rad2_c[j] },  min_d2[i] = min_j d2(q_i, c_j).
+ * vg_poly_kernel_sum:  out[0] = sum_ij (q_i.c_j / d + 1)^3, with skip_diagonal != 0 without the terms i == j; per-workgroup partials
+ *   folded by one owner in index order.
+ * All enqueue-only on `stream`.  Errors, before any launch: -1 a NULL pointer or an empty set; -2 d outside [16, 2048], d % 16 != 0
+ * or a row stride below d; -3 k outside [1, 8] or k >= n.  vg_pair_ws_bytes: -1 for an empty set or k outside [0, 8]. */
+long long vg_pair_ws_bytes(int nq, int nc, int k);
+int vg_knn_radii(const float* X, long long ld, int n, int d, int k, double* rad2 /*[n]*/, void* ws, void* stream);
+int vg_ball_counts(const float* Q, long long ldq, int nq, const float* Cn, long long ldc, int nc, int d, const double* rad2_c /*[nc]*/,
+                   int* count /*[nq]*/, double* min_d2 /*[nq]*/, void* ws, void* stream);
+int vg_poly_kernel_sum(const float* Q, long long ldq, int nq, const float* Cn, long long ldc, int nc, int d, int skip_diagonal,
+                       double* out /*[1]*/, void* ws, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Whole-network passes (what the nn.Modules call: one C call per forward / backward)
  * ---------------------------------------------------------------------------------------- */

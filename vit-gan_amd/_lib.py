@@ -177,6 +177,10 @@ _SIGNATURES = {
     "vg_vit_features": (c_int, [C.POINTER(VgVitNet), c_int, P, c_int, P, P, P, P]),
     "vg_moments_update": (c_int, [P, c_ll, c_int, c_int, P, P, P]),
     "vg_moments_finish": (c_int, [P, P, c_ll, c_int, P, P, P]),
+    "vg_pair_ws_bytes": (c_ll, [c_int, c_int, c_int]),
+    "vg_knn_radii": (c_int, [P, c_ll, c_int, c_int, c_int, P, P, P]),
+    "vg_ball_counts": (c_int, [P, c_ll, c_int, P, c_ll, c_int, c_int, P, P, P, P, P]),
+    "vg_poly_kernel_sum": (c_int, [P, c_ll, c_int, P, c_ll, c_int, c_int, c_int, P, P, P]),
     "vg_vit_backward": (c_int, [C.POINTER(VgVitNet), c_int, P, P, P, c_int, P]),
     "vg_vit_backward_stages": (c_int, [C.POINTER(VgVitNet), c_int, P, P, P, c_int, c_int, c_int, P]),
     "vg_vit_penalty_ws_bytes": (c_ll, [C.POINTER(VgVitDims), c_int]),

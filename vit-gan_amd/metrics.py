@@ -176,6 +176,156 @@ def frechet_distance(mu1, cov1, mu2, cov2) -> float:
     return max(a + b, 0.0)
 
 
+# ------------------------------------------------------------------------------------------------------------ pairs of features
+# What the moments throw away.  Squared Euclidean distances in fp64, every comparison inclusive:
+#   rad2_k(x_i; X)  the k-th smallest of { |x_i - x_j|^2 : j != i } - self excluded BY INDEX, a duplicate elsewhere is a neighbour at 0
+#   precision       the share of fake g with |g - r_j|^2 <= rad2_k(r_j; R) for some real r_j          (Kynkaanniemi et al. 2019)
+#   recall          the share of real r with |r - g_i|^2 <= rad2_k(g_i; G) for some fake g_i          (the same paper)
+#   density         1 / (k M) sum_i #{ j : |g_i - r_j|^2 <= rad2_k(r_j; R) }, M fakes                 (Naeem et al. 2020)
+#   coverage        the share of real r_j with min_i |r_j - g_i|^2 <= rad2_k(r_j; R)                  (the same paper)
+#   KID             the unbiased MMD^2 estimate with kappa(a, b) = (a.b / d + 1)^3 over the FULL sets (Binkowski et al. 2018):
+#                   ONE estimate, not the mean over subsets that the paper's code reports
+# On the device each is one launch of csrc/pairwise.hip (fp64 MFMA, no n x n buffer); a CPU tensor takes plain torch fp64.
+K_MAX = 8  # vg_knn_radii keeps the k smallest in registers
+
+
+def _check_feats(x: torch.Tensor, what: str) -> torch.Tensor:
+    if not torch.is_tensor(x) or x.dim() != 2 or x.shape[0] < 1:
+        raise ValueError(f"{what}: features must be an [n >= 1, d] tensor, got {tuple(getattr(x, 'shape', ())) or type(x).__name__}")
+    _check_d(x.shape[1])
+    if x.dtype in (torch.bfloat16, torch.float16):
+        x = x.float()
+    if x.dtype != torch.float32:
+        raise TypeError(f"{what}: features must be fp32, bf16 or fp16, got {x.dtype}")
+    x = x.detach()
+    if x.is_cuda and (x.stride(1) != 1 or x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    return x
+
+
+def _check_pair(q: torch.Tensor, c: torch.Tensor, what: str):
+    q, c = _check_feats(q, what), _check_feats(c, what)
+    if q.shape[1] != c.shape[1]:
+        raise ValueError(f"{what}: the widths differ, {q.shape[1]} and {c.shape[1]}")
+    if q.device != c.device:
+        raise ValueError(f"{what}: the two sets are on {q.device} and {c.device}")
+    return q, c
+
+
+def _check_k(k, n: int, what: str) -> int:
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= K_MAX:
+        raise ValueError(f"{what}: k must be an integer in [1, {K_MAX}], got {k!r}")
+    if k >= n:
+        raise ValueError(f"{what}: k = {k} needs more than k rows, got {n}")
+    return k
+
+
+def _pair_ws(nq: int, nc: int, k: int, device) -> torch.Tensor:
+    nbytes = _lib.lib().vg_pair_ws_bytes(nq, nc, k)
+    if nbytes <= 0:
+        raise RuntimeError("vg_pair_ws_bytes failed")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _cpu_d2(q: torch.Tensor, c: torch.Tensor):
+    """blocks (lo, d2 [b, nc]) of squared distances from DIFFERENCES in fp64, at most 2^24 elements at a time"""
+    q64, c64 = q.double(), c.double()
+    step = max(1, (1 << 24) // max(1, c64.shape[0] * c64.shape[1]))
+    for lo in range(0, q64.shape[0], step):
+        yield lo, ((q64[lo:lo + step, None, :] - c64[None, :, :]) ** 2).sum(-1)
+
+
+def knn_radii(x: torch.Tensor, k: int) -> torch.Tensor:
+    """fp64 [n]: the squared distance from each row of ``x`` [n, d] to its k-th nearest OTHER row (1 <= k <= 8, k < n)."""
+    x = _check_feats(x, "knn_radii")
+    n, d = int(x.shape[0]), int(x.shape[1])
+    k = _check_k(k, n, "knn_radii")
+    if x.is_cuda:
+        rad2 = torch.empty(n, dtype=torch.float64, device=x.device)
+        with torch.cuda.device(x.device):
+            ws = _pair_ws(n, n, k, x.device)
+            _lib.check(_lib.lib().vg_knn_radii(x.data_ptr(), x.stride(0), n, d, k, rad2.data_ptr(), ws.data_ptr(), _stream()), "vg_knn_radii")
+        return rad2
+    out = []
+    for lo, d2 in _cpu_d2(x, x):
+        rows = torch.arange(d2.shape[0])
+        d2[rows, lo + rows] = float("inf")
+        out.append(torch.kthvalue(d2, k, dim=1).values)
+    return torch.cat(out)
+
+
+def ball_counts(q: torch.Tensor, c: torch.Tensor, rad2_c: torch.Tensor):
+    """(count int32 [nq], min_d2 fp64 [nq]): for each row of ``q`` the number of centres ``c_j`` with |q - c_j|^2 <= rad2_c[j], and its
+    squared distance to the nearest centre.  No self-exclusion: the two sets are different sets."""
+    q, c = _check_pair(q, c, "ball_counts")
+    nq, nc, d = int(q.shape[0]), int(c.shape[0]), int(q.shape[1])
+    if not torch.is_tensor(rad2_c) or rad2_c.dtype != torch.float64 or tuple(rad2_c.shape) != (nc,) or rad2_c.device != c.device:
+        raise ValueError(f"ball_counts: rad2_c must be an fp64 [{nc}] tensor on {c.device}, got {getattr(rad2_c, 'dtype', None)} "
+                         f"{tuple(getattr(rad2_c, 'shape', ()))} on {getattr(rad2_c, 'device', None)}")
+    rad2_c = rad2_c.detach().contiguous()
+    if q.is_cuda:
+        count = torch.empty(nq, dtype=torch.int32, device=q.device)
+        min_d2 = torch.empty(nq, dtype=torch.float64, device=q.device)
+        with torch.cuda.device(q.device):
+            ws = _pair_ws(nq, nc, 0, q.device)
+            _lib.check(_lib.lib().vg_ball_counts(q.data_ptr(), q.stride(0), nq, c.data_ptr(), c.stride(0), nc, d, rad2_c.data_ptr(),
+                                                 count.data_ptr(), min_d2.data_ptr(), ws.data_ptr(), _stream()), "vg_ball_counts")
+        return count, min_d2
+    counts, mins = [], []
+    for _, d2 in _cpu_d2(q, c):
+        counts.append((d2 <= rad2_c[None, :]).sum(1).to(torch.int32))
+        mins.append(d2.min(1).values)
+    return torch.cat(counts), torch.cat(mins)
+
+
+def poly_kernel_sum(q: torch.Tensor, c: torch.Tensor, skip_diagonal: bool = False) -> torch.Tensor:
+    """fp64 scalar tensor: sum_ij (q_i . c_j / d + 1)^3, with ``skip_diagonal`` without the terms i == j."""
+    q, c = _check_pair(q, c, "poly_kernel_sum")
+    nq, nc, d = int(q.shape[0]), int(c.shape[0]), int(q.shape[1])
+    if q.is_cuda:
+        out = torch.empty(1, dtype=torch.float64, device=q.device)
+        with torch.cuda.device(q.device):
+            ws = _pair_ws(nq, nc, 0, q.device)
+            _lib.check(_lib.lib().vg_poly_kernel_sum(q.data_ptr(), q.stride(0), nq, c.data_ptr(), c.stride(0), nc, d, int(bool(skip_diagonal)),
+                                                     out.data_ptr(), ws.data_ptr(), _stream()), "vg_poly_kernel_sum")
+        return out[0]
+    kap = (q.double() @ c.double().t() / float(d) + 1.0) ** 3
+    total = kap.sum()
+    return total - torch.diagonal(kap).sum() if skip_diagonal else total
+
+
+def _prdc_from(count_g: torch.Tensor, count_r: torch.Tensor, min_r: torch.Tensor, rad2_r: torch.Tensor, k: int) -> Dict[str, float]:
+    """the four ratios from the two launches' outputs: integer counts over integer sizes, one division each"""
+    M, N = int(count_g.shape[0]), int(count_r.shape[0])
+    return {"precision": int((count_g > 0).sum()) / M, "recall": int((count_r > 0).sum()) / N,
+            "density": int(count_g.sum(dtype=torch.int64)) / (k * M), "coverage": int((min_r <= rad2_r).sum()) / N}
+
+
+def prdc(real: torch.Tensor, fake: torch.Tensor, k: int) -> Dict[str, float]:
+    """``dict(precision, recall, density, coverage)`` of ``fake`` [M, d] against ``real`` [N, d] with k-th-neighbour radii (the
+    definitions above).  Precision and recall depend on N and M: compare runs at the same sizes only."""
+    real, fake = _check_pair(real, fake, "prdc")
+    k = _check_k(k, min(int(real.shape[0]), int(fake.shape[0])), "prdc")
+    rad2_r, rad2_g = knn_radii(real, k), knn_radii(fake, k)
+    count_g, _ = ball_counts(fake, real, rad2_r)
+    count_r, min_r = ball_counts(real, fake, rad2_g)
+    return _prdc_from(count_g, count_r, min_r, rad2_r, k)
+
+
+def _kid_from(s_gg: float, s_rr: float, s_gr: float, M: int, N: int) -> float:
+    return s_gg / (M * (M - 1)) + s_rr / (N * (N - 1)) - 2.0 * s_gr / (M * N)
+
+
+def kid(real: torch.Tensor, fake: torch.Tensor) -> float:
+    """The unbiased MMD^2 estimate with the cubic kernel (a.b / d + 1)^3 over the FULL sets - one estimate, not the subset-bootstrap
+    mean of Binkowski et al.'s code; both sets need at least 2 rows."""
+    real, fake = _check_pair(real, fake, "kid")
+    M, N = int(fake.shape[0]), int(real.shape[0])
+    if M < 2 or N < 2:
+        raise ValueError(f"kid: both sets need at least 2 rows, got {N} real and {M} fake")
+    return _kid_from(float(poly_kernel_sum(fake, fake, True)), float(poly_kernel_sum(real, real, True)), float(poly_kernel_sum(fake, real)), M, N)
+
+
 # ------------------------------------------------------------------------------------------------------------------ feature nets
 def _vit_dims_tuple(dims) -> tuple:
     return tuple(int(getattr(dims, k)) for k in ("C", "IH", "P", "E", "H", "L", "R", "Kc"))
@@ -281,10 +431,31 @@ class FrechetDistance:
     of ``batch`` (a smaller last one), each batch goes through the feature network into a ``FeatureMoments``.  ``quantize``: the
     reference's uint8 treatment of the images (``quantize_images``) through the real set's own decode table.  ``ema``: score the
     averaged generator where the trainer keeps one (False: the raw one).  After a call ``last`` holds
-    ``dict(distance, mean_term, trace_term, n_real, n_fake)``."""
+    ``dict(distance, mean_term, trace_term, n_real, n_fake)``.
+
+    ``manifold_k`` (1..8) and ``kid`` switch on what a single distance cannot say - whether a run lost fidelity or coverage:
+    precision / recall / density / coverage with k-th-neighbour radii, and the full-set KID (the definitions above ``knn_radii``).
+    With either on, ``fit_real`` also keeps up to ``bank_real`` real feature rows on the device - of a ``DeviceDataset`` the images
+    at the evenly spaced indices floor(j N / n_keep), of an iterable the first n_keep seen; they are rows of the pass it makes anyway -
+    with their radii and their kernel self-sum, computed once; a call keeps the fake features of its ONE generator pass (no launch of
+    the generator or the feature net is added) and ``last`` gains ``precision, recall, density, coverage, kid`` (NaN for the half that is
+    off), ``manifold_k`` and ``n_real_bank``.  The return value stays the Frechet distance.  Like it, these numbers rank the epochs
+    of one run on a random ViT; they are not comparable with published values, and precision / recall depend on N and M.  Every rank
+    of a multi-rank run evaluates alike; nothing here is sharded."""
 
     def __init__(self, features, n_fake: int = 10000, batch: int = 256, seed: int = 0, quantize: bool = True, ema: bool = True,
-                 tag: Optional[str] = None):
+                 tag: Optional[str] = None, manifold_k: int = 0, kid: bool = False, bank_real: int = 10000):
+        if isinstance(manifold_k, bool) or not isinstance(manifold_k, int) or not 0 <= manifold_k <= K_MAX:
+            raise ValueError(f"manifold_k must be an integer in [0, {K_MAX}] (0: off), got {manifold_k!r}")
+        if not isinstance(kid, bool):
+            raise ValueError(f"kid must be a bool, got {kid!r}")
+        if isinstance(bank_real, bool) or not isinstance(bank_real, int) or bank_real < 2:
+            raise ValueError(f"bank_real must be an integer >= 2, got {bank_real!r}")
+        if manifold_k and isinstance(n_fake, int) and manifold_k >= n_fake:
+            raise ValueError(f"manifold_k = {manifold_k} needs more than k generated images, n_fake is {n_fake!r}")
+        self.manifold_k, self.kid, self.bank_real = manifold_k, kid, bank_real
+        self.bank: Optional[Dict[str, Any]] = None  # feats fp32 [n_keep, d]; rad2 fp64 [n_keep] with its k; self_sum
+        self.fake_feats: Optional[torch.Tensor] = None  # the last call's features, kept only with an option on
         if isinstance(n_fake, bool) or int(n_fake) != n_fake or n_fake < 2:
             raise ValueError(f"n_fake must be an integer >= 2, got {n_fake!r}")
         if isinstance(batch, bool) or int(batch) != batch or batch < 1:
@@ -328,11 +499,33 @@ class FrechetDistance:
         _check_d(f.shape[1])
         return f
 
-    def _accumulate(self, acc: Optional[FeatureMoments], images: torch.Tensor) -> FeatureMoments:
+    def _accumulate(self, acc: Optional[FeatureMoments], images: torch.Tensor, keep: Optional[list] = None, rows=None) -> FeatureMoments:
+        """one feature pass over ``images`` into ``acc``; with ``keep``, its rows ``rows`` (all of them: None) are kept as fp32"""
         f = self._feats(images)
         if acc is None:
             acc = FeatureMoments(f.shape[1], f.device)
+        if keep is not None and (rows is None or len(rows)):
+            keep.append((f if rows is None else f[torch.as_tensor(rows, device=f.device)]).detach().float())
         return acc.update(f)
+
+    @property
+    def _wants_bank(self) -> bool:
+        return bool(self.manifold_k) or self.kid
+
+    def _bank_ready(self, device) -> Dict[str, Any]:
+        """the real bank on ``device`` with what the options need: radii at this evaluator's k, the kernel self-sum - computed once"""
+        b = self.bank
+        if b is None:
+            raise RuntimeError(f"FrechetDistance: {'manifold_k' if self.manifold_k else 'kid'} needs the real feature bank and there "
+                               "is none; call fit_real, or load_real a file written with the option on")
+        if b["feats"].device != device:
+            b["feats"] = b["feats"].to(device)
+            b["rad2"] = None if b["rad2"] is None else b["rad2"].to(device)
+        if self.manifold_k and (b["rad2"] is None or b["k"] != self.manifold_k):
+            b["rad2"], b["k"] = knn_radii(b["feats"], self.manifold_k), self.manifold_k  # ValueError: k >= the rows kept
+        if self.kid and b["self_sum"] is None:
+            b["self_sum"] = float(poly_kernel_sum(b["feats"], b["feats"], True))
+        return b
 
     def fit_real(self, source: Union[DeviceDataset, Iterable]) -> "FrechetDistance":
         """The real set's moments, cached.  A ``DeviceDataset`` is visited in storage order, unflipped, ALL N images - the tail that
@@ -340,11 +533,18 @@ class FrechetDistance:
         Anything else is an iterable of image batches (or ``(images, labels)`` pairs): uint8 batches go through the table, float
         batches through ``quantize_images`` when ``quantize`` is on."""
         acc: Optional[FeatureMoments] = None
+        keep: Optional[list] = [] if self._wants_bank else None
+        kept = 0
         with torch.no_grad():
             if isinstance(source, DeviceDataset):
                 self.lut = source.lut.detach().float().cpu()
+                n_keep = min(self.bank_real, source.N)
+                picks = [(j * source.N) // n_keep for j in range(n_keep)] if keep is not None else []
                 for lo in range(0, source.N, self.batch):
-                    acc = self._accumulate(acc, source.decode(torch.arange(lo, min(lo + self.batch, source.N))))
+                    hi = min(lo + self.batch, source.N)
+                    rows = [p - lo for p in picks[kept:kept + self.batch] if p < hi] if keep is not None else None
+                    kept += len(rows or ())
+                    acc = self._accumulate(acc, source.decode(torch.arange(lo, hi)), keep, rows)
             else:
                 for item in source:
                     x = item[0] if isinstance(item, (tuple, list)) else item
@@ -356,29 +556,51 @@ class FrechetDistance:
                     elif self.quantize:
                         x = quantize_images(x, self.lut)
                     for lo in range(0, x.shape[0], self.batch):
-                        acc = self._accumulate(acc, x[lo:lo + self.batch])
+                        part = x[lo:lo + self.batch]
+                        take = min(part.shape[0], self.bank_real - kept) if keep is not None else 0
+                        kept += take
+                        acc = self._accumulate(acc, part, keep if take else None, None if take == part.shape[0] else list(range(take)))
         if acc is None or acc.n < 2:
             raise ValueError("fit_real: the source held fewer than 2 images")
         mean, cov = acc.moments()
         self.real = {"mean": mean, "cov": cov, "n": acc.n, "d": acc.d}
+        if keep is not None:
+            self.bank = {"feats": torch.cat(keep).contiguous(), "rad2": None, "k": 0, "self_sum": None}
+            self._bank_ready(self.bank["feats"].device)
         return self
 
     def save_real(self, path: str) -> None:
-        """mean, cov, n, d, the feature net's tag and the decode table as an ``.npz``."""
+        """mean, cov, n, d, the feature net's tag and the decode table as an ``.npz``; with a real feature bank also ``bank_feats``,
+        ``bank_k``, ``bank_rad2`` and ``bank_self_sum`` (NaN: not computed)."""
         if self.real is None:
             raise RuntimeError("save_real: no real statistics; call fit_real first")
+        extra = {}
+        if self.bank is not None:
+            b = self.bank
+            extra = {"bank_feats": b["feats"].cpu().numpy(), "bank_k": np.int64(b["k"] if b["rad2"] is not None else 0),
+                     "bank_rad2": b["rad2"].cpu().numpy() if b["rad2"] is not None else np.zeros(0),
+                     "bank_self_sum": np.float64(float("nan") if b["self_sum"] is None else b["self_sum"])}
         with open(path, "wb") as handle:  # a handle: numpy appends no suffix
             np.savez(handle, mean=self.real["mean"], cov=self.real["cov"], n=np.int64(self.real["n"]), d=np.int64(self.real["d"]),
-                     tag=np.array(self.tag), lut=self.lut.numpy())
+                     tag=np.array(self.tag), lut=self.lut.numpy(), **extra)
 
     def load_real(self, path: str) -> "FrechetDistance":
-        """Statistics written by ``save_real``; a file made under another feature network (tag) raises."""
+        """Statistics written by ``save_real``; a file made under another feature network (tag) raises, and so does a file without the
+        real feature bank when ``manifold_k`` or ``kid`` is on (the message names the option)."""
         with np.load(path, allow_pickle=False) as z:
             tag = str(z["tag"])
             if tag != self.tag:
                 raise ValueError(f"load_real: {path} holds the statistics of feature net {tag!r}, this evaluator's is {self.tag!r}")
             self.real = {"mean": z["mean"].astype(np.float64), "cov": z["cov"].astype(np.float64), "n": int(z["n"]), "d": int(z["d"])}
             self.lut = torch.from_numpy(z["lut"].astype(np.float32))
+            self.bank = None
+            if "bank_feats" in z.files:
+                k, ss = int(z["bank_k"]), float(z["bank_self_sum"])
+                self.bank = {"feats": torch.from_numpy(z["bank_feats"].astype(np.float32)), "k": k,
+                             "rad2": torch.from_numpy(z["bank_rad2"].astype(np.float64)) if k else None, "self_sum": None if ss != ss else ss}
+            elif self._wants_bank:
+                raise ValueError(f"load_real: {path} holds no real feature bank, which {'manifold_k' if self.manifold_k else 'kid'} needs; "
+                                 "write it with fit_real and save_real on an evaluator with the option on")
         return self
 
     # -- the generated side ------------------------------------------------------------------------------
@@ -401,13 +623,16 @@ class FrechetDistance:
         device = p.device if p is not None else torch.device("cpu")
         was = G.training
         G.eval()
+        if self._wants_bank and self.bank is None:
+            self._bank_ready(device)  # raises, naming the option
         acc: Optional[FeatureMoments] = None
+        keep: Optional[list] = [] if self._wants_bank else None
         try:
             with torch.no_grad():
                 for z, labels in self.latents(G, device):
                     x = G(z) if labels is None else G(z, labels)
                     x = quantize_images(x, self.lut) if self.quantize else x.float()
-                    acc = self._accumulate(acc, x)
+                    acc = self._accumulate(acc, x, keep)
         finally:
             G.train(was)
         if acc.d != self.real["d"]:
@@ -416,7 +641,28 @@ class FrechetDistance:
         mean, cov = acc.moments()
         a, b = frechet_terms(self.real["mean"], self.real["cov"], mean, cov)
         self.last = {"distance": max(a + b, 0.0), "mean_term": a, "trace_term": b, "n_real": self.real["n"], "n_fake": acc.n}
+        if keep is not None:
+            self.last.update(self._pair_metrics(torch.cat(keep).contiguous()))
         return self.last["distance"]
 
+    def _pair_metrics(self, fake: torch.Tensor) -> Dict[str, Any]:
+        """the manifold metrics and KID of the kept fake features against the real bank: the fakes' radii, two ball-count launches
+        (fakes in the reals' balls; reals in the fakes' balls, with each real's nearest fake), two kernel sums"""
+        bank = self._bank_ready(fake.device)
+        real = bank["feats"]
+        self.fake_feats = fake
+        nan = float("nan")
+        out: Dict[str, Any] = {"precision": nan, "recall": nan, "density": nan, "coverage": nan, "kid": nan,
+                               "manifold_k": self.manifold_k, "n_real_bank": int(real.shape[0])}
+        if self.manifold_k:
+            count_g, _ = ball_counts(fake, real, bank["rad2"])
+            count_r, min_r = ball_counts(real, fake, knn_radii(fake, self.manifold_k))
+            out.update(_prdc_from(count_g, count_r, min_r, bank["rad2"], self.manifold_k))
+        if self.kid:
+            M, N = int(fake.shape[0]), int(real.shape[0])
+            out["kid"] = _kid_from(float(poly_kernel_sum(fake, fake, True)), bank["self_sum"], float(poly_kernel_sum(fake, real)), M, N)
+        return out
 
-__all__ = ["FeatureMoments", "FrechetDistance", "FrozenViTFeatures", "frechet_distance", "frechet_terms", "quantize_images"]
+
+__all__ = ["FeatureMoments", "FrechetDistance", "FrozenViTFeatures", "frechet_distance", "frechet_terms", "quantize_images",
+           "knn_radii", "ball_counts", "poly_kernel_sum", "prdc", "kid"]

@@ -257,7 +257,7 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                 r1_gamma: float = 0.0, r1_interval: int = 1, conditional: bool = False,
                 lr_schedule: str = "", lr_warmup: int = 0, lr_total: Optional[int] = None, lr_final: float = 0.0,
                 lr_plateau: Optional[Tuple[float, int]] = None, dataset: Optional[DeviceDataset] = None,
-                fid: str = "", fid_samples: int = 10000):
+                fid: str = "", fid_samples: int = 10000, manifold_k: int = 0, kid: bool = False):
     """``loss``: "ns" (default: the executable v1 loss), "hinge", or "wasserstein" - the critic losses of the reference's
     unreached step (training.py:67-125); ``clip_d`` / ``clip_g``: its clip_grad_norm_ limits (5.0 / 0.5 there);
     ``diversity_weight``: its diversity term (0.1 there); ``instance_noise``: sigma of the noise on D's inputs (0.1
@@ -310,7 +310,14 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     the best-FID checkpoints are written and ``lr_plateau`` needs no ``fid_fn``.  The score ranks the epochs of a run; it is NOT
     comparable with published FID numbers (those need Inception weights: pass them as a callable).  The hook NEVER
     defaults to the discriminator being trained - features that move with training would make the curve meaningless; a user who hands
-    ``FrechetDistance`` the live ``D`` gets a copy frozen at that moment.  ``fid=""`` (default): everything as before, ``FID: nan``."""
+    ``FrechetDistance`` the live ``D`` gets a copy frozen at that moment.  ``fid=""`` (default): everything as before, ``FID: nan``.
+
+    ``manifold_k`` / ``kid`` (only with ``fid="random-vit"``): ``manifold_k`` in 1..8 adds precision, recall, density and coverage
+    with k-th-neighbour radii, ``kid=True`` the full-set KID, both from the features of the same evaluation pass against up to 10000
+    real feature rows kept by ``fit_real`` (metrics.py has the definitions).  One more header line names them, the epoch line ENDS in
+    `` | P: .. R: .. D: .. C: ..`` and / or `` | KID: ..``, and each entry of the returned history gains a third element, the dict
+    of these values.  They tell a loss of fidelity from a loss of coverage - mode collapse - which one distance cannot; like it they
+    rank the epochs of one run only.  Every rank evaluates alike.  Off (default): nothing changes."""
     global _log_file
     if fid not in FID_KINDS:
         raise ValueError(f"fid must be one of {FID_KINDS}, got {fid!r}")
@@ -318,6 +325,14 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
         raise ValueError("fid: the trainer builds the FID hook itself; pass either fid or fid_fn, not both")
     if fid and (isinstance(fid_samples, bool) or not isinstance(fid_samples, int) or fid_samples < 2):
         raise ValueError(f"fid_samples must be an integer >= 2, got {fid_samples!r}")
+    if isinstance(manifold_k, bool) or not isinstance(manifold_k, int) or not 0 <= manifold_k <= 8:
+        raise ValueError(f"manifold_k must be an integer in [0, 8] (0: off), got {manifold_k!r}")
+    if not isinstance(kid, bool):
+        raise ValueError(f"kid must be a bool, got {kid!r}")
+    if (manifold_k or kid) and fid != "random-vit":
+        raise ValueError('manifold_k / kid: these metrics are computed by the evaluator the trainer builds; pass fid="random-vit" with them')
+    if manifold_k and manifold_k >= fid_samples:
+        raise ValueError(f"manifold_k = {manifold_k} needs more than k generated images, fid_samples is {fid_samples}")
     if dataset is not None:  # the caller's errors whatever the machine: before the device check
         if data_loader is not None:
             raise ValueError("dataset: the step fetches its own batches from the dataset; pass either dataset or data_loader, not both")
@@ -403,7 +418,8 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     fid_eval = None
     if fid:  # the hook the trainer builds: a frozen random ViT of the model's geometry, never the discriminator in training
         from .metrics import FrechetDistance
-        fid_eval = FrechetDistance.random_vit(trainable_config(c, conditional), seed=FID_SEED, n_fake=fid_samples, latent_seed=FID_SEED)
+        more = {"manifold_k": manifold_k, "kid": kid} if (manifold_k or kid) else {}  # off: the constructor call of before
+        fid_eval = FrechetDistance.random_vit(trainable_config(c, conditional), seed=FID_SEED, n_fake=fid_samples, latent_seed=FID_SEED, **more)
 
     def dataset_epoch():  # the steps of one epoch: the engine fetches; the first one carries the batch it will train on, for the input grid
         for i in range(steps_per_epoch):
@@ -472,6 +488,10 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                 fid_eval.save_real(os.path.join(dirs.save, "real_stats.npz"))
             log(f"Frechet distance: feature net {fid_eval.tag}, latent seed {fid_eval.seed}, n_real {fid_eval.real['n']}, "
                 f"n_fake {fid_eval.n_fake}; real statistics in real_stats.npz; not comparable with published FID")
+            if fid_eval.bank is not None:
+                log(f"Manifold metrics: {fid_eval.bank['feats'].shape[0]} real feature rows kept"
+                    + (f"; precision / recall / density / coverage with k = {manifold_k}" if manifold_k else "")
+                    + ("; KID, cubic kernel, one estimate over the full sets" if kid else "") + "; they rank this run's epochs only")
             fid_fn = fid_eval
         for epoch in range(epochs):
             noise = construct_noise()
@@ -519,6 +539,13 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                 sd_, sg_ = eng.lr_scales
                 eng.set_lr_scale(d=sd_ * plateau.factor, g=sg_ * plateau.factor)
                 cr += f" | FID plateau: rate multipliers now {sd_ * plateau.factor:g}, {sg_ * plateau.factor:g}"
+            if fid_eval is not None and fid_eval.bank is not None:  # last on the line
+                q = {k_: fid_eval.last[k_] for k_ in ("precision", "recall", "density", "coverage", "kid")}
+                history[-1] = history[-1] + (q,)
+                if manifold_k:
+                    cr += " | P: {precision:.4f} R: {recall:.4f} D: {density:.4f} C: {coverage:.4f}".format(**q)
+                if kid:
+                    cr += f" | KID: {q['kid']:.6e}"
             log(f"Epoch [{epoch}/{epochs}] | Disc Loss: {d_real + d_fake:.8f}, Gen Loss: {g:.4f} | FID: {fid_score:.4f}{cr}")
             if save_artifacts:
                 save_figures(dirs.save, disc_losses=disc_losses, gen_losses=gen_losses, fid_scores=fid_scores)
