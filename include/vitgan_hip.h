@@ -836,6 +836,45 @@ int vg_gen_backward_cond(const VgGenNet* net, int B, void* ws, const void* d_img
 int vg_gen_backward_stages_cond(const VgGenNet* net, int B, void* ws, const void* d_img, int stage_begin, int stage_end,
                                 const VgGenCond* cond, void* stream);
 
+/* fp32 mode of the generator (opt-in, additive to ABI v9; every entry point above is unchanged): activations, saved tensors, gradients
+ * and GEMM operands are fp32, the GEMMs run on the exact f32-input MFMA, the SIREN's sine and cosine are the accurate library functions
+ * of fl(omega0 * z) - the reference's own arithmetic, for holding the generator to the fp32 oracle and sampling a reference checkpoint.
+ * Reads net->P (fp32 master) and accumulates G += dL/dP into net->G in the vg_gen_layout order; net->Pb is ignored.  Dropout at the bf16
+ * generator's sites and element indices (100 + 2l behind output_linear, 101 + 2l inside the MLP), so one seed draws the same masks in
+ * both modes; net->pos_table is honoured.  z fp32 [B, Z]; img / d_img fp32 [B, T*CW] (patch == 0) or NCHW (patch > 0).  ws:
+ * vg_gen_ws_bytes_f32(d, B) bytes (-1 for arguments the calls refuse), written by the forward and read by the backward of that forward.
+ * cond (NULL: unconditional) is the class table [K, T*E] and its gradient in fp32: w = mapping(z) + table[clamp(y)], the gradient by
+ * vg_class_grad (ascending n, accumulated).  One stream, no atomics: two runs are bit-equal.
+ * Refused on the host before any launch:  -1 a null pointer (net, P, z, ws, img; G and d_img for the backward; labels / table /
+ * table_grad of a cond) or B < 1;  -2 K outside [1, 16];  -3 a shape vg_gen_layout refuses, T > 80 or E > 1024 (E / H outside
+ * {32, 64, 96} is vg_gen_layout's). */
+typedef struct VgGenCondF32 {
+  const int* labels;
+  const float* table;
+  float* table_grad; /* NULL allowed for a forward */
+  int K;
+} VgGenCondF32;
+long long vg_gen_ws_bytes_f32(const VgGenDims* d, int B); /* host only */
+int vg_gen_forward_f32(const VgGenNet* net, int B, const float* z, void* ws, float* img, const VgGenCondF32* cond, void* stream);
+int vg_gen_backward_f32(const VgGenNet* net, int B, void* ws, const float* d_img, const VgGenCondF32* cond, void* stream);
+/* Its single operators (all tensors fp32, row-major):
+ * vg_sln_f32_fwd / _bwd: vg_sln_fwd / vg_sln_bwd above in fp32 over rows [R, E], E a multiple of 128 and at most 1024; mean / rstd [R]
+ *   saved.  bwd: dh = gres + LN'(dy w gs) (gres nullable); dw_acc [R, E] = (dw_accumulate 0) or += (1) dy (gs (xhat lw + lb) + bs);
+ *   dlw, dlb [E] and dgs, dbs [1] += their sums over the rows (all four NULL: skipped) - fp64 inside a 256-row chunk, the chunks folded
+ *   in order, bitwise repeatable.  part: vg_sln_f32_bwd_part_floats(R, E) floats of scratch, 8-byte aligned (-3 otherwise).
+ * vg_siren_f32_fwd:   Z[M,N] = X[M,K] W[N,K]^T + bias (the fp32 pre-activation, required), Y = sin(fl(omega0 * Z)).
+ * vg_siren_f32_dgrad: dX[M,K] = (dY[M,N] W[N,K]) * omega0 cos(fl(omega0 * aux)), aux [M,K] = the pre-activation of the layer below;
+ *   W == NULL is the last layer's elementwise form over [M, N]: dX = dY * omega0 cos(fl(omega0 * aux)) (K ignored).
+ *   Accurate sinf / cosf: the argument reaches hundreds of radians. */
+int vg_sln_f32_fwd(const float* h, int h_bcast_rows, const float* w, const float* lw, const float* lb, const float* gs, const float* bs,
+                   float* y, float* mean, float* rstd, int R, int E, float eps, void* stream);
+long long vg_sln_f32_bwd_part_floats(int R, int E);
+int vg_sln_f32_bwd(const float* dy, const float* h, int h_bcast_rows, const float* w, const float* mean, const float* rstd, const float* lw,
+                   const float* lb, const float* gs, const float* bs, const float* gres, float* dh, float* dw_acc, int dw_accumulate,
+                   float* dlw, float* dlb, float* dgs, float* dbs, float* part, int R, int E, void* stream);
+int vg_siren_f32_fwd(const float* X, const float* W, const float* bias, float* Y, float* Z, int M, int N, int K, float omega0, void* stream);
+int vg_siren_f32_dgrad(const float* dY, const float* W, const float* aux, float* dX, int M, int N, int K, float omega0, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,10 @@ class VgGenCond(C.Structure):
     _fields_ = [("labels", c_void_p), ("table_bf16", c_void_p), ("table_grad", c_void_p), ("K", c_int)]
 
 
+class VgGenCondF32(C.Structure):
+    _fields_ = [("labels", c_void_p), ("table", c_void_p), ("table_grad", c_void_p), ("K", c_int)]
+
+
 class VgSpectralDesc(C.Structure):
     _fields_ = ([("w_off", c_ll), ("N", c_int), ("K", c_int)] + [(n, c_ll) for n in ("u_off", "v_off", "s_off", "t_off", "w_tmp_off", "dot_off")]
                 + [(n, c_int) for n in ("blk_a", "blk_b", "blk_c", "reserved")])
@@ -210,6 +214,14 @@ _SIGNATURES = {
     "vg_gen_forward_cond": (c_int, [C.POINTER(VgGenNet), c_int, P, P, P, C.POINTER(VgGenCond), P]),
     "vg_gen_backward_cond": (c_int, [C.POINTER(VgGenNet), c_int, P, P, C.POINTER(VgGenCond), P]),
     "vg_gen_backward_stages_cond": (c_int, [C.POINTER(VgGenNet), c_int, P, P, c_int, c_int, C.POINTER(VgGenCond), P]),
+    "vg_gen_ws_bytes_f32": (c_ll, [C.POINTER(VgGenDims), c_int]),
+    "vg_gen_forward_f32": (c_int, [C.POINTER(VgGenNet), c_int, P, P, P, C.POINTER(VgGenCondF32), P]),
+    "vg_gen_backward_f32": (c_int, [C.POINTER(VgGenNet), c_int, P, P, C.POINTER(VgGenCondF32), P]),
+    "vg_sln_f32_fwd": (c_int, [P, c_int, P, P, P, P, P, P, P, P, c_int, c_int, c_float, P]),
+    "vg_sln_f32_bwd_part_floats": (c_ll, [c_int, c_int]),
+    "vg_sln_f32_bwd": (c_int, [P, P, c_int, P, P, P, P, P, P, P, P, P, P, c_int, P, P, P, P, P, c_int, c_int, P]),
+    "vg_siren_f32_fwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, P]),
+    "vg_siren_f32_dgrad": (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -18,6 +18,8 @@ __device__ __forceinline__ float f32_gelu_grad(float x) {
   return 0.5f * (1.0f + erff(x * 0.70710678118654752f)) + x * 0.39894228040143268f * expf(-0.5f * x * x);
 }
 
+// SIREN: the instantiation of the two sine epilogues (act 5, 6); the other codes run the <false> instantiation, which holds no sinf / cosf
+template <bool SIREN>
 __global__ __launch_bounds__(256) void vg_f32_gemm_kernel(const VgF32Gemm g) {
   __shared__ float As[F_BK][F_LD];
   __shared__ float Bs[F_BK][F_LD];
@@ -87,6 +89,16 @@ __global__ __launch_bounds__(256) void vg_f32_gemm_kernel(const VgF32Gemm g) {
         continue;
       }
       if (g.bias) v += g.bias[n];
+      if constexpr (SIREN) {  // the product omega0 * z is rounded to fp32 once, then the accurate sine / cosine of it
+        if (g.act == VG_F32_ACT_SIN) {
+          g.Z[(long long)m * g.ldz + n] = v;
+          v = sinf(g.omega0 * v);
+        } else {
+          v *= g.omega0 * cosf(g.omega0 * g.aux[(long long)m * g.ldaux + n]);
+        }
+        g.C[(long long)m * g.ldc + n] = v;
+        continue;
+      }
       if (g.act == VG_F32_ACT_GELU) {
         if (g.Z) g.Z[(long long)m * g.ldz + n] = v;
         v = f32_gelu(v);
@@ -116,9 +128,12 @@ int vg_f32_gemm_launch(const VgF32Gemm& g, hipStream_t st) {
   if ((g.sak != 1 && g.sam != 1) || (g.sbn != 1 && g.sbk != 1)) return -3;
   if (g.splits < 1 || g.kchunk < 1 || (long long)g.splits * g.kchunk < g.K) return -3;
   if (g.splits > 1 && (!g.c_split || (g.kchunk % F_BK))) return -3;
-  if ((g.act == VG_F32_MUL_GELU || g.act == VG_F32_MUL_TANH) && !g.aux) return -1;
+  if ((g.act == VG_F32_MUL_GELU || g.act == VG_F32_MUL_TANH || g.act == VG_F32_MUL_COS) && !g.aux) return -1;
+  const bool siren = g.act == VG_F32_ACT_SIN || g.act == VG_F32_MUL_COS;
+  if (siren && (g.c_split || g.drop.thr || g.res || (g.act == VG_F32_ACT_SIN && !g.Z))) return -3;
   dim3 grid((g.N + F_BN - 1) / F_BN, (g.M + F_BM - 1) / F_BM, g.splits);
-  hipLaunchKernelGGL(vg_f32_gemm_kernel, grid, dim3(256), 0, st, g);
+  if (siren) hipLaunchKernelGGL(vg_f32_gemm_kernel<true>, grid, dim3(256), 0, st, g);
+  else hipLaunchKernelGGL(vg_f32_gemm_kernel<false>, grid, dim3(256), 0, st, g);
   return (int)hipGetLastError();
 }
 
@@ -147,6 +162,24 @@ int vg_f32_linear_dgrad(const float* dY, const float* W, const float* aux, float
   g.B = W; g.sbk = K; g.sbn = 1;   // B(n, k) = W[n][k]
   g.M = M; g.N = K; g.K = N; g.kchunk = N;
   g.C = dX; g.ldc = K; g.act = act; g.aux = aux; g.ldaux = K;
+  return vg_f32_gemm_launch(g, st);
+}
+
+int vg_f32_siren_fwd(const float* X, const float* W, const float* bias, float* Y, float* Z, int M, int N, int K, float omega0, hipStream_t st) {
+  if (!Z) return -1;
+  VgF32Gemm g = f32_prob();
+  g.A = X; g.sam = K; g.sak = 1;
+  g.B = W; g.sbk = 1; g.sbn = K;
+  g.M = M; g.N = N; g.K = K; g.kchunk = K;
+  g.C = Y; g.ldc = N; g.bias = bias; g.act = VG_F32_ACT_SIN; g.Z = Z; g.ldz = N; g.omega0 = omega0;
+  return vg_f32_gemm_launch(g, st);
+}
+int vg_f32_siren_dgrad(const float* dY, const float* W, const float* aux, float* dX, int M, int N, int K, float omega0, hipStream_t st) {
+  VgF32Gemm g = f32_prob();
+  g.A = dY; g.sam = N; g.sak = 1;
+  g.B = W; g.sbk = K; g.sbn = 1;
+  g.M = M; g.N = K; g.K = N; g.kchunk = N;
+  g.C = dX; g.ldc = K; g.act = VG_F32_MUL_COS; g.aux = aux; g.ldaux = K; g.omega0 = omega0;
   return vg_f32_gemm_launch(g, st);
 }
 

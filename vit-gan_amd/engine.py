@@ -270,6 +270,8 @@ class GanEngine:
             raise TypeError("GanEngine needs a ViTDiscriminator/VisionTransformer and a SirenGenerator")
         if getattr(vit, "precision", "bf16") != "bf16":
             raise ValueError("GanEngine: the fused step is bf16; it does not take a discriminator in precision='fp32'")
+        if getattr(generator, "precision", "bf16") != "bf16":
+            raise ValueError("GanEngine: the fused step is bf16; it does not take a generator in precision='fp32'")
         self.gp_w = float(o["gp_weight"])
         if self.gp_w != 0.0:
             vit.require_short_attention("gp_weight > 0 (the gradient penalty)")

@@ -85,6 +85,40 @@ class _GenFn(torch.autograd.Function):
         return None, None, None, None, None
 
 
+class _GenF32Fn(torch.autograd.Function):
+    """The fp32 mode (``SirenGenerator.precision = "fp32"``): vg_gen_forward_f32 / vg_gen_backward_f32 on the fp32 master parameters;
+    the gradients land in the same flat gradient buffer, the image comes back in fp32."""
+
+    @staticmethod
+    def forward(ctx, mod: "SirenGenerator", z, anchor, drop_p, labels=None):
+        ctx.drop = (float(drop_p), int(torch.randint(0, 2 ** 62, (1,)).item()) if drop_p > 0 else 0)
+        B = z.shape[0]
+        zin = z.detach().float().contiguous()
+        ws = torch.empty(mod._ws_bytes_f32(B), dtype=torch.uint8, device=z.device)
+        img = torch.empty(B, mod.channels, mod.image_size, mod.image_size, dtype=torch.float32, device=z.device)
+        net = mod._net(ctx.drop)
+        cond = None if labels is None else C.byref(mod._cond_f32(labels))
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _lib.check(_lib.lib().vg_gen_forward_f32(C.byref(net), B, zin.data_ptr(), ws.data_ptr(), img.data_ptr(), cond, st), "vg_gen_forward_f32")
+        ctx.mod, ctx.ws, ctx.B, ctx.labels = mod, ws, B, labels
+        return img
+
+    @staticmethod
+    def backward(ctx, dimg):
+        mod = ctx.mod
+        mod._flat.attach_grads()
+        d = dimg.detach().float().contiguous()
+        net = mod._net(ctx.drop)
+        cond = None if ctx.labels is None else C.byref(mod._cond_f32(ctx.labels))
+        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _lib.check(_lib.lib().vg_gen_backward_f32(C.byref(net), ctx.B, ctx.ws.data_ptr(), d.data_ptr(), cond, st), "vg_gen_backward_f32")
+        ctx.ws = None
+        return None, None, None, None, None
+
+
+PRECISIONS = ("bf16", "fp32")
+
+
 def fourier_position_table(T: int, E: int, image_size: int, patch_size: int) -> torch.Tensor:
     """[T, E] fp32: token t at (x, y) in [0,1)^2 (patch-grid cell centre, or (0.5, row centre) for the v1 row tokens);
     column 4*j + c = (sin, cos)(2 pi f_j x), (sin, cos)(2 pi f_j y), E/4 log-spaced frequencies from 1 to side/2."""
@@ -165,6 +199,24 @@ class SirenGenerator(nn.Module):
             slots[flat.CLASS_TABLE_KEY] = (self._class_off, (n_classes, T * E))
         self.reset_parameters()
         self._flat = FlatParams(dict(self.named_parameters()), slots, total)
+        # "bf16" (default): the fused engine above.  "fp32": fp32 activations, gradients and GEMM operands on the exact f32-input MFMA
+        # with the accurate sine - the reference's own arithmetic, for checking the generator against the fp32 model or sampling a
+        # reference checkpoint.  Not a constructor argument: set ``generator.precision = "fp32"``.  GanEngine stays bf16 and refuses it.
+        self._precision = "bf16"
+
+    @property
+    def precision(self) -> str:
+        return self._precision
+
+    @precision.setter
+    def precision(self, value: str) -> None:
+        if not isinstance(value, str) or value not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}, got {value!r}")
+        if value == "fp32" and _lib.lib().vg_gen_ws_bytes_f32(C.byref(self._dims), 1) <= 0:
+            d = self._dims
+            raise ValueError(f"precision='fp32' takes at most 80 tokens, head widths 32 / 64 / 96 and an embedding of at most 1024; this "
+                             f"generator has {d.T} tokens, head width {d.E // d.H}, embedding {d.E}")
+        self._precision = value
 
     def reset_parameters(self):
         """Init distributions of the reference: nn.Linear default U(+-1/sqrt(in)); SIREN U(+-1/in) for
@@ -211,6 +263,17 @@ class SirenGenerator(nn.Module):
             raise RuntimeError("vg_gen_ws_bytes failed")
         return n
 
+    def _ws_bytes_f32(self, B):
+        n = _lib.lib().vg_gen_ws_bytes_f32(C.byref(self._dims), B)
+        if n <= 0:
+            raise RuntimeError("vg_gen_ws_bytes_f32 failed")
+        return n
+
+    def _cond_f32(self, labels) -> "_lib.VgGenCondF32":
+        """the class-conditioning argument of the fp32 calls: the labels, and the table's fp32 master and fp32 gradient"""
+        fp, off = self._flat, self._class_off
+        return _lib.VgGenCondF32(labels.data_ptr(), fp.flat.data_ptr() + 4 * off, fp.grad.data_ptr() + 4 * off, self.n_classes)
+
     def _net(self, drop=(0.0, 0)):
         fp = self._flat
         tab = self.fourier_table
@@ -237,4 +300,5 @@ class SirenGenerator(nn.Module):
         if not self._flat.aliased():
             self._flat.named = dict(self.named_parameters())
             self._flat.rebuild()
-        return _GenFn.apply(self, z, self.embedding, self.dropout_p if self.training else 0.0, self._labels(labels, z.shape[0], z.device))
+        fn = _GenF32Fn if self._precision == "fp32" else _GenFn
+        return fn.apply(self, z, self.embedding, self.dropout_p if self.training else 0.0, self._labels(labels, z.shape[0], z.device))
