@@ -875,6 +875,88 @@ int vg_sln_f32_bwd(const float* dy, const float* h, int h_bcast_rows, const floa
 int vg_siren_f32_fwd(const float* X, const float* W, const float* bias, float* Y, float* Z, int M, int N, int K, float omega0, void* stream);
 int vg_siren_f32_dgrad(const float* dY, const float* W, const float* aux, float* dX, int M, int N, int K, float omega0, void* stream);
 
+/* Per-step telemetry, written by the step itself (additive to ABI 9; csrc/telemetry.hip).  The reference's trainer collects per-step
+ * series - gen_losses, disc_losses, gradient_norms_gen / _disc, disc_real_accuracies / disc_fake_accuracies (src/v2/training.py:80-84,
+ * 112-123) - on the host; here the step writes them into rings on the device, keyed on the device step counter, and the host reads
+ * them when it synchronises anyway.  All three entries are enqueue-only (no allocation, no synchronisation, no memset / memcpy node),
+ * deterministic (no float atomics; every sum is a fixed tree) and use plain vector stores.
+ *
+ * vg_grad_stats: segmented gradient norms over a flat fp32 gradient buffer g[0, n) (16-byte aligned, n < 2^31).
+ *   chunks: int32 [n_chunks][3] on the device = (first element, count, segment) with 1 <= count <= 4096; a chunk never crosses a
+ *     segment, the chunks of a segment are adjacent and ascending.  seg_first: int32 [n_seg + 1] on the device, the index of each
+ *     segment's first chunk (seg_first[n_seg] = n_chunks).  scratch: 2 n_chunks floats, 8-byte aligned.
+ *   Pass 1 (at most 2048 workgroups of 256 threads walking the table grid-stride; ONE partial per chunk, so the result does not depend
+ *     on the grid): the chunk is split at g's 16-byte boundaries into a head of (-first) & 3 elements, nv float4 and a tail.  Thread t:
+ *     a = 0; for k = 0..3 with v = t + 256 k < nv: a += (x0 x0 + x1 x1) + (x2 x2 + x3 x3) of vector v; thread t < head then adds the
+ *     square of head element t, thread t < tail the square of tail element t (products and sums rounded separately, fp32).  The 256
+ *     values are folded by the wave butterfly (xor 32, 16, 8, 4, 2, 1) and then as (w0 + w1) + (w2 + w3).  Elements that are NaN or
+ *     +-Inf are counted.  Nothing outside a chunk is read; a chunk that does not lie inside [0, n) is skipped.
+ *   Pass 2 (one workgroup): per segment s the chunk partials are added in chunk order in fp64;
+ *     norm_seg[s] = (float)(gscale sqrt(sum_s)),
+ *     totals[0] = sum_s norm_seg[s]   (the rounded norms, added in segment order in fp64: sum(p.grad.norm() for p in parameters)),
+ *     totals[1] = gscale sqrt(sum_s sum_s)   (what clip_grad_norm_ sees),  totals[2] = min(non-finite elements, 2^24),  totals[3] = 0.
+ *   totals: 4 floats, 16-byte aligned.  Returns -1: a null pointer;  -2: n, n_chunks or n_seg out of range (n_seg <= 2048, n_seg <=
+ *   n_chunks), gscale not positive and finite;  -3: a misaligned buffer - all before any launch.
+ *
+ * vg_logit_stats: statistics of n logits (1 <= n <= 16384) per row pointer; workgroup j of the launch reads x_j and writes slot
+ *   role + j of out[3][4] (role: 0 = D on real, 1 = D on fake, 2 = the generator's pass; x1 may be NULL: one workgroup; with x1,
+ *   role <= 1) as (mean, fraction of logits > 0, fraction of logits < 0, n) in one 16-byte store.  +-0 and NaN count in neither
+ *   fraction ((real_output > 0) / (fake_output < 0), training.py:115-116).  Sum: thread t of 1024 adds x[t], x[t + 1024], .. in index
+ *   order, the wave butterfly, then the 16 wave sums by one more butterfly (lanes >= 16 hold +0); mean = sum / (float) n; the counts
+ *   are integers and each fraction is one fp32 division.  -1: x0 or out NULL;  -2: n or role out of range;  -3: out misaligned.
+ *
+ * vg_telemetry_commit: with t = step_dev[0] as vg_zero_tick left it (t < 1: nothing is written), row r = (t - 1) % cap receives
+ *   ring_step[r] = t, ring[r][f] = field f (VG_TEL_*, below) gathered from the device pointers of *src (passed by value: a host
+ *   pointer, read before the call returns), ring_seg_d[r][0, n_seg_d) = src->seg_d and ring_seg_g likewise.  A NULL source makes its
+ *   fields NaN; the penalty field is NaN - written, not left over - when penalty_due is 0 (a step of lazy R1 on which the penalty does
+ *   not run).  The row is a function of the counter: writing it twice (the warm-up of a captured step and its first replay) is
+ *   idempotent.  One workgroup.  -1: a null pointer (a ring of a given source included);  -2: cap < 1, a negative size, penalty_due
+ *   not 0 / 1;  -3: a source with size 0. */
+#define VG_TEL_LOSS_D_REAL 0
+#define VG_TEL_LOSS_D_FAKE 1
+#define VG_TEL_LOSS_G 2
+#define VG_TEL_D_REAL_MEAN 3
+#define VG_TEL_D_FAKE_MEAN 4
+#define VG_TEL_D_REAL_ACC 5   /* fraction of D's real logits > 0 */
+#define VG_TEL_D_FAKE_ACC 6   /* fraction of D's fake logits < 0 */
+#define VG_TEL_G_MEAN 7       /* the generator's pass through D: mean logit */
+#define VG_TEL_G_FRAC_POS 8   /* ... and the fraction of its logits > 0 */
+#define VG_TEL_GNORM_D_SUM 9
+#define VG_TEL_GNORM_D_L2 10
+#define VG_TEL_GNORM_G_SUM 11
+#define VG_TEL_GNORM_G_L2 12
+#define VG_TEL_NONFINITE_D 13
+#define VG_TEL_NONFINITE_G 14
+#define VG_TEL_PENALTY 15     /* gp_loss or r1_loss of this step */
+#define VG_TEL_BCR_REAL 16
+#define VG_TEL_BCR_FAKE 17
+#define VG_TEL_ADA_P 18
+#define VG_TEL_ADA_RT 19
+#define VG_TEL_LR_D 20
+#define VG_TEL_LR_G 21
+#define VG_TEL_DIVERSITY 22
+#define VG_TEL_NF 24          /* floats per row (23 is reserved and NaN) */
+typedef struct VgTelemetrySrc {
+  const float* losses;       /* [3] d_real, d_fake, g */
+  const float* logit_stats;  /* [3][4] as vg_logit_stats writes it */
+  const float* grad_d;       /* [4] totals of vg_grad_stats over the discriminator's gradient */
+  const float* grad_g;       /* [4] ... over the generator's */
+  const float* penalty;      /* [1] */
+  const float* bcr;          /* [2] real, fake */
+  const float* ada_state;    /* [4] (p, acc_sign, acc_count, r_last) */
+  const float* lr;           /* [2] d, g */
+  const float* diversity;    /* [1] */
+  const float* seg_d;        /* [n_seg_d] norm_seg of the discriminator */
+  const float* seg_g;        /* [n_seg_g] */
+  int n_seg_d, n_seg_g;
+  int penalty_due;           /* 0 or 1 */
+} VgTelemetrySrc;
+int vg_grad_stats(const float* g, long long n, const int* chunks, int n_chunks, const int* seg_first, int n_seg, float gscale,
+                  float* scratch, float* norm_seg, float* totals /*[4]*/, void* stream);
+int vg_logit_stats(const float* x0, const float* x1, int n, int role, float* out /*[3][4]*/, void* stream);
+int vg_telemetry_commit(const VgTelemetrySrc* src, const int* step_dev, int cap, int* ring_step, float* ring, float* ring_seg_d,
+                        float* ring_seg_g, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

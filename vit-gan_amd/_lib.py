@@ -78,6 +78,17 @@ class VgLrSched(C.Structure):
     _fields_ = [("base", c_float), ("kind", c_int), ("warmup", c_int), ("total", c_int), ("final_ratio", c_float)]
 
 
+class VgTelemetrySrc(C.Structure):
+    _fields_ = ([(n, c_void_p) for n in ("losses", "logit_stats", "grad_d", "grad_g", "penalty", "bcr", "ada_state", "lr", "diversity",
+                                         "seg_d", "seg_g")] + [(n, c_int) for n in ("n_seg_d", "n_seg_g", "penalty_due")])
+
+
+# VG_TEL_* of include/vitgan_hip.h: the fields of one telemetry row, by index (23 is reserved)
+TEL_FIELDS = ("loss_d_real", "loss_d_fake", "loss_g", "d_real_mean", "d_fake_mean", "d_real_acc", "d_fake_acc", "g_mean", "g_frac_pos",
+              "gnorm_d_sum", "gnorm_d_l2", "gnorm_g_sum", "gnorm_g_l2", "nonfinite_d", "nonfinite_g", "penalty", "bcr_real", "bcr_fake",
+              "ada_p", "ada_rt", "lr_d", "lr_g", "diversity")
+TEL_NF = 24
+
 P = c_void_p
 _SIGNATURES = {
     "vg_abi_version": (c_int, []),
@@ -222,6 +233,9 @@ _SIGNATURES = {
     "vg_sln_f32_bwd": (c_int, [P, P, c_int, P, P, P, P, P, P, P, P, P, P, c_int, P, P, P, P, P, c_int, c_int, P]),
     "vg_siren_f32_fwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, P]),
     "vg_siren_f32_dgrad": (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, P]),
+    "vg_grad_stats": (c_int, [P, c_ll, P, c_int, P, c_int, c_float, P, P, P, P]),
+    "vg_logit_stats": (c_int, [P, P, c_int, c_int, P, P]),
+    "vg_telemetry_commit": (c_int, [C.POINTER(VgTelemetrySrc), P, c_int, P, P, P, P, P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -101,6 +101,13 @@ int vg_adamw_ema_dlr_launch(float* p, const float* g, float* m, float* v, bf16* 
 // controller of the two learning rates (slot 0 = D, 1 = G; VgLrSched of include/vitgan_hip.h): one workgroup, fp64, rounded once
 struct VgLrSched;
 int vg_lr_schedule_launch(const VgLrSched* d, const VgLrSched* g, const int* step_dev, const float* scale_dev, float* lr_out, hipStream_t st);
+// per-step telemetry (telemetry.hip): segmented gradient norms (two launches), logit statistics, the ring commit
+struct VgTelemetrySrc;
+int vg_grad_stats_launch(const float* g, long long n, const int* chunks, int n_chunks, const int* seg_first, int n_seg, float gscale,
+                         float* scratch, float* norm_seg, float* totals, hipStream_t st);
+int vg_logit_stats_launch(const float* x0, const float* x1, int n, int role, float* out, hipStream_t st);
+int vg_telemetry_commit_launch(const VgTelemetrySrc* src, const int* step_dev, int cap, int* ring_step, float* ring, float* ring_seg_d,
+                               float* ring_seg_g, hipStream_t st);
 int vg_ema_launch(float* ema, const float* p, long long n, float decay, int start, int step, const int* step_dev, hipStream_t st);
 int vg_cast_f32_bf16_launch(const float* src, bf16* dst, long long n, hipStream_t st);
 int vg_widen_bf16_f32_launch(const bf16* src, float* dst, long long n, hipStream_t st);  // metrics.hip

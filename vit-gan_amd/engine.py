@@ -57,7 +57,7 @@ class GanEngine:
                  aug_p: Optional[float] = None, ada_target: float = 0.0, ada_interval: int = 4, ada_kimg: float = 500.0,
                  r1_gamma: float = 0.0, r1_interval: int = 1, n_classes: int = 0,
                  lr_schedule: str = "", lr_warmup: int = 0, lr_total: int = 0, lr_final: float = 0.0,
-                 dataset: Optional[DeviceDataset] = None):
+                 dataset: Optional[DeviceDataset] = None, telemetry: int = 0):
         """concurrent_wgrad: the discriminator's weight gradients on a side stream beside its input gradients.  Off by default
         since the persistent GEMMs (csrc/gemm_wr.hip, gemm_tn.hip: their workgroups hold the CUs for a whole launch) - the
         side stream measured 6.70 against 6.67 ms/step.
@@ -212,7 +212,17 @@ class GanEngine:
         the counter ``state_dict()`` carries, so a resumed run continues the epoch where it stopped; the state records (N, B, world,
         shuffle, flip, data seed) and ``load_state_dict`` refuses another.  The set must match the discriminator's geometry, carry
         labels iff ``n_classes > 0`` (their values are not read on the host; the kernels clamp) and hold one global batch.  None
-        (default): no buffer, no call, and the step is launch for launch and bit for bit the host-fed one."""
+        (default): no buffer, no call, and the step is launch for launch and bit for bit the host-fed one.
+        telemetry: an integer ``cap >= 1`` makes the step RECORD itself (the reference's per-step series - losses, D's real / fake
+        accuracies, the gradient norms of both networks, src/v2/training.py:80-84,112-123 - which a run of bare hipGraph replays hides
+        from the host): at most seven launches more, all inside the captured step - vg_logit_stats behind D's loss launch (on the rows
+        ADA reads: the selected logits when class-conditional, all B Kc otherwise), vg_grad_stats (two launches) on D's gradient between
+        the clipping and AdamW (the gradient AdamW consumes: exchanged, projected, clipped), the same pair for the generator, and
+        vg_telemetry_commit last, which writes row ``(t - 1) % cap`` of the rings from the device step counter t.  ``history()`` reads
+        what has been recorded since its last call, ``first_nonfinite_step`` the first recorded step with a NaN / Inf gradient element.
+        The rings are a log, not training state: ``state_dict()`` does not carry them, and the warm-up of a captured step and its first
+        replay write the same row with the same values.  Not with ``two_stream`` nor a process group of more than one rank (the
+        statistics are per process, like ADA's).  0 (default): no buffer, no launch, the same bits."""
         self._check_options(discriminator, generator, dict(locals()))
         self._carve()
         self._attach()
@@ -252,6 +262,11 @@ class GanEngine:
         self.ada, self.aug_p0 = self.ada_target > 0.0, 1.0 if p0 is None else p0
         self.gated = p0 is not None  # the gated kernels and a device-resident probability
         world = world_size(pg)
+        self.tel_cap = ops.parse_telemetry(o["telemetry"])  # 0 = off
+        if self.tel_cap and two_stream:
+            raise ValueError("telemetry: the recording launches are placed in the single-chain schedule; switch two_stream off")
+        if self.tel_cap and world > 1:
+            raise ValueError("telemetry: the statistics are per process and are not exchanged; a process group of more than one rank is not built")
         if self.ada and (world > 1 or (o["exchange_single_rank"] and dist.is_available() and dist.is_initialized())):
             raise ValueError("ada_target: the controller's statistics are per process and are not exchanged; under data parallelism use a "
                              "fixed aug_p")
@@ -437,6 +452,14 @@ class GanEngine:
         if self.lr_opts is not None:
             self.lr_scale, self.lr_now = torch.ones(2, dtype=torch.float32, device=dev), f32(2)
             self.lr_slot = (self.lr_now[0:1], self.lr_now[1:2])  # slot 0 = D, 1 = G: the _dlr calls' lr_dev
+        if self.tel_cap:  # the per-step record: one plan per gradient buffer, the logit statistics, the three rings (a log, not state)
+            cap = self.tel_cap
+            self.tel_d, self.tel_g = ops.GradStatsPlan(fd.slots, fd.total, dev), ops.GradStatsPlan(fg.slots, fg.total, dev)
+            self.tel_logit = torch.full((3, 4), float("nan"), dtype=torch.float32, device=dev)  # slots: D on real, D on fake, G's pass
+            self.tel_sel_g = f32(B) if self.cond else None  # the generator pass's selected logits
+            self.tel_ring_step = torch.zeros(cap, dtype=torch.int32, device=dev)
+            self.tel_ring = torch.full((cap, _lib.TEL_NF), float("nan"), dtype=torch.float32, device=dev)
+            self.tel_ring_seg = (f32(cap, self.tel_d.n_seg), f32(cap, self.tel_g.n_seg))
         # ---- the views: what each pass reads and writes, chosen here once
         halves = lambda t: (t[:B], t[B:2 * B])  # noqa: E731
         self.fake = self.imgs[B:]
@@ -450,6 +473,7 @@ class GanEngine:
             self.d_pass = (4 * B, self.imgs4) + (self.cr_rows[1::2] if self.aug else self.cr_rows[0::2])
         else:
             self.d_pass = (2 * B, self.d_in, self.logits, self.dlogits)  # (images, input, adversarial logits, their gradient)
+        self.tel_adv = (self.d_pass[2][:B], self.d_pass[2][B:2 * B])  # the adversarial rows' halves: what the logit statistics read
         # the generator's pass through D: D sees T_2(fake) (site 1) under diffaug, its input gradient goes back through the adjoint
         self.g_in, self.g_dimg = (self.imgs_aug[:B], self.imgs_aug[B:]) if self.aug else (self.fake, self.dfake)
         self.g_rows = (self.logits_g, self.dlogits_g) if self.bcr or self.ada else (self.lg_half[0], self.dlg_half[0])
@@ -493,6 +517,8 @@ class GanEngine:
             if eng is not None:
                 eng.sync_from_modules()
         self._hooks = [m.register_load_state_dict_post_hook(_hook) for m in (vit, self.gen)]
+        self._tel_cursor = 0  # the last step history() has returned
+        self.first_nonfinite_step: Optional[int] = None  # the first recorded step with a NaN / Inf gradient element (history() sets it)
         self.steps, self._graphs = 0, {}  # the captured step(s), by kind: False = the plain launch list, True = with the R1 call
         self.graph_fallback_reason: Optional[str] = None
         if self._use_graph and self.sync.active:
@@ -553,7 +579,8 @@ class GanEngine:
         """The loss of n logit rows in ``role`` (0 = D on real, 1 = D on fake, 2 = the generator's) into the role's slot of ``losses``."""
         if self.cond:  # the label-selected logit of each row: real labels for D on real, the fake labels for D on fake and for G
             _call("vg_gan_loss_cond", _p(logits), _p(self.fake_labels if role else self.real_labels), _p(dlogits),
-                  _p(self.sel_half[role] if role < 2 else None), _p(self.loss_slot[role]), n, self.Kc, self.kind, role, 1.0, st)
+                  _p(self.sel_half[role] if role < 2 else (self.tel_sel_g if self.tel_cap else None)), _p(self.loss_slot[role]), n, self.Kc,
+                  self.kind, role, 1.0, st)
             return
         _call("vg_gan_loss", _p(logits), _p(dlogits), _p(self.loss_slot[role]), n * self.Kc, self.kind, role, 1.0, st)
 
@@ -646,12 +673,53 @@ class GanEngine:
         clip_grad_norm_ before optimizer.step()), then AdamW on the whole range."""
         if clip is not None:
             _call("vg_grad_clip", _p(r[1]), r[-1], 1.0 / self.world, float(clip), _p(self.clip_slot[slot]), st)
+        self._tel_grad(slot, st)
         self._adamw_range(r, slot, st)
+
+    # ---- telemetry: every launch the option adds; nothing without it
+    def _tel_grad(self, slot: int, st) -> None:
+        """The per-tensor norms of network ``slot``'s gradient as its AdamW is about to read it (two launches)."""
+        if self.tel_cap:
+            plan, fp = ((self.tel_d, self.vit._flat), (self.tel_g, self.gen._flat))[slot]
+            plan.enqueue(fp.grad, 1.0 / self.world, st)
+
+    def _tel_logits(self, x0, x1, n: int, role: int, st) -> None:
+        """mean and the fractions > 0 / < 0 of n logits per row pointer into slot ``role`` (and ``role + 1``) of ``tel_logit``."""
+        if self.tel_cap:
+            _call("vg_logit_stats", _p(x0), _p(x1), n, role, _p(self.tel_logit), st)
+
+    def _tel_d_logits(self, real, fake, st) -> None:
+        """D's own pass: the rows ADA reads - the B selected logits of each half when class-conditional, all B Kc otherwise."""
+        if self.tel_cap and self.cond:
+            self._tel_logits(self.sel_half[0], self.sel_half[1], self.B, 0, st)
+        elif self.tel_cap:
+            self._tel_logits(real, fake, self.B * self.Kc, 0, st)
+
+    def _tel_g_logits(self, lg, st) -> None:
+        """The generator's pass: the B logits selected by the fake labels when class-conditional, all B Kc otherwise."""
+        if self.tel_cap and self.cond:
+            self._tel_logits(self.tel_sel_g, None, self.B, 2, st)
+        elif self.tel_cap:
+            self._tel_logits(lg, None, self.B * self.Kc, 2, st)
+
+    def _tel_commit(self, r1_due: bool, st) -> None:
+        """The step's last launch: this step's row of the rings, gathered from where the step left each value."""
+        if not self.tel_cap:
+            return
+        pen = self.gp_loss if self.gp_w != 0.0 else self.r1_loss
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        src = _lib.VgTelemetrySrc(ptr(self.losses), ptr(self.tel_logit), ptr(self.tel_d.totals), ptr(self.tel_g.totals), ptr(pen),
+                                  ptr(self.bcr_losses if self.bcr else None), ptr(self.ada_state if self.ada else None), ptr(self.lr_now),
+                                  ptr(self.div_loss if self.div_w != 0.0 else None), ptr(self.tel_d.norm_seg), ptr(self.tel_g.norm_seg),
+                                  self.tel_d.n_seg, self.tel_g.n_seg, int(self.gp_w != 0.0 or bool(r1_due)))
+        _call("vg_telemetry_commit", C.byref(src), _p(self.step_t), self.tel_cap, _p(self.tel_ring_step), _p(self.tel_ring),
+              _p(self.tel_ring_seg[0]), _p(self.tel_ring_seg[1]), st)
 
     def _adamw_g_sharded(self, st) -> None:
         """The generator's AdamW with the mapping Linear sharded: the whole buffer but that layer as usual, of the layer this rank's
         share only; then the updated fp32 master shares to every rank and the layer's bf16 shadow cast from them there (the GEMMs of
         every rank read the whole shadow; gathering the master, not the shadow, keeps every rank's master current)."""
+        self._tel_grad(1, st)
         for r in self.r_g_pieces:  # below the layer, this rank's share of it (its average comes from the gathered master), above it
             self._adamw_range(r, 1, st)
         w0, w1 = self._map_range()
@@ -917,6 +985,7 @@ class GanEngine:
             else:
                 _call("vg_gan_loss_pair", _p(adv), _p(dadv), _p(self.losses), B * self.Kc, 0, B * self.Kc, 1, self.kind, 1.0, st)
             self._ada_update(adv, st)
+            self._tel_d_logits(*self.tel_adv, st)
             if self.bcr:
                 _call("vg_bcr_loss", *map(_p, self.cr_rows), _p(self.bcr_losses), B, B, self.Kc, self.bcr_w[0], self.bcr_w[1],
                       int(not self.aug), int(bool(self.aug)), 1.0, st)
@@ -927,6 +996,8 @@ class GanEngine:
                 self._loss(self.lg_half[half], self.dlg_half[half], B, half, st)
                 if half == 0:
                     self._ada_update(self.lg_half[0], st)
+                else:  # both halves' logits are in place behind the second loss launch: one launch for the two
+                    self._tel_d_logits(self.lg_half[0], self.lg_half[1], st)
                 self._d_backward(net, B, self.ws_d, self.dlg_half[half], 1, None, st, exchange=half == 1)
         self.sync.wait()
         if self.spec is not None:  # dL/dW_eff -> dL/dW on the exchanged total of both passes and the penalty (the map is linear)
@@ -940,6 +1011,7 @@ class GanEngine:
         lg, dlg = self.g_rows
         self._d_forward(nd_c, B, self.g_in, self.ws_d, lg, st)
         self._loss(lg, dlg, B, 2, st)
+        self._tel_g_logits(lg, st)
         self._d_backward(nd_c, B, self.ws_d, dlg, 0, self.g_dimg, st)
         if self.aug:
             self._augment_adjoint(self.g_dimg, self.dfake, B, self.aug, 1, st)
@@ -950,6 +1022,41 @@ class GanEngine:
             self._adamw_g_sharded(st)
         else:
             self._adamw(self.r_g, 1, st, self.clip_g)
+        self._tel_commit(r1_due, st)
+
+    # ------------------------------------------------------------------------------------------ the per-step record
+    def history(self) -> dict:
+        """The records of the steps since the previous call, oldest first (synchronises once): ``step`` int64 [n]; one float32 [n]
+        array per field of ``_lib.TEL_FIELDS`` (the three losses, D's real / fake logit mean and accuracy, the generator pass's logit
+        mean and fraction > 0, ``gnorm_{d,g}_{sum,l2}``, ``nonfinite_{d,g}``, ``penalty``, ``bcr_real`` / ``bcr_fake``, ``ada_p`` /
+        ``ada_rt``, ``lr_d`` / ``lr_g``, ``diversity`` - NaN where the option is off, and ``penalty`` NaN on a step where lazy R1 was
+        not due); ``grad_norms_d`` / ``grad_norms_g`` [n, n_seg] with ``keys_d`` / ``keys_g``, the state_dict keys of the tensors; and
+        ``dropped``, the steps that fell out of a ring shorter than the gap between two calls."""
+        if not self.tel_cap:
+            raise RuntimeError("history(): this engine records nothing (built with telemetry=0)")
+        import numpy as np
+        torch.cuda.synchronize(self.dev)
+        t = int(self.step_t.item())
+        steps_dev, ring = self.tel_ring_step.cpu().numpy(), self.tel_ring.cpu().numpy()
+        seg_d, seg_g = (r.cpu().numpy() for r in self.tel_ring_seg)
+        cap, last = self.tel_cap, min(self._tel_cursor, t)
+        want = list(range(max(last + 1, t - cap + 1), t + 1))
+        rows = [(s - 1) % cap for s in want]
+        stale = [s for s, r in zip(want, rows) if steps_dev[r] != s]
+        if stale:
+            raise RuntimeError(f"history(): the rings do not hold step(s) {stale[:4]} the counter says were run")
+        idx = np.asarray(rows, dtype=np.int64)
+        pre = "vit." if self._disc is not self.vit else ""
+        out = {"step": np.asarray(want, dtype=np.int64), "dropped": (t - last) - len(want),
+               "grad_norms_d": seg_d[idx].copy(), "grad_norms_g": seg_g[idx].copy(),
+               "keys_d": [pre + k for k in self.tel_d.keys], "keys_g": list(self.tel_g.keys)}
+        for f, name in enumerate(_lib.TEL_FIELDS):
+            out[name] = ring[idx, f].astype(np.float32)
+        bad = [int(s) for s, a, b in zip(want, out["nonfinite_d"], out["nonfinite_g"]) if a != 0 or b != 0]
+        if bad and self.first_nonfinite_step is None:
+            self.first_nonfinite_step = bad[0]
+        self._tel_cursor = t
+        return out
 
     # ------------------------------------------------------------------------------------------
     def _optional_state(self):
@@ -989,6 +1096,7 @@ class GanEngine:
         if reset_optimizer:
             for t in (self.m_d, self.v_d, self.m_g, self.v_g, self.step_t):
                 t.zero_()
+            self._tel_cursor = 0  # the record follows the device counter
             # the latent noise is keyed on the device step counter just cleared: move to a fresh stream, keyed on the steps this
             # engine has really done, so a restarted run does not replay the first run's latent sequence
             self._noise_seed = (self._noise_seed * 0x9E3779B97F4A7C15 + 0xD1B54A32D192ED03 * (self.steps + 1)) & 0xFFFFFFFFFFFFFFFF
@@ -1153,6 +1261,7 @@ class GanEngine:
         if self.dataset is not None and int(sd["noise_seed"]) & 0xFFFFFFFFFFFFFFFF != self._noise_seed:
             self._graphs = {}  # the latent stream's seed is an argument of a captured node there (``_fetch``): capture again
         self.steps, self._noise_seed = int(sd["steps"]), int(sd["noise_seed"]) & 0xFFFFFFFFFFFFFFFF
+        self._tel_cursor = int(sd["step_t"].reshape(-1)[0])  # the record continues behind the restored counter
         if self.ema_g is not None:
             self._ema_loads += 1
             # no average in the state: the step after the loaded counter copies.  ema_start is an argument of the captured kernel

@@ -475,6 +475,85 @@ def lr_schedule(step: torch.Tensor, d, g, scale: Optional[torch.Tensor] = None, 
     return out
 
 
+def parse_telemetry(telemetry) -> int:
+    """``GanEngine(telemetry=...)``: the capacity of the per-step rings, an integer >= 1, or 0 (the default) for none.  Anything else -
+    a bool, a float, a negative number - is the caller's error; host only."""
+    if isinstance(telemetry, bool) or not isinstance(telemetry, int) or not 0 <= telemetry < 2 ** 24:
+        raise ValueError(f"telemetry must be 0 (off) or the ring capacity, an integer >= 1 (steps kept between two history() calls), got {telemetry!r}")
+    return int(telemetry)
+
+
+GRAD_CHUNK = 4096  # elements per chunk of vg_grad_stats at most
+
+
+def grad_chunks(slots, limit: int = GRAD_CHUNK):
+    """The chunk table of vg_grad_stats from a slot table (``flat.vit_slots`` / ``flat.gen_slots`` / a FlatParams' ``slots``, the class
+    table included when it has one): ``(chunks, seg_first, keys)`` - chunks int32 [n_chunks, 3] = (first element, count, segment) with
+    count <= ``limit``, seg_first int32 [n_seg + 1], keys the segment names.  One segment per slot in the table's own order (the
+    state_dict's); a chunk never crosses a slot, the chunks of a slot are adjacent and ascending, and nothing between two slots (the
+    layouts' alignment padding) is covered.  Host only (numpy)."""
+    import numpy as np
+    if isinstance(limit, bool) or not isinstance(limit, int) or not 1 <= limit <= GRAD_CHUNK:
+        raise ValueError(f"grad_chunks: limit must be in [1, {GRAD_CHUNK}], got {limit!r}")
+    rows, seg_first, keys = [], [0], []
+    for s, (key, (off, shape)) in enumerate(slots.items()):
+        n = 1
+        for d in shape:
+            n *= int(d)
+        if n < 1 or off < 0 or off + n >= 2 ** 31:
+            raise ValueError(f"grad_chunks: slot {key!r} = ({off}, {tuple(shape)}) is empty or outside a 2^31-element buffer")
+        starts = np.arange(int(off), int(off) + n, limit, dtype=np.int64)
+        counts = np.minimum(limit, int(off) + n - starts)
+        rows.append(np.stack([starts, counts, np.full_like(starts, s)], axis=1))
+        seg_first.append(seg_first[-1] + len(starts))
+        keys.append(key)
+    if not rows:
+        raise ValueError("grad_chunks: an empty slot table")
+    return np.concatenate(rows).astype(np.int32), np.asarray(seg_first, dtype=np.int32), keys
+
+
+class GradStatsPlan:
+    """The device side of one buffer's vg_grad_stats: the chunk table, the segment index, the scratch and the outputs, allocated once."""
+
+    def __init__(self, slots, total: int, device, limit: int = GRAD_CHUNK):
+        chunks, seg_first, self.keys = grad_chunks(slots, limit)
+        self.total, self.n_chunks, self.n_seg = int(total), int(chunks.shape[0]), len(self.keys)
+        if int((chunks[:, 0].astype("int64") + chunks[:, 1]).max()) > self.total:
+            raise ValueError("grad_stats: a slot ends behind the buffer")
+        self.chunks = torch.from_numpy(chunks).to(device).contiguous()
+        self.seg_first = torch.from_numpy(seg_first).to(device)
+        self.scratch = torch.zeros(2 * self.n_chunks, dtype=torch.float32, device=device)
+        self.norm_seg = torch.zeros(self.n_seg, dtype=torch.float32, device=device)
+        self.totals = torch.zeros(4, dtype=torch.float32, device=device)  # (sum of norms, l2, non-finite elements, 0)
+
+    def enqueue(self, grad: torch.Tensor, gscale: float, st) -> None:
+        _lib.check(_lib.lib().vg_grad_stats(_p(grad), self.total, _p(self.chunks), self.n_chunks, _p(self.seg_first), self.n_seg, float(gscale),
+                                            _p(self.scratch), _p(self.norm_seg), _p(self.totals), st), "vg_grad_stats")
+
+
+def grad_stats(flat_grad: torch.Tensor, slots, gscale: float = 1.0, limit: int = GRAD_CHUNK):
+    """Per-tensor gradient norms of one flat fp32 gradient buffer (vg_grad_stats; nothing synchronises): a dict with ``norms``
+    [n_seg] = gscale ||g_s||_2 per slot of ``slots`` in its order, ``keys``, and the device scalars ``sum_norms`` (the sum of those,
+    ``sum(p.grad.norm() for p in parameters)``), ``l2`` (the norm of the whole gradient, what ``clip_grad_norm_`` sees) and
+    ``nonfinite`` (NaN / Inf elements, saturating at 2^24).  Padding between slots is never read."""
+    _need_cuda(flat_grad, "grad_stats")
+    if flat_grad.dtype != torch.float32 or flat_grad.dim() != 1 or not flat_grad.is_contiguous():
+        raise ValueError("grad_stats: flat_grad is a contiguous one-dimensional fp32 tensor")
+    plan = GradStatsPlan(slots, flat_grad.numel(), flat_grad.device, limit)
+    plan.enqueue(flat_grad, gscale, _st())
+    return {"norms": plan.norm_seg, "keys": plan.keys, "sum_norms": plan.totals[0], "l2": plan.totals[1], "nonfinite": plan.totals[2]}
+
+
+def logit_stats(x: torch.Tensor):
+    """``(mean, frac_pos, frac_neg)`` of the logits ``x`` (any shape, 1 to 16384 elements), a device tensor of three floats
+    (vg_logit_stats): the fractions of elements > 0 and < 0 - exact zeros and NaN count in neither."""
+    _need_cuda(x, "logit_stats")
+    xs = _f32(x).reshape(-1)
+    out = torch.zeros(3, 4, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().vg_logit_stats(_p(xs), None, xs.numel(), 0, _p(out), _st()), "vg_logit_stats")
+    return out[0, :3]
+
+
 class ConsistencyLossFn(torch.autograd.Function):
     """Balanced consistency regularisation between D(x) and D(T(x)) (include/vitgan_hip.h, vg_bcr_loss): one launch computes both segment
     means and both gradients, so the backward only scales what the forward saved."""

@@ -152,6 +152,21 @@ def save_figures(save_dir: str, **series) -> None:
         plt.plot(fids, label="FID Score")
         plt.xlabel("Iterations"); plt.ylabel("FID"); plt.legend()
         plt.savefig(os.path.join(save_dir, "fid_score.png")); plt.close()
+    # the two figures of the per-step record (utils.py:71-97): only when their series are present
+    if len(series.get("gradient_norms_gen", ())) and len(series.get("gradient_norms_disc", ())):
+        plt.figure(figsize=(10, 5))
+        plt.title("Gradient Norms During Training")
+        plt.plot(series["gradient_norms_gen"], label="Gen Grad Norm")
+        plt.plot(series["gradient_norms_disc"], label="Disc Grad Norm")
+        plt.xlabel("Iterations"); plt.ylabel("Gradient Norm"); plt.legend()
+        plt.savefig(os.path.join(save_dir, "gradient_norms.png")); plt.close()
+    if len(series.get("disc_real_accuracies", ())) and len(series.get("disc_fake_accuracies", ())):
+        plt.figure(figsize=(10, 5))
+        plt.title("Discriminator Accuracy During Training")
+        plt.plot(series["disc_real_accuracies"], label="Disc Real Acc")
+        plt.plot(series["disc_fake_accuracies"], label="Disc Fake Acc")
+        plt.xlabel("Iterations"); plt.ylabel("Accuracy"); plt.legend()
+        plt.savefig(os.path.join(save_dir, "accuracies.png")); plt.close()
 
 
 def get_data_loader(c: Config):
@@ -257,7 +272,8 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                 r1_gamma: float = 0.0, r1_interval: int = 1, conditional: bool = False,
                 lr_schedule: str = "", lr_warmup: int = 0, lr_total: Optional[int] = None, lr_final: float = 0.0,
                 lr_plateau: Optional[Tuple[float, int]] = None, dataset: Optional[DeviceDataset] = None,
-                fid: str = "", fid_samples: int = 10000, manifold_k: int = 0, kid: bool = False):
+                fid: str = "", fid_samples: int = 10000, manifold_k: int = 0, kid: bool = False,
+                telemetry: Union[bool, int] = False):
     """``loss``: "ns" (default: the executable v1 loss), "hinge", or "wasserstein" - the critic losses of the reference's
     unreached step (training.py:67-125); ``clip_d`` / ``clip_g``: its clip_grad_norm_ limits (5.0 / 0.5 there);
     ``diversity_weight``: its diversity term (0.1 there); ``instance_noise``: sigma of the noise on D's inputs (0.1
@@ -317,7 +333,18 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     real feature rows kept by ``fit_real`` (metrics.py has the definitions).  One more header line names them, the epoch line ENDS in
     `` | P: .. R: .. D: .. C: ..`` and / or `` | KID: ..``, and each entry of the returned history gains a third element, the dict
     of these values.  They tell a loss of fidelity from a loss of coverage - mode collapse - which one distance cannot; like it they
-    rank the epochs of one run only.  Every rank evaluates alike.  Off (default): nothing changes."""
+    rank the epochs of one run only.  Every rank evaluates alike.  Off (default): nothing changes.
+
+    ``telemetry``: the step records itself on the device (``GanEngine(telemetry=...)``): ``True`` keeps one epoch's steps, an integer
+    that many.  At the epoch's synchronisation point the trainer reads ``eng.history()``, extends the reference's per-step series
+    (``gradient_norms_gen`` / ``gradient_norms_disc``: the sums of the per-tensor norms; ``disc_real_accuracies`` /
+    ``disc_fake_accuracies``, src/v2/training.py:80-84,112-123), hands them to ``save_figures`` (``gradient_norms.png``,
+    ``accuracies.png``) and rewrites ``telemetry.npz`` in the run's directory: ``step``, every field of the record, the per-tensor norms
+    ``grad_norms_d`` / ``grad_norms_g`` with ``keys_d`` / ``keys_g``, cumulative over the run.  The epoch line gains the reference's own
+    commented fields (training.py:229) from the epoch's last step, `` | Disc Real Acc: .. | Disc Fake Acc: .. | Grad Norm Gen: .. | Grad
+    Norm Disc: ..``; the first non-finite gradient is logged once (``Non-finite gradient at step N``) and a warning line says when
+    records fell out of a ring shorter than the epoch.  The returned dict gains ``"telemetry"``, the cumulative record.  ``False``
+    (default): the lines, files and series are exactly what they were."""
     global _log_file
     if fid not in FID_KINDS:
         raise ValueError(f"fid must be one of {FID_KINDS}, got {fid!r}")
@@ -352,6 +379,10 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     parse_ada_options(aug_p, ada_target, ada_interval, ada_kimg, parse_aug_policy(diffaug), loss)
     from .ops import parse_r1_options
     parse_r1_options(r1_gamma, r1_interval, gp_weight)
+    if telemetry is not False and telemetry is not True:
+        from .ops import parse_telemetry
+        if parse_telemetry(telemetry) < 1:
+            raise ValueError(f"telemetry must be False, True (a ring of one epoch's steps) or a capacity >= 1, got {telemetry!r}")
     plateau = parse_lr_plateau(lr_plateau, fid_fn if fid_fn is not None else (fid or None))
     if not 0.0 <= float(ema_decay) < 1.0:
         raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
@@ -381,6 +412,9 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
         per_epoch = len(data_loader) if data_loader is not None else steps_per_epoch
         lr_total = epochs * per_epoch if (lr_schedule or lr_warmup) else 0
     lr_opts = parse_lr_schedule(lr_schedule, lr_warmup, lr_total, lr_final)
+    tel_cap = 0 if telemetry is False else int(telemetry)
+    if telemetry is True:  # one epoch's steps
+        tel_cap = max(1, len(data_loader) if data_loader is not None and hasattr(data_loader, "__len__") else steps_per_epoch)
     if not torch.cuda.is_available():
         raise RuntimeError("train_model needs an MI355X: the HIP engine has no CPU path")
     dev = torch.device(device)
@@ -396,7 +430,8 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                     instance_noise=instance_noise, gp_weight=gp_weight, diffaug=diffaug, ema_decay=ema_decay, ema_start=ema_start,
                     spectral_norm=spectral_norm, bcr=bcr, bcr_aug=bcr_aug, aug_p=aug_p, ada_target=ada_target, ada_interval=ada_interval,
                     ada_kimg=ada_kimg, r1_gamma=r1_gamma, r1_interval=r1_interval, n_classes=K,
-                    lr_schedule=lr_schedule, lr_warmup=lr_warmup, lr_total=lr_total, lr_final=lr_final, dataset=dataset)
+                    lr_schedule=lr_schedule, lr_warmup=lr_warmup, lr_total=lr_total, lr_final=lr_final, dataset=dataset,
+                    **({"telemetry": tel_cap} if tel_cap else {}))
 
     def gan_checkpoint():  # gan.state_dict(), the discriminator's normalised matrices as the network applies them
         sd = gan.state_dict()
@@ -457,6 +492,14 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
 
     best_fid = float("inf")
     disc_losses, gen_losses, fid_scores, history = [], [], [], []
+    tel: Dict[str, Any] = {}  # the cumulative per-step record (telemetry on): name -> numpy array, plus keys_d / keys_g
+    nonfinite_logged = False
+
+    def tel_series():  # the reference's per-step series for save_figures; nothing when off
+        if not tel:
+            return {}
+        return {"gradient_norms_gen": tel["gnorm_g_sum"].tolist(), "gradient_norms_disc": tel["gnorm_d_sum"].tolist(),
+                "disc_real_accuracies": tel["d_real_acc"].tolist(), "disc_fake_accuracies": tel["d_fake_acc"].tolist()}
     epoch = 0
     fatal: Optional[BaseException] = None
     try:
@@ -525,7 +568,23 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                     torch.save(gan_checkpoint(), os.path.join(dirs.checkpoints, f"best_model_epoch_{epoch}_fid_{int(fid_score)}.pth"))
                     if G_ema is not None:  # refreshed just above, for fid_fn
                         torch.save(G_ema.state_dict(), os.path.join(dirs.checkpoints, "generator_ema.pth"))
-            cr = ""
+            cr = tel_line = ""  # tel_line: the record's four fields, a variable of its own (the blocks below own ``cr``)
+            if tel_cap:  # the epoch's steps, read at the synchronisation point above
+                import numpy as np
+                rec = eng.history()
+                dropped = rec.pop("dropped")
+                for k_, v_ in rec.items():
+                    tel[k_] = v_ if (k_ not in tel or k_.startswith("keys_")) else np.concatenate([tel[k_], v_])
+                if dropped:
+                    log(f"Warning: telemetry ring of {tel_cap} step(s) is shorter than the epoch: {dropped} step record(s) were dropped")
+                if eng.first_nonfinite_step is not None and not nonfinite_logged:
+                    nonfinite_logged = True
+                    log(f"Non-finite gradient at step {eng.first_nonfinite_step}")
+                if save_artifacts:
+                    np.savez(os.path.join(dirs.save, "telemetry.npz"), **{k_: np.asarray(v_) for k_, v_ in tel.items()})
+                if len(rec["step"]):
+                    tel_line = (f" | Disc Real Acc: {rec['d_real_acc'][-1]:.4f} | Disc Fake Acc: {rec['d_fake_acc'][-1]:.4f}"
+                           f" | Grad Norm Gen: {rec['gnorm_g_sum'][-1]:.4f} | Grad Norm Disc: {rec['gnorm_d_sum'][-1]:.4f}")
             if eng.bcr:
                 cr_real, cr_fake = eng.bcr_losses.tolist()
                 cr = f" | Consistency real: {cr_real:.6f}, fake: {cr_fake:.6f}"
@@ -546,9 +605,9 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
                     cr += " | P: {precision:.4f} R: {recall:.4f} D: {density:.4f} C: {coverage:.4f}".format(**q)
                 if kid:
                     cr += f" | KID: {q['kid']:.6e}"
-            log(f"Epoch [{epoch}/{epochs}] | Disc Loss: {d_real + d_fake:.8f}, Gen Loss: {g:.4f} | FID: {fid_score:.4f}{cr}")
+            log(f"Epoch [{epoch}/{epochs}] | Disc Loss: {d_real + d_fake:.8f}, Gen Loss: {g:.4f} | FID: {fid_score:.4f}{tel_line}{cr}")
             if save_artifacts:
-                save_figures(dirs.save, disc_losses=disc_losses, gen_losses=gen_losses, fid_scores=fid_scores)
+                save_figures(dirs.save, disc_losses=disc_losses, gen_losses=gen_losses, fid_scores=fid_scores, **tel_series())
     except KeyboardInterrupt as ke:
         log(f"{ke} raised!")
     except _lib.HipError as e:  # a failed launch / rejected kernel arguments is never a "successful" run
@@ -562,7 +621,7 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
     finally:
         model_path = os.path.join(dirs.save, "final_model.ckpt")
         if save_artifacts and fatal is None:  # no further GPU work, no checkpoint of a broken run
-            save_figures(dirs.save, disc_losses=disc_losses, gen_losses=gen_losses, fid_scores=fid_scores)
+            save_figures(dirs.save, disc_losses=disc_losses, gen_losses=gen_losses, fid_scores=fid_scores, **tel_series())
             torch.save(gan_checkpoint(), model_path)
             if eng.spec is not None:
                 torch.save(D.state_dict(), os.path.join(dirs.save, "discriminator_raw.pth"))
@@ -586,4 +645,6 @@ def train_model(config: Optional[Dict[str, Any]] = None, steps_per_epoch: int = 
         out["generator_ema"] = G_ema
     if fid_eval is not None:
         out["fid"] = fid_eval
+    if tel_cap:
+        out["telemetry"] = tel
     return out
