@@ -538,3 +538,170 @@ DGRAD_SHAPES = (
     [(M_RESIDUES, 136, 200), (M_RESIDUES, 384, 256), (M_RESIDUES, 1536, 384)]
     + [([4100], 96, 768), ([256, 1024, 2816], 384, 8192), ([16640], 384, 384), ([16640], 1536, 384)]
 )
+
+
+# ------------------------------------------------------------------------ the full-row kernel (csrc/gemm_row.hip)
+# A mirror of its dispatch: vg_row_nwg deals units = M / 16 over min(256, ceil(units / 2)) workgroups, workgroup w owns the units
+# [w units / nwg, (w + 1) units / nwg), and the `while (n > 0)` loop at the end of the kernel cuts them into tiles of at most
+# MAXMT m-tiles.  tests/test_exact_probes_cpu.py holds the workgroup count against vg_row_parts and proves that ROW_M
+# reaches every tile height the kernel is instantiated for.
+ROW_MAXMT = {384: 9, 512: 6}
+ROW_MINUNITS = 2
+
+
+def row_tiles(M, E):
+    """per workgroup of the row kernel at [M, E]: (first row, [heights of its tiles, in m-tiles of 16 rows])"""
+    assert M >= 16 and M % 16 == 0, M
+    maxmt = ROW_MAXMT[E]
+    units = M // 16
+    nwg = min(256, -(-units // ROW_MINUNITS))
+    out = []
+    for w in range(nwg):
+        u0, u1 = w * units // nwg, (w + 1) * units // nwg
+        n, tiles = u1 - u0, []
+        while n > 0:
+            mt = n if n <= maxmt else (8 if maxmt == 9 else (maxmt if n >= 2 * maxmt else (n + 1) // 2))
+            tiles.append(mt)
+            n -= mt
+        out.append((16 * u0, tiles))
+    return out
+
+
+def row_owner(M, E, device="cpu"):
+    """(rows per workgroup [nwg], workgroup of every row [M]) as int64 tensors"""
+    tiles = row_tiles(M, E)
+    rows = torch.tensor([16 * sum(t) for _, t in tiles], device=device)
+    assert int(rows.sum()) == M and [f for f, _ in tiles] == (rows.cumsum(0) - rows).tolist()
+    return rows, torch.repeat_interleave(torch.arange(len(tiles), device=device), rows)
+
+
+# row counts that reach every height: 1 (16 rows), 1 + 2 (48 rows), h = 1..MAXMT alone (4096 h rows: 256 workgroups of h units), and
+# workgroups of several tiles (384: 8 + 2 | 9, 8 + 2 | 8 + 3, 8 + 8 | 8 + 9;  512: 4 + 3 | 6, 5 + 5 | 6 + 5, 6 + 5 + 5 | 6 + 6 + 5)
+ROW_M = {384: [16, 48] + [4096 * k for k in range(1, 10)] + [38912, 43008, 66560],
+         512: [16, 48] + [4096 * k for k in range(1, 7)] + [26624, 43008, 66560]}
+ROW_K = (128, 192, 320)                # 4, 6 and 10 stages of the 4-slot ring: exactly the ring, a wrap, a wrap that is no multiple of 4
+ROW_TALL = {384: 38912, 512: 26624}    # the tall row count that runs at every K: several tiles per workgroup and the tallest tile
+
+
+def row_cases(E):
+    """(M, K) of the exact row probes: K cycles over ROW_M; 16, 48 and ROW_TALL run at every K"""
+    cases = [(M, ROW_K[i % 3]) for i, M in enumerate(ROW_M[E])]
+    return cases + [(M, K) for M in (16, 48, ROW_TALL[E]) for K in ROW_K if (M, K) not in cases]
+
+
+def grid_of(t, what="value"):
+    """the largest 2^-k (k <= 16) that every element of t is a multiple of"""
+    for k in range(17):
+        s = t * 2.0 ** k
+        if torch.equal(s, torch.round(s)):
+            return 2.0 ** -k
+    raise AssertionError(f"{what}: not on a dyadic grid of 2^-16 or coarser")
+
+
+def assert_f32_exact(t, what):
+    assert torch.equal(t, t.float().double()), f"{what}: not exact in fp32"
+    return t
+
+
+def assert_exact_sum(terms, dims, what, limit=EXACT_LIMIT):
+    """an fp32 sum of `terms` over `dims` is exact in any order: the terms lie on a grid 2^-k and sum |terms| < 2^24 grid steps"""
+    q = grid_of(terms, what)
+    top = float(terms.abs().sum(dims).max()) / q
+    assert top < limit, f"{what}: sum |terms| reaches {top} >= {limit} steps of {q}"
+
+
+def row_bwd_terms(d, h, rstd, gamma, gres=None, lb=None, wmod=None, gs=None, bs=None):
+    """The backward of Linear <- LayerNorm (wmod None) or Linear <- self-modulated LayerNorm, from d = dY W [M, E], the
+    normalised rows h = (x - mean) rstd, rstd [M] and the LayerNorm's weight gamma (lw), as the kernels' epilogue forms it; plain
+    torch in the dtype of its inputs.  Returns the terms whose column sums are d gamma (d lw) and d beta (d lb), the terms of d gs
+    and d bs and d w (self-modulated form only), dx, and the magnitudes that dx's fp32 arithmetic rounds relative to."""
+    rs = rstd[:, None]
+    o = {}
+    if wmod is not None:
+        o["l"] = l = h * gamma + lb
+        o["gl"] = gs * l + bs
+        o["dw"] = d * o["gl"]
+        o["dwm"] = dwm = d * wmod
+        o["t_gs"], o["t_bs"] = dwm * l, dwm
+        d = dwm * gs
+    o["t_gamma"], o["t_beta"] = d * h, d
+    o["gg"] = gg = d * gamma
+    o["ggh"] = ggh = gg * h
+    c1, c2 = gg.mean(1, keepdim=True), ggh.mean(1, keepdim=True)
+    core = rs * (gg - c1 - h * c2)
+    mag = rs * (gg.abs() + c1.abs() + (h * c2).abs())
+    o["dx"] = core if gres is None else core + gres
+    o["dx_mag"] = mag if gres is None else mag + gres.abs()
+    return o
+
+
+class RowBwdProbe:
+    """Exact inputs of vg_linear_dgrad_ln_bwd / vg_linear_dgrad_sln_bwd at [M, K] -> [M, E], with their exact consequences (fp64, on
+    the generator's device).  The caller of these kernels supplies mean and rstd, so the probe chooses them: integers x in [-4, 4],
+    per-row mean in {-1, 0, 1} and rstd in {0.5, 1} (drawn per row: a statistic read from the wrong row shows), so that
+    h = (x - mean) rstd is a multiple of 1/2.  d = bf16(dY W) is an integer (counting regime); gamma (lw), lb, wmod, gs and bs are
+    dyadic with small numerators.  Every product of the epilogue is then exact in fp32 and every sum of them exact in any order
+    (asserted here, on the fp64 values), which leaves the five roundings of dx as the kernel's only freedom.
+    sln: the self-modulated form, d_eff = d wmod gs;  bcast > 0: x has that many rows, broadcast over the batch."""
+
+    GS, BS = 1.5, -0.25
+    DX_FLOOR = 2.0 ** -20  # the kernel forms dx with five fp32 roundings of at most 2^-24 each, relative to dx_mag: 3x headroom
+
+    def __init__(self, M, K, E, g, sln=False, bcast=0, density=0.5, limit=EXACT_LIMIT):
+        self.M, self.K, self.E, self.sln, self.bcast, self.limit = M, K, E, sln, bcast, limit
+        self.dY = counting((M, K), g, -1, 1, density)
+        self.W = counting((K, E), g, -1, 1, density)   # nn.Linear(E, K).weight: the Linear the LayerNorm feeds
+        self.x = counting((bcast or M, E), g, -4, 4)
+        self.mean = counting((M,), g, -1, 1)
+        self.rstd = 0.5 * (1.0 + counting((M,), g, 0, 1))
+        self.gres = counting((M, E), g, -8, 8)
+        self.lb = self.wmod = None
+        if sln:
+            self.gamma = dyadic((E,), g, 2, 3)         # lw
+            self.lb = dyadic((E,), g, 4, 4)
+            self.wmod = dyadic((M, E), g, 2, 2)
+        else:
+            self.gamma = 1.0 + dyadic((E,), g, 16, 4)
+        self.d = check_exact_gemm(self.dY, self.W, out_dtype=BF, what="d")
+        xf = self.x.repeat(-(-M // bcast), 1)[:M] if bcast else self.x
+        self.h = (xf - self.mean[:, None]) * self.rstd[:, None]
+        sl = dict(lb=self.lb, wmod=self.wmod, gs=self.GS, bs=self.BS) if sln else {}
+        self.t = t = row_bwd_terms(self.d, self.h, self.rstd, self.gamma, **sl)
+        assert_f32_exact(self.h, "h")
+        for name in ("l", "gl", "dw", "dwm", "t_gs", "t_gamma", "t_beta", "gg", "ggh"):
+            if name in t:
+                assert_f32_exact(t[name], name)
+        for name, dims in (("t_gamma", 0), ("t_beta", 0), ("gg", 1), ("ggh", 1)):
+            assert_exact_sum(t[name], dims, name, limit)
+
+    def dx(self, with_gres):
+        """(fp64 dx, the floor of its fp32 arithmetic)"""
+        if with_gres:
+            return self.t["dx"] + self.gres, self.DX_FLOOR * (self.t["dx_mag"] + self.gres.abs())
+        return self.t["dx"], self.DX_FLOOR * self.t["dx_mag"]
+
+    def check_scalar_budget(self, owner, nwg, limit=EXACT_LIMIT):
+        """d gs / d bs: a workgroup's sum over its rows AND all columns stays exact (it does not grow with M)"""
+        for name in ("t_gs", "t_bs"):
+            q = grid_of(self.t[name], name)
+            top = float(per_workgroup(self.t[name].abs(), owner, nwg).sum(1).max()) / q
+            assert top < limit, f"{name}: a workgroup's sum |terms| reaches {top} >= {limit} steps of {q}"
+
+
+def per_workgroup(terms, owner, nwg):
+    """[nwg, E]: column sums of terms [M, E] over each workgroup's rows, in fp64"""
+    return torch.zeros(nwg, terms.shape[1], dtype=torch.float64, device=terms.device).index_add_(0, owner, terms.double())
+
+
+def assert_colsum(part_w, stored, owner, rows, what):
+    """part_w [nwg, E], the kernel's fp32 column sums per workgroup, against the fp64 sums of the kernel's own stored bf16 rows:
+    |err| <= rows_w 2^-24 sum_w |o| per column, the standard bound of an fp32 sum of rows_w terms in any order"""
+    s64 = stored.double()
+    want, mag = per_workgroup(s64, owner, rows.numel()), per_workgroup(s64.abs(), owner, rows.numel())
+    err = (part_w.double() - want).abs()
+    bad = ~(err <= rows[:, None].double() * 2.0 ** -24 * mag)
+    n = int(bad.sum())
+    if n:
+        w, c = (int(v) for v in bad.nonzero()[0])
+        raise AssertionError(f"{what}: {n} column sums outside the fp32 summation bound; first at workgroup {w} column {c}: got "
+                             f"{float(part_w[w, c])!r} want {float(want[w, c])!r}")

@@ -205,29 +205,66 @@ def test_linear_wgrad_group(M):
 
 
 # ---------------------------------------------------------------------------------------- vg_linear_ln_fwd (full rows)
-def _pack(E, W, K):
+def row_call(E, name, *args):
+    """a full-row entry point at width E: the plain name at 384, the `_e` form (which takes the width) otherwise"""
+    u = X.gpu()
+    if E == 384:
+        u.call(name, *args)
+    else:
+        u.call(name + "_e", E, *args)
+
+
+def _pack(E, W, K, transposed=False):
+    """the packed stage images of W: [E, K] (forward), or transposed [K, E] (the input gradient dX = dY W)"""
     u = X.gpu()
     L = u._lib.lib()
     n = L.vg_row_pack_elems(K) if E == 384 else L.vg_row_pack_elems_e(E, K)
     assert n == E * K
     Wp = torch.empty(n, dtype=BF, device=CUDA)
     dW = W.to(BF)
-    if E == 384:
-        u.call("vg_row_pack_weight", u.ptr(dW), K, K, 0, u.ptr(Wp), u.stream())
-    else:
-        u.call("vg_row_pack_weight_e", E, u.ptr(dW), K, K, 0, u.ptr(Wp), u.stream())
+    row_call(E, "vg_row_pack_weight", u.ptr(dW), W.shape[1], K, 1 if transposed else 0, u.ptr(Wp), u.stream())
     return Wp
 
 
 MEAN_TOL = 2.0 ** -21  # of max|Y| over the row: the sum of exact integers is exact, then one multiply by fp32(1/E)
 RSTD_TOL = 2.0 ** -16  # relative: fp32 sum of E squared deviations, eps added by fma, rsqrtf
+YN_FLOOR = 2.0 ** -14  # of the magnitudes the fp32 arithmetic of Yn rounds relative to: its share where the terms cancel
+
+
+def plain_yn(gam, bet):
+    """z = (y - mean) rstd -> (Yn, its fp32 floor) of the plain LayerNorm"""
+    def yn_of(z):
+        zg = z * gam
+        return zg + bet, YN_FLOOR * (zg.abs() + bet.abs())
+    return yn_of
+
+
+def check_row_fwd(y, Y, Yn, mean, rstd, M, yn_of):
+    """the outputs of a full-row forward against the exact sum y (fp64): Y bitwise, mean / rstd against the fp64 statistics of y,
+    Yn within one bf16 ulp of yn_of((y - mean) rstd) plus the fp32 arithmetic's share; nothing unwritten, no guard row touched"""
+    _check_out(Y, M, X.rne(y, BF), "Y")
+    for t, w in ((Yn, "Yn"), (mean, "mean"), (rstd, "rstd")):
+        X.assert_written(t, M, w)
+        X.assert_guard(t, M, w)
+    mu = y.mean(1)
+    var = ((y - mu[:, None]) ** 2).mean(1)
+    rs = 1.0 / torch.sqrt(var + float(torch.tensor(1e-5, dtype=F32)))
+    em = (mean[:M, 0].double() - mu).abs()
+    assert bool((em <= MEAN_TOL * y.abs().amax(1)).all()), f"mean off by {float(em.max())}"
+    er = ((rstd[:M, 0].double() - rs) / rs).abs()
+    assert bool((er <= RSTD_TOL).all()), f"rstd off by {float(er.max())} relative"
+    yn, floor = yn_of((y - mu[:, None]) * rs[:, None])
+    # one bf16 ulp of the exact value, plus the fp32 arithmetic's share where the terms cancel
+    X.assert_ulps(Yn[:M], yn, "Yn", 1.0, floor=floor)
 
 
 @pytest.mark.parametrize("E", [384, 512])
 @pytest.mark.parametrize("K", [384, 1536])
 def test_linear_ln_fwd_counting(E, K):
     """Y = res + A W^T + bias bitwise; mean / rstd against fp64 statistics of that Y; Yn within one bf16 ulp.
-    units = M / 16 from 1 to 40 (tiles of every height and the split of units over workgroups), then the step's M"""
+    units = M / 16 from 1 to 40 (every split of up to 40 units over workgroups of 1 or 2: tiles of 1 and 2 m-tiles), then the
+    step's M = 16 640 (tiles of 4 and 5 m-tiles).  Every other tile height, the dropout and the other epilogues of this kernel:
+    tests/test_exact_row_gpu.py."""
     u = X.gpu()
     g = X.gen(E + K, CUDA)
     dens = 0.5
@@ -247,28 +284,10 @@ def test_linear_ln_fwd_counting(E, K):
         Y, Yn = X.guarded(M, E, BF, CUDA), X.guarded(M, E, BF, CUDA)
         mean, rstd = X.guarded(M, 1, F32, CUDA), X.guarded(M, 1, F32, CUDA)
         dA, dr = A.to(BF), (res.to(BF) if with_res else None)
-        args = (u.ptr(dA), u.ptr(Wp), u.ptr(dbias), u.ptr(dr), u.ptr(Y), u.ptr(Yn),
-                u.ptr(mean), u.ptr(rstd), u.ptr(dg), u.ptr(dbt), M, K, 1e-5, 0.0, 0, 0, None, u.stream())
-        if E == 384:
-            u.call("vg_linear_ln_fwd", *args)
-        else:
-            u.call("vg_linear_ln_fwd_e", E, *args)
+        row_call(E, "vg_linear_ln_fwd", u.ptr(dA), u.ptr(Wp), u.ptr(dbias), u.ptr(dr), u.ptr(Y), u.ptr(Yn),
+                 u.ptr(mean), u.ptr(rstd), u.ptr(dg), u.ptr(dbt), M, K, 1e-5, 0.0, 0, 0, None, u.stream())
         u.sync()
-        _check_out(Y, M, X.rne(y, BF), "Y")
-        for t, w in ((Yn, "Yn"), (mean, "mean"), (rstd, "rstd")):
-            X.assert_written(t, M, w)
-            X.assert_guard(t, M, w)
-        mu = y.mean(1)
-        var = ((y - mu[:, None]) ** 2).mean(1)
-        rs = 1.0 / torch.sqrt(var + float(torch.tensor(1e-5, dtype=F32)))
-        em = (mean[:M, 0].double() - mu).abs()
-        assert bool((em <= MEAN_TOL * y.abs().amax(1)).all()), f"mean off by {float(em.max())}"
-        er = ((rstd[:M, 0].double() - rs) / rs).abs()
-        assert bool((er <= RSTD_TOL).all()), f"rstd off by {float(er.max())} relative"
-        z = (y - mu[:, None]) * rs[:, None] * gam
-        yn = z + bet
-        # one bf16 ulp of the exact value, plus the fp32 arithmetic's share where z + beta cancels
-        X.assert_ulps(Yn[:M], yn, "Yn", 1.0, floor=2.0 ** -14 * (z.abs() + bet.abs()))
+        check_row_fwd(y, Y, Yn, mean, rstd, M, plain_yn(gam, bet))
 
     X.collect([(16 * un, r) for un in range(1, 41) for r in (0, 1)] + [(16640, 1), (16640, 0)], one)
 

@@ -6,8 +6,12 @@ LayerNorm in front of them (modules.py:178-181).  Inputs are rounded to bf16 fir
 bf16 once (as the unfused kernels did at their HBM round trip), so the references do the same: tolerance 2^-7 of max|ref|
 for bf16 outputs (plus one ulp of the intermediate), 3e-5 for fp32 statistics, 1e-4 for the column sums.
 
-Row counts: M = 16 * units over min(256, ceil(units / 2)) workgroups - the sizes below give tiles of 1..9 m-tiles, several
-tiles per workgroup (M = 66 560: 16-17 units each) and the full C2 launches (M = 16 640 / 33 280: 4-5 and 8-9 units)."""
+Row counts: M = 16 * units over min(256, ceil(units / 2)) workgroups, so a workgroup holds 3 or more units only above 8 192 rows.
+SHAPES reaches tiles of 1, 2, 4, 5, 8 and 9 m-tiles at E = 384 and of 1, 2, 4, 5 and 6 at E = 512: several tiles per workgroup
+(M = 66 560: 16-17 units each) and the full C2 launches (M = 16 640 / 33 280: 4-5 and 8-9 units); SLN_SHAPES reaches tiles of 2
+m-tiles only (exact_util.row_tiles mirrors the dispatch; tests/test_exact_probes_cpu.py holds these sets).  The other heights
+(3, 6, 7; 3 at E = 512), every height of the self-modulated epilogues, K below 384 and bit-exact, per-workgroup checks of all
+four epilogues: tests/test_exact_row_gpu.py."""
 import ctypes as C
 import math
 
