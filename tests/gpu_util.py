@@ -1,20 +1,11 @@
 """Helpers for the -m gpu parity tests: raw C-ABI calls on torch device tensors."""
-import ctypes as C
-
 import torch
 
 import vit_gan_amd  # noqa: F401
 from vit_gan_amd import _lib
 
 BF = torch.bfloat16
-
-
-def ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+ptr, stream, call = _lib.ptr, _lib.stream, _lib.call
 
 
 def dev(t, dtype=None):
@@ -27,10 +18,6 @@ def dev(t, dtype=None):
 def rbf(t):
     """round to bf16 and back: the fp32 value the kernel actually sees"""
     return t.to(BF).float()
-
-
-def call(name, *args):
-    _lib.check(getattr(_lib.lib(), name)(*args), name)
 
 
 def sync():

@@ -33,6 +33,155 @@ def test_library_exports_every_declared_symbol():
     assert lib.vg_abi_version() == _lib.ABI_VERSION == 9
 
 
+# ---- the binding is derived from include/vitgan_hip.h (_lib.Header): held against the C compiler's reading of the same file ----
+HEADER_PATH = os.path.join(ROOT, "include", "vitgan_hip.h")
+C_SCALARS = {C.c_int: "int", C.c_float: "float", C.c_longlong: "long long", C.c_ulonglong: "unsigned long long"}
+SPECTRAL_TABLES = {("vg_spectral_plan", "table_host"), ("vg_spectral_update", "table_host"), ("vg_spectral_update", "table_dev"),
+                   ("vg_spectral_project", "table_host"), ("vg_spectral_project", "table_dev")}
+
+
+def _host_cc():
+    import shutil
+    hipcc = os.path.realpath(shutil.which("hipcc") or "/opt/rocm/bin/hipcc")
+    near = [os.path.join(os.path.dirname(hipcc), *rel, "clang") for rel in ((), ("..", "lib", "llvm", "bin"), ("..", "llvm", "bin"))]
+    cc = shutil.which("cc") or next((p for p in near if os.path.exists(p)), None)
+    assert cc, f"no host C compiler: neither cc on PATH nor a clang next to hipcc ({', '.join(near)})"
+    return cc
+
+
+def _c_signature(name):
+    """the function pointer type of ``name`` as the binding reads it: the return type and the scalars from the ctypes classes it chose,
+    the pointers from the parsed text"""
+    res, args = _lib._SIGNATURES[name]
+    params = [C_SCALARS.get(t, ctext) for t, (ctext, _) in zip(args, _lib._HEADER.prototypes[name][1])]
+    assert len(params) == len(args) == len(_lib._HEADER.prototypes[name][1]), name
+    return f"{C_SCALARS[res]} (*)({', '.join(params) or 'void'})"
+
+
+@pytest.fixture(scope="module")
+def compiled_layout(tmp_path_factory):
+    """{'VgVitDims': sizeof, 'VgVitDims.C': offsetof, ...} from a C program over the header, which also static-asserts every prototype"""
+    import subprocess
+    d = tmp_path_factory.mktemp("abi")
+    lines = ["#include <stddef.h>", "#include <stdio.h>", '#include "vitgan_hip.h"']
+    for name in _lib._SIGNATURES:
+        lines.append(f'_Static_assert(__builtin_types_compatible_p(__typeof__(&{name}), {_c_signature(name)}), "{name}");')
+    lines.append("int main(void) {")
+    for sname, cls in _lib._HEADER.structs.items():
+        lines.append(f'  printf("{sname} %zu\\n", sizeof({sname}));')
+        lines += [f'  printf("{sname}.{field} %zu\\n", offsetof({sname}, {field}));' for field, _ in cls._fields_]
+    lines += ["  return 0;", "}", ""]
+    (d / "abi.c").write_text("\n".join(lines))
+    r = subprocess.run([_host_cc(), "-std=c11", "-I", os.path.dirname(HEADER_PATH), str(d / "abi.c"), "-o", str(d / "abi")],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, "the header read as C disagrees with the binding derived from it:\n" + r.stderr[-3000:]
+    out = subprocess.run([str(d / "abi")], capture_output=True, text=True, check=True).stdout
+    return {k: int(v) for k, v in (ln.split() for ln in out.splitlines())}
+
+
+def test_struct_layouts_match_the_compiler(compiled_layout):
+    """sizeof and every offsetof of every struct of the header, as the host C compiler lays them out, against ctypes"""
+    structs = _lib._HEADER.structs
+    assert len(structs) == 13 and all(getattr(_lib, n) is cls for n, cls in structs.items())
+    want = {}
+    for sname, cls in structs.items():
+        want[sname] = C.sizeof(cls)
+        want.update({f"{sname}.{field}": getattr(cls, field).offset for field, _ in cls._fields_})
+    assert compiled_layout == want, {k: (compiled_layout.get(k), want.get(k)) for k in set(want) | set(compiled_layout)
+                                     if compiled_layout.get(k) != want.get(k)}
+    # what the parser must have made of the three kinds of field: an array, a nested struct by value, a pointer
+    assert _lib.VgVitWsMap.gin.size == 16 and dict(_lib.VgVitNet._fields_)["d"] is _lib.VgVitDims
+    assert all(t is C.c_void_p for cls in structs.values() for _, t in cls._fields_ if issubclass(t, (C._Pointer, C.c_void_p)))
+
+
+def test_signatures_match_the_compiler(compiled_layout):
+    """Every prototype, rendered back from the binding (argument count, order, scalar kinds; pointers as parsed), is the type the
+    compiler gives the declaration: the fixture's program static-asserts all of them, so it compiled.  A wrong rendering must not."""
+    import subprocess
+    assert len(_lib._SIGNATURES) == len(_lib._HEADER.prototypes) == 145
+    assert _c_signature("vg_abi_version") == "int (*)(void)"
+    assert _c_signature("vg_zero_tick") == "int (*)(float*, long long, int*, void*)"
+    assert _lib._SIGNATURES["vg_spectral_plan"][1][2:] == [C.POINTER(C.c_longlong)] * 2
+    assert _lib._SIGNATURES["vg_ctx_create"][1] == [C.POINTER(C.c_void_p)]
+    assert _lib._SIGNATURES["vg_lr_schedule"][1][:2] == [C.POINTER(_lib.VgLrSched)] * 2
+    src = ('#include "vitgan_hip.h"\n_Static_assert(__builtin_types_compatible_p(__typeof__(&vg_zero_tick), '
+           'int (*)(float*, int, int*, void*)), "vg_zero_tick");\n')  # (long long n read as int)
+    r = subprocess.run([_host_cc(), "-std=c11", "-fsyntax-only", "-I", os.path.dirname(HEADER_PATH), "-x", "c", "-"], input=src,
+                       capture_output=True, text=True)
+    assert r.returncode != 0 and "vg_zero_tick" in r.stderr
+
+
+@pytest.mark.parametrize("text, names", [
+    ("int vg_f(const void* a, short n, void* stream);", ("vg_f", "short", "'n'")),
+    ("int vg_f(const short* a);", ("vg_f", "short", "'a'")),
+    ("short vg_f(int a);", ("vg_f", "short")),
+    ("int vg_f(int a, int);", ("vg_f",)),
+    ("int vg_f(int a)\nint vg_g(void);", ("vg_f", "cannot split")),
+    ("int vg_g(void);\nint vg_f(int a", ("vg_f", "cannot split")),
+    ("typedef struct S { int a; short b; } S;", ("struct S", "short", "'b'")),
+    ("typedef struct S { int a, *b; } S;", ("struct S",)),
+    ("typedef struct S { int a; } S;\nint vg_f(const T* s);", ("vg_f", "'s'")),
+    ("#define VG_TEL_A 0\n#define VG_TEL_B 1\n#define VG_TEL_D 3\n#define VG_TEL_NF 8\n", ("VG_TEL_D", "gap")),
+    ("#define VG_TEL_A 0\n#define VG_TEL_B 1\n#define VG_TEL_NF 2\n", ("VG_TEL_NF",)),
+    ("#define VG_LR_A 1\n", ("VG_LR_A",)),
+    ("#define VG_X (1 << 4)\n", ("VG_X",)),
+])
+def test_header_parser_refuses_what_it_does_not_understand(text, names):
+    """No default to int: an unknown type, a prototype or a field it cannot split and a gap in an enumeration raise and name the offender."""
+    with pytest.raises(_lib.HeaderError) as e:
+        _lib.Header("/* c */\n#ifndef H\n#define H\n" + text + "\n#endif\n")
+    assert all(n in str(e.value) for n in names), str(e.value)
+
+
+def test_header_parser_reads_the_constants():
+    h = _lib.Header("#define VG_ABI_VERSION 3 /* v */\n#define VG_TEL_A 0\n#define VG_TEL_B_C 1 // x\n#define VG_TEL_NF 4\n#define VG_LR_X 0\n"
+                    "typedef struct VgS { long long a[2], b; const float* p; } VgS;\nlong long vg_f(const VgS* s, unsigned long long k);\n")
+    assert (h.defines["VG_ABI_VERSION"], h.tel_fields, h.lr_kinds) == (3, ("a", "b_c"), {"x": 0})
+    assert [(n, C.sizeof(t)) for n, t in h.structs["VgS"]._fields_] == [("a", 16), ("b", 8), ("p", 8)]
+    assert h.signatures["vg_f"] == (C.c_longlong, [C.POINTER(h.structs["VgS"]), C.c_ulonglong])
+    text = open(HEADER_PATH).read()
+    assert (_lib.ABI_VERSION, _lib.TEL_NF, len(_lib.TEL_FIELDS)) == (int(re.search(r"#define VG_ABI_VERSION (\d+)", text).group(1)), 24, 23)
+    assert _lib.TEL_FIELDS[0] == "loss_d_real" and _lib.TEL_FIELDS[22] == "diversity" and _lib.LR_KINDS == {"constant": 0, "linear": 1, "cosine": 2}
+
+
+def test_spectral_tables_are_the_only_struct_pointers_bound_as_addresses():
+    """A pointer to a header struct is POINTER(that struct) - but for the spectral descriptor table, which the caller keeps as bytes on
+    the host and on the device (one of the two arguments is a device address): exactly these five parameters, bound as plain addresses."""
+    structs = _lib._HEADER.structs
+    plain, typed = set(), 0
+    for name, (_, params) in _lib._HEADER.prototypes.items():
+        for (ctext, pname), t in zip(params, _lib._SIGNATURES[name][1]):
+            if ctext.replace("const ", "").rstrip("*") in structs:
+                assert ctext.count("*") == 1, (name, pname)
+                if t is C.c_void_p:
+                    plain.add((name, pname))
+                else:
+                    assert t is C.POINTER(structs[ctext.replace("const ", "").rstrip("*")]), (name, pname, t)
+                    typed += 1
+    assert plain == SPECTRAL_TABLES and typed >= 30
+
+
+def test_one_call_path():
+    """_lib.call resolves through lib() on every call (the step-trace recorder swaps the handle) and reports the symbol it called."""
+    seen = []
+
+    class Proxy:
+        def __getattr__(self, name):
+            seen.append(name)
+            return getattr(handle, name)
+    handle = _lib.lib()
+    try:
+        _lib._lib = Proxy()
+        with pytest.raises(_lib.HipError, match=r"^vg_attention_l2_fwd failed: argument validation -1$"):
+            _lib.call("vg_attention_l2_fwd", None, None, None, 1, 1, 1, 32, 1.0, None)
+        with pytest.raises(_lib.HipError, match=r"^vg_vit_layout \(why\) failed: argument validation -3$"):
+            _lib.call("vg_vit_layout", C.byref(_lib.VgVitDims(3, 32, 4, 100, 4, 6, 2, 1)), C.byref(_lib.VgVitLayout()), what="vg_vit_layout (why)")
+    finally:
+        _lib._lib = handle
+    assert seen == ["vg_attention_l2_fwd", "vg_vit_layout"] and _lib.ptr(None) is None
+    assert _lib.bind(C.CDLL(_lib.LIB_PATH), ["vg_row_pack_elems"]).vg_row_pack_elems.restype is C.c_longlong
+
+
 def test_argument_validation_without_gpu():
     """Entry points reject bad arguments before touching the device (negative codes)."""
     lib = _lib.lib()

@@ -14,29 +14,23 @@ import os
 import statistics
 import sys
 
-import torch  # noqa: F401  (first: one HIP runtime for torch and the libraries)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: F401,E402  (first: one HIP runtime for torch and the libraries)
+import vit_gan_amd  # noqa: F401,E402
+from vit_gan_amd import _lib  # noqa: E402
 
 BF = torch.bfloat16
-P, I, F = C.c_void_p, C.c_int, C.c_float
-FWD, BWD = [P, P, P, I, I, I, I, F, P], [P, P, P, P, P, I, I, I, I, F, P]
 libs = []
 for path in sys.argv[1:]:
-    h = C.CDLL(os.path.abspath(path))
-    for stem in ("vg_attention", "vg_attention_fp8", "vg_attention_l2", "vg_attention_cls"):
-        getattr(h, stem + "_fwd").argtypes = FWD
-        getattr(h, stem + "_bwd").argtypes = BWD
-    h.vg_attention_bwd_bwd.argtypes = [P, P, P, P, P, P, I, I, I, I, F, P]
+    h = _lib.bind(C.CDLL(os.path.abspath(path)), [stem + end for stem in ("vg_attention", "vg_attention_fp8", "vg_attention_l2", "vg_attention_cls")
+                                                  for end in ("_fwd", "_bwd")] + ["vg_attention_bwd_bwd"])
     libs.append((f"{len(libs)}:{path}", h))  # (the position keeps two paths with the same tail apart)
-st = P(torch.cuda.current_stream().cuda_stream)
+st, p = _lib.stream(), _lib.ptr
 ROUNDS, REPS = int(os.environ.get("ROUNDS", "7")), int(os.environ.get("REPS", "20"))
 ONLY = os.environ.get("ONLY", "")  # time only the lines whose name contains this
 ROLES = os.environ.get("ROLES", "").split(",") if os.environ.get("ROLES") else None
 assert ROLES is None or sorted(ROLES) == ["copy", "new", "parent"] and len(libs) == 3, "ROLES names three libraries: parent, copy, new"
 above = []
-
-
-def p(t):
-    return P(t.data_ptr())
 
 
 def bench(name, make):

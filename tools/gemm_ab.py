@@ -9,23 +9,18 @@ import os
 import statistics
 import sys
 
-import torch  # noqa: F401  (first: one HIP runtime for torch and the libraries)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: F401,E402  (first: one HIP runtime for torch and the libraries)
+import vit_gan_amd  # noqa: F401,E402
+from vit_gan_amd import _lib  # noqa: E402
 
 BF = torch.bfloat16
-P = C.c_void_p
 libs = []
 for path in sys.argv[1:]:
-    h = C.CDLL(os.path.abspath(path))
-    h.vg_linear_fwd.argtypes = [P] * 7 + [C.c_int] * 4 + [C.c_float, P]
-    h.vg_linear_dgrad.argtypes = [P, P, P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, C.c_float, P]
-    h.vg_linear_wgrad.argtypes = [P, P, P, P, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P]  # ABI >= 4
+    h = _lib.bind(C.CDLL(os.path.abspath(path)), ("vg_linear_fwd", "vg_linear_dgrad", "vg_linear_wgrad"))
     libs.append((os.path.basename(path), h))
-st = P(torch.cuda.current_stream().cuda_stream)
+st, p = _lib.stream(), _lib.ptr
 ROUNDS, REPS = int(os.environ.get("ROUNDS", "7")), int(os.environ.get("REPS", "20"))
-
-
-def p(t):
-    return None if t is None else P(t.data_ptr())
 
 
 def bench(name, calls, flops):

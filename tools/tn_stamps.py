@@ -5,23 +5,25 @@ import ctypes as C
 import os
 import sys
 
-import numpy as np
-import torch
-
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, root)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import vit_gan_amd  # noqa: F401,E402
+from vit_gan_amd import _lib  # noqa: E402
+
 M, N, K, SPL = 33280, int(os.environ.get("N", "1152")), 384, int(os.environ.get("WG_SPLITS", "10"))
 nwg = (N // 128) * (K // 384) * SPL
 stamps = torch.zeros(nwg * 8 * 8, dtype=torch.int64, device="cuda")
 os.environ["VG_STAMP_PTR"] = hex(stamps.data_ptr())
-L = C.CDLL(os.path.join(root, "vit-gan_amd", "libvitgan_hip_tnst.so"))
-P = C.c_void_p
-L.vg_linear_wgrad.argtypes = [P, P, P, P, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, P]
+L = _lib.bind(C.CDLL(os.path.join(root, "vit-gan_amd", "libvitgan_hip_tnst.so")), ["vg_linear_wgrad"])
+P = _lib.ptr
 BF = torch.bfloat16
 dy = torch.randn(M, N, device="cuda").to(BF); x = torch.randn(M, K, device="cuda").to(BF)
 dw = torch.empty(N, K, device="cuda"); slab = torch.empty(SPL * N * K, device="cuda")
-st = P(torch.cuda.current_stream().cuda_stream)
+st = _lib.stream()
 for _ in range(5):
-    L.vg_linear_wgrad(P(dy.data_ptr()), P(x.data_ptr()), P(dw.data_ptr()), P(slab.data_ptr()), slab.numel(), M, N, K, SPL, 0, st)
+    L.vg_linear_wgrad(P(dy), P(x), P(dw), P(slab), slab.numel(), M, N, K, SPL, 0, st)
 torch.cuda.synchronize()
 t = stamps.cpu().numpy().reshape(nwg, 8, 8).astype(np.float64)
 steps = t[:, :, 5]

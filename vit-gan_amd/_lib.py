@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import subprocess
 from typing import Optional
 
@@ -13,230 +14,118 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VITGAN_HIP_LIB", os.path.join(_HERE, "libvitgan_hip.so"))  # override: kernel experiments only
 CSRC = os.path.join(_HERE, "csrc")
 
+HEADER = os.path.normpath(os.path.join(_HERE, "..", "include", "vitgan_hip.h"))
+
 c_void_p, c_int, c_float, c_ll = C.c_void_p, C.c_int, C.c_float, C.c_longlong
-ABI_VERSION = 9  # VG_ABI_VERSION of include/vitgan_hip.h this binding was written against
+_SCALARS = {"int": c_int, "float": c_float, "long long": c_ll, "unsigned long long": C.c_ulonglong}
+_POINTEES = set(_SCALARS) | {"void", "double", "unsigned", "unsigned char"}  # what a plain address may point at
+_TYPED_POINTERS = {"long long*": C.POINTER(c_ll), "void**": C.POINTER(c_void_p)}  # out-parameters filled through byref()
+# The spectral table is kept twice by the caller, as bytes on the host and as the same bytes on the device, and the calls take both:
+# one of the two is a device address, so neither is bound as a pointer to the ctypes struct.
+_BYTE_TABLES = ("table_host", "table_dev")
 
 
-class VgVitDims(C.Structure):
-    _fields_ = [(n, c_int) for n in ("C", "IH", "P", "E", "H", "L", "R", "Kc")]
+class HeaderError(ValueError):
+    pass
 
 
-class VgVitLayout(C.Structure):
-    _fields_ = [(n, c_ll) for n in (
-        "conv_w", "conv_b", "pos", "cls", "layer0", "layer_stride", "wqkv", "wo", "w1", "w2",
-        "ln1_w", "ln1_b", "bqkv", "bo", "ln2_w", "ln2_b", "b1", "b2", "layer_weights",
-        "lnf_w", "lnf_b", "hw1", "hb1", "hw2", "hb2", "total")]
+class Header:
+    """What the binding needs of the C header: ``structs`` {name: ctypes.Structure class}, ``prototypes`` {function: (return type,
+    [(type, parameter)])} as C text, ``signatures`` {function: (restype, [ctypes of the arguments])}, ``defines`` {name: int} and the two
+    enumerations kept as defines, ``lr_kinds`` (VG_LR_*) and ``tel_fields`` (VG_TEL_* but the row width VG_TEL_NF).  It reads the constructs
+    include/vitgan_hip.h uses and raises HeaderError, naming the offender, on anything else."""
+
+    def __init__(self, text: str):
+        self.structs, self.prototypes, self.signatures, self.defines = {}, {}, {}, {}
+        text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+        text = re.sub(r"^[ \t]*#[ \t]*ifdef __cplusplus\n.*?^[ \t]*#[ \t]*endif[^\n]*$", "", text, flags=re.S | re.M)  # extern "C" { and }
+        for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(VG_\w+)[ \t]*(.*)$", text, flags=re.M):
+            if not re.fullmatch(r"-?\d+", value.strip()):
+                raise HeaderError(f"#define {name}: {value.strip()!r} is not an integer")
+            self.defines[name] = int(value)
+        text = re.sub(r"^[ \t]*#[^\n]*$", "", text, flags=re.M)
+
+        def struct(m):
+            self._struct(m.group(1) or m.group(3), m.group(2), m.group(3))
+            return ""
+        text = re.sub(r"\btypedef\s+struct\s*(\w*)\s*\{([^{}]*)\}\s*(\w+)\s*;", struct, text)
+        *statements, rest = text.split(";")
+        for st in statements + [rest]:
+            if st.strip():
+                self._prototype(" ".join(st.split()), terminated=st is not rest)
+        self.lr_kinds = self._enum("VG_LR_")
+        self.tel_fields = tuple(self._enum("VG_TEL_", reserved="VG_TEL_NF"))
+
+    @staticmethod
+    def _declarator(decl: str, where: str):
+        """'const float* lr_dev' -> ('const float*', 'lr_dev', None);  'long long gin[2]' -> ('long long', 'gin', 2)"""
+        m = re.fullmatch(r"(.*?)(\w+)\s*(?:\[\s*(\d+)\s*\])?", decl.strip())
+        if not m or not re.fullmatch(r"[\w\s*]*", m.group(1)):
+            raise HeaderError(f"{where}: cannot read the declaration {decl.strip()!r}")
+        return re.sub(r"\s*\*\s*", "*", " ".join(m.group(1).split())), m.group(2), m.group(3) and int(m.group(3))
+
+    def _ctype(self, ctext: str, name: str, where: str, parameter: bool):
+        base = " ".join(re.sub(r"\bconst\b", "", ctext).replace("*", " ").split())
+        if "*" not in ctext:
+            t = _SCALARS.get(base) or (None if parameter else self.structs.get(base))  # a nested struct is held by value
+        elif parameter and ctext in _TYPED_POINTERS:
+            t = _TYPED_POINTERS[ctext]
+        elif parameter and base in self.structs and ctext.count("*") == 1:
+            t = c_void_p if name in _BYTE_TABLES else C.POINTER(self.structs[base])
+        else:
+            t = c_void_p if base in _POINTEES else None
+        if t is None:
+            raise HeaderError(f"{where}: no ctypes mapping for the type {ctext!r} of {name!r}")
+        return t
+
+    def _struct(self, tag: str, body: str, name: str) -> None:
+        if tag != name:
+            raise HeaderError(f"struct {name}: tag {tag!r} differs from the typedef name")
+        fields = []
+        *decls, rest = body.split(";")
+        if rest.strip():
+            raise HeaderError(f"struct {name}: field {rest.strip()!r} has no ';'")
+        for decl in decls:
+            first, *more = (self._declarator(x, f"struct {name}") for x in decl.split(","))  # 'long long gin[2], gmid[2]': one type
+            if any(ctext for ctext, _, _ in more):
+                raise HeaderError(f"struct {name}: cannot read the declaration {decl.strip()!r}")
+            for _, field, count in [first] + more:
+                t = self._ctype(first[0], field, f"struct {name}", parameter=False)
+                fields.append((field, t * count if count else t))
+        self.structs[name] = type(name, (C.Structure,), {"_fields_": fields})
+
+    def _prototype(self, st: str, terminated: bool) -> None:
+        fn = (re.search(r"\bvg_\w+", st) or re.search(r"\w+", st)).group(0)
+        m = re.fullmatch(r"([\w\s*]+?)\s*\b(vg_\w+)\s*\(([^()]*)\)", st)
+        if not m or not terminated:
+            raise HeaderError(f"{fn}: cannot split the prototype {st[:120]!r}" + ("" if terminated else " (no ';')"))
+        ret = " ".join(m.group(1).split())
+        if ret not in _SCALARS:
+            raise HeaderError(f"{fn}: no ctypes mapping for the return type {ret!r}")
+        params = [] if m.group(3).strip() == "void" else [self._declarator(p, fn) for p in m.group(3).split(",")]
+        if any(count is not None or not ctext for ctext, _, count in params):
+            raise HeaderError(f"{fn}: cannot read the parameter list ({m.group(3).strip()})")
+        self.prototypes[fn] = (ret, [(ctext, p) for ctext, p, _ in params])
+        self.signatures[fn] = (_SCALARS[ret], [self._ctype(ctext, p, fn, parameter=True) for ctext, p, _ in params])
+
+    def _enum(self, prefix: str, reserved: str = None) -> dict:
+        """{lower-cased suffix: value} of the ``#define prefix*`` group (without ``reserved``), which must number 0..n-1 without a gap"""
+        group = sorted((v, k[len(prefix):].lower()) for k, v in self.defines.items() if k.startswith(prefix) and k != reserved)
+        for i, (v, name) in enumerate(group):
+            if v != i:
+                raise HeaderError(f"{prefix}{name.upper()} = {v}: the {prefix}* indices must run 0..n-1 without a gap, expected {i}")
+        if group and reserved is not None and len(group) >= self.defines.get(reserved, 0):
+            raise HeaderError(f"{reserved} = {self.defines.get(reserved)} does not lie above the {len(group)} {prefix}* indices")
+        return {name: v for v, name in group}
 
 
-class VgVitNet(C.Structure):
-    _fields_ = [("d", VgVitDims), ("P", c_void_p), ("Pb", c_void_p), ("G", c_void_p),
-                ("dropout_p", c_float), ("dropout_seed", C.c_ulonglong), ("dropout_step", c_void_p), ("ctx", c_void_p),
-                ("attn_fp8", c_int), ("dense_top", c_int)]
-
-
-class VgVitWsMap(C.Structure):
-    _fields_ = ([(n, c_ll) for n in ("X", "xn1", "qkv", "ao", "xmid", "xn2", "z1", "a1", "lse", "mean1", "rstd1", "mean2", "rstd2")]
-                + [(n, c_ll * 2) for n in ("gin", "gmid", "dqkv", "dz1")] + [("total", c_ll), ("xtop", c_ll), ("dxtop", c_ll)])
-
-
-class VgGenWsMap(C.Structure):
-    _fields_ = ([(n, c_ll) for n in ("wmod", "s1", "qkv", "cat", "htmp", "s2", "hout", "sf", "y1", "zf1", "zf2")]
-                + [("g", c_ll * 3), ("dw_acc", c_ll), ("total", c_ll)])
-
-
-class VgGenDims(C.Structure):
-    _fields_ = ([(n, c_int) for n in ("Z", "T", "E", "H", "L", "O", "CW")] + [("omega0", c_float)]
-                + [(n, c_int) for n in ("patch", "C", "IH")])
-
-
-class VgGenLayout(C.Structure):
-    _fields_ = [(n, c_ll) for n in (
-        "emb", "map_w", "map_b", "layer0", "layer_stride", "wqkv", "wo", "wm",
-        "sln1_w", "sln1_b", "sln1_s", "sln2_w", "sln2_b", "sln2_s", "bo", "bm", "layer_weights",
-        "slnf_w", "slnf_b", "slnf_s", "s1_w", "s1_b", "s2_w", "s2_b", "total")]
-
-
-class VgGenNet(C.Structure):
-    _fields_ = [("d", VgGenDims), ("P", c_void_p), ("Pb", c_void_p), ("G", c_void_p),
-                ("dropout_p", c_float), ("dropout_seed", C.c_ulonglong), ("dropout_step", c_void_p), ("pos_table", c_void_p)]
-
-
-class VgGenCond(C.Structure):
-    _fields_ = [("labels", c_void_p), ("table_bf16", c_void_p), ("table_grad", c_void_p), ("K", c_int)]
-
-
-class VgGenCondF32(C.Structure):
-    _fields_ = [("labels", c_void_p), ("table", c_void_p), ("table_grad", c_void_p), ("K", c_int)]
-
-
-class VgSpectralDesc(C.Structure):
-    _fields_ = ([("w_off", c_ll), ("N", c_int), ("K", c_int)] + [(n, c_ll) for n in ("u_off", "v_off", "s_off", "t_off", "w_tmp_off", "dot_off")]
-                + [(n, c_int) for n in ("blk_a", "blk_b", "blk_c", "reserved")])
-
-
-class VgLrSched(C.Structure):
-    _fields_ = [("base", c_float), ("kind", c_int), ("warmup", c_int), ("total", c_int), ("final_ratio", c_float)]
-
-
-class VgTelemetrySrc(C.Structure):
-    _fields_ = ([(n, c_void_p) for n in ("losses", "logit_stats", "grad_d", "grad_g", "penalty", "bcr", "ada_state", "lr", "diversity",
-                                         "seg_d", "seg_g")] + [(n, c_int) for n in ("n_seg_d", "n_seg_g", "penalty_due")])
-
-
-# VG_TEL_* of include/vitgan_hip.h: the fields of one telemetry row, by index (23 is reserved)
-TEL_FIELDS = ("loss_d_real", "loss_d_fake", "loss_g", "d_real_mean", "d_fake_mean", "d_real_acc", "d_fake_acc", "g_mean", "g_frac_pos",
-              "gnorm_d_sum", "gnorm_d_l2", "gnorm_g_sum", "gnorm_g_l2", "nonfinite_d", "nonfinite_g", "penalty", "bcr_real", "bcr_fake",
-              "ada_p", "ada_rt", "lr_d", "lr_g", "diversity")
-TEL_NF = 24
-
-P = c_void_p
-_SIGNATURES = {
-    "vg_abi_version": (c_int, []),
-    "vg_linear_fwd": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
-    "vg_linear_gelu_fwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P]),
-    "vg_linear_dgrad": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P, c_float, P]),
-    "vg_linear_wgrad_slab_floats": (c_ll, [c_int, c_int, c_int]),
-    "vg_linear_wgrad": (c_int, [P, P, P, P, c_ll, c_int, c_int, c_int, c_int, c_int, P]),
-    "vg_linear_wgrad_group": (c_int, [c_int, P, P, P, P, P, c_int, c_int, P, c_ll, P, c_ll, c_int, P]),
-    "vg_layernorm_fwd": (c_int, [P, c_ll, P, P, P, c_ll, P, P, c_int, c_int, c_float, P]),
-    "vg_layernorm_bwd_parts": (c_int, [c_int]),
-    "vg_layernorm_bwd": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, P]),
-    "vg_sln_fwd": (c_int, [P, c_int, P, P, P, P, P, P, P, P, c_int, c_int, c_float, P]),
-    "vg_sln_bwd": (c_int, [P, P, c_int, P, P, P, P, P, P, P, P, P, P, c_int, P, c_int, c_int, P]),
-    "vg_row_pack_elems": (c_ll, [c_int]),
-    "vg_row_pack_weight": (c_int, [P, c_int, c_int, c_int, P, P]),
-    "vg_row_parts": (c_int, [c_int]),
-    "vg_linear_ln_fwd": (c_int, [P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_float, c_float, C.c_ulonglong, c_int, P, P]),
-    "vg_linear_dgrad_ln_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_float, C.c_ulonglong, c_int, P, P]),
-    "vg_row_pack_elems_e": (c_ll, [c_int, c_int]),
-    "vg_row_pack_weight_e": (c_int, [c_int, P, c_int, c_int, c_int, P, P]),
-    "vg_linear_ln_fwd_e": (c_int, [c_int, P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_float, c_float, C.c_ulonglong, c_int, P, P]),
-    "vg_linear_dgrad_ln_bwd_e": (c_int, [c_int, P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_float, C.c_ulonglong, c_int, P, P]),
-    "vg_linear_sln_fwd_e": (c_int, [c_int, P, P, P, P, P, c_int, P, P, P, P, P, P, P, P, P, c_int, c_int, c_float, c_float, C.c_ulonglong, c_int, P, P]),
-    "vg_linear_dgrad_sln_bwd_e": (c_int, [c_int, P, P, P, c_int, P, P, P, P, P, P, P, P, P, P, P, c_int, P, c_int, c_int, c_float, C.c_ulonglong, c_int, P, P]),
-    "vg_encoder_mlp_image_elems": (c_ll, []),
-    "vg_encoder_mlp_pack": (c_int, [P, P, P, P]),
-    "vg_encoder_mlp_fwd": (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, P, c_int, c_float, c_float, C.c_ulonglong, c_int, P, P]),
-    "vg_encoder_post_attention_image_elems": (c_ll, []),
-    "vg_encoder_post_attention_pack": (c_int, [P, P, P, P, P]),
-    "vg_encoder_post_attention_fwd": (c_int, [P] * 20 + [c_int, c_float, c_float, C.c_ulonglong, c_int, c_int, P, P]),
-    "vg_linear_sln_fwd": (c_int, [P, P, P, P, P, c_int, P, P, P, P, P, P, P, P, P, c_int, c_int, c_float, c_float, C.c_ulonglong, c_int, P, P]),
-    "vg_linear_dgrad_sln_bwd": (c_int, [P, P, P, c_int, P, P, P, P, P, P, P, P, P, P, P, c_int, P, c_int, c_int, c_float, C.c_ulonglong, c_int, P, P]),
-    "vg_colsum_f32": (c_int, [P, c_int, c_int, P, c_int, P, c_int, P, c_int, P, c_int, c_int, P]),
-    "vg_colsum_bf16_parts": (c_int, [c_int]),
-    "vg_colsum_bf16": (c_int, [P, c_ll, c_int, c_int, P, P, c_int, P]),
-    "vg_dropout_apply": (c_int, [P, P, c_ll, c_float, C.c_ulonglong, c_int, P, P]),
-    "vg_attention_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
-    "vg_attention_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
-    "vg_attention_cls_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
-    "vg_attention_cls_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
-    "vg_unfold_tokens_fwd": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, c_int, P]),
-    "vg_unfold_tokens_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
-    "vg_attention_fp8_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
-    "vg_attention_fp8_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
-    "vg_attention_l2_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
-    "vg_attention_l2_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
-    "vg_act_fwd": (c_int, [P, P, c_ll, c_int, P]),
-    "vg_act_bwd": (c_int, [P, P, P, c_ll, c_int, P]),
-    "vg_act_bwd_bwd": (c_int, [P, P, P, P, P, c_ll, c_int, P]),
-    "vg_layernorm_bwd_bwd_parts": (c_int, [c_int]),
-    "vg_layernorm_bwd_bwd": (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, P]),
-    "vg_attention_bwd_bwd": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
-    "vg_zero_tick": (c_int, [P, c_ll, P, P]),
-    "vg_step_inputs": (c_int, [P, P, c_ll, P, c_ll, C.c_ulonglong, P, P]),
-    "vg_dataset_fetch": (c_int, [P, P, c_ll, c_int, c_int, c_int, P, P, P, P, c_int, c_int, c_int, c_int, C.c_ulonglong, P, P]),
-    "vg_diffaug_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, C.c_ulonglong, c_int, P, P]),
-    "vg_diffaug_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, C.c_ulonglong, c_int, P, P]),
-    "vg_diffaug_p_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, C.c_ulonglong, c_int, P, P, P]),
-    "vg_diffaug_p_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, C.c_ulonglong, c_int, P, P, P]),
-    "vg_ada_update": (c_int, [P, c_int, P, c_float, c_float, c_int, P, P]),
-    "vg_gan_loss": (c_int, [P, P, P, c_int, c_int, c_int, c_float, P]),
-    "vg_gan_loss_pair": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P]),
-    "vg_bcr_loss": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_float, P]),
-    "vg_adamw_step": (c_int, [P, P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_float, c_int, P, c_float, P]),
-    "vg_adamw_ema_step": (c_int, [P, P, P, P, P, P, c_ll, c_float, c_float, c_float, c_float, c_float, c_int, P, c_float, c_float, c_int, P]),
-    "vg_adamw_step_dlr": (c_int, [P, P, P, P, P, c_ll, P, c_float, c_float, c_float, c_float, c_int, P, c_float, P]),
-    "vg_adamw_ema_step_dlr": (c_int, [P, P, P, P, P, P, c_ll, P, c_float, c_float, c_float, c_float, c_int, P, c_float, c_float, c_int, P]),
-    "vg_lr_schedule": (c_int, [C.POINTER(VgLrSched), C.POINTER(VgLrSched), P, P, P, P]),
-    "vg_ema_update": (c_int, [P, P, c_ll, c_float, c_int, c_int, P, P]),
-    "vg_diversity_loss": (c_int, [P, P, P, P, c_int, c_int, c_float, P]),
-    "vg_grad_clip": (c_int, [P, c_ll, c_float, c_float, P, P]),
-    "vg_cast_f32_bf16": (c_int, [P, P, c_ll, P]),
-    "vg_head_fwd": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
-    "vg_head_bwd_parts": (c_int, [c_int]),
-    "vg_head_bwd_part_width": (c_int, [c_int, c_int]),
-    "vg_head_bwd": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
-    "vg_batch_sum": (c_int, [P, P, c_int, c_int, c_int, P]),
-    "vg_embed_small_grads": (c_int, [P, P, P, P, c_int, c_int, P]),
-    "vg_take_rows": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
-    "vg_scatter_cls": (c_int, [P, P, P, c_int, c_int, c_int, c_float, C.c_ulonglong, c_int, P, P]),
-    "vg_scatter_cls_pair": (c_int, [P, P, P, P, c_int, c_int, c_int, P]),
-    "vg_fill_cls": (c_int, [P, P, c_int, c_int, c_int, c_float, C.c_ulonglong, c_int, P, P]),
-    "vg_patchify": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, P]),
-    "vg_unpatchify": (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
-    "vg_slab_reduce": (c_int, [P, c_ll, c_int, P, c_ll, c_int, P]),
-    "vg_slab_reduce_pair": (c_int, [P, P, c_ll, c_int, P, P, c_ll, c_int, P]),
-    "vg_sin_grad": (c_int, [P, P, P, c_ll, c_float, P]),
-    "vg_add_table": (c_int, [P, P, c_ll, c_int, c_int, P]),
-    "vg_spectral_plan": (c_int, [P, c_int, C.POINTER(c_ll), C.POINTER(c_ll)]),
-    "vg_spectral_update": (c_int, [P, P, c_ll, P, c_ll, P, c_ll, P, P, c_int, c_int, P]),
-    "vg_spectral_project": (c_int, [P, P, c_ll, P, c_ll, P, c_ll, P, P, c_int, P]),
-    "vg_ctx_create": (c_int, [C.POINTER(c_void_p)]),
-    "vg_ctx_destroy": (c_int, [c_void_p]),
-    "vg_vit_layout": (c_int, [C.POINTER(VgVitDims), C.POINTER(VgVitLayout)]),
-    "vg_vit_ws_bytes": (c_ll, [C.POINTER(VgVitDims), c_int]),
-    "vg_vit_ws_map": (c_int, [C.POINTER(VgVitDims), c_int, C.POINTER(VgVitWsMap)]),
-    "vg_gen_ws_map": (c_int, [C.POINTER(VgGenDims), c_int, C.POINTER(VgGenWsMap)]),
-    "vg_gen_backward_stages": (c_int, [C.POINTER(VgGenNet), c_int, P, P, c_int, c_int, P]),
-    "vg_vit_forward": (c_int, [C.POINTER(VgVitNet), c_int, P, c_int, P, P, P]),
-    "vg_vit_features": (c_int, [C.POINTER(VgVitNet), c_int, P, c_int, P, P, P, P]),
-    "vg_moments_update": (c_int, [P, c_ll, c_int, c_int, P, P, P]),
-    "vg_moments_finish": (c_int, [P, P, c_ll, c_int, P, P, P]),
-    "vg_pair_ws_bytes": (c_ll, [c_int, c_int, c_int]),
-    "vg_knn_radii": (c_int, [P, c_ll, c_int, c_int, c_int, P, P, P]),
-    "vg_ball_counts": (c_int, [P, c_ll, c_int, P, c_ll, c_int, c_int, P, P, P, P, P]),
-    "vg_poly_kernel_sum": (c_int, [P, c_ll, c_int, P, c_ll, c_int, c_int, c_int, P, P, P]),
-    "vg_vit_backward": (c_int, [C.POINTER(VgVitNet), c_int, P, P, P, c_int, P]),
-    "vg_vit_backward_stages": (c_int, [C.POINTER(VgVitNet), c_int, P, P, P, c_int, c_int, c_int, P]),
-    "vg_vit_penalty_ws_bytes": (c_ll, [C.POINTER(VgVitDims), c_int]),
-    "vg_vit_penalty": (c_int, [C.POINTER(VgVitNet), c_int, P, P, P, c_float, P, P, P, P]),
-    "vg_vit_r1": (c_int, [C.POINTER(VgVitNet), c_int, P, c_float, P, P, P, P]),
-    "vg_vit_ws_bytes_f32": (c_ll, [C.POINTER(VgVitDims), c_int]),
-    "vg_vit_forward_f32": (c_int, [C.POINTER(VgVitNet), c_int, P, P, P, P]),
-    "vg_vit_backward_f32": (c_int, [C.POINTER(VgVitNet), c_int, P, P, P, c_int, P]),
-    "vg_linear_f32_fwd": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, C.c_ulonglong, c_int, P, P]),
-    "vg_linear_f32_dgrad": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
-    "vg_linear_f32_wgrad_slab_floats": (c_ll, [c_int, c_int, c_int]),
-    "vg_linear_f32_wgrad": (c_int, [P, P, P, P, P, c_ll, c_int, c_int, c_int, P]),
-    "vg_attention_f32_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
-    "vg_attention_f32_bwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
-    "vg_layernorm_f32_fwd": (c_int, [P, P, P, P, P, P, c_int, c_int, c_float, P]),
-    "vg_layernorm_f32_bwd_part_floats": (c_ll, [c_int, c_int]),
-    "vg_layernorm_f32_bwd": (c_int, [P, P, P, P, P, P, P, P, P, P, c_int, c_int, P]),
-    "vg_gen_layout": (c_int, [C.POINTER(VgGenDims), C.POINTER(VgGenLayout)]),
-    "vg_gen_ws_bytes": (c_ll, [C.POINTER(VgGenDims), c_int]),
-    "vg_gen_forward": (c_int, [C.POINTER(VgGenNet), c_int, P, P, P, P]),
-    "vg_gen_backward": (c_int, [C.POINTER(VgGenNet), c_int, P, P, P]),
-    "vg_draw_labels": (c_int, [P, c_int, c_int, C.c_ulonglong, c_int, P, P]),
-    "vg_class_add": (c_int, [P, P, P, c_int, c_int, c_int, P]),
-    "vg_class_grad": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
-    "vg_gan_loss_cond": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
-    "vg_gan_loss_cond_pair": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P]),
-    "vg_gen_forward_cond": (c_int, [C.POINTER(VgGenNet), c_int, P, P, P, C.POINTER(VgGenCond), P]),
-    "vg_gen_backward_cond": (c_int, [C.POINTER(VgGenNet), c_int, P, P, C.POINTER(VgGenCond), P]),
-    "vg_gen_backward_stages_cond": (c_int, [C.POINTER(VgGenNet), c_int, P, P, c_int, c_int, C.POINTER(VgGenCond), P]),
-    "vg_gen_ws_bytes_f32": (c_ll, [C.POINTER(VgGenDims), c_int]),
-    "vg_gen_forward_f32": (c_int, [C.POINTER(VgGenNet), c_int, P, P, P, C.POINTER(VgGenCondF32), P]),
-    "vg_gen_backward_f32": (c_int, [C.POINTER(VgGenNet), c_int, P, P, C.POINTER(VgGenCondF32), P]),
-    "vg_sln_f32_fwd": (c_int, [P, c_int, P, P, P, P, P, P, P, P, c_int, c_int, c_float, P]),
-    "vg_sln_f32_bwd_part_floats": (c_ll, [c_int, c_int]),
-    "vg_sln_f32_bwd": (c_int, [P, P, c_int, P, P, P, P, P, P, P, P, P, P, c_int, P, P, P, P, P, c_int, c_int, P]),
-    "vg_siren_f32_fwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, P]),
-    "vg_siren_f32_dgrad": (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, P]),
-    "vg_grad_stats": (c_int, [P, c_ll, P, c_int, P, c_int, c_float, P, P, P, P]),
-    "vg_logit_stats": (c_int, [P, P, c_int, c_int, P, P]),
-    "vg_telemetry_commit": (c_int, [C.POINTER(VgTelemetrySrc), P, c_int, P, P, P, P, P]),
-}
+with open(HEADER) as _f:
+    _HEADER = Header(_f.read())
+globals().update(_HEADER.structs)  # VgVitDims, VgVitNet, ...: one ctypes.Structure per typedef struct, fields in the header's order
+_SIGNATURES = _HEADER.signatures
+ABI_VERSION = _HEADER.defines["VG_ABI_VERSION"]
+TEL_NF = _HEADER.defines["VG_TEL_NF"]  # floats per telemetry row; TEL_FIELDS names them by index (the slots above are reserved)
+TEL_FIELDS, LR_KINDS = _HEADER.tel_fields, _HEADER.lr_kinds
 
 _lib: Optional[C.CDLL] = None
 
@@ -252,6 +141,15 @@ def build(verbose: bool = False) -> str:
     return LIB_PATH
 
 
+def bind(handle: C.CDLL, names=None) -> C.CDLL:
+    """Give the entry points of the header (``names``: only those - a build of another ABI version may lack the rest) their restype /
+    argtypes on ``handle``: this library, or another build of it loaded beside it."""
+    for name in _SIGNATURES if names is None else names:
+        fn = getattr(handle, name)
+        fn.restype, fn.argtypes = _SIGNATURES[name]
+    return handle
+
+
 def lib() -> C.CDLL:
     """The loaded library; raises loudly when it has not been built."""
     global _lib
@@ -263,10 +161,7 @@ def lib() -> C.CDLL:
             raise RuntimeError(
                 f"{LIB_PATH} is missing: the HIP extension is the only compute path of this package. "
                 "Build it with `python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc).")
-        handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype, fn.argtypes = res, args
+        handle = bind(C.CDLL(LIB_PATH))
         if handle.vg_abi_version() != ABI_VERSION:
             raise RuntimeError("libvitgan_hip.so ABI version mismatch; rebuild")
         _lib = handle
@@ -281,7 +176,7 @@ def context() -> c_void_p:
     global _ctx
     if _ctx is None:
         h = c_void_p()
-        check(lib().vg_ctx_create(C.byref(h)), "vg_ctx_create")
+        call("vg_ctx_create", C.byref(h))
         _ctx = h
     return _ctx
 
@@ -294,3 +189,19 @@ def check(rc: int, what: str) -> None:
     if rc != 0:
         kind = "argument validation" if rc < 0 else "hipError_t"
         raise HipError(f"{what} failed: {kind} {rc}")
+
+
+def call(name: str, *args, what: Optional[str] = None) -> None:
+    """One status-returning entry point, by name; ``what`` replaces the name in the error text.  Resolved through lib() every time."""
+    check(getattr(lib(), name)(*args), what or name)
+
+
+def ptr(t):
+    """A tensor's device pointer (None stays NULL)."""
+    return None if t is None else c_void_p(t.data_ptr())
+
+
+def stream() -> c_void_p:
+    """The current torch stream as the ABI's ``void* stream``."""
+    import torch
+    return c_void_p(torch.cuda.current_stream().cuda_stream)

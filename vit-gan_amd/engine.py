@@ -34,15 +34,6 @@ from .spectral import SpectralState, parse_spectral_set, vit_matrix_keys
 LOSS_KINDS = {"ns": 0, "hinge": 1, "wasserstein": 2}  # "wasserstein": the critic losses of src/v2/training.py:72,97
 
 
-def _p(t):
-    """A tensor's device pointer.  Every sub-range the step addresses is a VIEW made once in ``_carve``: no call site adds byte offsets."""
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _call(name: str, *args) -> None:
-    _lib.check(getattr(_lib.lib(), name)(*args), name)
-
-
 class GanEngine:
     def __init__(self, discriminator, generator: SirenGenerator, batch: int, loss: str = "ns",
                  lr_d: float = 5e-4, lr_g: float = 5e-4, weight_decay: float = 1e-3, betas=(0.9, 0.999),
@@ -573,35 +564,35 @@ class GanEngine:
 
     # ---- the helpers every schedule is written in: one call site per job
     def _d_forward(self, net, n: int, src, ws, logits, st) -> None:
-        _call("vg_vit_forward", C.byref(net), n, _p(src), 1, _p(ws), _p(logits), st)
+        _lib.call("vg_vit_forward", C.byref(net), n, _lib.ptr(src), 1, _lib.ptr(ws), _lib.ptr(logits), st)
 
     def _loss(self, logits, dlogits, n: int, role: int, st) -> None:
         """The loss of n logit rows in ``role`` (0 = D on real, 1 = D on fake, 2 = the generator's) into the role's slot of ``losses``."""
         if self.cond:  # the label-selected logit of each row: real labels for D on real, the fake labels for D on fake and for G
-            _call("vg_gan_loss_cond", _p(logits), _p(self.fake_labels if role else self.real_labels), _p(dlogits),
-                  _p(self.sel_half[role] if role < 2 else (self.tel_sel_g if self.tel_cap else None)), _p(self.loss_slot[role]), n, self.Kc,
-                  self.kind, role, 1.0, st)
+            _lib.call("vg_gan_loss_cond", _lib.ptr(logits), _lib.ptr(self.fake_labels if role else self.real_labels), _lib.ptr(dlogits),
+                      _lib.ptr(self.sel_half[role] if role < 2 else (self.tel_sel_g if self.tel_cap else None)), _lib.ptr(self.loss_slot[role]), n, self.Kc,
+                      self.kind, role, 1.0, st)
             return
-        _call("vg_gan_loss", _p(logits), _p(dlogits), _p(self.loss_slot[role]), n * self.Kc, self.kind, role, 1.0, st)
+        _lib.call("vg_gan_loss", _lib.ptr(logits), _lib.ptr(dlogits), _lib.ptr(self.loss_slot[role]), n * self.Kc, self.kind, role, 1.0, st)
 
     def _g_forward(self, ng, st) -> None:
         """fake = G(z), conditioned on the fake labels when the engine is class-conditional"""
         if self.cond:
-            _call("vg_gen_forward_cond", C.byref(ng), self.B, _p(self.z), _p(self.ws_g), _p(self.fake), C.byref(self._gcond), st)
+            _lib.call("vg_gen_forward_cond", C.byref(ng), self.B, _lib.ptr(self.z), _lib.ptr(self.ws_g), _lib.ptr(self.fake), C.byref(self._gcond), st)
         else:
-            _call("vg_gen_forward", C.byref(ng), self.B, _p(self.z), _p(self.ws_g), _p(self.fake), st)
+            _lib.call("vg_gen_forward", C.byref(ng), self.B, _lib.ptr(self.z), _lib.ptr(self.ws_g), _lib.ptr(self.fake), st)
 
     def _d_backward(self, nd, n_img: int, ws, dl, want_w: int, dimg, st, exchange: bool = True) -> None:
         """D backward; under data parallelism, when the pass completes D.grad (``exchange``), in ``dp_chunks`` pieces (head + upper
         blocks first) so that the all-reduce of each finished piece - a contiguous tail of the flat gradient buffer - overlaps the
         backward of the blocks below it; only the last piece's exchange is exposed."""
         if not (self.sync.active and want_w and exchange):
-            _call("vg_vit_backward", C.byref(nd), n_img, _p(ws), _p(dl), _p(dimg), want_w, st)
+            _lib.call("vg_vit_backward", C.byref(nd), n_img, _lib.ptr(ws), _lib.ptr(dl), _lib.ptr(dimg), want_w, st)
             return
         fd = self.vit._flat
         lay = flat.vit_layout(self.vit._dims)
         for s0, s1, lo, hi in backward_pieces(self.vit._dims.L, self.dp_chunks, lay.layer0, lay.layer_stride, fd.total):
-            _call("vg_vit_backward_stages", C.byref(nd), n_img, _p(ws), _p(dl), _p(dimg), want_w, s0, s1, st)
+            _lib.call("vg_vit_backward_stages", C.byref(nd), n_img, _lib.ptr(ws), _lib.ptr(dl), _lib.ptr(dimg), want_w, s0, s1, st)
             self.sync.reduce_range(fd.grad, lo, hi)
 
     def _instance_noise(self, part) -> None:
@@ -614,30 +605,31 @@ class GanEngine:
     def _augment(self, src, dst, params, n: int, policy: int, site: int, st) -> None:
         """T(src) -> dst for n images at an augmentation site of the step: the gated kernel with the device-resident probability when
         the engine has one (sites 0 and 1: an engine with a probability has no site 2), else the plain call."""
-        _call("vg_diffaug_p_fwd" if self.gated else "vg_diffaug_fwd", _p(src), _p(dst), _p(params), *self._aug_site(n, policy, site, st))
+        _lib.call("vg_diffaug_p_fwd" if self.gated else "vg_diffaug_fwd", _lib.ptr(src), _lib.ptr(dst), _lib.ptr(params), *self._aug_site(n, policy, site, st))
 
     def _augment_adjoint(self, dy, dx, n: int, policy: int, site: int, st) -> None:
         """dx = T^T(dy), the transform of ``_augment`` at the same site and step, gated like it."""
-        _call("vg_diffaug_p_bwd" if self.gated else "vg_diffaug_bwd", _p(dy), _p(dx), 0, *self._aug_site(n, policy, site, st))
+        _lib.call("vg_diffaug_p_bwd" if self.gated else "vg_diffaug_bwd", _lib.ptr(dy), _lib.ptr(dx), 0, *self._aug_site(n, policy, site, st))
 
     def _aug_site(self, n: int, policy: int, site: int, st):
         """what the four augmentation calls share: geometry, policy, the draw's key, and for the gated ones the probability"""
         d_ = self.vit._dims
-        return (n, d_.C, d_.IH, policy, self._aug_seed, site, _p(self.step_t)) + ((_p(self.ada_state), st) if self.gated else (st,))
+        return (n, d_.C, d_.IH, policy, self._aug_seed, site, _lib.ptr(self.step_t)) + ((_lib.ptr(self.ada_state), st) if self.gated else (st,))
 
     def _ada_update(self, logits_real, st) -> None:
         """The controller on the real rows of the adversarial logits (the first B rows of ``logits_real``); nothing without ADA."""
         if self.ada and self.cond:  # the B selected real logits D(x, y): what the conditional loss was taken on
-            _call("vg_ada_update", _p(self.sel_half[0]), self.B, _p(self.ada_state), self.ada_target, self.ada_step_per_image,
-                  self.ada_interval, _p(self.step_t), st)
+            _lib.call("vg_ada_update", _lib.ptr(self.sel_half[0]), self.B, _lib.ptr(self.ada_state), self.ada_target, self.ada_step_per_image,
+                      self.ada_interval, _lib.ptr(self.step_t), st)
         elif self.ada:
-            _call("vg_ada_update", _p(logits_real), self.B * self.Kc, _p(self.ada_state), self.ada_target, self.ada_step_per_image,
-                  self.ada_interval, _p(self.step_t), st)
+            _lib.call("vg_ada_update", _lib.ptr(logits_real), self.B * self.Kc, _lib.ptr(self.ada_state), self.ada_target, self.ada_step_per_image,
+                      self.ada_interval, _lib.ptr(self.step_t), st)
 
     def _diversity(self, st) -> None:
         """total_gen_loss = loss + w * diversity_loss(fake_images): its gradient joins dL/d fake; nothing at weight 0."""
         if self.div_w != 0.0:
-            _call("vg_diversity_loss", _p(self.fake), _p(self.dfake), _p(self.div_loss), _p(self.div_scratch), self.B, self.img_numel, self.div_w, st)
+            _lib.call("vg_diversity_loss", _lib.ptr(self.fake), _lib.ptr(self.dfake), _lib.ptr(self.div_loss), _lib.ptr(self.div_scratch), self.B,
+                      self.img_numel, self.div_w, st)
 
     def _map_range(self):
         lay, d = flat.gen_layout(self.gen._dims), self.gen._dims
@@ -651,7 +643,7 @@ class GanEngine:
         """Both networks' rates of this step from the counter vg_zero_tick has just advanced (one launch); nothing without a schedule."""
         if self.lr_opts is not None:
             d, g = (ops.lr_sched_struct(self.hyp[k], *self.lr_opts) for k in ("lr_d", "lr_g"))
-            _call("vg_lr_schedule", C.byref(d), C.byref(g), _p(self.step_t), _p(self.lr_scale), _p(self.lr_now), st)
+            _lib.call("vg_lr_schedule", C.byref(d), C.byref(g), _lib.ptr(self.step_t), _lib.ptr(self.lr_scale), _lib.ptr(self.lr_now), st)
 
     def _adamw_range(self, r, slot: int, st) -> None:
         """AdamW on one range (``_range``) of network ``slot`` (0 = D, 1 = G) - with the weights' moving average in the same pass when
@@ -661,18 +653,18 @@ class GanEngine:
             return
         h = self.hyp
         dlr = "" if self.lr_opts is None else "_dlr"
-        lr = _p(self.lr_slot[slot]) if dlr else h["lr_g" if slot else "lr_d"]
-        tail = (n, lr, h["b1"], h["b2"], h["eps"], h["wd"], 0, _p(self.step_t), 1.0 / self.world)
+        lr = _lib.ptr(self.lr_slot[slot]) if dlr else h["lr_g" if slot else "lr_d"]
+        tail = (n, lr, h["b1"], h["b2"], h["eps"], h["wd"], 0, _lib.ptr(self.step_t), 1.0 / self.world)
         if ema is None:
-            _call("vg_adamw_step" + dlr, *map(_p, bufs), *tail, st)
+            _lib.call("vg_adamw_step" + dlr, *map(_lib.ptr, bufs), *tail, st)
         else:
-            _call("vg_adamw_ema_step" + dlr, *map(_p, bufs), _p(ema), *tail, self.ema_decay, self._ema_from, st)
+            _lib.call("vg_adamw_ema_step" + dlr, *map(_lib.ptr, bufs), _lib.ptr(ema), *tail, self.ema_decay, self._ema_from, st)
 
     def _adamw(self, r, slot: int, st, clip=None) -> None:
         """A whole network's optimizer step (``slot``: 0 = D, 1 = G): the clipping (on the exchanged, global gradient, like
         clip_grad_norm_ before optimizer.step()), then AdamW on the whole range."""
         if clip is not None:
-            _call("vg_grad_clip", _p(r[1]), r[-1], 1.0 / self.world, float(clip), _p(self.clip_slot[slot]), st)
+            _lib.call("vg_grad_clip", _lib.ptr(r[1]), r[-1], 1.0 / self.world, float(clip), _lib.ptr(self.clip_slot[slot]), st)
         self._tel_grad(slot, st)
         self._adamw_range(r, slot, st)
 
@@ -686,7 +678,7 @@ class GanEngine:
     def _tel_logits(self, x0, x1, n: int, role: int, st) -> None:
         """mean and the fractions > 0 / < 0 of n logits per row pointer into slot ``role`` (and ``role + 1``) of ``tel_logit``."""
         if self.tel_cap:
-            _call("vg_logit_stats", _p(x0), _p(x1), n, role, _p(self.tel_logit), st)
+            _lib.call("vg_logit_stats", _lib.ptr(x0), _lib.ptr(x1), n, role, _lib.ptr(self.tel_logit), st)
 
     def _tel_d_logits(self, real, fake, st) -> None:
         """D's own pass: the rows ADA reads - the B selected logits of each half when class-conditional, all B Kc otherwise."""
@@ -707,13 +699,13 @@ class GanEngine:
         if not self.tel_cap:
             return
         pen = self.gp_loss if self.gp_w != 0.0 else self.r1_loss
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        ptr = _lib.ptr
         src = _lib.VgTelemetrySrc(ptr(self.losses), ptr(self.tel_logit), ptr(self.tel_d.totals), ptr(self.tel_g.totals), ptr(pen),
                                   ptr(self.bcr_losses if self.bcr else None), ptr(self.ada_state if self.ada else None), ptr(self.lr_now),
                                   ptr(self.div_loss if self.div_w != 0.0 else None), ptr(self.tel_d.norm_seg), ptr(self.tel_g.norm_seg),
                                   self.tel_d.n_seg, self.tel_g.n_seg, int(self.gp_w != 0.0 or bool(r1_due)))
-        _call("vg_telemetry_commit", C.byref(src), _p(self.step_t), self.tel_cap, _p(self.tel_ring_step), _p(self.tel_ring),
-              _p(self.tel_ring_seg[0]), _p(self.tel_ring_seg[1]), st)
+        _lib.call("vg_telemetry_commit", C.byref(src), _lib.ptr(self.step_t), self.tel_cap, _lib.ptr(self.tel_ring_step), _lib.ptr(self.tel_ring),
+                  _lib.ptr(self.tel_ring_seg[0]), _lib.ptr(self.tel_ring_seg[1]), st)
 
     def _adamw_g_sharded(self, st) -> None:
         """The generator's AdamW with the mapping Linear sharded: the whole buffer but that layer as usual, of the layer this rank's
@@ -726,9 +718,9 @@ class GanEngine:
         self.sync.all_gather_range(self.gen._flat.flat, w0, w1)
         self.sync.wait()
         master, _, _, _, shadow, ema, n = self.r_g_map
-        _call("vg_cast_f32_bf16", _p(master), _p(shadow), n, st)
+        _lib.call("vg_cast_f32_bf16", _lib.ptr(master), _lib.ptr(shadow), n, st)
         if ema is not None:  # the layer's average from the gathered master: what the fused kernel of a replicated run writes
-            _call("vg_ema_update", _p(ema), _p(master), n, self.ema_decay, self._ema_from, 0, _p(self.step_t), st)
+            _lib.call("vg_ema_update", _lib.ptr(ema), _lib.ptr(master), n, self.ema_decay, self._ema_from, 0, _lib.ptr(self.step_t), st)
 
     def gather_master(self) -> None:
         """A no-op, kept for callers: the sharded update of the mapping Linear all-gathers its fp32 master inside the step, so every
@@ -742,17 +734,17 @@ class GanEngine:
         fg = self.gen._flat
         if not self.sync.active:
             if self.cond:
-                _call("vg_gen_backward_cond", C.byref(ng), self.B, _p(self.ws_g), _p(self.dfake), C.byref(self._gcond), st)
+                _lib.call("vg_gen_backward_cond", C.byref(ng), self.B, _lib.ptr(self.ws_g), _lib.ptr(self.dfake), C.byref(self._gcond), st)
             else:
-                _call("vg_gen_backward", C.byref(ng), self.B, _p(self.ws_g), _p(self.dfake), st)
+                _lib.call("vg_gen_backward", C.byref(ng), self.B, _lib.ptr(self.ws_g), _lib.ptr(self.dfake), st)
             return
         lay = flat.gen_layout(self.gen._dims)
         # (a class table sits behind the C layout and is final with the LAST stage: the pieces tile the C layout, the table follows them)
         for s0, s1, lo, hi in backward_pieces(self.gen._dims.L, self.dp_chunks, lay.layer0, lay.layer_stride, lay.total if self.cond else fg.total):
             if self.cond:
-                _call("vg_gen_backward_stages_cond", C.byref(ng), self.B, _p(self.ws_g), _p(self.dfake), s0, s1, C.byref(self._gcond), st)
+                _lib.call("vg_gen_backward_stages_cond", C.byref(ng), self.B, _lib.ptr(self.ws_g), _lib.ptr(self.dfake), s0, s1, C.byref(self._gcond), st)
             else:
-                _call("vg_gen_backward_stages", C.byref(ng), self.B, _p(self.ws_g), _p(self.dfake), s0, s1, st)
+                _lib.call("vg_gen_backward_stages", C.byref(ng), self.B, _lib.ptr(self.ws_g), _lib.ptr(self.dfake), s0, s1, st)
             if lo == 0 and (self.compress_map or self.shard_map):  # [embedding | mapping weight | mapping bias, lowest blocks]
                 w0, w1 = self._map_range()
                 self.sync.reduce_range(fg.grad, 0, w0)
@@ -841,13 +833,13 @@ class GanEngine:
         fd, fg = self.vit._flat, self.gen._flat
         noisy = self.inst_sigma > 0.0
         self._fetch(st0)
-        _call("vg_zero_tick", _p(fd.grad), fd.total, _p(self.step_t), st0)
+        _lib.call("vg_zero_tick", _lib.ptr(fd.grad), fd.total, _lib.ptr(self.step_t), st0)
         self._lr_tick(st0)
         self.grad2.zero_()
         s1.wait_stream(s0)
         # chain 1 (side stream): G forward, then D on the fake batch (weight gradients into grad2)
         with torch.cuda.stream(s1):
-            _call("vg_gen_forward", C.byref(ng), B, _p(self.z), _p(self.ws_g), _p(self.fake), st1)
+            _lib.call("vg_gen_forward", C.byref(ng), B, _lib.ptr(self.z), _lib.ptr(self.ws_g), _lib.ptr(self.fake), st1)
             if noisy:
                 self._instance_noise(self.noise_parts[1])
             self._d_forward(nd_b, B, self.d_in_half[1], self.ws_d2, self.lg_half[1], st1)
@@ -878,7 +870,7 @@ class GanEngine:
         self._d_backward(nd_c, h, self.ws_d, dlg0, 0, df0, st0)
         s0.wait_stream(s1)
         self._diversity(st0)
-        _call("vg_gen_backward", C.byref(ng), B, _p(self.ws_g), _p(self.dfake), st0)
+        _lib.call("vg_gen_backward", C.byref(ng), B, _lib.ptr(self.ws_g), _lib.ptr(self.dfake), st0)
         self._adamw(self.r_g, 1, st0, self.clip_g)
 
     def _inputs(self, real: Optional[torch.Tensor], labels=None, fake_labels=None) -> None:
@@ -899,14 +891,14 @@ class GanEngine:
             self.imgs[:self.B].copy_(real)
         want_z = not self.external_noise
         if direct or want_z:
-            _call("vg_step_inputs", _p(real) if direct else None, _p(self.imgs), real.numel() if direct else 0,
-                  _p(self.z) if want_z else None, self.z.numel() if want_z else 0, self._noise_seed, _p(self.step_t), st)
+            _lib.call("vg_step_inputs", _lib.ptr(real) if direct else None, _lib.ptr(self.imgs), real.numel() if direct else 0,
+                      _lib.ptr(self.z) if want_z else None, self.z.numel() if want_z else 0, self._noise_seed, _lib.ptr(self.step_t), st)
         if self.cond:  # the real labels into their static buffer; the fake ones supplied with z, or drawn like z: one launch, keyed on the counter
             self.real_labels.copy_(labels)
             if fake_labels is not None:
                 self.fake_labels.copy_(fake_labels)
             else:
-                _call("vg_draw_labels", _p(self.fake_labels), self.B, self.n_classes, self._aug_seed, 3, _p(self.step_t), st)
+                _lib.call("vg_draw_labels", _lib.ptr(self.fake_labels), self.B, self.n_classes, self._aug_seed, 3, _lib.ptr(self.step_t), st)
 
     def _fetch(self, st) -> None:
         """The head of a step with a dataset, inside what the hipGraph captures: the real batch (images, labels, indices) from the device
@@ -914,12 +906,13 @@ class GanEngine:
         ds = self.dataset
         if ds is None:
             return
-        _call("vg_dataset_fetch", _p(ds.images), _p(ds.labels), ds.N, ds.C, ds.IH, ds.layout, _p(ds.lut_bf16), _p(self.real_dst),
-              _p(self.real_labels), _p(self.batch_indices), self.B, self.sync.rank, self.world, ds.flags, self.data_seed, _p(self.step_t), st)
+        _lib.call("vg_dataset_fetch", _lib.ptr(ds.images), _lib.ptr(ds.labels), ds.N, ds.C, ds.IH, ds.layout, _lib.ptr(ds.lut_bf16), _lib.ptr(self.real_dst),
+                  _lib.ptr(self.real_labels), _lib.ptr(self.batch_indices), self.B, self.sync.rank, self.world, ds.flags, self.data_seed, _lib.ptr(self.step_t),
+                  st)
         if not self.external_noise:
-            _call("vg_step_inputs", None, None, 0, _p(self.z), self.z.numel(), self._noise_seed, _p(self.step_t), st)
+            _lib.call("vg_step_inputs", None, None, 0, _lib.ptr(self.z), self.z.numel(), self._noise_seed, _lib.ptr(self.step_t), st)
             if self.cond:
-                _call("vg_draw_labels", _p(self.fake_labels), self.B, self.n_classes, self._aug_seed, 3, _p(self.step_t), st)
+                _lib.call("vg_draw_labels", _lib.ptr(self.fake_labels), self.B, self.n_classes, self._aug_seed, 3, _lib.ptr(self.step_t), st)
 
     def _penalty(self, st) -> None:
         """gradient_penalty(D, noisy_real, noisy_fake) joins the D loss (training.py:101-106), on what D's own pass sees."""
@@ -932,8 +925,8 @@ class GanEngine:
                 self.gp_eps.uniform_()  # epsilon = torch.rand(B, 1, 1, 1), utils.py:129
             pnet = _lib.VgVitNet(self.vit._dims, fd.flat.data_ptr(), fd.shadow.data_ptr(), fd.grad.data_ptr(), self.p_d, self.seed * 8 + 3,
                                  self.step_t.data_ptr(), None, 0, 1)
-            _call("vg_vit_penalty", C.byref(pnet), self.B, _p(real), _p(fake), _p(self.gp_eps), self.gp_w, _p(self.ws_d), _p(self.ws_gp),
-                  _p(self.gp_loss), st)
+            _lib.call("vg_vit_penalty", C.byref(pnet), self.B, _lib.ptr(real), _lib.ptr(fake), _lib.ptr(self.gp_eps), self.gp_w, _lib.ptr(self.ws_d),
+                      _lib.ptr(self.ws_gp), _lib.ptr(self.gp_loss), st)
         else:
             from . import ops2
             from .penalty import gradient_penalty
@@ -948,8 +941,8 @@ class GanEngine:
         fd = self.vit._flat
         pnet = _lib.VgVitNet(self.vit._dims, fd.flat.data_ptr(), fd.shadow.data_ptr(), fd.grad.data_ptr(), self.p_d, self.seed * 8 + 3,
                              self.step_t.data_ptr(), None, 0, 1)
-        _call("vg_vit_r1", C.byref(pnet), self.B, _p(self.d_in_half[0]), 0.5 * self.r1_gamma * self.r1_interval, _p(self.ws_d), _p(self.ws_gp),
-              _p(self.r1_loss), st)
+        _lib.call("vg_vit_r1", C.byref(pnet), self.B, _lib.ptr(self.d_in_half[0]), 0.5 * self.r1_gamma * self.r1_interval, _lib.ptr(self.ws_d),
+                  _lib.ptr(self.ws_gp), _lib.ptr(self.r1_loss), st)
 
     def _enqueue_body(self, r1_due: bool = False) -> None:
         """Everything of a step behind its inputs (``_inputs``): what the hipGraph captures.  ``r1_due``: the kind of step - with the
@@ -962,7 +955,7 @@ class GanEngine:
         fd, fg = self.vit._flat, self.gen._flat
         self._fetch(st)
         # gan.discriminator.zero_grad() (training.py:177) and the device step counter += 1, one launch
-        _call("vg_zero_tick", _p(fd.grad), fd.total, _p(self.step_t), st)
+        _lib.call("vg_zero_tick", _lib.ptr(fd.grad), fd.total, _lib.ptr(self.step_t), st)
         self._lr_tick(st)
         self._g_forward(ng, st)
         if self.inst_sigma > 0.0:
@@ -980,15 +973,15 @@ class GanEngine:
             self._d_forward(nd, n, src, self.ws_d, self.logits, st)
             # D(real) -> slot 0, D(fake) -> slot 1: both halves of the adversarial rows in one launch
             if self.cond:  # ... on the label-selected logit of each row: the means are over B samples, the other logits get +0
-                _call("vg_gan_loss_cond_pair", _p(adv), _p(self.labels_d), _p(dadv), _p(self.selected), _p(self.losses), B, 0, B, 1, self.Kc,
-                      self.kind, 1.0, st)
+                _lib.call("vg_gan_loss_cond_pair", _lib.ptr(adv), _lib.ptr(self.labels_d), _lib.ptr(dadv), _lib.ptr(self.selected), _lib.ptr(self.losses), B, 0,
+                          B, 1, self.Kc, self.kind, 1.0, st)
             else:
-                _call("vg_gan_loss_pair", _p(adv), _p(dadv), _p(self.losses), B * self.Kc, 0, B * self.Kc, 1, self.kind, 1.0, st)
+                _lib.call("vg_gan_loss_pair", _lib.ptr(adv), _lib.ptr(dadv), _lib.ptr(self.losses), B * self.Kc, 0, B * self.Kc, 1, self.kind, 1.0, st)
             self._ada_update(adv, st)
             self._tel_d_logits(*self.tel_adv, st)
             if self.bcr:
-                _call("vg_bcr_loss", *map(_p, self.cr_rows), _p(self.bcr_losses), B, B, self.Kc, self.bcr_w[0], self.bcr_w[1],
-                      int(not self.aug), int(bool(self.aug)), 1.0, st)
+                _lib.call("vg_bcr_loss", *map(_lib.ptr, self.cr_rows), _lib.ptr(self.bcr_losses), B, B, self.Kc, self.bcr_w[0], self.bcr_w[1],
+                          int(not self.aug), int(bool(self.aug)), 1.0, st)
             self._d_backward(nd, n, self.ws_d, self.dlogits, 1, None, st)
         else:  # the reference's two passes; the second one finishes D.grad: exchange it as it completes
             for half, net in ((0, nd), (1, nd_b)):
@@ -1127,7 +1120,7 @@ class GanEngine:
                 self._ema_shadow = torch.empty(fg.total, dtype=torch.bfloat16, device=self.dev)
             key = (self.steps, self._ema_loads)
             if self._ema_cast_key != key:
-                _call("vg_cast_f32_bf16", _p(self.ema_g), _p(self._ema_shadow), fg.total, st)
+                _lib.call("vg_cast_f32_bf16", _lib.ptr(self.ema_g), _lib.ptr(self._ema_shadow), fg.total, st)
                 self._ema_cast_key = key
             master, shadow = self.ema_g, self._ema_shadow
         else:
@@ -1142,10 +1135,10 @@ class GanEngine:
         img = torch.empty(n, gen.channels, gen.image_size, gen.image_size, dtype=torch.bfloat16, device=self.dev)
         y = gen._labels(labels, int(z.shape[0]), self.dev)
         if y is None:
-            _call("vg_gen_forward", C.byref(net), n, _p(zin), _p(self._sample_ws), _p(img), st)
+            _lib.call("vg_gen_forward", C.byref(net), n, _lib.ptr(zin), _lib.ptr(self._sample_ws), _lib.ptr(img), st)
         else:
             cond = _lib.VgGenCond(y.data_ptr(), shadow.data_ptr() + 2 * gen._class_off, None, self.n_classes)
-            _call("vg_gen_forward_cond", C.byref(net), n, _p(zin), _p(self._sample_ws), _p(img), C.byref(cond), st)
+            _lib.call("vg_gen_forward_cond", C.byref(net), n, _lib.ptr(zin), _lib.ptr(self._sample_ws), _lib.ptr(img), C.byref(cond), st)
         return img.to(gen.out_dtype)
 
     def ema_state_dict(self) -> dict:

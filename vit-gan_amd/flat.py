@@ -21,7 +21,7 @@ def vit_dims_struct(channels, image, patch, embed, heads, layers, mlp_ratio, cla
 
 def vit_layout(d: _lib.VgVitDims) -> _lib.VgVitLayout:
     lay = _lib.VgVitLayout()
-    _lib.check(_lib.lib().vg_vit_layout(C.byref(d), C.byref(lay)), "vg_vit_layout (unsupported ViT shape)")
+    _lib.call("vg_vit_layout", C.byref(d), C.byref(lay), what="vg_vit_layout (unsupported ViT shape)")
     return lay
 
 
@@ -62,7 +62,7 @@ def vit_slots(d: _lib.VgVitDims, prefix: str = "vit.") -> "OrderedDict[str, Slot
 
 def gen_layout(d: _lib.VgGenDims) -> _lib.VgGenLayout:
     lay = _lib.VgGenLayout()
-    _lib.check(_lib.lib().vg_gen_layout(C.byref(d), C.byref(lay)), "vg_gen_layout (unsupported generator shape)")
+    _lib.call("vg_gen_layout", C.byref(d), C.byref(lay), what="vg_gen_layout (unsupported generator shape)")
     return lay
 
 

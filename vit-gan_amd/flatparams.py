@@ -7,7 +7,6 @@ the MFMA GEMMs.  One buffer = one fused AdamW launch and one all-reduce per netw
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, Tuple
 
 import torch
@@ -15,10 +14,6 @@ from torch import nn
 
 from . import _lib
 from .flat import numel
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 class FlatParams:
@@ -69,8 +64,7 @@ class FlatParams:
         """bf16 copy of the master weights for the GEMMs (one streaming kernel)."""
         if self.shadow is None:
             raise RuntimeError("the HIP path needs the parameters on a cuda device")
-        _lib.check(_lib.lib().vg_cast_f32_bf16(self.flat.data_ptr(), self.shadow.data_ptr(), self.total, _stream()),
-                   "vg_cast_f32_bf16")
+        _lib.call("vg_cast_f32_bf16", self.flat.data_ptr(), self.shadow.data_ptr(), self.total, _lib.stream())
         if self.spectral is not None:  # the normalised matrices: the scaled cast from the stored sigma (no iteration)
             self.spectral.update(self.flat, self.shadow, iterate=False)
 

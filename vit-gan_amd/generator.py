@@ -62,10 +62,9 @@ class _GenFn(torch.autograd.Function):
         net = mod._net(ctx.drop)
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         if labels is None:
-            _lib.check(_lib.lib().vg_gen_forward(C.byref(net), B, zin.data_ptr(), ws.data_ptr(), img.data_ptr(), st), "vg_gen_forward")
+            _lib.call("vg_gen_forward", C.byref(net), B, zin.data_ptr(), ws.data_ptr(), img.data_ptr(), st)
         else:
-            _lib.check(_lib.lib().vg_gen_forward_cond(C.byref(net), B, zin.data_ptr(), ws.data_ptr(), img.data_ptr(), C.byref(mod._cond(labels)), st),
-                       "vg_gen_forward_cond")
+            _lib.call("vg_gen_forward_cond", C.byref(net), B, zin.data_ptr(), ws.data_ptr(), img.data_ptr(), C.byref(mod._cond(labels)), st)
         ctx.mod, ctx.ws, ctx.B, ctx.labels = mod, ws, B, labels
         return img.to(mod.out_dtype)
 
@@ -77,10 +76,9 @@ class _GenFn(torch.autograd.Function):
         net = mod._net(ctx.drop)
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         if ctx.labels is None:
-            _lib.check(_lib.lib().vg_gen_backward(C.byref(net), ctx.B, ctx.ws.data_ptr(), d.data_ptr(), st), "vg_gen_backward")
+            _lib.call("vg_gen_backward", C.byref(net), ctx.B, ctx.ws.data_ptr(), d.data_ptr(), st)
         else:
-            _lib.check(_lib.lib().vg_gen_backward_cond(C.byref(net), ctx.B, ctx.ws.data_ptr(), d.data_ptr(), C.byref(mod._cond(ctx.labels)), st),
-                       "vg_gen_backward_cond")
+            _lib.call("vg_gen_backward_cond", C.byref(net), ctx.B, ctx.ws.data_ptr(), d.data_ptr(), C.byref(mod._cond(ctx.labels)), st)
         ctx.ws = None
         return None, None, None, None, None
 
@@ -99,7 +97,7 @@ class _GenF32Fn(torch.autograd.Function):
         net = mod._net(ctx.drop)
         cond = None if labels is None else C.byref(mod._cond_f32(labels))
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _lib.check(_lib.lib().vg_gen_forward_f32(C.byref(net), B, zin.data_ptr(), ws.data_ptr(), img.data_ptr(), cond, st), "vg_gen_forward_f32")
+        _lib.call("vg_gen_forward_f32", C.byref(net), B, zin.data_ptr(), ws.data_ptr(), img.data_ptr(), cond, st)
         ctx.mod, ctx.ws, ctx.B, ctx.labels = mod, ws, B, labels
         return img
 
@@ -111,7 +109,7 @@ class _GenF32Fn(torch.autograd.Function):
         net = mod._net(ctx.drop)
         cond = None if ctx.labels is None else C.byref(mod._cond_f32(ctx.labels))
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _lib.check(_lib.lib().vg_gen_backward_f32(C.byref(net), ctx.B, ctx.ws.data_ptr(), d.data_ptr(), cond, st), "vg_gen_backward_f32")
+        _lib.call("vg_gen_backward_f32", C.byref(net), ctx.B, ctx.ws.data_ptr(), d.data_ptr(), cond, st)
         ctx.ws = None
         return None, None, None, None, None
 

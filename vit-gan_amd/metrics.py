@@ -33,10 +33,6 @@ from .data import DeviceDataset
 D_MIN, D_MAX = 16, 2048  # vg_moments_update: d % 16 == 0 inside these
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _check_d(d: int) -> int:
     if isinstance(d, bool) or int(d) != d or not D_MIN <= int(d) <= D_MAX or int(d) % 16:
         raise ValueError(f"the feature width must be a multiple of 16 in [{D_MIN}, {D_MAX}] (vg_moments_update), got {d!r}")
@@ -84,8 +80,7 @@ class FeatureMoments:
             if feats.stride(1) != 1 or feats.stride(0) < self.d:
                 feats = feats.contiguous()
             with torch.cuda.device(self.device):
-                _lib.check(_lib.lib().vg_moments_update(feats.data_ptr(), feats.stride(0), n, self.d, self.sum.data_ptr(),
-                                                        self.gram.data_ptr(), _stream()), "vg_moments_update")
+                _lib.call("vg_moments_update", feats.data_ptr(), feats.stride(0), n, self.d, self.sum.data_ptr(), self.gram.data_ptr(), _lib.stream())
         else:
             x = feats.double()
             self.sum.add_(x.sum(0))
@@ -117,8 +112,7 @@ class FeatureMoments:
             mean = torch.empty(self.d, dtype=torch.float64, device=self.device)
             cov = torch.empty(self.d, self.d, dtype=torch.float64, device=self.device)
             with torch.cuda.device(self.device):
-                _lib.check(_lib.lib().vg_moments_finish(self.sum.data_ptr(), self.gram.data_ptr(), self._n, self.d, mean.data_ptr(),
-                                                        cov.data_ptr(), _stream()), "vg_moments_finish")
+                _lib.call("vg_moments_finish", self.sum.data_ptr(), self.gram.data_ptr(), self._n, self.d, mean.data_ptr(), cov.data_ptr(), _lib.stream())
             return mean, cov
         nn_ = float(self._n)
         mean = self.sum / nn_
@@ -244,7 +238,7 @@ def knn_radii(x: torch.Tensor, k: int) -> torch.Tensor:
         rad2 = torch.empty(n, dtype=torch.float64, device=x.device)
         with torch.cuda.device(x.device):
             ws = _pair_ws(n, n, k, x.device)
-            _lib.check(_lib.lib().vg_knn_radii(x.data_ptr(), x.stride(0), n, d, k, rad2.data_ptr(), ws.data_ptr(), _stream()), "vg_knn_radii")
+            _lib.call("vg_knn_radii", x.data_ptr(), x.stride(0), n, d, k, rad2.data_ptr(), ws.data_ptr(), _lib.stream())
         return rad2
     out = []
     for lo, d2 in _cpu_d2(x, x):
@@ -268,8 +262,8 @@ def ball_counts(q: torch.Tensor, c: torch.Tensor, rad2_c: torch.Tensor):
         min_d2 = torch.empty(nq, dtype=torch.float64, device=q.device)
         with torch.cuda.device(q.device):
             ws = _pair_ws(nq, nc, 0, q.device)
-            _lib.check(_lib.lib().vg_ball_counts(q.data_ptr(), q.stride(0), nq, c.data_ptr(), c.stride(0), nc, d, rad2_c.data_ptr(),
-                                                 count.data_ptr(), min_d2.data_ptr(), ws.data_ptr(), _stream()), "vg_ball_counts")
+            _lib.call("vg_ball_counts", q.data_ptr(), q.stride(0), nq, c.data_ptr(), c.stride(0), nc, d, rad2_c.data_ptr(), count.data_ptr(), min_d2.data_ptr(),
+                      ws.data_ptr(), _lib.stream())
         return count, min_d2
     counts, mins = [], []
     for _, d2 in _cpu_d2(q, c):
@@ -286,8 +280,8 @@ def poly_kernel_sum(q: torch.Tensor, c: torch.Tensor, skip_diagonal: bool = Fals
         out = torch.empty(1, dtype=torch.float64, device=q.device)
         with torch.cuda.device(q.device):
             ws = _pair_ws(nq, nc, 0, q.device)
-            _lib.check(_lib.lib().vg_poly_kernel_sum(q.data_ptr(), q.stride(0), nq, c.data_ptr(), c.stride(0), nc, d, int(bool(skip_diagonal)),
-                                                     out.data_ptr(), ws.data_ptr(), _stream()), "vg_poly_kernel_sum")
+            _lib.call("vg_poly_kernel_sum", q.data_ptr(), q.stride(0), nq, c.data_ptr(), c.stride(0), nc, d, int(bool(skip_diagonal)), out.data_ptr(),
+                      ws.data_ptr(), _lib.stream())
         return out[0]
     kap = (q.double() @ c.double().t() / float(d) + 1.0) ** 3
     total = kap.sum()
@@ -372,20 +366,19 @@ class FrozenViTFeatures:
             images = images.float()
         x = images.detach().contiguous()
         B = int(x.shape[0])
-        lib = _lib.lib()
         with torch.cuda.device(x.device):
             if self.shadow is None:  # the bf16 operands of the GEMMs, cast once: the parameters never change
                 self.shadow = torch.empty(self.flat.numel(), dtype=torch.bfloat16, device=x.device)
-                _lib.check(lib.vg_cast_f32_bf16(self.flat.data_ptr(), self.shadow.data_ptr(), self.flat.numel(), _stream()), "vg_cast_f32_bf16")
-            nbytes = lib.vg_vit_ws_bytes(C.byref(d), B)
+                _lib.call("vg_cast_f32_bf16", self.flat.data_ptr(), self.shadow.data_ptr(), self.flat.numel(), _lib.stream())
+            nbytes = _lib.lib().vg_vit_ws_bytes(C.byref(d), B)
             if nbytes <= 0:
                 raise RuntimeError("vg_vit_ws_bytes failed")
             ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
             logits = torch.empty(B, d.Kc, dtype=torch.float32, device=x.device)
             feats = torch.empty(B, d.E, dtype=torch.float32, device=x.device)
             net = _lib.VgVitNet(d, self.flat.data_ptr(), self.shadow.data_ptr(), None, 0.0, 0, None, None, self.attn_fp8, int(dense_top))
-            _lib.check(lib.vg_vit_features(C.byref(net), B, x.data_ptr(), int(x.dtype == torch.bfloat16), ws.data_ptr(), logits.data_ptr(),
-                                           feats.data_ptr(), _stream()), "vg_vit_features")
+            _lib.call("vg_vit_features", C.byref(net), B, x.data_ptr(), int(x.dtype == torch.bfloat16), ws.data_ptr(), logits.data_ptr(), feats.data_ptr(),
+                      _lib.stream())
         return feats
 
 

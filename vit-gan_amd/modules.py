@@ -149,10 +149,6 @@ def vit_init_weights(m):
 # --------------------------------------------------------------------------------------------
 # whole-network autograd node: ONE C call per forward and per backward
 # --------------------------------------------------------------------------------------------
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _fresh_seed() -> int:
     """Per-forward dropout seed drawn from torch's CPU generator (reproducible under torch.manual_seed)."""
     return int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -170,8 +166,7 @@ class _VitF32Fn(torch.autograd.Function):
         ws = torch.empty(mod._ws_bytes_f32(B), dtype=torch.uint8, device=x.device)
         logits = torch.empty(B, mod._dims.Kc, dtype=torch.float32, device=x.device)
         net = mod._net(need_grad=False, drop=ctx.drop)
-        _lib.check(_lib.lib().vg_vit_forward_f32(C.byref(net), B, xin.data_ptr(), ws.data_ptr(), logits.data_ptr(), _stream()),
-                   "vg_vit_forward_f32")
+        _lib.call("vg_vit_forward_f32", C.byref(net), B, xin.data_ptr(), ws.data_ptr(), logits.data_ptr(), _lib.stream())
         ctx.mod, ctx.ws, ctx.B, ctx.xdtype = mod, ws, B, x.dtype
         ctx.need_dx = x.requires_grad
         ctx.xshape = x.shape
@@ -186,9 +181,8 @@ class _VitF32Fn(torch.autograd.Function):
         dl = dlogits.detach().float().contiguous()
         dimg = torch.empty(ctx.xshape, dtype=torch.float32, device=dl.device) if ctx.need_dx else None
         net = mod._net(need_grad=want_w, drop=ctx.drop)
-        _lib.check(_lib.lib().vg_vit_backward_f32(C.byref(net), ctx.B, ctx.ws.data_ptr(), dl.data_ptr(),
-                                                  None if dimg is None else dimg.data_ptr(), int(want_w), _stream()),
-                   "vg_vit_backward_f32")
+        _lib.call("vg_vit_backward_f32", C.byref(net), ctx.B, ctx.ws.data_ptr(), dl.data_ptr(), None if dimg is None else dimg.data_ptr(), int(want_w),
+                  _lib.stream())
         ctx.ws = None
         return None, (None if dimg is None else dimg.to(ctx.xdtype)), None, None
 
@@ -210,8 +204,7 @@ class _VitFn(torch.autograd.Function):
         ws = torch.empty(mod._ws_bytes(B), dtype=torch.uint8, device=x.device)
         logits = torch.empty(B, mod._dims.Kc, dtype=torch.float32, device=x.device)
         net = mod._net(need_grad=False, drop=ctx.drop)
-        _lib.check(_lib.lib().vg_vit_forward(C.byref(net), B, xin.data_ptr(), int(xin.dtype == torch.bfloat16),
-                                             ws.data_ptr(), logits.data_ptr(), _stream()), "vg_vit_forward")
+        _lib.call("vg_vit_forward", C.byref(net), B, xin.data_ptr(), int(xin.dtype == torch.bfloat16), ws.data_ptr(), logits.data_ptr(), _lib.stream())
         ctx.mod, ctx.ws, ctx.B, ctx.xdtype = mod, ws, B, x.dtype
         ctx.need_dx = x.requires_grad
         ctx.xshape = x.shape
@@ -226,9 +219,8 @@ class _VitFn(torch.autograd.Function):
         dl = dlogits.detach().float().contiguous()
         dimg = torch.empty(ctx.xshape, dtype=torch.bfloat16, device=dl.device) if ctx.need_dx else None
         net = mod._net(need_grad=want_w, drop=ctx.drop)
-        _lib.check(_lib.lib().vg_vit_backward(C.byref(net), ctx.B, ctx.ws.data_ptr(), dl.data_ptr(),
-                                              None if dimg is None else dimg.data_ptr(), int(want_w), _stream()),
-                   "vg_vit_backward")
+        _lib.call("vg_vit_backward", C.byref(net), ctx.B, ctx.ws.data_ptr(), dl.data_ptr(), None if dimg is None else dimg.data_ptr(), int(want_w),
+                  _lib.stream())
         ctx.ws = None
         return None, (None if dimg is None else dimg.to(ctx.xdtype)), None, None
 
@@ -355,8 +347,8 @@ class VisionTransformer(nn.Module):
         feats = torch.empty(B, self._dims.E, dtype=torch.float32, device=x.device)
         net = self._net(need_grad=False)
         net.dense_top = int(dense_top)
-        _lib.check(_lib.lib().vg_vit_features(C.byref(net), B, xin.data_ptr(), int(xin.dtype == torch.bfloat16), ws.data_ptr(),
-                                              logits.data_ptr(), feats.data_ptr(), _stream()), "vg_vit_features")
+        _lib.call("vg_vit_features", C.byref(net), B, xin.data_ptr(), int(xin.dtype == torch.bfloat16), ws.data_ptr(), logits.data_ptr(), feats.data_ptr(),
+                  _lib.stream())
         return logits, feats
 
     def composed_forward(self, x):

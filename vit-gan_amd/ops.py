@@ -18,14 +18,6 @@ from . import _lib
 BF = torch.bfloat16
 
 
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def _need_cuda(t: torch.Tensor, what: str) -> None:
     if not t.is_cuda:
         raise RuntimeError(f"{what}: the HIP path needs cuda tensors (got {t.device}); there is no CPU fallback")
@@ -54,7 +46,7 @@ def _wgrad(dy_b, x_b, M, N, K):
     splits = max(1, min(8, 512 // max(tiles, 1), max(1, (M // 64) // 4)))
     dW = torch.empty(N, K, dtype=torch.float32, device=dy_b.device)
     slab = torch.empty(splits * N * K, dtype=torch.float32, device=dy_b.device)
-    _lib.check(_lib.lib().vg_linear_wgrad(_p(dy_b), _p(x_b), _p(dW), _p(slab), slab.numel(), M, N, K, splits, 0, _st()), "vg_linear_wgrad")
+    _lib.call("vg_linear_wgrad", _lib.ptr(dy_b), _lib.ptr(x_b), _lib.ptr(dW), _lib.ptr(slab), slab.numel(), M, N, K, splits, 0, _lib.stream())
     return dW
 
 
@@ -62,7 +54,7 @@ def _bias_grad(dy_b, M, N):
     parts = _lib.lib().vg_colsum_bf16_parts(M)
     ws = torch.empty(parts * N, dtype=torch.float32, device=dy_b.device)
     db = torch.empty(N, dtype=torch.float32, device=dy_b.device)
-    _lib.check(_lib.lib().vg_colsum_bf16(_p(dy_b), N, M, N, _p(ws), _p(db), 0, _st()), "vg_colsum_bf16")
+    _lib.call("vg_colsum_bf16", _lib.ptr(dy_b), N, M, N, _lib.ptr(ws), _lib.ptr(db), 0, _lib.stream())
     return db
 
 
@@ -87,7 +79,7 @@ class LinearFn(torch.autograd.Function):
         if rb is not None and N != N0:
             raise RuntimeError("residual with a padded output is not supported")
         y = torch.empty(M, N, dtype=BF, device=x.device)
-        _lib.check(_lib.lib().vg_linear_fwd(_p(xb), _p(wb), _p(bb), _p(rb), _p(y), None, None, M, N, K, 0, 0.0, _st()), "vg_linear_fwd")
+        _lib.call("vg_linear_fwd", _lib.ptr(xb), _lib.ptr(wb), _lib.ptr(bb), _lib.ptr(rb), _lib.ptr(y), None, None, M, N, K, 0, 0.0, _lib.stream())
         ctx.save_for_backward(xb, wb)
         ctx.dims = (M, N, K, N0, K0, bias is not None, res is not None, x.shape, x.dtype)
         return y[:, :N0].reshape(x.shape[:-1] + (N0,)).to(x.dtype)
@@ -102,7 +94,7 @@ class LinearFn(torch.autograd.Function):
             t[:, :N0] = dyb
             dyb = t
         dx = torch.empty(M, K, dtype=BF, device=dy.device)
-        _lib.check(_lib.lib().vg_linear_dgrad(_p(dyb), _p(wb), _p(dx), M, N, K, 0, None, None, 0.0, _st()), "vg_linear_dgrad")
+        _lib.call("vg_linear_dgrad", _lib.ptr(dyb), _lib.ptr(wb), _lib.ptr(dx), M, N, K, 0, None, None, 0.0, _lib.stream())
         dW = _wgrad(dyb, xb, M, N, K)[:N0, :K0]
         db = _bias_grad(dyb, M, N)[:N0] if has_b else None
         dres = dy if has_r else None
@@ -126,9 +118,8 @@ class MlpFn(torch.autograd.Function):
         a = torch.empty(M, Hd, dtype=BF, device=x.device)
         z = torch.empty(M, Hd, dtype=BF, device=x.device) if act == 1 else None
         y = torch.empty(M, N, dtype=BF, device=x.device)
-        L = _lib.lib()
-        _lib.check(L.vg_linear_fwd(_p(xb), _p(w1b), _p(b1f), None, _p(a), _p(z), None, M, Hd, K, act, 0.0, _st()), "vg_linear_fwd")
-        _lib.check(L.vg_linear_fwd(_p(a), _p(w2b), _p(b2f), None, _p(y), None, None, M, N, Hd, 0, 0.0, _st()), "vg_linear_fwd")
+        _lib.call("vg_linear_fwd", _lib.ptr(xb), _lib.ptr(w1b), _lib.ptr(b1f), None, _lib.ptr(a), _lib.ptr(z), None, M, Hd, K, act, 0.0, _lib.stream())
+        _lib.call("vg_linear_fwd", _lib.ptr(a), _lib.ptr(w2b), _lib.ptr(b2f), None, _lib.ptr(y), None, None, M, N, Hd, 0, 0.0, _lib.stream())
         ctx.save_for_backward(xb, w1b, w2b, a, z if z is not None else a)
         ctx.dims = (M, K, Hd, N, N0, act, x.shape, x.dtype)
         return y[:, :N0].reshape(x.shape[:-1] + (N0,)).to(x.dtype)
@@ -137,7 +128,6 @@ class MlpFn(torch.autograd.Function):
     def backward(ctx, dy):
         xb, w1b, w2b, a, z = ctx.saved_tensors
         M, K, Hd, N, N0, act, xshape, xdtype = ctx.dims
-        L = _lib.lib()
         dyb = _bf(dy).reshape(M, N0)
         if N != N0:
             t = torch.zeros(M, N, dtype=BF, device=dy.device)
@@ -145,9 +135,9 @@ class MlpFn(torch.autograd.Function):
             dyb = t
         dz = torch.empty(M, Hd, dtype=BF, device=dy.device)
         mode = 4 if act == 1 else 6  # gelu'(z) / 1 - tanh^2
-        _lib.check(L.vg_linear_dgrad(_p(dyb), _p(w2b), _p(dz), M, N, Hd, mode, _p(z), None, 0.0, _st()), "vg_linear_dgrad")
+        _lib.call("vg_linear_dgrad", _lib.ptr(dyb), _lib.ptr(w2b), _lib.ptr(dz), M, N, Hd, mode, _lib.ptr(z), None, 0.0, _lib.stream())
         dx = torch.empty(M, K, dtype=BF, device=dy.device)
-        _lib.check(L.vg_linear_dgrad(_p(dz), _p(w1b), _p(dx), M, Hd, K, 0, None, None, 0.0, _st()), "vg_linear_dgrad")
+        _lib.call("vg_linear_dgrad", _lib.ptr(dz), _lib.ptr(w1b), _lib.ptr(dx), M, Hd, K, 0, None, None, 0.0, _lib.stream())
         dW2 = _wgrad(dyb, a, M, N, Hd)[:N0]
         db2 = _bias_grad(dyb, M, N)[:N0]
         dW1 = _wgrad(dz, xb, M, Hd, K)
@@ -168,7 +158,7 @@ class LayerNormFn(torch.autograd.Function):
         y = torch.empty(R, E, dtype=BF, device=x.device)
         mean = torch.empty(R, dtype=torch.float32, device=x.device)
         rstd = torch.empty(R, dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib().vg_layernorm_fwd(_p(xb), E, _p(g), _p(b), _p(y), E, _p(mean), _p(rstd), R, E, eps, _st()), "vg_layernorm_fwd")
+        _lib.call("vg_layernorm_fwd", _lib.ptr(xb), E, _lib.ptr(g), _lib.ptr(b), _lib.ptr(y), E, _lib.ptr(mean), _lib.ptr(rstd), R, E, eps, _lib.stream())
         ctx.save_for_backward(xb, g, mean, rstd)
         ctx.dims = (R, E, x.shape, x.dtype)
         return y.reshape(x.shape).to(x.dtype)
@@ -177,15 +167,15 @@ class LayerNormFn(torch.autograd.Function):
     def backward(ctx, dy):
         xb, g, mean, rstd = ctx.saved_tensors
         R, E, xshape, xdtype = ctx.dims
-        L = _lib.lib()
         dyb = _bf(dy).reshape(R, E)
-        parts = L.vg_layernorm_bwd_parts(R)
+        parts = _lib.lib().vg_layernorm_bwd_parts(R)
         part = torch.empty(parts, 3 * E, dtype=torch.float32, device=dy.device)
         dx = torch.empty(R, E, dtype=BF, device=dy.device)
-        _lib.check(L.vg_layernorm_bwd(_p(dyb), _p(xb), _p(mean), _p(rstd), _p(g), None, _p(dx), _p(part), R, E, _st()), "vg_layernorm_bwd")
+        _lib.call("vg_layernorm_bwd", _lib.ptr(dyb), _lib.ptr(xb), _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(g), None, _lib.ptr(dx), _lib.ptr(part), R, E,
+                  _lib.stream())
         dg = torch.empty(E, dtype=torch.float32, device=dy.device)
         db = torch.empty(E, dtype=torch.float32, device=dy.device)
-        _lib.check(L.vg_colsum_f32(_p(part), parts, 3 * E, _p(dg), E, _p(db), E, None, E, None, 0, 0, _st()), "vg_colsum_f32")
+        _lib.call("vg_colsum_f32", _lib.ptr(part), parts, 3 * E, _lib.ptr(dg), E, _lib.ptr(db), E, None, E, None, 0, 0, _lib.stream())
         return dx.reshape(xshape).to(xdtype), dg, db, None
 
 
@@ -205,9 +195,7 @@ class AttentionFn(torch.autograd.Function):
         qb = _bf(qkv).reshape(B * S, E3)
         out = torch.empty(B * S, E, dtype=BF, device=qkv.device)
         lse = torch.empty(B, heads, S, dtype=torch.float32, device=qkv.device)
-        L = _lib.lib()
-        fn = L.vg_attention_fwd if lp == 1 else L.vg_attention_l2_fwd
-        _lib.check(fn(_p(qb), _p(out), _p(lse), B, heads, S, HE, scale, _st()), "vg_attention_fwd")
+        _lib.call("vg_attention_fwd" if lp == 1 else "vg_attention_l2_fwd", _lib.ptr(qb), _lib.ptr(out), _lib.ptr(lse), B, heads, S, HE, scale, _lib.stream())
         ctx.save_for_backward(qb, out, lse)
         ctx.dims = (B, heads, S, HE, scale, qkv.dtype, lp)
         return out.reshape(B, S, E).to(qkv.dtype)
@@ -218,9 +206,8 @@ class AttentionFn(torch.autograd.Function):
         B, H, S, HE, scale, dt, lp = ctx.dims
         dob = _bf(dout).reshape(B * S, H * HE)
         dqkv = torch.empty_like(qb)
-        L = _lib.lib()
-        fn = L.vg_attention_bwd if lp == 1 else L.vg_attention_l2_bwd
-        _lib.check(fn(_p(qb), _p(out), _p(dob), _p(lse), _p(dqkv), B, H, S, HE, scale, _st()), "vg_attention_bwd")
+        _lib.call("vg_attention_bwd" if lp == 1 else "vg_attention_l2_bwd", _lib.ptr(qb), _lib.ptr(out), _lib.ptr(dob), _lib.ptr(lse), _lib.ptr(dqkv), B, H, S,
+                  HE, scale, _lib.stream())
         return dqkv.reshape(B, S, 3 * H * HE).to(dt), None, None, None
 
 
@@ -239,7 +226,7 @@ class UnfoldTokensFn(torch.autograd.Function):
         is_bf = images.dtype == BF
         src = images.contiguous() if is_bf else images.float().contiguous()
         out = torch.empty(B, n * n, C * W * W, dtype=BF, device=images.device)
-        _lib.check(_lib.lib().vg_unfold_tokens_fwd(_p(src), int(is_bf), _p(out), B, C, IH, patch, overlap, _st()), "vg_unfold_tokens_fwd")
+        _lib.call("vg_unfold_tokens_fwd", _lib.ptr(src), int(is_bf), _lib.ptr(out), B, C, IH, patch, overlap, _lib.stream())
         ctx.geo = (B, C, IH, patch, overlap, images.dtype)
         return out.to(images.dtype)
 
@@ -248,7 +235,7 @@ class UnfoldTokensFn(torch.autograd.Function):
         B, C, IH, patch, overlap, dt = ctx.geo
         d = _bf(dtok).contiguous()
         dimg = torch.empty(B, C, IH, IH, dtype=BF, device=dtok.device)
-        _lib.check(_lib.lib().vg_unfold_tokens_bwd(_p(d), _p(dimg), B, C, IH, patch, overlap, _st()), "vg_unfold_tokens_bwd")
+        _lib.call("vg_unfold_tokens_bwd", _lib.ptr(d), _lib.ptr(dimg), B, C, IH, patch, overlap, _lib.stream())
         return dimg.to(dt), None, None
 
 
@@ -344,10 +331,9 @@ class DiffAugmentFn(torch.autograd.Function):
         xb = _bf(x)
         y = torch.empty_like(xb)
         if p is None:
-            _lib.check(_lib.lib().vg_diffaug_fwd(_p(xb), _p(y), None, B, Cc, IH, policy, seed, site, _p(step), _st()), "vg_diffaug_fwd")
+            _lib.call("vg_diffaug_fwd", _lib.ptr(xb), _lib.ptr(y), None, B, Cc, IH, policy, seed, site, _lib.ptr(step), _lib.stream())
         else:
-            _lib.check(_lib.lib().vg_diffaug_p_fwd(_p(xb), _p(y), None, B, Cc, IH, policy, seed, site, _p(step), _p(p), _st()),
-                       "vg_diffaug_p_fwd")
+            _lib.call("vg_diffaug_p_fwd", _lib.ptr(xb), _lib.ptr(y), None, B, Cc, IH, policy, seed, site, _lib.ptr(step), _lib.ptr(p), _lib.stream())
         # the adjoint must see the counter value (and the probability) of THIS forward, whatever the caller does to them before backward()
         ctx.key = (policy, seed, site, None if step is None else step.clone(), x.dtype, None if p is None else p.clone())
         return y.to(x.dtype)
@@ -360,10 +346,9 @@ class DiffAugmentFn(torch.autograd.Function):
         d = _bf(dy)
         dx = torch.empty_like(d)
         if p is None:
-            _lib.check(_lib.lib().vg_diffaug_bwd(_p(d), _p(dx), 0, B, Cc, IH, policy, seed, site, _p(step), _st()), "vg_diffaug_bwd")
+            _lib.call("vg_diffaug_bwd", _lib.ptr(d), _lib.ptr(dx), 0, B, Cc, IH, policy, seed, site, _lib.ptr(step), _lib.stream())
         else:
-            _lib.check(_lib.lib().vg_diffaug_p_bwd(_p(d), _p(dx), 0, B, Cc, IH, policy, seed, site, _p(step), _p(p), _st()),
-                       "vg_diffaug_p_bwd")
+            _lib.call("vg_diffaug_p_bwd", _lib.ptr(d), _lib.ptr(dx), 0, B, Cc, IH, policy, seed, site, _lib.ptr(step), _lib.ptr(p), _lib.stream())
         return dx.to(dt), None, None, None, None, None
 
 
@@ -420,7 +405,7 @@ def r1_due(step_index: int, interval: int) -> bool:
     return (int(step_index) - 1) % int(interval) == 0
 
 
-LR_KINDS = {"constant": 0, "linear": 1, "cosine": 2}  # VG_LR_* of include/vitgan_hip.h
+LR_KINDS = _lib.LR_KINDS  # VG_LR_* of include/vitgan_hip.h: {"constant": 0, "linear": 1, "cosine": 2}
 
 
 def parse_lr_schedule(kind, warmup, total, final):
@@ -471,7 +456,7 @@ def lr_schedule(step: torch.Tensor, d, g, scale: Optional[torch.Tensor] = None, 
     scale = torch.ones(2, dtype=torch.float32, device=step.device) if scale is None else scale
     out = torch.empty(2, dtype=torch.float32, device=step.device) if out is None else out
     sd, sg = lr_sched_struct(*d), lr_sched_struct(*g)
-    _lib.check(_lib.lib().vg_lr_schedule(C.byref(sd), C.byref(sg), _p(step), _p(scale), _p(out), _st()), "vg_lr_schedule")
+    _lib.call("vg_lr_schedule", C.byref(sd), C.byref(sg), _lib.ptr(step), _lib.ptr(scale), _lib.ptr(out), _lib.stream())
     return out
 
 
@@ -527,8 +512,8 @@ class GradStatsPlan:
         self.totals = torch.zeros(4, dtype=torch.float32, device=device)  # (sum of norms, l2, non-finite elements, 0)
 
     def enqueue(self, grad: torch.Tensor, gscale: float, st) -> None:
-        _lib.check(_lib.lib().vg_grad_stats(_p(grad), self.total, _p(self.chunks), self.n_chunks, _p(self.seg_first), self.n_seg, float(gscale),
-                                            _p(self.scratch), _p(self.norm_seg), _p(self.totals), st), "vg_grad_stats")
+        _lib.call("vg_grad_stats", _lib.ptr(grad), self.total, _lib.ptr(self.chunks), self.n_chunks, _lib.ptr(self.seg_first), self.n_seg, float(gscale),
+                  _lib.ptr(self.scratch), _lib.ptr(self.norm_seg), _lib.ptr(self.totals), st)
 
 
 def grad_stats(flat_grad: torch.Tensor, slots, gscale: float = 1.0, limit: int = GRAD_CHUNK):
@@ -540,7 +525,7 @@ def grad_stats(flat_grad: torch.Tensor, slots, gscale: float = 1.0, limit: int =
     if flat_grad.dtype != torch.float32 or flat_grad.dim() != 1 or not flat_grad.is_contiguous():
         raise ValueError("grad_stats: flat_grad is a contiguous one-dimensional fp32 tensor")
     plan = GradStatsPlan(slots, flat_grad.numel(), flat_grad.device, limit)
-    plan.enqueue(flat_grad, gscale, _st())
+    plan.enqueue(flat_grad, gscale, _lib.stream())
     return {"norms": plan.norm_seg, "keys": plan.keys, "sum_norms": plan.totals[0], "l2": plan.totals[1], "nonfinite": plan.totals[2]}
 
 
@@ -550,7 +535,7 @@ def logit_stats(x: torch.Tensor):
     _need_cuda(x, "logit_stats")
     xs = _f32(x).reshape(-1)
     out = torch.zeros(3, 4, dtype=torch.float32, device=x.device)
-    _lib.check(_lib.lib().vg_logit_stats(_p(xs), None, xs.numel(), 0, _p(out), _st()), "vg_logit_stats")
+    _lib.call("vg_logit_stats", _lib.ptr(xs), None, xs.numel(), 0, _lib.ptr(out), _lib.stream())
     return out[0, :3]
 
 
@@ -569,8 +554,8 @@ class ConsistencyLossFn(torch.autograd.Function):
         lx, la = logits_x.detach().float().contiguous(), logits_a.detach().float().contiguous()
         dx, da = torch.empty_like(lx), torch.empty_like(la)
         parts = torch.empty(2, dtype=torch.float32, device=lx.device)
-        _lib.check(_lib.lib().vg_bcr_loss(_p(lx), _p(la), _p(dx), _p(da), _p(parts), n_real, n - n_real, Kc, w_real, w_fake, 0, 0, 1.0, _st()),
-                   "vg_bcr_loss")
+        _lib.call("vg_bcr_loss", _lib.ptr(lx), _lib.ptr(la), _lib.ptr(dx), _lib.ptr(da), _lib.ptr(parts), n_real, n - n_real, Kc, w_real, w_fake, 0, 0, 1.0,
+                  _lib.stream())
         ctx.save_for_backward(dx, da)
         ctx.dts = (logits_x.dtype, logits_a.dtype)
         ctx.mark_non_differentiable(parts)
@@ -623,7 +608,7 @@ class ConditionalGanLossFn(torch.autograd.Function):
         n, Kc = lg.shape
         dl, sel = torch.empty_like(lg), torch.empty(n, dtype=torch.float32, device=lg.device)
         out = torch.empty(1, dtype=torch.float32, device=lg.device)
-        _lib.check(_lib.lib().vg_gan_loss_cond(_p(lg), _p(labels), _p(dl), _p(sel), _p(out), n, Kc, kind, role, 1.0, _st()), "vg_gan_loss_cond")
+        _lib.call("vg_gan_loss_cond", _lib.ptr(lg), _lib.ptr(labels), _lib.ptr(dl), _lib.ptr(sel), _lib.ptr(out), n, Kc, kind, role, 1.0, _lib.stream())
         ctx.save_for_backward(dl)
         ctx.dt = logits.dtype
         ctx.mark_non_differentiable(sel)
@@ -660,7 +645,7 @@ def draw_labels(n: int, K: int, seed: int, site: int, step: Optional[torch.Tenso
         raise ValueError(f"draw_labels: n >= 1 and 1 <= K <= 16, got n={n!r}, K={K!r}")
     dev = step.device if step is not None else torch.device("cuda" if device is None else device)
     out = torch.empty(n, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().vg_draw_labels(_p(out), n, int(K), int(seed) & 0xFFFFFFFFFFFFFFFF, int(site), _p(step), _st()), "vg_draw_labels")
+    _lib.call("vg_draw_labels", _lib.ptr(out), n, int(K), int(seed) & 0xFFFFFFFFFFFFFFFF, int(site), _lib.ptr(step), _lib.stream())
     return out
 
 
@@ -671,7 +656,7 @@ def class_add(wmod, table, labels):
         raise ValueError("class_add: wmod [B, N] and table [K, N] with N % 8 == 0")
     y = check_labels(labels, wmod.shape[0], table.shape[0], "class_add", wmod.device)
     out, tb = _bf(wmod).clone(), _bf(table)
-    _lib.check(_lib.lib().vg_class_add(_p(out), _p(tb), _p(y), out.shape[0], out.shape[1], tb.shape[0], _st()), "vg_class_add")
+    _lib.call("vg_class_add", _lib.ptr(out), _lib.ptr(tb), _lib.ptr(y), out.shape[0], out.shape[1], tb.shape[0], _lib.stream())
     return out
 
 
@@ -686,7 +671,7 @@ def class_grad(dw, labels, K: int, out: Optional[torch.Tensor] = None):
     if out is not None and (out.dtype != torch.float32 or tuple(out.shape) != (K, d.shape[1]) or not out.is_contiguous() or out.device != d.device):
         raise ValueError(f"class_grad: out is a contiguous fp32 [{K}, {d.shape[1]}] tensor on the gradient's device")
     res = torch.empty(K, d.shape[1], dtype=torch.float32, device=d.device) if out is None else out
-    _lib.check(_lib.lib().vg_class_grad(_p(d), _p(y), _p(res), d.shape[0], d.shape[1], int(K), int(out is not None), _st()), "vg_class_grad")
+    _lib.call("vg_class_grad", _lib.ptr(d), _lib.ptr(y), _lib.ptr(res), d.shape[0], d.shape[1], int(K), int(out is not None), _lib.stream())
     return res
 
 

@@ -21,7 +21,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .ops import BF, _bf, _bias_grad, _f32, _need_cuda, _p, _st, _wgrad
+from .ops import BF, _bf, _bias_grad, _f32, _need_cuda, _wgrad
 
 ACTS = {"gelu": 1, "tanh": 3}
 
@@ -93,7 +93,7 @@ class deferred_weight_grads:
         self.items.append((slot, dyb, xb, M, N, K))
 
     def flush(self) -> None:
-        L, st, dev = _lib.lib(), _st(), self.grad.device
+        st, dev = _lib.stream(), self.grad.device
         # contribution index of an item = how many earlier items went to the same weight
         seen, sets = {}, {}
         for it in self.items:
@@ -115,7 +115,7 @@ class deferred_weight_grads:
                 Ns, Ks = (C.c_int * n)(*[t[4] for t in its]), (C.c_int * n)(*[t[5] for t in its])
                 offs = (C.c_longlong * n)(*[t[0].offset - region for t in its])
                 dst = C.c_void_p(self.grad.data_ptr() + 4 * region)
-                rc = L.vg_linear_wgrad_group(n, dys, xs, Ns, Ks, offs, M, splits, _p(slab), slab.numel(), dst, rf, 1, st)
+                rc = _lib.lib().vg_linear_wgrad_group(n, dys, xs, Ns, Ks, offs, M, splits, _lib.ptr(slab), slab.numel(), dst, rf, 1, st)
                 if rc == 0:
                     continue
                 if rc != -2:  # -2: the items do not tile the region (a frozen weight, a weight used twice): one by one below
@@ -125,8 +125,8 @@ class deferred_weight_grads:
                 need = splits * N * K
                 if slab is None or slab.numel() < need:
                     slab = torch.empty(need, dtype=torch.float32, device=dev)
-                _lib.check(L.vg_linear_wgrad(_p(dyb), _p(xb), C.c_void_p(self.grad.data_ptr() + 4 * slot.offset), _p(slab), slab.numel(),
-                                             Mi, N, K, splits, 1, st), "vg_linear_wgrad")
+                _lib.call("vg_linear_wgrad", _lib.ptr(dyb), _lib.ptr(xb), C.c_void_p(self.grad.data_ptr() + 4 * slot.offset), _lib.ptr(slab), slab.numel(), Mi,
+                          N, K, splits, 1, st)
 
 
 def _pad8(n: int) -> int:
@@ -163,7 +163,7 @@ class _LinearDgrad(torch.autograd.Function):
         dyb = _pad_cols(_bf(dy), N)
         wb = _pad_rows_to(_bf(weight), N)
         dx = torch.empty(M, K, dtype=BF, device=dy.device)
-        _lib.check(_lib.lib().vg_linear_dgrad(_p(dyb), _p(wb), _p(dx), M, N, K, 0, None, None, 0.0, _st()), "vg_linear_dgrad")
+        _lib.call("vg_linear_dgrad", _lib.ptr(dyb), _lib.ptr(wb), _lib.ptr(dx), M, N, K, 0, None, None, 0.0, _lib.stream())
         ctx.save_for_backward(dyb, wb)
         ctx.dims = (M, N, N0, K, dy.dtype)
         ctx.slot = slot
@@ -175,7 +175,7 @@ class _LinearDgrad(torch.autograd.Function):
         M, N, N0, K, dt = ctx.dims
         ub = _bf(ddx)
         d_dy = torch.empty(M, N, dtype=BF, device=ddx.device)   # d(dY) = ddX W^T: the forward Linear kernel
-        _lib.check(_lib.lib().vg_linear_fwd(_p(ub), _p(wb), None, None, _p(d_dy), None, None, M, N, K, 0, 0.0, _st()), "vg_linear_fwd")
+        _lib.call("vg_linear_fwd", _lib.ptr(ub), _lib.ptr(wb), None, None, _lib.ptr(d_dy), None, None, M, N, K, 0, 0.0, _lib.stream())
         if _QUEUE is not None and ctx.slot is not None and N == N0:
             _QUEUE.push(ctx.slot, dyb, ub, M, N, K)              # dW = dY^T ddX, grouped with the block's other weights on exit
             return d_dy.to(dt), None, None
@@ -198,7 +198,7 @@ class Linear2(torch.autograd.Function):
         wb = _pad_rows_to(_bf(weight), N)
         bb = None if bias is None else _pad_rows_to(_f32(bias), N)
         y = torch.empty(M, N, dtype=BF, device=x.device)
-        _lib.check(_lib.lib().vg_linear_fwd(_p(xb), _p(wb), _p(bb), None, _p(y), None, None, M, N, K, 0, 0.0, _st()), "vg_linear_fwd")
+        _lib.call("vg_linear_fwd", _lib.ptr(xb), _lib.ptr(wb), _lib.ptr(bb), None, _lib.ptr(y), None, None, M, N, K, 0, 0.0, _lib.stream())
         ctx.save_for_backward(xb, weight)
         ctx.dims = (M, N, N0, K, bias is not None, x.shape, x.dtype)
         ctx.slot = slot
@@ -231,16 +231,16 @@ class _LayerNormBwd(torch.autograd.Function):
     @staticmethod
     def forward(ctx, dy, x, gamma, mean, rstd):
         R, E = x.shape
-        L = _lib.lib()
         dyb, xb, g = _bf(dy), _bf(x), _f32(gamma)
-        parts = L.vg_layernorm_bwd_parts(R)
+        parts = _lib.lib().vg_layernorm_bwd_parts(R)
         part = torch.empty(parts, 3 * E, dtype=torch.float32, device=dy.device)
         dx = torch.empty(R, E, dtype=BF, device=dy.device)
-        _lib.check(L.vg_layernorm_bwd(_p(dyb), _p(xb), _p(mean), _p(rstd), _p(g), None, _p(dx), _p(part), R, E, _st()), "vg_layernorm_bwd")
+        _lib.call("vg_layernorm_bwd", _lib.ptr(dyb), _lib.ptr(xb), _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(g), None, _lib.ptr(dx), _lib.ptr(part), R, E,
+                  _lib.stream())
         dg = torch.empty(E, dtype=torch.float32, device=dy.device)
         db = torch.empty(E, dtype=torch.float32, device=dy.device)
         if not _INPUT_GRAD_ONLY:  # (else: never read - LayerNorm2.backward drops them)
-            _lib.check(L.vg_colsum_f32(_p(part), parts, 3 * E, _p(dg), E, _p(db), E, None, E, None, 0, 0, _st()), "vg_colsum_f32")
+            _lib.call("vg_colsum_f32", _lib.ptr(part), parts, 3 * E, _lib.ptr(dg), E, _lib.ptr(db), E, None, E, None, 0, 0, _lib.stream())
         ctx.save_for_backward(dyb, xb, g, mean, rstd)
         ctx.dims = (R, E, dy.dtype, x.dtype)
         ctx.mark_non_differentiable(dg, db)
@@ -250,16 +250,15 @@ class _LayerNormBwd(torch.autograd.Function):
     def backward(ctx, u, _ug, _ub):
         dyb, xb, g, mean, rstd = ctx.saved_tensors
         R, E, dyt, xt = ctx.dims
-        L = _lib.lib()
         ub = _bf(u)
         d_dy = torch.empty(R, E, dtype=BF, device=u.device)
         d_x = torch.empty(R, E, dtype=BF, device=u.device)
-        parts = L.vg_layernorm_bwd_bwd_parts(R)
+        parts = _lib.lib().vg_layernorm_bwd_bwd_parts(R)
         part = torch.empty(parts, E, dtype=torch.float32, device=u.device)
-        _lib.check(L.vg_layernorm_bwd_bwd(_p(ub), _p(dyb), _p(xb), _p(mean), _p(rstd), _p(g), _p(d_dy), _p(d_x), _p(part), R, E, _st()),
-                   "vg_layernorm_bwd_bwd")
+        _lib.call("vg_layernorm_bwd_bwd", _lib.ptr(ub), _lib.ptr(dyb), _lib.ptr(xb), _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(g), _lib.ptr(d_dy), _lib.ptr(d_x),
+                  _lib.ptr(part), R, E, _lib.stream())
         d_g = torch.empty(E, dtype=torch.float32, device=u.device)
-        _lib.check(L.vg_colsum_f32(_p(part), parts, E, _p(d_g), E, None, 0, None, 0, None, 0, 0, _st()), "vg_colsum_f32")
+        _lib.call("vg_colsum_f32", _lib.ptr(part), parts, E, _lib.ptr(d_g), E, None, 0, None, 0, None, 0, 0, _lib.stream())
         return d_dy.to(dyt), d_x.to(xt), d_g, None, None
 
 
@@ -274,7 +273,7 @@ class LayerNorm2(torch.autograd.Function):
         y = torch.empty(R, E, dtype=BF, device=x.device)
         mean = torch.empty(R, dtype=torch.float32, device=x.device)
         rstd = torch.empty(R, dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib().vg_layernorm_fwd(_p(xb), E, _p(g), _p(b), _p(y), E, _p(mean), _p(rstd), R, E, eps, _st()), "vg_layernorm_fwd")
+        _lib.call("vg_layernorm_fwd", _lib.ptr(xb), E, _lib.ptr(g), _lib.ptr(b), _lib.ptr(y), E, _lib.ptr(mean), _lib.ptr(rstd), R, E, eps, _lib.stream())
         ctx.save_for_backward(x, gamma, mean, rstd)
         ctx.dims = (R, E)
         return y.reshape(x.shape).to(x.dtype)
@@ -297,7 +296,7 @@ class _ActBwd(torch.autograd.Function):
     def forward(ctx, dy, h, act):
         dyb, hb = _bf(dy).reshape(-1), _bf(h).reshape(-1)
         dh = torch.empty_like(hb)
-        _lib.check(_lib.lib().vg_act_bwd(_p(dyb), _p(hb), _p(dh), hb.numel(), act, _st()), "vg_act_bwd")
+        _lib.call("vg_act_bwd", _lib.ptr(dyb), _lib.ptr(hb), _lib.ptr(dh), hb.numel(), act, _lib.stream())
         ctx.save_for_backward(dyb, hb)
         ctx.meta = (act, dy.shape, dy.dtype, h.dtype)
         return dh.reshape(dy.shape).to(dy.dtype)
@@ -308,7 +307,7 @@ class _ActBwd(torch.autograd.Function):
         act, shape, dyt, ht = ctx.meta
         ub = _bf(u).reshape(-1)
         d_dy, d_h = torch.empty_like(hb), torch.empty_like(hb)
-        _lib.check(_lib.lib().vg_act_bwd_bwd(_p(ub), _p(dyb), _p(hb), _p(d_dy), _p(d_h), hb.numel(), act, _st()), "vg_act_bwd_bwd")
+        _lib.call("vg_act_bwd_bwd", _lib.ptr(ub), _lib.ptr(dyb), _lib.ptr(hb), _lib.ptr(d_dy), _lib.ptr(d_h), hb.numel(), act, _lib.stream())
         return d_dy.reshape(shape).to(dyt), d_h.reshape(shape).to(ht), None
 
 
@@ -320,7 +319,7 @@ class Act2(torch.autograd.Function):
             raise RuntimeError("ops2.act: element count must be a multiple of 4")
         hb = _bf(h).reshape(-1)
         y = torch.empty_like(hb)
-        _lib.check(_lib.lib().vg_act_fwd(_p(hb), _p(y), hb.numel(), act, _st()), "vg_act_fwd")
+        _lib.call("vg_act_fwd", _lib.ptr(hb), _lib.ptr(y), hb.numel(), act, _lib.stream())
         ctx.save_for_backward(h)
         ctx.act = act
         return y.reshape(h.shape).to(h.dtype)
@@ -341,8 +340,7 @@ class _AttentionBwd(torch.autograd.Function):
         E = E3 // 3
         qb, dob = _bf(qkv).reshape(B * S, E3), _bf(dout).reshape(B * S, E)
         dqkv = torch.empty_like(qb)
-        _lib.check(_lib.lib().vg_attention_bwd(_p(qb), _p(out), _p(dob), _p(lse), _p(dqkv), B, heads, S, E // heads, scale, _st()),
-                   "vg_attention_bwd")
+        _lib.call("vg_attention_bwd", _lib.ptr(qb), _lib.ptr(out), _lib.ptr(dob), _lib.ptr(lse), _lib.ptr(dqkv), B, heads, S, E // heads, scale, _lib.stream())
         ctx.save_for_backward(qb, dob, lse)
         ctx.meta = (B, heads, S, E // heads, scale, dout.dtype, qkv.dtype)
         return dqkv.reshape(B, S, E3).to(qkv.dtype)
@@ -354,8 +352,8 @@ class _AttentionBwd(torch.autograd.Function):
         ub = _bf(u).reshape(B * S, 3 * H * HE)
         d_do = torch.empty_like(dob)
         d_q = torch.empty_like(qb)
-        _lib.check(_lib.lib().vg_attention_bwd_bwd(_p(qb), _p(dob), _p(lse), _p(ub), _p(d_do), _p(d_q), B, H, S, HE, scale, _st()),
-                   "vg_attention_bwd_bwd")
+        _lib.call("vg_attention_bwd_bwd", _lib.ptr(qb), _lib.ptr(dob), _lib.ptr(lse), _lib.ptr(ub), _lib.ptr(d_do), _lib.ptr(d_q), B, H, S, HE, scale,
+                  _lib.stream())
         return d_do.reshape(B, S, H * HE).to(dot), d_q.reshape(B, S, 3 * H * HE).to(qt), None, None, None, None
 
 
@@ -368,7 +366,7 @@ class Attention2(torch.autograd.Function):
         qb = _bf(qkv).reshape(B * S, E3)
         out = torch.empty(B * S, E, dtype=BF, device=qkv.device)
         lse = torch.empty(B, heads, S, dtype=torch.float32, device=qkv.device)
-        _lib.check(_lib.lib().vg_attention_fwd(_p(qb), _p(out), _p(lse), B, heads, S, E // heads, scale, _st()), "vg_attention_fwd")
+        _lib.call("vg_attention_fwd", _lib.ptr(qb), _lib.ptr(out), _lib.ptr(lse), B, heads, S, E // heads, scale, _lib.stream())
         ctx.save_for_backward(qkv, out, lse)
         ctx.meta = (heads, scale)
         return out.reshape(B, S, E).to(qkv.dtype)

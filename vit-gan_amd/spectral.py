@@ -47,10 +47,6 @@ def vit_matrix_keys(n_layers: int, which: str) -> List[str]:
     return keys
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 class SpectralState:
     """The table, ``u / v / sigma / sigma0`` and the two calls for ``entries`` = [(element offset, N, K)] of a flat buffer of
     ``total`` elements.  The entries are kept in ascending offset order."""
@@ -64,7 +60,7 @@ class SpectralState:
         for d, (off, N, K) in zip(self.table, self.entries):
             d.w_off, d.N, d.K = off, N, K
         ns, nc = C.c_longlong(0), C.c_longlong(0)
-        _lib.check(_lib.lib().vg_spectral_plan(C.cast(self.table, C.c_void_p), self.n, C.byref(ns), C.byref(nc)), "vg_spectral_plan")
+        _lib.call("vg_spectral_plan", C.cast(self.table, C.c_void_p), self.n, C.byref(ns), C.byref(nc))
         self.state_floats, self.scratch_floats = int(ns.value), int(nc.value)
         self.device = torch.device(device)
         raw = torch.frombuffer(bytearray(bytes(self.table)), dtype=torch.uint8)
@@ -103,16 +99,14 @@ class SpectralState:
 
     # ------------------------------------------------------------------ the two calls (enqueue only)
     def update(self, flat: torch.Tensor, shadow: torch.Tensor, iterate: bool = True, stream=None) -> None:
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        _lib.check(_lib.lib().vg_spectral_update(p(flat), p(shadow), self.total, p(self.state), self.state_floats, p(self.scratch),
-                                                 self.scratch_floats, C.cast(self.table, C.c_void_p), p(self.table_dev), self.n, int(bool(iterate)),
-                                                 _stream() if stream is None else stream), "vg_spectral_update")
+        p = _lib.ptr
+        _lib.call("vg_spectral_update", p(flat), p(shadow), self.total, p(self.state), self.state_floats, p(self.scratch), self.scratch_floats,
+                  C.cast(self.table, C.c_void_p), p(self.table_dev), self.n, int(bool(iterate)), _lib.stream() if stream is None else stream)
 
     def project(self, grad: torch.Tensor, flat: torch.Tensor, stream=None) -> None:
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        _lib.check(_lib.lib().vg_spectral_project(p(grad), p(flat), self.total, p(self.state), self.state_floats, p(self.scratch),
-                                                  self.scratch_floats, C.cast(self.table, C.c_void_p), p(self.table_dev), self.n,
-                                                  _stream() if stream is None else stream), "vg_spectral_project")
+        p = _lib.ptr
+        _lib.call("vg_spectral_project", p(grad), p(flat), self.total, p(self.state), self.state_floats, p(self.scratch), self.scratch_floats,
+                  C.cast(self.table, C.c_void_p), p(self.table_dev), self.n, _lib.stream() if stream is None else stream)
 
     @torch.no_grad()
     def effective(self, flat: torch.Tensor) -> torch.Tensor:
