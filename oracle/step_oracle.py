@@ -13,7 +13,9 @@ it is not in the reference and is pinned only against torch.nn.functional.
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, Mapping, Tuple
+import contextlib
+import dataclasses
+from typing import Callable, Dict, Mapping, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -72,6 +74,25 @@ def gradient_penalty(d_fn: Callable[[Tensor], Tensor], real: Tensor, fake: Tenso
     return ((norm - 1) ** 2).mean()
 
 
+@dataclasses.dataclass
+class StepHooks:
+    """What a variant of the alternating step does differently from ``GanStepOracle.step``; every field None is the plain step.
+
+    d_inputs(real, fake_detached) -> (real_in, fake_in): what D sees in its own step; the gradient penalty follows it.
+    g_input(fake) -> tensor: what D sees in the generator's pass, differentiable with respect to ``fake``.
+    d_extra(oracle, real, fake_detached, real_in, fake_in) -> (term, parts): a term added to D's loss.  With it the step runs ONE
+        backward over loss_real + loss_fake + term; ``parts`` is kept as ``oracle.last_extra``.
+    losses: (d_real, d_fake, g), each a function of the logits alone, in place of the three loss functions of ``oracle.loss``.
+    weights: an object with ``scaled(d)`` - a context manager in force during D's own step and again during the generator's pass -,
+        ``project(d)`` called on D's accumulated gradients before clipping and ``remeasure(d)`` called after D's update; ``d`` is
+        ``oracle.d``."""
+    d_inputs: Optional[Callable] = None
+    g_input: Optional[Callable] = None
+    d_extra: Optional[Callable] = None
+    losses: Optional[Tuple[Callable, Callable, Callable]] = None
+    weights: Optional[object] = None
+
+
 class GanStepOracle:
     """Holds leaf tensors for D (v2 ViT) and G (v1 SLN/SIREN) and runs reference steps."""
 
@@ -101,34 +122,57 @@ class GanStepOracle:
             return bf16_model.gen_forward(self.g, z, self.gdims, masks=masks)
         return gen_forward(self.g, z, self.gdims, masks=masks)
 
-    def step(self, real: Tensor, z: Tensor, noisy_inputs=None, masks=None, gp_epsilon: Tensor = None) -> Dict[str, float]:
+    def step(self, real: Tensor, z: Tensor, noisy_inputs=None, masks=None, gp_epsilon: Tensor = None,
+             hooks: StepHooks = None) -> Dict[str, float]:
         """noisy_inputs: optional (noisy_real, noisy_fake) the discriminator sees in ITS step (training.py:83-90:
         real / fake + 0.1 randn); the generator's pass through D always uses the clean fake.
         masks (test hook): explicit dropout multipliers standing in for nn.Dropout's RNG, a dict with the keys "d_real",
-        "d_fake", "d_gen" (the three discriminator passes) and "g", each a mask mapping of vit_forward / gen_forward."""
-        mk = masks or {}
+        "d_fake", "d_gen" (the three discriminator passes) and "g", each a mask mapping of vit_forward / gen_forward.
+        hooks: what a variant of the step does differently (``StepHooks``); None is the plain step."""
+        mk, h = masks or {}, hooks or StepHooks()
+        f_real, f_fake, f_gen = h.losses or (lambda t: d_loss_real(t, self.loss), lambda t: d_loss_fake(t, self.loss),
+                                             lambda t: g_loss(t, self.loss))
+        scaled = (lambda: h.weights.scaled(self.d)) if h.weights is not None else contextlib.nullcontext
         for p in self.d.values():
             p.grad = None
-        loss_real = d_loss_real(self.D(real if noisy_inputs is None else noisy_inputs[0], mk.get("d_real")), self.loss)
-        loss_real.backward()
-        fake = self.G(z, mk.get("g"))
-        loss_fake = d_loss_fake(self.D(fake.detach() if noisy_inputs is None else noisy_inputs[1], mk.get("d_fake")), self.loss)
-        loss_fake.backward()
-        self.last_gp = None
-        if self.gp_weight:  # loss += c.lambda_gp * gradient_penalty(D, noisy_real, noisy_fake), training.py:101-106 (fp32 path)
-            r_in = real if noisy_inputs is None else noisy_inputs[0]
-            f_in = fake.detach() if noisy_inputs is None else noisy_inputs[1]
-            gp = gradient_penalty(lambda t: vit_forward(self.d, t, self.ddims), r_in, f_in, gp_epsilon)
-            (self.gp_weight * gp).backward()
-            self.last_gp = float(gp.detach())
+        d_inputs = h.d_inputs if noisy_inputs is None else (lambda r, f: noisy_inputs)
+        with scaled():
+            if d_inputs is not None:  # what D sees depends on the fake: G runs first
+                fake = self.G(z, mk.get("g"))
+                r_in, f_in = d_inputs(real, fake.detach())
+            else:
+                r_in = real
+            loss_real = f_real(self.D(r_in, mk.get("d_real")))
+            if h.d_extra is None:
+                loss_real.backward()
+            if d_inputs is None:
+                fake = self.G(z, mk.get("g"))
+                f_in = fake.detach()
+            loss_fake = f_fake(self.D(f_in, mk.get("d_fake")))
+            self.last_extra = None
+            if h.d_extra is None:
+                loss_fake.backward()
+            else:  # one backward over the adversarial losses and the extra term
+                extra, self.last_extra = h.d_extra(self, real, fake.detach(), r_in, f_in)
+                (loss_real + loss_fake + extra).backward()
+            self.last_gp = None
+            if self.gp_weight:  # loss += c.lambda_gp * gradient_penalty(D, noisy_real, noisy_fake), training.py:101-106 (fp32 path)
+                gp = gradient_penalty(lambda t: vit_forward(self.d, t, self.ddims), r_in, f_in, gp_epsilon)
+                (self.gp_weight * gp).backward()
+                self.last_gp = float(gp.detach())
+        if h.weights is not None:
+            h.weights.project(self.d)
         if self.clip_d is not None:
             torch.nn.utils.clip_grad_norm_(list(self.d.values()), max_norm=self.clip_d)
         self.opt_d.step()
+        if h.weights is not None:
+            h.weights.remeasure(self.d)
         for p in self.g.values():
             p.grad = None
-        loss_g = g_loss(self.D(fake, mk.get("d_gen")), self.loss)
-        total_g = loss_g + self.diversity_weight * diversity_loss(fake) if self.diversity_weight else loss_g
-        total_g.backward()
+        with scaled():
+            loss_g = f_gen(self.D(fake if h.g_input is None else h.g_input(fake), mk.get("d_gen")))
+            total_g = loss_g + self.diversity_weight * diversity_loss(fake) if self.diversity_weight else loss_g
+            total_g.backward()
         if self.clip_g is not None:
             torch.nn.utils.clip_grad_norm_(list(self.g.values()), max_norm=self.clip_g)
         self.opt_g.step()

@@ -1,4 +1,6 @@
 """Helpers for the -m gpu parity tests: raw C-ABI calls on torch device tensors."""
+import ctypes
+
 import torch
 
 import vit_gan_amd  # noqa: F401
@@ -22,6 +24,44 @@ def rbf(t):
 
 def sync():
     torch.cuda.synchronize()
+
+
+def off(t, elems):
+    """the address of element ``elems`` of ``t``"""
+    return ctypes.c_void_p(t.data_ptr() + t.element_size() * elems)
+
+
+GUARD, MARK = 64, -777.25  # elements in front of and behind a guarded buffer's body, and what they hold
+
+
+def guard_mark(dtype):
+    """the guard pattern as ``dtype`` holds it (bf16 rounds it, int32 truncates it)"""
+    return torch.tensor(MARK).to(dtype).item()
+
+
+def guarded(n, fill, dtype=torch.float32):
+    """a [GUARD | n | GUARD] device buffer: the guards hold a recognisable pattern, the body ``fill`` (a value or a tensor); a kernel is
+    handed ``off(buf, GUARD)``"""
+    buf = torch.full((n + 2 * GUARD,), guard_mark(dtype), dtype=dtype, device="cuda")
+    buf[GUARD:GUARD + n] = fill if not torch.is_tensor(fill) else fill.reshape(-1).to(dtype).cuda()
+    return buf
+
+
+def assert_intact(buf, what):
+    m = guard_mark(buf.dtype)
+    assert bool((buf[:GUARD] == m).all()) and bool((buf[-GUARD:] == m).all()), f"{what}: a guard element was written"
+
+
+def adamw_state(n, seed):
+    """(p, m, v, g, generator) with per-element edges: gradients of exactly 0 (eps dominates), ~1e-6, ~1 and ~1e3; moments carried over
+    from earlier steps (some zero); |p| from 1e-4 to 10.  The generator is handed back for what a caller draws on top (an average)."""
+    gen = torch.Generator().manual_seed(seed)
+    p = torch.sign(torch.randn(n, generator=gen)) * 10.0 ** (torch.rand(n, generator=gen) * 5 - 4)
+    g = torch.randn(n, generator=gen) * torch.tensor([0.0, 1e-6, 1.0, 1e3])[torch.arange(n) % 4]
+    h = torch.tensor([1.0, 1e-6, 1e3, 0.0])[torch.randperm(n, generator=gen) % 4]
+    m = torch.randn(n, generator=gen) * h * 0.3
+    v = (torch.randn(n, generator=gen) * h) ** 2
+    return p, m, v, g, gen
 
 
 def dropout_mask(shape, p, seed, site, step=None):

@@ -11,6 +11,7 @@ import pytest
 
 import ada_ref as ar
 import diffaug_ref as dr
+import engine_util as eu
 import vit_gan_amd  # noqa: F401
 from vit_gan_amd import _lib
 
@@ -274,40 +275,25 @@ def test_trainer_refuses_bad_arguments_without_a_device():
         tm(diffaug="color", ada_target=0.6, loss="wasserstein")
 
 
-def _group_worker(port, out):
+def _group_worker(rank, world):
     import torch.distributed as dist
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=0, world_size=1)
-    try:
-        import vit_gan_amd  # noqa: F401
-        from vit_gan_amd.engine import GanEngine
-        D, G = _nets()
-        res = []
-        for kw in (dict(ada_target=0.6, exchange_single_rank=True), dict(aug_p=0.5, exchange_single_rank=True)):
-            try:
-                GanEngine(D, G, batch=4, diffaug="color", process_group=dist.group.WORLD, **kw)
-                res.append("built")
-            except Exception as e:
-                res.append(f"{type(e).__name__}: {e}")
-        out.put(res)
-    finally:
-        dist.destroy_process_group()
+    import vit_gan_amd  # noqa: F401
+    from vit_gan_amd.engine import GanEngine
+    D, G = _nets()
+    res = []
+    for kw in (dict(ada_target=0.6, exchange_single_rank=True), dict(aug_p=0.5, exchange_single_rank=True)):
+        try:
+            GanEngine(D, G, batch=4, diffaug="color", process_group=dist.group.WORLD, **kw)
+            res.append("built")
+        except Exception as e:
+            res.append(f"{type(e).__name__}: {e}")
+    return res
 
 
 def test_engine_refuses_ada_with_an_active_process_group():
     """the controller's statistics are per process: refused where the exchange is active (a one-rank group that runs the exchange
     stands in for more ranks); a fixed aug_p gets as far as the device check"""
-    import socket
-    import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    out = ctx.Queue()
-    pr = ctx.Process(target=_group_worker, args=(port, out))
-    pr.start()
-    res = out.get(timeout=120)
-    pr.join(timeout=60)
+    (res,) = eu.run_ranks(_group_worker, 1, 120)
     assert res[0].startswith("ValueError") and "data parallelism" in res[0], res
     assert res[1].startswith("RuntimeError") and ("cuda" in res[1] or "MI355X" in res[1]), res
 

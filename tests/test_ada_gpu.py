@@ -4,7 +4,6 @@ restatement, and the engine with a fixed and with an adapted probability: trajec
 must stay what they were.
 
 No tolerance anywhere but one: r_last is one fp32 division (1 ulp)."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -12,21 +11,13 @@ import torch
 
 import ada_ref as ar
 import diffaug_ref as dr
+import engine_util as eu
+import gpu_util as u
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 GEOMETRIES = [(7, 3, 32), (5, 1, 32), (5, 3, 36), (5, 8, 9)]  # B, C, IH; 8 x 9 x 9: planes of 81 elements, the 2-byte access path
 POLICY = "color,translation,cutout"
-
-
-def _lib():
-    import vit_gan_amd  # noqa: F401
-    from vit_gan_amd import _lib as L
-    return L
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _images(B, Cc, IH, seed):
@@ -44,26 +35,23 @@ def _prob(v):
 
 def _fwd(x, policy, seed, site, step, prob=None):
     """(y, params) of vg_diffaug_fwd, or of vg_diffaug_p_fwd when ``prob`` (a device tensor) is given; no synchronisation"""
-    L = _lib()
     B, Cc, IH, _ = x.shape
     y = torch.full_like(x, float("nan"))
     params = torch.full((B, 8), float("nan"), dtype=torch.float32, device=x.device)
     if prob is None:
-        L.check(L.lib().vg_diffaug_fwd(_p(x), _p(y), _p(params), B, Cc, IH, policy, seed, site, _p(step), None), "vg_diffaug_fwd")
+        u.call("vg_diffaug_fwd", u.ptr(x), u.ptr(y), u.ptr(params), B, Cc, IH, policy, seed, site, u.ptr(step), None)
     else:
-        L.check(L.lib().vg_diffaug_p_fwd(_p(x), _p(y), _p(params), B, Cc, IH, policy, seed, site, _p(step), _p(prob), None), "vg_diffaug_p_fwd")
+        u.call("vg_diffaug_p_fwd", u.ptr(x), u.ptr(y), u.ptr(params), B, Cc, IH, policy, seed, site, u.ptr(step), u.ptr(prob), None)
     return y, params
 
 
 def _bwd(dy, policy, seed, site, step, prob=None, into=None):
-    L = _lib()
     B, Cc, IH, _ = dy.shape
     dx = torch.full_like(dy, float("nan")) if into is None else into.clone()
     if prob is None:
-        L.check(L.lib().vg_diffaug_bwd(_p(dy), _p(dx), int(into is not None), B, Cc, IH, policy, seed, site, _p(step), None), "vg_diffaug_bwd")
+        u.call("vg_diffaug_bwd", u.ptr(dy), u.ptr(dx), int(into is not None), B, Cc, IH, policy, seed, site, u.ptr(step), None)
     else:
-        L.check(L.lib().vg_diffaug_p_bwd(_p(dy), _p(dx), int(into is not None), B, Cc, IH, policy, seed, site, _p(step), _p(prob), None),
-                "vg_diffaug_p_bwd")
+        u.call("vg_diffaug_p_bwd", u.ptr(dy), u.ptr(dx), int(into is not None), B, Cc, IH, policy, seed, site, u.ptr(step), u.ptr(prob), None)
     return dx
 
 
@@ -141,15 +129,14 @@ def test_p_half_seeds_sites_counters(B):
 
 def test_captured_launch_follows_the_device_probability():
     """ONE captured launch; prob_dev is rewritten between the replays and the effective policies follow it"""
-    L = _lib()
     B, Cc, IH = 64, 3, 32
     x = _images(B, Cc, IH, 10)
     y, params = torch.empty_like(x), torch.zeros(B, 8, dtype=torch.float32, device="cuda")
     step, prob = _step(5), _prob(0.0)
 
     def launch():
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        L.check(L.lib().vg_diffaug_p_fwd(_p(x), _p(y), _p(params), B, Cc, IH, 7, 77, 0, _p(step), _p(prob), st), "vg_diffaug_p_fwd")
+        st = u.stream()
+        u.call("vg_diffaug_p_fwd", u.ptr(x), u.ptr(y), u.ptr(params), B, Cc, IH, 7, 77, 0, u.ptr(step), u.ptr(prob), st)
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s):
@@ -181,7 +168,6 @@ def _ulp_apart(a, b):
 
 @pytest.mark.parametrize("n", [1, 7, 256, 1000])
 def test_controller_kernel_equals_the_restatement(n):
-    L = _lib()
     rng = np.random.default_rng(n)
     special = np.array([0.0, -0.0, np.inf, -np.inf, np.nan], dtype=np.float32)
     target, spi, interval = np.float32(0.6), np.float32(1.0 / 4096), 4
@@ -195,7 +181,7 @@ def test_controller_kernel_equals_the_restatement(n):
             if trial == 0:
                 st0[0] = np.float32([0.0, 1.0, 0.999, 0.001, 0.5, 0.25][cases % 6])  # the clamps from both sides
             state, logits, step = torch.from_numpy(st0.copy()).cuda(), torch.from_numpy(lg).cuda(), _step(stepv)
-            L.check(L.lib().vg_ada_update(_p(logits), n, _p(state), float(target), float(spi), interval, _p(step), None), "vg_ada_update")
+            u.call("vg_ada_update", u.ptr(logits), n, u.ptr(state), float(target), float(spi), interval, u.ptr(step), None)
             got, want = state.cpu().numpy(), ar.controller(st0, lg, target, spi, interval, stepv)
             assert np.array_equal(got[:3].view(np.int32), want[:3].view(np.int32)), (n, trial, stepv, st0, got, want)
             assert _ulp_apart(got[3], want[3]), (n, trial, stepv, got, want)
@@ -208,7 +194,7 @@ def test_controller_kernel_equals_the_restatement(n):
     st0 = np.array([0.5, 0, 0, 0], dtype=np.float32)
     lg = np.array([1.0] * 4 + [-1.0], dtype=np.float32)  # acc_sign 3, acc_count 5, target 0.6f: fl(0.6f * 5) = 3 exactly
     state = torch.from_numpy(st0.copy()).cuda()
-    L.check(L.lib().vg_ada_update(_p(torch.from_numpy(lg).cuda()), 5, _p(state), float(target), float(spi), 1, _p(_step(1)), None), "vg_ada_update")
+    u.call("vg_ada_update", u.ptr(torch.from_numpy(lg).cuda()), 5, u.ptr(state), float(target), float(spi), 1, u.ptr(_step(1)), None)
     want = ar.controller(st0, lg, target, spi, 1, 1)
     assert want[0] == np.float32(0.5) and np.array_equal(state.cpu().numpy()[:3], want[:3])
 
@@ -235,8 +221,7 @@ def _steps(eng, n, B, first=0, each=None):
 
 
 def _engine(**kw):
-    from test_engine_gpu import _bench_like
-    return _bench_like(B_ENG, **kw)
+    return eu.bench_like(B_ENG, **kw)
 
 
 def test_engine_trajectory_is_the_restatement():

@@ -13,48 +13,31 @@ import torch
 
 import bcr_ref as br
 import diffaug_ref as dr
+import engine_util as eu
+import gpu_util as u
+from gpu_util import GUARD
 from second_order_ref import assert_elementwise
 from test_bcr_cpu import SCALES, SIZES, W_FAKE, W_REAL, check, logits
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
-GUARD = 64  # floats in front of and behind every output
 PARTNER = "translation,cutout"
 POLICY = "color,translation,cutout"
 
 
-def _lib():
-    import vit_gan_amd  # noqa: F401
-    from vit_gan_amd import _lib as L
-    return L
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _guarded(n, fill):
-    """a [GUARD | n | GUARD] buffer: the guards hold a recognisable pattern, the body ``fill`` (a value or a tensor)"""
-    buf = torch.full((n + 2 * GUARD,), -777.25, dtype=torch.float32, device="cuda")
-    buf[GUARD:GUARD + n] = fill if not torch.is_tensor(fill) else fill.reshape(-1).cuda()
-    return buf
-
-
 def _launch(lx, la, n_real, w_real, w_fake, grad_scale=1.0, into_x=None, into_a=None):
     """one vg_bcr_loss launch on guarded buffers; overwrite targets start as NaN.  Returns cpu (loss [2], gx, ga)."""
-    L = _lib()
     n, Kc = lx.shape
     lxd, lad = lx.contiguous().cuda(), la.contiguous().cuda()
     nan = float("nan")
-    dx = _guarded(n * Kc, nan if into_x is None else into_x)
-    da = _guarded(n * Kc, nan if into_a is None else into_a)
-    out = _guarded(2, nan)
-    off = lambda t: C.c_void_p(t.data_ptr() + 4 * GUARD)  # noqa: E731
-    L.check(L.lib().vg_bcr_loss(_p(lxd), _p(lad), off(dx), off(da), off(out), n_real, n - n_real, Kc, w_real, w_fake, int(into_x is not None),
-                                int(into_a is not None), grad_scale, None), "vg_bcr_loss")
+    dx = u.guarded(n * Kc, nan if into_x is None else into_x)
+    da = u.guarded(n * Kc, nan if into_a is None else into_a)
+    out = u.guarded(2, nan)
+    u.call("vg_bcr_loss", u.ptr(lxd), u.ptr(lad), u.off(dx, GUARD), u.off(da, GUARD), u.off(out, GUARD), n_real, n - n_real, Kc, w_real, w_fake,
+           int(into_x is not None), int(into_a is not None), grad_scale, None)
     torch.cuda.synchronize()
     for name, t in (("dlog_x", dx), ("dlog_a", da), ("loss_out", out)):
-        assert bool((t[:GUARD] == -777.25).all()) and bool((t[-GUARD:] == -777.25).all()), f"{name}: a guard element was written"
+        u.assert_intact(t, name)
     body = lambda t, m: t[GUARD:GUARD + m].cpu()  # noqa: E731
     return body(out, 2), body(dx, n * Kc).view(n, Kc), body(da, n * Kc).view(n, Kc)
 
@@ -129,7 +112,7 @@ def test_4b_forward_at_c2_equals_two_2b_forwards():
     import vit_gan_amd  # noqa: F401
     from vit_gan_amd.config import Config
     from vit_gan_amd.modules import ViTDiscriminator
-    L = _lib()
+    from vit_gan_amd import _lib as L
     B = 256
     torch.manual_seed(0)
     D = ViTDiscriminator(Config(embeddings_dimension=384, classes_count=1, dropout_rate=0.0, batch_size=B)).cuda()
@@ -145,11 +128,10 @@ def test_4b_forward_at_c2_equals_two_2b_forwards():
     for dense in (0, 1):
         net = L.VgVitNet(d, fd.flat.data_ptr(), fd.shadow.data_ptr(), fd.grad.data_ptr(), 0.0, 5, step.data_ptr(), None, 0, dense)
         whole = torch.full((4 * B, d.Kc), float("nan"), dtype=torch.float32, device="cuda")
-        L.check(L.lib().vg_vit_forward(C.byref(net), 4 * B, _p(imgs), 1, _p(ws), _p(whole), None), "vg_vit_forward")
+        u.call("vg_vit_forward", C.byref(net), 4 * B, u.ptr(imgs), 1, u.ptr(ws), u.ptr(whole), None)
         halves = torch.full((4 * B, d.Kc), float("nan"), dtype=torch.float32, device="cuda")
         for h in range(2):
-            L.check(L.lib().vg_vit_forward(C.byref(net), 2 * B, _p(imgs[2 * B * h:]), 1, _p(ws), C.c_void_p(halves.data_ptr() + 4 * 2 * B * d.Kc * h),
-                                           None), "vg_vit_forward")
+            u.call("vg_vit_forward", C.byref(net), 2 * B, u.ptr(imgs[2 * B * h:]), 1, u.ptr(ws), u.off(halves, 2 * B * d.Kc * h), None)
         torch.cuda.synchronize()
         assert bool(torch.isfinite(whole).all()) and float(whole.std()) > 0
         assert torch.equal(whole.view(torch.int32), halves.view(torch.int32)), f"dense_top {dense}"
@@ -157,44 +139,19 @@ def test_4b_forward_at_c2_equals_two_2b_forwards():
 
 
 # ------------------------------------------------------------------------------------------------------------- the engine
-def _reference_step(oracle, real, z, bcr_w, params_d, params_g, params_c, gp_epsilon=None):
-    """The bCR step from the step oracle's public pieces (GanStepOracle.D / .G, the loss functions, gradient_penalty), the float64
-    augmentation fed the engine's own parameters and bcr_ref's formula: the adversarial losses and the penalty on T_1(x) (diffaug) or x,
-    the consistency loss between D(x) and D(T x) with gradient through both."""
-    from oracle import step_oracle as so
-    from oracle.vit_oracle import vit_forward
-    B = real.shape[0]
-    for p in oracle.d.values():
-        p.grad = None
-    fake = oracle.G(z)
-    x = torch.cat([real, fake.detach()])
-    if params_d is not None:
-        t = dr.augment(x, params_d)[0].float()
-        adv = t
-    else:
-        t = dr.augment(x, params_c)[0].float()
-        adv = x
-    loss_real = so.d_loss_real(oracle.D(adv[:B]), oracle.loss)
-    loss_fake = so.d_loss_fake(oracle.D(adv[B:]), oracle.loss)
-    lx = torch.cat([oracle.D(x[:B]).reshape(B, -1), oracle.D(x[B:]).reshape(B, -1)])
-    la = torch.cat([oracle.D(t[:B]).reshape(B, -1), oracle.D(t[B:]).reshape(B, -1)])
-    cr, parts = br.autograd_consistency(lx, la, B, *bcr_w)
-    (loss_real + loss_fake + cr).backward()
-    gp = None
-    if oracle.gp_weight:
-        gp = so.gradient_penalty(lambda v: vit_forward(oracle.d, v, oracle.ddims), adv[:B], adv[B:], gp_epsilon)
-        (oracle.gp_weight * gp).backward()
-    if oracle.clip_d is not None:
-        torch.nn.utils.clip_grad_norm_(list(oracle.d.values()), max_norm=oracle.clip_d)
-    oracle.opt_d.step()
-    for p in oracle.g.values():
-        p.grad = None
-    g_in = fake if params_g is None else dr.augment(fake, params_g)[0].float()
-    loss_g = so.g_loss(oracle.D(g_in), oracle.loss)
-    loss_g.backward()
-    oracle.opt_g.step()
-    return {"d_real": float(loss_real.detach()), "d_fake": float(loss_fake.detach()), "g": float(loss_g.detach()),
-            "gp": None if gp is None else float(gp.detach()), "cr": [float(p.detach()) for p in parts]}
+def _bcr_hooks(bcr_w, params_d, params_g, params_c):
+    """StepHooks of the bCR step: the float64 augmentation fed the engine's own parameters and bcr_ref's formula - the adversarial losses
+    and the penalty on T_1(x) (diffaug) or x, the consistency loss between D(x) and D(T x) with gradient through both"""
+    from oracle.step_oracle import StepHooks
+
+    def consistency(oracle, real, fake, real_in, fake_in):
+        n = real.shape[0]
+        t_real, t_fake = (real_in, fake_in) if params_d is not None else dr.augment(torch.cat([real, fake]), params_c)[0].float().split(n)
+        lx = torch.cat([oracle.D(real).reshape(n, -1), oracle.D(fake).reshape(n, -1)])
+        la = torch.cat([oracle.D(t_real).reshape(n, -1), oracle.D(t_fake).reshape(n, -1)])
+        return br.autograd_consistency(lx, la, n, *bcr_w)
+    return StepHooks(d_inputs=None if params_d is None else (lambda real, fake: dr.augment(torch.cat([real, fake]), params_d)[0].float().split(real.shape[0])),
+                     g_input=None if params_g is None else (lambda fake: dr.augment(fake, params_g)[0].float()), d_extra=consistency)
 
 
 @pytest.mark.parametrize("gp", [False, True], ids=["ns", "wasserstein_gp"])
@@ -203,12 +160,11 @@ def test_bcr_engine_step_matches_the_reference_step(diffaug, gp):
     """adversarial losses, the penalty and the first AdamW update at the tolerances of
     test_diffaug_gpu.test_augmented_engine_step_matches_the_reference_step; the consistency losses against bcr_ref on the engine's own
     logits inside the operator bound"""
-    from test_engine_gpu import _build
     from vit_gan_amd.engine import GanEngine
     B = 8
     bcr_w = (W_REAL, W_FAKE)
     loss = "wasserstein" if gp else "ns"
-    D, G, oracle = _build(B, loss)
+    D, G, oracle = eu.build(B, loss)
     kw = dict(diffaug=POLICY) if diffaug else dict(bcr_aug=PARTNER)
     if gp:
         oracle.gp_weight, oracle.clip_d = 10.0, 5.0
@@ -240,151 +196,89 @@ def test_bcr_engine_step_matches_the_reference_step(diffaug, gp):
     ref_cr = br.consistency(lg[:2 * B], lg[2 * B:], B, *bcr_w)
     assert_elementwise(eng.bcr_losses, ref_cr["loss"], ref_cr["loss_mag"], br.kappa_losses(2 * B, B, 1), "bcr_losses", rel=0.0)
     assert float(eng.bcr_losses.min()) > 0
-    ref = _reference_step(oracle, real.to(BF).float(), z, bcr_w, pd, pg, pc, eps if gp else None)
+    ref = oracle.step(real.to(BF).float(), z, gp_epsilon=eps if gp else None, hooks=_bcr_hooks(bcr_w, pd, pg, pc))
     got = losses.cpu().tolist()
-    print(f"bCR step (diffaug {diffaug}, gp {gp}): engine {got} cr {eng.bcr_losses.tolist()} gp {float(eng.gp_loss):.5f}; reference {ref}")
-    for v, k in zip(got, ("d_real", "d_fake", "g")):
-        assert abs(v - ref[k]) < 2e-2, (k, got, ref)
+    print(f"bCR step (diffaug {diffaug}, gp {gp}): engine {got} cr {eng.bcr_losses.tolist()} gp {float(eng.gp_loss):.5f}; reference {ref} "
+          f"cr {[float(p.detach()) for p in oracle.last_extra]} gp {oracle.last_gp}")
+    eu.assert_losses_match(got, ref, 2e-2)
     if gp:
-        assert abs(float(eng.gp_loss) - ref["gp"]) < 0.03 * abs(ref["gp"]) + 1e-3
-    k = "vit.encoder.1.fc2.weight"
-    upd, ref_upd = D.state_dict()[k].detach().cpu() - w0[k], oracle.d[k].detach() - w0[k]
-    assert float((upd - ref_upd).abs().max()) < 1.1e-3 and float(((upd - ref_upd).abs() < 1e-4).float().mean()) > 0.9
+        eu.assert_penalty_matches(float(eng.gp_loss), oracle.last_gp, 0.03, 1e-3)
+    eu.assert_first_update_matches(D, w0, oracle, "vit.encoder.1.fc2.weight", 1.1e-3, 1e-4, 0.9)
 
 
-def _steps(eng, n, B, data_seed=4, first=0):
-    g = torch.Generator().manual_seed(data_seed)
-    data = [((torch.rand(B, 3, 32, 32, generator=g) * 2 - 1).cuda(), torch.randn(B, 1024, generator=g).cuda()) for _ in range(first + n)]
-    losses, cr, params = [], [], []
-    for real, z in data[first:]:
-        losses.append(eng.step(real, z).clone())
-        if eng.bcr:
-            cr.append(eng.bcr_losses.clone())
-            params.append(eng.aug_params["c" if eng.bcr_policy else "d"].cpu().clone())
-    torch.cuda.synchronize()
-    return (torch.stack(losses).cpu(), torch.stack(cr).cpu() if cr else None, [t.detach().clone().cpu() for t in eng._state_tensors()], params)
+def _extras(eng):
+    """what a bCR run records per step: the two consistency losses and the partner's parameters"""
+    return ["bcr_losses", ("params", lambda e: e.aug_params["c" if e.bcr_policy else "d"])] if eng is None or eng.bcr else []
 
 
-def _same(a, b, what):
-    assert torch.equal(a[0], b[0]), (what, a[0], b[0])
-    assert (a[1] is None and b[1] is None) or torch.equal(a[1], b[1]), (what, a[1], b[1])
-    for i, (u, v) in enumerate(zip(a[2], b[2])):
-        assert torch.equal(u, v), f"{what}: state tensor {i}"
+def _steps(eng, n, B, first=0):
+    return eu.run_steps(eng, eu.batches(B, n, skip=first), extras=_extras(eng))
 
 
 def _graph_against_eager(**extra):
-    """three replays of the captured bCR step against three eager steps: (problems, graph_active, graph_fallback_reason)"""
-    from test_engine_gpu import _bench_like
+    """three replays of the captured bCR step against three eager steps"""
     B, n = 4, 3
-    runs, problems = {}, []
-    for name, use_graph in (("eager", False), ("graph", True)):
-        eng, D, G, _ = _bench_like(B, use_graph=use_graph, bcr=(W_REAL, W_FAKE), bcr_aug=PARTNER, **extra)
+
+    def make(use_graph):
+        eng, D, G, _ = eu.bench_like(B, use_graph=use_graph, bcr=(W_REAL, W_FAKE), bcr_aug=PARTNER, **extra)
         if eng.gp_w:  # a fixed epsilon: torch.rand's stream differs between a captured and an eager step
             eng.gp_epsilon = torch.rand(B, 1, 1, 1, generator=torch.Generator().manual_seed(2)).cuda()
-        runs[name] = _steps(eng, n, B)
-        active, reason = eng.graph_active, eng.graph_fallback_reason
-        if active != use_graph or reason is not None or int(eng.step_t) != n:
-            problems.append(f"{name}: graph_active {active}, fallback {reason!r}, step counter {int(eng.step_t)}")
-        seen = runs[name][3]
+        return eng
+    runs, engines = eu.graph_against_eager(make, eu.batches(B, n), extras=_extras(None))
+    for name, run in runs.items():
+        seen = run.extras["params"]
         for i in range(n):  # every replay draws the site-2 parameters of its own counter value, and they move
-            if not np.array_equal(seen[i].numpy(), dr.draw(eng._aug_seed, 2, i + 1, 2 * B, 32, 6)):
-                problems.append(f"{name}: site-2 parameters of step {i + 1}")
-        if torch.equal(seen[0], seen[1]) or torch.equal(seen[1], seen[2]):
-            problems.append(f"{name}: site-2 parameters do not move")
-        eng.close()
-    e, g = runs["eager"], runs["graph"]
-    if not (torch.isfinite(e[0]).all() and torch.isfinite(e[1]).all() and float(e[1].min()) > 0):
-        problems.append(f"eager losses {e[0]} consistency {e[1]}")
-    if not torch.equal(g[0], e[0]):
-        problems.append(f"losses: graph {g[0]} eager {e[0]}")
-    if not torch.equal(g[1], e[1]):
-        problems.append(f"bcr_losses: graph {g[1]} eager {e[1]}")
-    problems += [f"state tensor {i}" for i, (u, v) in enumerate(zip(g[2], e[2])) if not torch.equal(u, v)]
-    return problems, active, reason
+            assert np.array_equal(seen[i].numpy(), dr.draw(engines[name]._aug_seed, 2, i + 1, 2 * B, 32, 6)), f"{name}: site-2 parameters of step {i + 1}"
+        assert not torch.equal(seen[0], seen[1]) and not torch.equal(seen[1], seen[2]), f"{name}: site-2 parameters do not move"
+        engines[name].close()
+    e, cr = runs["eager"], torch.stack(runs["eager"].extras["bcr_losses"])
+    assert torch.isfinite(e.losses).all() and torch.isfinite(cr).all() and float(cr.min()) > 0, (e.losses, cr)
+    return engines["graph"].graph_active, engines["graph"].graph_fallback_reason
 
 
 def test_bcr_graph_replay_equals_eager():
-    problems, active, reason = _graph_against_eager()
-    assert not problems and active and reason is None, (problems, active, reason)
+    active, reason = _graph_against_eager()
+    assert active and reason is None, (active, reason)
 
 
-def _rccl_worker(port, out):
-    import os, sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path[:0] = [os.path.dirname(here), here]
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    import torch.distributed as dist
-    try:
-        torch.cuda.set_device(0)
-        dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-        import vit_gan_amd  # noqa: F401
-        out.put(("ok", _graph_against_eager(spectral_norm="all", ema_decay=0.999, gp_weight=10.0, exchange_single_rank=True, loss="wasserstein",
-                                            clip_d=5.0)))
-        dist.destroy_process_group()
-    except Exception as e:
-        import traceback
-        out.put(("err", f"{type(e).__name__}: {e}\n{traceback.format_exc()[-1500:]}"))
+def _rccl_worker(rank, world):
+    import vit_gan_amd  # noqa: F401
+    return _graph_against_eager(spectral_norm="all", ema_decay=0.999, gp_weight=10.0, exchange_single_rank=True, loss="wasserstein", clip_d=5.0)
 
 
 @pytest.mark.timeout(300)
 def test_bcr_graph_replay_with_spectral_ema_penalty_and_exchange():
     """the same with spectral_norm="all", ema_decay, gp_weight=10 and the staged backward with its all-reduces on a one-rank RCCL group,
     all together (the group needs a process of its own, as in test_spectral_gpu)"""
-    import socket
-    import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    out = ctx.Queue()
-    p = ctx.Process(target=_rccl_worker, args=(port, out))
-    p.start()
-    status, val = out.get(timeout=240)
-    p.join(timeout=60)
-    assert status == "ok", val
-    problems, active, reason = val
-    assert not problems and active and reason is None, val
+    ((active, reason),) = eu.run_ranks(_rccl_worker, 1, 240, backend="nccl", gpu=True)
+    assert active and reason is None, (active, reason)
 
 
 def test_off_is_off_and_on_changes_the_trajectory():
-    from test_engine_gpu import _bench_like
     B, n = 4, 2
-    plain, _, _, _ = _bench_like(B, diffaug=POLICY)
-    off, _, _, _ = _bench_like(B, diffaug=POLICY, bcr=(0, 0))
+    plain, _, _, _ = eu.bench_like(B, diffaug=POLICY)
+    off, _, _, _ = eu.bench_like(B, diffaug=POLICY, bcr=(0, 0))
     assert not off.bcr and not hasattr(off, "imgs4") and not hasattr(off, "bcr_losses") and not hasattr(off, "logits_g")
     assert off.logits.shape[0] == 2 * B and off.ws_d.numel() == plain.ws_d.numel() and "bcr" not in off.state_dict()
     a, b = _steps(plain, n, B), _steps(off, n, B)
-    _same(a, b, "bcr=(0, 0)")
-    on, _, _, _ = _bench_like(B, diffaug=POLICY, bcr=(10, 10))
+    eu.assert_same_run(a, b, "bcr=(0, 0)")
+    on, _, _, _ = eu.bench_like(B, diffaug=POLICY, bcr=(10, 10))
     assert on.logits.shape[0] == 4 * B and on.ws_d.numel() > plain.ws_d.numel()
     c = _steps(on, n, B)
-    assert torch.isfinite(c[0]).all() and not torch.equal(c[2][0], a[2][0])
+    assert torch.isfinite(c.losses).all() and not torch.equal(c.state[0], a.state[0])
 
 
 def test_resume_equals_the_uninterrupted_run():
-    from test_engine_gpu import _bench_like
     B = 4
     kw = dict(diffaug=POLICY, bcr=(W_REAL, W_FAKE), instance_noise=0.0)
-    eng, _, _, _ = _bench_like(B, **kw)
-    whole = _steps(eng, 4, B)
-    eng.close()
-    a, D1, G1, _ = _bench_like(B, **kw)
-    first = _steps(a, 2, B)
-    nets, st = (D1.state_dict(), G1.state_dict()), a.state_dict()
+    _, _, _, st, made = eu.resume_against_whole(lambda **net: eu.bench_like(B, **net, **kw), eu.batches(B, 4), 2, extras=_extras(None))
     assert tuple(st["bcr"]) == (W_REAL, W_FAKE, 0)
-    a.close()
-    b, D2, G2, _ = _bench_like(B, seed=99, **kw)  # other initial weights: everything comes from the saved state
-    D2.load_state_dict(nets[0]), G2.load_state_dict(nets[1])
-    b.load_state_dict(st)
-    second = _steps(b, 2, B, first=2)
-    assert torch.equal(torch.cat([first[0], second[0]]), whole[0]) and torch.equal(torch.cat([first[1], second[1]]), whole[1])
-    for i, (x, y) in enumerate(zip(second[2], whole[2])):
-        assert torch.equal(x, y), f"state tensor {i}"
+    b = made[2][0]
     # a state saved with other weights (or without bCR) is refused under strict, and loads without it: bCR holds no state
     for other in ((1.0, W_FAKE, 0), None):
         with pytest.raises(ValueError, match="consistency regularisation"):
             b.load_state_dict({**st, "bcr": other})
     b.load_state_dict({**st, "bcr": (1.0, 1.0, 0)}, strict=False)
-    off, _, _, _ = _bench_like(B, diffaug=POLICY)
+    off, _, _, _ = eu.bench_like(B, diffaug=POLICY)
     with pytest.raises(ValueError, match="consistency regularisation"):
         off.load_state_dict({**off.state_dict(), "bcr": st["bcr"]})

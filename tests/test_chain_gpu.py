@@ -12,15 +12,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import gpu_util as u
+
 pytestmark = pytest.mark.gpu
 
 BF_TOL = 2.0 ** -7
 E, HID = 384, 768
-
-
-def _u():
-    import gpu_util
-    return gpu_util
 
 
 def _mask(u, M, p, seed, site):
@@ -48,7 +45,6 @@ MLP_SHAPES = [16, 48, 128, 144, 2080, 4160, 16640, 33280, 66560]
 @pytest.mark.parametrize("M", MLP_SHAPES)
 @pytest.mark.parametrize("drop", [0.0, 0.1])
 def test_encoder_mlp_fwd(M, drop):
-    u = _u()
     g = torch.Generator().manual_seed(M + 7)
     xn = u.rbf(torch.randn(M, E, generator=g))
     W1 = u.rbf(torch.randn(HID, E, generator=g) / math.sqrt(E))
@@ -103,7 +99,6 @@ def test_encoder_mlp_fwd(M, drop):
 
 def test_encoder_mlp_fwd_rows_do_not_depend_on_their_tile():
     """the same 2 080 rows as a problem of their own and as the head of 33 280 rows: bit-equal"""
-    u = _u()
     g = torch.Generator().manual_seed(5)
     M1, M2 = 2080, 33280
     xn = u.rbf(torch.randn(M2, E, generator=g))
@@ -137,7 +132,6 @@ def _mask_site(u, M, p, seed, site):
 def test_encoder_post_attention_fwd(M, drop):
     """vg_encoder_post_attention_fwd: out-projection + dropout + residual, norm2, fc1, GELU, fc2 + dropout + residual and the next norm1 in one
     launch (src/v2/modules.py:179-182, :168), every stored tensor against fp32 PyTorch with bf16 roundings where the kernel stores."""
-    u = _u()
     g = torch.Generator().manual_seed(M + 11)
     ao = u.rbf(torch.randn(M, E, generator=g))
     x = u.rbf(torch.randn(M, E, generator=g))

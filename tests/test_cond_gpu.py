@@ -1,7 +1,6 @@
 """Class conditioning on the GPU: the five kernels against the off-device restatement (tests/cond_ref.py) bit for bit, the
 conditional generator against the oracle's extended-latent form, the conditional GanEngine step against a CPU reference step built
 from the step oracle's pieces, hipGraph replay against eager, every option it combines with, resume, and the trainer."""
-import ctypes as C
 import functools
 import glob
 import os
@@ -11,45 +10,14 @@ import pytest
 import torch
 
 import cond_ref as cr
+import engine_util as eu
+import gpu_util as u
+from gpu_util import GUARD
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
-GUARD = 64  # elements in front of and behind every output
-MARK = -777.25
 SEED = 0x1234ABCD5678EF01
 K3 = 3
-
-
-def _lib():
-    import vit_gan_amd  # noqa: F401
-    from vit_gan_amd import _lib as L
-    return L
-
-
-def _call(name, *args):
-    L = _lib()
-    L.check(getattr(L.lib(), name)(*args), name)
-
-
-def _p(t, off=0):
-    return None if t is None else C.c_void_p(t.data_ptr() + off * t.element_size())
-
-
-def _mark(dtype):
-    """the guard pattern as ``dtype`` holds it (bf16 rounds it, int32 truncates it)"""
-    return torch.tensor(MARK).to(dtype).item()
-
-
-def _guarded(n, fill, dtype=torch.float32):
-    """a [GUARD | n | GUARD] buffer: the guards hold a recognisable pattern, the body ``fill`` (a value or a tensor)"""
-    buf = torch.full((n + 2 * GUARD,), _mark(dtype), dtype=dtype, device="cuda")
-    buf[GUARD:GUARD + n] = fill if not torch.is_tensor(fill) else fill.reshape(-1).to(dtype).cuda()
-    return buf
-
-
-def _intact(buf, what):
-    m = _mark(buf.dtype)
-    assert bool((buf[:GUARD] == m).all()) and bool((buf[-GUARD:] == m).all()), f"{what}: a guard element was written"
 
 
 def _i32(t):
@@ -62,10 +30,10 @@ def test_draw_labels_equals_the_restatement(K):
     from vit_gan_amd import ops
     step = torch.tensor([5], dtype=torch.int32, device="cuda")
     for n in (1, 67, 1024):
-        buf = _guarded(n, -1, torch.int32)
-        _call("vg_draw_labels", _p(buf, GUARD), n, K, SEED, 3, _p(step), None)
+        buf = u.guarded(n, -1, torch.int32)
+        u.call("vg_draw_labels", u.off(buf, GUARD), n, K, SEED, 3, u.ptr(step), None)
         torch.cuda.synchronize()
-        _intact(buf, "labels")
+        u.assert_intact(buf, "labels")
         assert np.array_equal(buf[GUARD:GUARD + n].cpu().numpy(), cr.draw_labels(n, K, SEED, 3, 5)), (n, K)
         assert np.array_equal(ops.draw_labels(n, K, SEED, 3, step).cpu().numpy(), cr.draw_labels(n, K, SEED, 3, 5))
         assert np.array_equal(ops.draw_labels(n, K, SEED, 2, None).cpu().numpy(), cr.draw_labels(n, K, SEED, 2, None)), "no device counter"
@@ -84,11 +52,11 @@ def test_class_add_equals_the_restatement(B, N):
     w = (torch.randn(B, N, generator=g) * 2).to(BF)
     table = (torch.rand(K3, N, generator=g) * 2 - 1).to(BF)
     for name, y in _label_sets(B, g):
-        buf = _guarded(B * N, w, BF)
+        buf = u.guarded(B * N, w, BF)
         td, yd = table.cuda(), y.to(torch.int32).cuda()
-        _call("vg_class_add", _p(buf, GUARD), _p(td), _p(yd), B, N, K3, None)
+        u.call("vg_class_add", u.off(buf, GUARD), u.ptr(td), u.ptr(yd), B, N, K3, None)
         torch.cuda.synchronize()
-        _intact(buf, "wmod")
+        u.assert_intact(buf, "wmod")
         want = cr.class_add(cr.bits_of(w), cr.bits_of(table), y.numpy())
         assert np.array_equal(cr.bits_of(buf[GUARD:GUARD + B * N]).reshape(B, N), want), (name, B, N)
         assert np.array_equal(cr.bits_of(ops.class_add(w.cuda(), td, y.cuda())), want), "ops.class_add"
@@ -106,10 +74,10 @@ def test_class_grad_equals_the_restatement(B, N):
     for name, y in _label_sets(B, g):
         yd = y.to(torch.int32).cuda()
         for accumulate in (0, 1):
-            buf = _guarded(K3 * N, float("nan") if not accumulate else old)
-            _call("vg_class_grad", _p(dwd), _p(yd), _p(buf, GUARD), B, N, K3, accumulate, None)
+            buf = u.guarded(K3 * N, float("nan") if not accumulate else old)
+            u.call("vg_class_grad", u.ptr(dwd), u.ptr(yd), u.off(buf, GUARD), B, N, K3, accumulate, None)
             torch.cuda.synchronize()
-            _intact(buf, "dtable")
+            u.assert_intact(buf, "dtable")
             got = buf[GUARD:GUARD + K3 * N].cpu().view(K3, N)
             want = cr.class_grad(dw.numpy(), y.numpy(), K3, into=old.numpy() if accumulate else None)
             assert np.array_equal(got.numpy().view(np.uint32), want.view(np.uint32)), (name, B, N, accumulate)
@@ -121,7 +89,7 @@ def test_class_grad_equals_the_restatement(B, N):
         # the rows summed over k are the column sums of dw (another order: not bitwise)
         tab = ops.class_grad(dwd, y.cuda(), K3)
         col = torch.empty(N, dtype=torch.float32, device="cuda")
-        _call("vg_colsum_f32", _p(dwd), B, N, _p(col), N, None, 0, None, 0, None, 0, 0, None)
+        u.call("vg_colsum_f32", u.ptr(dwd), B, N, u.ptr(col), N, None, 0, None, 0, None, 0, 0, None)
         torch.cuda.synchronize()
         err, scale = float((tab.double().sum(0) - col.double()).abs().max()), float(col.abs().max())
         assert err <= 1e-6 * scale, f"{name}: sum over classes {err:.3e} off the column sums, max {scale:.3e}"
@@ -133,11 +101,11 @@ def _cond_launch(lg, y, kind, role, grad_scale=1.0, selected=True):
     """one vg_gan_loss_cond launch on guarded buffers whose bodies start as NaN: cpu (loss [1], dlogits [n, Kc], selected [n])"""
     n, Kc = lg.shape
     nan = float("nan")
-    dl, sel, out = _guarded(n * Kc, nan), _guarded(n, nan), _guarded(1, nan)
-    _call("vg_gan_loss_cond", _p(lg), _p(y), _p(dl, GUARD), _p(sel, GUARD) if selected else None, _p(out, GUARD), n, Kc, kind, role, grad_scale, None)
+    dl, sel, out = u.guarded(n * Kc, nan), u.guarded(n, nan), u.guarded(1, nan)
+    u.call("vg_gan_loss_cond", u.ptr(lg), u.ptr(y), u.off(dl, GUARD), u.off(sel, GUARD) if selected else None, u.off(out, GUARD), n, Kc, kind, role, grad_scale, None)
     torch.cuda.synchronize()
     for name, t in (("dlogits", dl), ("selected", sel), ("loss_out", out)):
-        _intact(t, name)
+        u.assert_intact(t, name)
     return out[GUARD:GUARD + 1].cpu(), dl[GUARD:GUARD + n * Kc].cpu().view(n, Kc), sel[GUARD:GUARD + n].cpu()
 
 
@@ -154,7 +122,7 @@ def test_cond_loss_equals_the_plain_loss_on_the_gathered_logits(n, Kc, kind):
         for gs in (1.0, 0.5):
             loss, dl, sel = _cond_launch(lg, y, kind, role, gs)
             ref_d, ref_l = torch.full((n,), float("nan"), device="cuda"), torch.full((1,), float("nan"), device="cuda")
-            _call("vg_gan_loss", _p(s), _p(ref_d), _p(ref_l), n, kind, role, gs, None)
+            u.call("vg_gan_loss", u.ptr(s), u.ptr(ref_d), u.ptr(ref_l), n, kind, role, gs, None)
             torch.cuda.synchronize()
             assert torch.equal(_i32(loss), _i32(ref_l)), (role, gs, loss, ref_l)
             assert torch.equal(_i32(dl[picked]), _i32(ref_d)), "the selected gradients"
@@ -171,11 +139,11 @@ def test_cond_loss_equals_the_plain_loss_on_the_gathered_logits(n, Kc, kind):
     if n >= 2:
         n0 = n // 3 + 1
         nan = float("nan")
-        dl, sel, out = _guarded(n * Kc, nan), _guarded(n, nan), _guarded(2, nan)
-        _call("vg_gan_loss_cond_pair", _p(lg), _p(y), _p(dl, GUARD), _p(sel, GUARD), _p(out, GUARD), n0, 0, n - n0, 1, Kc, kind, 1.0, None)
+        dl, sel, out = u.guarded(n * Kc, nan), u.guarded(n, nan), u.guarded(2, nan)
+        u.call("vg_gan_loss_cond_pair", u.ptr(lg), u.ptr(y), u.off(dl, GUARD), u.off(sel, GUARD), u.off(out, GUARD), n0, 0, n - n0, 1, Kc, kind, 1.0, None)
         torch.cuda.synchronize()
         for name, t in (("dlogits", dl), ("selected", sel), ("loss_out", out)):
-            _intact(t, name)
+            u.assert_intact(t, name)
         a = _cond_launch(lg[:n0].contiguous(), y[:n0].contiguous(), kind, 0)
         b = _cond_launch(lg[n0:].contiguous(), y[n0:].contiguous(), kind, 1)
         assert torch.equal(_i32(out[GUARD:GUARD + 2]), _i32(torch.cat([a[0], b[0]])))
@@ -196,14 +164,14 @@ def test_labels_out_of_range_are_clamped_inside_every_kernel():
         for a, b in zip(got, want):
             assert bool(torch.isfinite(a).all()) and torch.equal(_i32(a), _i32(b))
     w, table, dw = (torch.randn(B, N, generator=g)).to(BF), torch.randn(Kc, N, generator=g).to(BF), torch.randn(B, N, generator=g)
-    buf = _guarded(B * N, w, BF)
+    buf = u.guarded(B * N, w, BF)
     td, yd, dwd = table.cuda(), bad.cuda(), dw.cuda()  # (held: a temporary's block could be handed out again before the launch)
-    _call("vg_class_add", _p(buf, GUARD), _p(td), _p(yd), B, N, Kc, None)
-    tab = _guarded(Kc * N, float("nan"))
-    _call("vg_class_grad", _p(dwd), _p(yd), _p(tab, GUARD), B, N, Kc, 0, None)
+    u.call("vg_class_add", u.off(buf, GUARD), u.ptr(td), u.ptr(yd), B, N, Kc, None)
+    tab = u.guarded(Kc * N, float("nan"))
+    u.call("vg_class_grad", u.ptr(dwd), u.ptr(yd), u.off(tab, GUARD), B, N, Kc, 0, None)
     torch.cuda.synchronize()
-    _intact(buf, "wmod")
-    _intact(tab, "dtable")
+    u.assert_intact(buf, "wmod")
+    u.assert_intact(tab, "dtable")
     assert np.array_equal(cr.bits_of(buf[GUARD:GUARD + B * N]).reshape(B, N), cr.class_add(cr.bits_of(w), cr.bits_of(table), good.numpy()))
     assert np.array_equal(tab[GUARD:GUARD + Kc * N].cpu().numpy().reshape(Kc, N), cr.class_grad(dw.numpy(), good.numpy(), Kc))
     for fn in (lambda: ops.conditional_gan_loss(lg, bad.cuda()), lambda: ops.class_add(w.cuda(), table.cuda(), bad.cuda()),
@@ -304,80 +272,46 @@ def test_zero_table_is_the_unconditional_generator_bit_for_bit():
 
 # ----------------------------------------------------------------------------------------------------------------------- engine
 B8 = 8
-G16 = dict(latent=256, image_size=16, channels=3, embed=384, heads=4, layers=2, siren_hidden=256)
+G16 = eu.COND_G
 
 
 def _nets(n_classes=K3, Kc=K3, d_drop=0.0, g_drop=0.0, seed=3):
     """D: E = 128, H = 4, L = 2, 16 x 16 images, patch 4, Kc logits; G: two SLN blocks on 16 row tokens"""
-    import vit_gan_amd  # noqa: F401
-    from vit_gan_amd.config import Config
-    from vit_gan_amd.generator import SirenGenerator
-    from vit_gan_amd.modules import ViTDiscriminator
-    torch.manual_seed(seed)
-    D = ViTDiscriminator(Config(embeddings_dimension=128, attention_heads_count=4, transformer_blocks_count=2, image_size=16, patch_size=4,
-                                classes_count=Kc, dropout_rate=d_drop, batch_size=B8))
-    G = SirenGenerator(dropout=g_drop, n_classes=n_classes, **G16)
-    return D, G
+    assert (d_drop, g_drop) in ((0.0, 0.0), (0.1, 0.2))
+    return eu.build_nets(B8, seed, dropout=d_drop > 0, cond=(n_classes, Kc))
 
 
-def _engine(n_classes=K3, Kc=K3, train=True, **kw):
+def _engine(n_classes=K3, Kc=K3, train=True, seed=3, **kw):
     from vit_gan_amd.engine import GanEngine
-    D, G = _nets(n_classes, Kc, 0.1 if train else 0.0, 0.2 if train else 0.0)
+    D, G = _nets(n_classes, Kc, 0.1 if train else 0.0, 0.2 if train else 0.0, seed)
     D, G = (D.train(), G.train()) if train else (D.eval(), G.eval())
     opts = dict(batch=B8, seed=77, n_classes=n_classes)
     opts.update(kw)
     return GanEngine(D.cuda(), G.cuda(), **opts), D, G
 
 
-def _data(n, seed=4):
-    g = torch.Generator().manual_seed(seed)
-    return [((torch.rand(B8, 3, 16, 16, generator=g) * 2 - 1).cuda(), torch.randint(0, K3, (B8,), generator=g).cuda()) for _ in range(n)]
+def _data(n):
+    return eu.batches(B8, n, image=16, latent=0, labels=K3)
 
 
 def _run(eng, data):
-    """(losses [n, 3], state tensors, fake labels per step, selected logits per step) of the steps on ``data``"""
-    losses, fakes, sel = [], [], []
-    for real, y in data:
-        losses.append((eng.step(real, labels=y) if eng.cond else eng.step(real)).clone())
-        if eng.cond:
-            fakes.append(eng.fake_labels.clone())
-            sel.append(eng.selected.clone())
-    torch.cuda.synchronize()
-    return (torch.stack(losses).cpu(), [t.detach().clone().cpu() for t in eng._state_tensors()], [f.cpu() for f in fakes], [s.cpu() for s in sel])
-
-
-def _same_run(a, b, what):
-    assert torch.equal(a[0], b[0]), (what, a[0], b[0])
-    assert len(a[1]) == len(b[1])
-    for i, (u, v) in enumerate(zip(a[1], b[1])):
-        assert torch.equal(u, v), f"{what}: state tensor {i}"
-    for i, (u, v) in enumerate(zip(a[2], b[2])):
-        assert torch.equal(u, v), f"{what}: fake labels of step {i + 1}"
+    """the steps on ``data``, with the fake labels and the selected logits of every step"""
+    if eng.cond:
+        return eu.run_steps(eng, data, extras=("fake_labels", "selected"), step=lambda e, b: e.step(b[0], labels=b[1]))
+    return eu.run_steps(eng, data, step=lambda e, b: e.step(b[0]))
 
 
 def _finite(run, what):
-    assert bool(torch.isfinite(run[0]).all()), (what, run[0])
-    for i, t in enumerate(run[1]):
+    assert bool(torch.isfinite(run.losses).all()), (what, run.losses)
+    for i, t in enumerate(run.state):
         assert bool(torch.isfinite(t.float()).all()), f"{what}: state tensor {i}"
 
 
-def _cond_reference_step(oracle, real, z_ext, y_real, y_fake):
-    """the conditional step from the step oracle's public pieces: the label-selected losses on D's K-way head, the generator in its
-    extended-latent form (its AdamW is elementwise, so the update of [W | table^T] is the update of W and of the table)"""
-    B = real.shape[0]
-    for p in oracle.d.values():
-        p.grad = None
-    fake = oracle.G(z_ext)
-    loss_real = cr.torch_cond_loss(oracle.D(real).reshape(B, -1), y_real, oracle.loss, 0)
-    loss_fake = cr.torch_cond_loss(oracle.D(fake.detach()).reshape(B, -1), y_fake, oracle.loss, 1)
-    (loss_real + loss_fake).backward()
-    oracle.opt_d.step()
-    for p in oracle.g.values():
-        p.grad = None
-    loss_g = cr.torch_cond_loss(oracle.D(fake).reshape(B, -1), y_fake, oracle.loss, 2)
-    loss_g.backward()
-    oracle.opt_g.step()
-    return {"d_real": float(loss_real.detach()), "d_fake": float(loss_fake.detach()), "g": float(loss_g.detach())}
+def _label_selected(loss, y_real, y_fake):
+    """StepHooks of the conditional step: the label-selected losses on D's K-way head"""
+    from oracle.step_oracle import StepHooks
+    return StepHooks(losses=tuple((lambda t, y=y, role=role: cr.torch_cond_loss(t.reshape(len(y), -1), y, loss, role))
+                                  for role, y in enumerate((y_real, y_fake, y_fake))))
 
 
 @pytest.mark.parametrize("loss,fuse", [("ns", True), ("hinge", False)])
@@ -398,11 +332,11 @@ def test_conditional_step_matches_the_reference_step(loss, fuse):
     losses = eng.step(real.cuda(), z.cuda(), y_real.cuda(), y_fake.cuda())
     torch.cuda.synchronize()
     assert torch.equal(eng.real_labels.cpu(), y_real.int()) and torch.equal(eng.fake_labels.cpu(), y_fake.int())
-    ref = _cond_reference_step(oracle, real.to(BF).float(), cr.extended_latent(z, y_fake, K3), y_real, y_fake)
+    # the generator in its extended-latent form (its AdamW is elementwise, so the update of [W | table^T] is the update of W and of the table)
+    ref = oracle.step(real.to(BF).float(), cr.extended_latent(z, y_fake, K3), hooks=_label_selected(loss, y_real, y_fake))
     got = losses.cpu().tolist()
     print(f"conditional step ({loss}, fused {fuse}): engine {got}; reference {ref}")
-    for v, k in zip(got, ("d_real", "d_fake", "g")):
-        assert abs(v - ref[k]) < 2e-2, (k, got, ref)
+    eu.assert_losses_match(got, ref, 2e-2)
     # selected = the gather of D's own logits; the other logits carry +0.  (Rows [0, B) of logits / dlogits were reused by the
     # generator's pass, which reads the fake labels too; rows [B, 2B) still hold the fake half of D's own pass.)
     lg, y2 = eng.logits.cpu(), torch.cat([y_fake, y_fake]).reshape(-1, 1)
@@ -410,9 +344,7 @@ def test_conditional_step_matches_the_reference_step(loss, fuse):
     picked = torch.zeros(2 * B8, K3, dtype=torch.bool).scatter_(1, y2, True)
     assert int((_i32(eng.dlogits.cpu()[~picked]) != 0).sum()) == 0
     # the first AdamW update, at the tolerances of test_bcr_gpu.test_bcr_engine_step_matches_the_reference_step
-    k = "vit.encoder.1.fc2.weight"
-    upd, ref_upd = D.state_dict()[k].detach().cpu() - d0[k], oracle.d[k].detach() - d0[k]
-    assert float((upd - ref_upd).abs().max()) < 1.1e-3 and float(((upd - ref_upd).abs() < 1e-4).float().mean()) > 0.9
+    eu.assert_first_update_matches(D, d0, oracle, "vit.encoder.1.fc2.weight", 1.1e-3, 1e-4, 0.9)
     # the table: the first AdamW step is lr sign(g), so an element whose gradient lies under the generator's gradient tolerance (0.12 of
     # max|g|, test_net_gpu) may take the other sign - 2 lr = 1e-3 off; every element above it moves as the reference's does
     upd = G.class_embedding.weight.detach().cpu() - table0
@@ -426,15 +358,9 @@ def test_conditional_step_matches_the_reference_step(loss, fuse):
 
 
 def _graph_against_eager(n, **kw):
-    runs, engines = {}, {}
-    data = _data(n)
-    for name, use_graph in (("eager", False), ("graph", True)):
-        eng, D, G = _engine(use_graph=use_graph, **kw)
-        runs[name] = _run(eng, data)
-        assert eng.graph_active == use_graph and eng.graph_fallback_reason is None and int(eng.step_t) == n, name
-        engines[name] = (eng, D, G)
+    runs, engines = eu.graph_against_eager(lambda use_graph: _engine(use_graph=use_graph, **kw), _data(n), "graph against eager",
+                                           extras=("fake_labels", "selected"), step=lambda e, b: e.step(b[0], labels=b[1]))
     _finite(runs["eager"], "eager")
-    _same_run(runs["graph"], runs["eager"], "graph against eager")
     return runs, engines
 
 
@@ -442,7 +368,7 @@ def test_six_steps_of_graph_replay_equal_eager_and_draw_fresh_labels():
     runs, engines = _graph_against_eager(6)
     eng = engines["graph"][0]
     for name in ("eager", "graph"):
-        fakes = runs[name][2]
+        fakes = runs[name].extras["fake_labels"]
         for i, f in enumerate(fakes):  # drawn in front of step i + 1, when the device counter still holds i
             assert np.array_equal(f.numpy(), cr.draw_labels(B8, K3, eng._aug_seed, cr.LABEL_SITE, i)), (name, i)
         assert len({tuple(f.tolist()) for f in fakes}) > 1, "the fake labels move between replays"
@@ -460,7 +386,7 @@ def test_conditional_step_with_each_option(name, kw):
     runs, engines = _graph_against_eager(3, **kw)
     eng, D, G = engines["graph"]
     if name == "diffaug_ada":  # the controller fires every step on the B selected real logits of that step
-        sel = runs["graph"][3][-1][:B8]
+        sel = runs["graph"].extras["selected"][-1][:B8]
         assert eng.ada_rt == pytest.approx(float(torch.sign(sel).mean()), abs=1e-6), (eng.ada_rt, sel)
         assert 0.0 <= eng.ada_p <= 1.0
     if name == "bcr":
@@ -483,24 +409,9 @@ def test_conditional_step_with_each_option(name, kw):
 
 
 def test_resume_through_state_dict_and_class_count_mismatch():
-    from vit_gan_amd.engine import GanEngine
-    data = _data(6)
-    whole, _, _ = _engine()
-    want = _run(whole, data)
-    first, D1, G1 = _engine()
-    head = _run(first, data[:3])
-    sd, d_sd, g_sd = first.state_dict(), D1.state_dict(), G1.state_dict()
-    assert sd["n_classes"] == K3 and "class_embedding.weight" in g_sd
-    D2, G2 = _nets(d_drop=0.1, g_drop=0.2, seed=99)
-    D2.load_state_dict(d_sd)
-    G2.load_state_dict(g_sd)
-    second = GanEngine(D2.train().cuda(), G2.train().cuda(), batch=B8, seed=77, n_classes=K3)
-    second.load_state_dict(sd)
-    tail = _run(second, data[3:])
-    assert torch.equal(torch.cat([head[0], tail[0]]), want[0])
-    for i, (u, v) in enumerate(zip(tail[1], want[1])):
-        assert torch.equal(u, v), f"state tensor {i}"
-    assert all(torch.equal(u, v) for u, v in zip(head[2] + tail[2], want[2]))
+    _, _, _, sd, made = eu.resume_against_whole(_engine, _data(6), 3, extras=("fake_labels", "selected"), step=lambda e, b: e.step(b[0], labels=b[1]))
+    (whole, _, _), (first, _, G1), (second, _, _) = made
+    assert sd["n_classes"] == K3 and "class_embedding.weight" in G1.state_dict()
     plain, _, _ = _engine(n_classes=0)
     with pytest.raises(ValueError, match="n_classes=3, this engine has n_classes=0"):
         plain.load_state_dict(sd)
@@ -523,20 +434,20 @@ def test_off_is_off_and_on_is_on():
         # (role 1): vg_gan_loss_pair on B Kc samples each gives the step's two losses and every gradient
         lg = eng.logits.clone()
         ref_d, ref_l = torch.empty_like(lg), torch.empty(2, device="cuda")
-        _call("vg_gan_loss_pair", _p(lg), _p(ref_d), _p(ref_l), B8 * K3, 2, B8 * K3, 1, 0, 1.0, None)
+        u.call("vg_gan_loss_pair", u.ptr(lg), u.ptr(ref_d), u.ptr(ref_l), B8 * K3, 2, B8 * K3, 1, 0, 1.0, None)
         torch.cuda.synchronize()
-        assert torch.equal(_i32(one[0][0, [2, 1]]), _i32(ref_l)) and torch.equal(_i32(eng.dlogits), _i32(ref_d))
+        assert torch.equal(_i32(one.losses[0, [2, 1]]), _i32(ref_l)) and torch.equal(_i32(eng.dlogits), _i32(ref_d))
         assert int((eng.dlogits == 0).sum()) == 0, "every one of the B Kc logits carries gradient"
         rest = _run(eng, data[1:])
-        runs[name] = (torch.cat([one[0], rest[0]]), rest[1], [], [])
+        runs[name] = eu.join_runs(one, rest)
         with pytest.raises(ValueError, match="labels"):
             eng.step(data[0][0], labels=data[0][1])
         eng.close()
     _finite(runs["eager"], "unconditional")
-    _same_run(runs["graph"], runs["eager"], "unconditional: graph against eager")
+    eu.assert_same_run(runs["graph"], runs["eager"], "unconditional: graph against eager")
     cond, _, _ = _engine()
     on = _run(cond, data)
-    assert not torch.equal(on[0], runs["eager"][0]) and not torch.equal(on[0][:, 0], runs["eager"][0][:, 0])
+    assert not torch.equal(on.losses, runs["eager"].losses) and not torch.equal(on.losses[:, 0], runs["eager"].losses[:, 0])
     for bad in (dict(), dict(labels=data[0][1].float()), dict(labels=data[0][1][:4]), dict(labels=data[0][1].cpu()),
                 dict(labels=data[0][1], fake_labels=data[0][1])):
         with pytest.raises(ValueError, match="labels"):

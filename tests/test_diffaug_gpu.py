@@ -5,13 +5,13 @@ Error bound of the operator tests: ``assert_elementwise`` as it stands - rel |re
 rounding of the output) - with kappa = diffaug_ref.kappa(C, IH), the depth of the fp32 evaluation derived there from the reduction tree
 and the operation count of the kernels as written, and mag the magnitude sum of the member-by-member composition.
 tests/test_diffaug_cpu.py shows that a float32 evaluation of the restatement lies inside the same bound."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 import diffaug_ref as dr
+import engine_util as eu
+import gpu_util as u
 from second_order_ref import assert_elementwise
 
 pytestmark = pytest.mark.gpu
@@ -19,31 +19,19 @@ BF = torch.bfloat16
 GEOMETRIES = [(3, 32), (3, 36), (3, 64), (3, 128), (3, 224), (1, 32)]
 
 
-def _lib():
-    import vit_gan_amd  # noqa: F401
-    from vit_gan_amd import _lib as L
-    return L
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def _fwd(x, policy, seed, site, step=None, want_params=True):
-    L = _lib()
     B, Cc, IH, _ = x.shape
     y = torch.full_like(x, float("nan"))
     params = torch.full((B, 8), float("nan"), dtype=torch.float32, device=x.device) if want_params else None
-    L.check(L.lib().vg_diffaug_fwd(_p(x), _p(y), _p(params), B, Cc, IH, policy, seed, site, _p(step), None), "vg_diffaug_fwd")
+    u.call("vg_diffaug_fwd", u.ptr(x), u.ptr(y), u.ptr(params), B, Cc, IH, policy, seed, site, u.ptr(step), None)
     torch.cuda.synchronize()
     return y, (None if params is None else params.cpu())
 
 
 def _bwd(dy, policy, seed, site, step=None, into=None):
-    L = _lib()
     B, Cc, IH, _ = dy.shape
     dx = torch.full_like(dy, float("nan")) if into is None else into.clone()
-    L.check(L.lib().vg_diffaug_bwd(_p(dy), _p(dx), int(into is not None), B, Cc, IH, policy, seed, site, _p(step), None), "vg_diffaug_bwd")
+    u.call("vg_diffaug_bwd", u.ptr(dy), u.ptr(dx), int(into is not None), B, Cc, IH, policy, seed, site, u.ptr(step), None)
     torch.cuda.synchronize()
     return dx
 
@@ -164,48 +152,21 @@ def test_autograd_operator_is_the_adjoint_kernel():
 POLICY = "color,translation,cutout"
 
 
-def _reference_step(oracle, real, z, params_d, params_g, gp_epsilon=None):
-    """The augmented step from the step oracle's public pieces (GanStepOracle.D / .G, the loss functions, gradient_penalty) and the
-    float64 operator fed the engine's own parameters: D sees T_1([real ; fake]) - the penalty too - the generator's pass T_2(fake),
-    with autograd carrying the gradient back through T_2."""
-    from oracle import step_oracle as so
-    from oracle.vit_oracle import vit_forward
-    B = real.shape[0]
-    for p in oracle.d.values():
-        p.grad = None
-    fake = oracle.G(z)
-    pair = dr.augment(torch.cat([real, fake.detach()]), params_d)[0].float()
-    loss_real = so.d_loss_real(oracle.D(pair[:B]), oracle.loss)
-    loss_real.backward()
-    loss_fake = so.d_loss_fake(oracle.D(pair[B:]), oracle.loss)
-    loss_fake.backward()
-    gp = None
-    if oracle.gp_weight:
-        gp = so.gradient_penalty(lambda t: vit_forward(oracle.d, t, oracle.ddims), pair[:B], pair[B:], gp_epsilon)
-        (oracle.gp_weight * gp).backward()
-    if oracle.clip_d is not None:
-        torch.nn.utils.clip_grad_norm_(list(oracle.d.values()), max_norm=oracle.clip_d)
-    oracle.opt_d.step()
-    for p in oracle.g.values():
-        p.grad = None
-    loss_g = so.g_loss(oracle.D(dr.augment(fake, params_g)[0].float()), oracle.loss)
-    total = loss_g + oracle.diversity_weight * so.diversity_loss(fake) if oracle.diversity_weight else loss_g
-    total.backward()
-    if oracle.clip_g is not None:
-        torch.nn.utils.clip_grad_norm_(list(oracle.g.values()), max_norm=oracle.clip_g)
-    oracle.opt_g.step()
-    return {"d_real": float(loss_real.detach()), "d_fake": float(loss_fake.detach()), "g": float(loss_g.detach()),
-            "gp": None if gp is None else float(gp.detach())}
+def _augmented(params_d, params_g):
+    """StepHooks of the augmented step: the float64 operator fed the engine's own parameters - D sees T_1([real ; fake]), the penalty
+    too, the generator's pass T_2(fake), with autograd carrying the gradient back through T_2"""
+    from oracle.step_oracle import StepHooks
+    return StepHooks(d_inputs=lambda real, fake: dr.augment(torch.cat([real, fake]), params_d)[0].float().split(real.shape[0]),
+                     g_input=lambda fake: dr.augment(fake, params_g)[0].float())
 
 
 @pytest.mark.parametrize("gp", [False, True])
 def test_augmented_engine_step_matches_the_reference_step(gp):
     """losses and the first AdamW update at the tolerances of test_wasserstein_losses_and_gradient_clipping (its configuration plus the
     augmentation); with gp_weight = 10 and a fixed epsilon at those of test_engine_step_with_gradient_penalty (its configuration)"""
-    from test_engine_gpu import _build
     from vit_gan_amd.engine import GanEngine
     B = 8
-    D, G, oracle = _build(B, "wasserstein")
+    D, G, oracle = eu.build(B, "wasserstein")
     if gp:
         oracle.gp_weight, oracle.clip_d = 10.0, 5.0
         eng = GanEngine(D, G, batch=B, loss="wasserstein", gp_weight=10.0, clip_d=5.0, external_noise=True, d_dropout=0.0, g_dropout=0.0,
@@ -228,56 +189,34 @@ def test_augmented_engine_step_matches_the_reference_step(gp):
     assert not np.array_equal(pd[:B].numpy(), pd[B:].numpy()) and not np.array_equal(pd[B:].numpy(), pg.numpy())  # real, fake, T_2: own draws
     # what D was fed in the generator's pass is T_2 of the engine's own fake
     assert_elementwise(eng.imgs_aug[:B], *dr.augment(eng.imgs[B:].cpu(), pg), dr.kappa(3, 32), "T_2(fake) inside the step")
-    ref = _reference_step(oracle, real.to(BF).float(), z, pd, pg, eps if gp else None)
+    ref = oracle.step(real.to(BF).float(), z, gp_epsilon=eps if gp else None, hooks=_augmented(pd, pg))
     got = losses.cpu().tolist()
-    print(f"augmented step (gp {gp}): engine {got} gp {float(eng.gp_loss):.5f}; reference {ref}")
-    for v, k in zip(got, ("d_real", "d_fake", "g")):
-        assert abs(v - ref[k]) < 2e-2, (k, got, ref)
+    print(f"augmented step (gp {gp}): engine {got} gp {float(eng.gp_loss):.5f}; reference {ref} gp {oracle.last_gp}")
+    eu.assert_losses_match(got, ref, 2e-2)
     if gp:
-        assert abs(float(eng.gp_loss) - ref["gp"]) < 0.03 * abs(ref["gp"]) + 1e-3
-    k = "vit.encoder.1.fc2.weight"
-    upd, ref_upd = D.state_dict()[k].detach().cpu() - w0[k], oracle.d[k].detach() - w0[k]
-    assert float((upd - ref_upd).abs().max()) < 1.1e-3 and float(((upd - ref_upd).abs() < 1e-4).float().mean()) > 0.9
+        eu.assert_penalty_matches(float(eng.gp_loss), oracle.last_gp, 0.03, 1e-3)
+    eu.assert_first_update_matches(D, w0, oracle, "vit.encoder.1.fc2.weight", 1.1e-3, 1e-4, 0.9)
 
 
 def test_augmented_graph_replay_equals_eager_and_draws_fresh_transforms():
-    from test_engine_gpu import _bench_like, _run_steps
     B, n = 4, 3
-    runs, params = {}, {}
-    for name, use_graph in (("eager", False), ("graph", True)):
-        eng, D, G, _ = _bench_like(B, use_graph=use_graph, diffaug=POLICY)
-        g = torch.Generator().manual_seed(4)
-        losses, seen = [], []
-        for _ in range(n):
-            real = (torch.rand(B, 3, 32, 32, generator=g) * 2 - 1).cuda()
-            z = torch.randn(B, 1024, generator=g).cuda()
-            losses.append(eng.step(real, z).clone())
-            seen.append(torch.cat([eng.aug_params["d"], eng.aug_params["g"]]).cpu().clone())
-        torch.cuda.synchronize()
-        assert eng.graph_active == use_graph and eng.graph_fallback_reason is None and int(eng.step_t) == n
-        runs[name] = (torch.stack(losses).cpu(), [t.detach().clone().cpu() for t in eng._state_tensors()])
-        params[name] = seen
+    runs, made = eu.graph_against_eager(lambda use_graph: eu.bench_like(B, use_graph=use_graph, diffaug=POLICY), eu.batches(B, n),
+                                        extras=[("params", lambda e: torch.cat([e.aug_params["d"], e.aug_params["g"]]))])
+    for name, run in runs.items():
+        eng, seen = made[name][0], run.extras["params"]
         for i in range(n):  # every step - every replay - has the parameters of ITS counter value, and they move
             want = np.concatenate([dr.draw(eng._aug_seed, 0, i + 1, 2 * B, 32, 7), dr.draw(eng._aug_seed, 1, i + 1, B, 32, 7)])
             assert np.array_equal(seen[i].numpy(), want), (name, i)
         assert not torch.equal(seen[0], seen[1]) and not torch.equal(seen[1], seen[2])
-    assert torch.isfinite(runs["eager"][0]).all()
-    assert torch.equal(runs["graph"][0], runs["eager"][0]), (runs["graph"][0], runs["eager"][0])
-    for i, (a, b) in enumerate(zip(runs["graph"][1], runs["eager"][1])):
-        assert torch.equal(a, b), f"state tensor {i} of the replayed steps differs from the eager run"
+    assert torch.isfinite(runs["eager"].losses).all()
     # and the augmentation is really in the step: the plain engine takes another trajectory
-    plain, _, _, _ = _bench_like(B, use_graph=False)
-    assert not torch.equal(_run_steps(plain, n, B)[0], runs["eager"][0])
+    plain, _, _, _ = eu.bench_like(B, use_graph=False)
+    assert not torch.equal(eu.run_steps(plain, eu.batches(B, n)).losses, runs["eager"].losses)
 
 
 def test_empty_policy_is_the_plain_step():
-    from test_engine_gpu import _bench_like, _run_steps
     B, n = 4, 2
-    a, _, _, _ = _bench_like(B)
-    b, _, _, _ = _bench_like(B, diffaug="")
+    a, _, _, _ = eu.bench_like(B)
+    b, _, _, _ = eu.bench_like(B, diffaug="")
     assert b.aug == 0 and not hasattr(b, "imgs_aug")
-    la, sa = _run_steps(a, n, B)
-    lb, sb = _run_steps(b, n, B)
-    assert torch.equal(la, lb)
-    for i, (u, v) in enumerate(zip(sa, sb)):
-        assert torch.equal(u, v), f"state tensor {i}"
+    eu.assert_same_run(eu.run_steps(a, eu.batches(B, n)), eu.run_steps(b, eu.batches(B, n)), "diffaug=''")

@@ -1,13 +1,14 @@
 """The generator's weight EMA on the GPU: vg_adamw_ema_step / vg_ema_update against vg_adamw_step (bit-equal weights, moments and
 shadow) and the float64 average of tests/ema_ref.py; the engine's average along a trajectory, under hipGraph replay, on the two-stream
 and the sharded schedule; sampling from the average; carrying an engine across a restart; the trainer's artefacts."""
-import ctypes as C
 import os
 
 import pytest
 import torch
 
+import engine_util as eu
 from ema_ref import check_ema_step, check_ema_trajectory, copies
+import gpu_util as u
 
 pytestmark = pytest.mark.gpu
 
@@ -17,25 +18,10 @@ STEPS = [1, 2, 3, 10, 100, 10 ** 4, 10 ** 6]
 DECAYS = (0.0, 0.5, 0.999, 0.9999)
 
 
-def _u():
-    import gpu_util as u
-    return u
-
-
-def _off(t, elems):
-    return C.c_void_p(t.data_ptr() + t.element_size() * elems)
-
-
 def _state(n, seed):
-    """Per-element edges, like test_optimizer_gpu._state: gradients of exactly 0, ~1e-6, ~1 and ~1e3; moments carried over from
-    earlier steps (some zero); |p| from 1e-4 to 10.  The average before the step: equal to p, 1e-6 and 1e-3 of p away, of p's order,
-    and (every 8th element of the upper half) unrelated to p."""
-    gen = torch.Generator().manual_seed(seed)
-    p = torch.sign(torch.randn(n, generator=gen)) * 10.0 ** (torch.rand(n, generator=gen) * 5 - 4)
-    g = torch.randn(n, generator=gen) * torch.tensor([0.0, 1e-6, 1.0, 1e3])[torch.arange(n) % 4]
-    h = torch.tensor([1.0, 1e-6, 1e3, 0.0])[torch.randperm(n, generator=gen) % 4]
-    m = torch.randn(n, generator=gen) * h * 0.3
-    v = (torch.randn(n, generator=gen) * h) ** 2
+    """gpu_util.adamw_state and the average before the step: equal to p, 1e-6 and 1e-3 of p away, of p's order, and (every 8th element of
+    the upper half) unrelated to p."""
+    p, m, v, g, gen = u.adamw_state(n, seed)
     rel = torch.tensor([0.0, 1e-6, 1e-3, 1.0])[torch.randperm(n, generator=gen) % 4]
     e = p - p * rel * torch.randn(n, generator=gen)
     e[n // 2::8] = 10.0 ** (torch.rand(len(e[n // 2::8]), generator=gen) * 5 - 4)
@@ -43,7 +29,6 @@ def _state(n, seed):
 
 
 def _kernel_case(t, start, decay, device_counter, n, lo, total, seed):
-    u = _u()
     p0, m0, v0, g, e0 = _state(total, seed)
     s = slice(lo, lo + n)
     if copies(t, start):  # a copying step must not even look at the old average
@@ -54,16 +39,16 @@ def _kernel_case(t, start, decay, device_counter, n, lo, total, seed):
     # the reference bits: plain AdamW on the same inputs
     Pr, Mr, Vr, Gr = (u.dev(x.clone()) for x in (p0, m0, v0, g))
     SHr = torch.full((total,), -7.0, dtype=BF, device="cuda")
-    u.call("vg_adamw_step", _off(Pr, lo), _off(Gr, lo), _off(Mr, lo), _off(Vr, lo), _off(SHr, lo), n, *HYP, host_t, u.ptr(step_dev), 0.5,
+    u.call("vg_adamw_step", u.off(Pr, lo), u.off(Gr, lo), u.off(Mr, lo), u.off(Vr, lo), u.off(SHr, lo), n, *HYP, host_t, u.ptr(step_dev), 0.5,
            u.stream())
     # the fused kernel
     P, M, V, G_, E = (u.dev(x.clone()) for x in (p0, m0, v0, g, e0))
     SH = torch.full((total,), -7.0, dtype=BF, device="cuda")
-    u.call("vg_adamw_ema_step", _off(P, lo), _off(G_, lo), _off(M, lo), _off(V, lo), _off(SH, lo), _off(E, lo), n, *HYP, host_t,
+    u.call("vg_adamw_ema_step", u.off(P, lo), u.off(G_, lo), u.off(M, lo), u.off(V, lo), u.off(SH, lo), u.off(E, lo), n, *HYP, host_t,
            u.ptr(step_dev), 0.5, decay, start, u.stream())
     # the average alone, from the fused kernel's weights
     E2 = u.dev(e0.clone())
-    u.call("vg_ema_update", _off(E2, lo), _off(P, lo), n, decay, start, host_t, u.ptr(step_dev), u.stream())
+    u.call("vg_ema_update", u.off(E2, lo), u.off(P, lo), n, decay, start, host_t, u.ptr(step_dev), u.stream())
     u.sync()
     if device_counter:
         assert int(step_dev[0]) == t, f"{what}: the counter was written"
@@ -96,7 +81,6 @@ def test_fused_kernel_matches_adamw_bits_and_the_fp64_average(t, device_counter)
 
 
 def test_rejected_calls_launch_nothing():
-    u = _u()
     from vit_gan_amd import _lib
     n = 4096
     bufs = [torch.full((n,), 0.25, device="cuda") for _ in range(5)]
@@ -114,39 +98,16 @@ def test_rejected_calls_launch_nothing():
 
 
 # ---- engine ---------------------------------------------------------------------------------------------------------------------------
-def _modules(seed=5):
-    import vit_gan_amd  # noqa: F401
-    from vit_gan_amd.config import Config
-    from vit_gan_amd.generator import SirenGenerator
-    from vit_gan_amd.modules import ViTDiscriminator
-    torch.manual_seed(seed)
-    cfg = Config(embeddings_dimension=384, classes_count=1, dropout_rate=0.1, batch_size=4, transformer_blocks_count=2)
-    return ViTDiscriminator(cfg).train().cuda(), SirenGenerator(layers=2, dropout=0.2).train().cuda()
-
-
 def _engine(seed=5, **kw):
-    """The small configuration of tests/test_engine_gpu.py (_bench_like): train-mode dropout, fused real+fake pass, B = 4."""
-    from vit_gan_amd.engine import GanEngine
-    D, G = _modules(seed)
-    opts = dict(batch=4, seed=77, external_noise=True)
+    """The small train-mode configuration with dropout, fused real+fake pass, B = 4; the noise comes from the caller unless told otherwise."""
+    opts = dict(external_noise=True)
     opts.update(kw)
-    return GanEngine(D, G, **opts), D, G
-
-
-def _batches(n, B=4, data_seed=4, skip=0):
-    g = torch.Generator().manual_seed(data_seed)
-    out = []
-    for i in range(skip + n):
-        real = (torch.rand(B, 3, 32, 32, generator=g) * 2 - 1)
-        z = torch.randn(B, 1024, generator=g)
-        if i >= skip:
-            out.append((real.cuda(), z.cuda()))
-    return out
+    return eu.train_engine(4, seed, **opts)[:3]
 
 
 def _run(eng, n, skip=0, masters=None):
     losses = []
-    for real, z in _batches(n, eng.B, skip=skip):
+    for real, z in eu.batches(eng.B, n, skip=skip):
         losses.append(eng.step(real, z if eng.external_noise else None).clone())
         if masters is not None:
             masters.append(eng.gen._flat.flat.detach().clone())
@@ -356,48 +317,33 @@ def test_loading_engine_state_checks_what_it_is_given():
     assert not torch.equal(eng.ema_g, G._flat.flat)
 
 
-def _shard_worker(port, out):
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    import torch.distributed as dist
-    try:
-        torch.cuda.set_device(0)
-        dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-        import vit_gan_amd  # noqa: F401
-        from vit_gan_amd.config import Config
-        from vit_gan_amd.engine import GanEngine
-        from vit_gan_amd.generator import SirenGenerator
-        from vit_gan_amd.modules import ViTDiscriminator
-        B = 16
-        res = []
-        for use_graph, shard in ((False, False), (False, True), (True, True)):
-            torch.manual_seed(0)
-            D = ViTDiscriminator(Config(embeddings_dimension=128, classes_count=1, batch_size=B, transformer_blocks_count=3)).cuda().train()
-            G = SirenGenerator(embed=128, layers=2, siren_hidden=256).cuda().train()
-            eng = GanEngine(D, G, batch=B, seed=4, use_graph=use_graph, external_noise=True, ema_decay=0.999, ema_start=2,
-                            exchange_single_rank=shard, shard_mapping_update=shard)
-            assert eng.shard_map == shard and eng.sync.active == shard
-            g = torch.Generator().manual_seed(9)
-            ls = []
-            for _ in range(4):
-                real = (torch.rand(B, 3, 32, 32, generator=g) * 2 - 1).cuda()
-                z = torch.randn(B, 1024, generator=g).cuda()
-                ls.append(eng.step(real, z).clone())
-            torch.cuda.synchronize()
-            res.append((torch.stack(ls).cpu(), G._flat.flat.detach().cpu().clone(), eng.ema_g.detach().cpu().clone(), eng.graph_active,
-                        eng.graph_fallback_reason))
-            eng.close()
-        plain, shard_eager, shard_graph = res
-        report = {"graph": shard_graph[3] and shard_graph[4] is None,
-                  "averaged": not torch.equal(plain[2], plain[1]),
-                  "eager_master": torch.equal(shard_eager[1], plain[1]), "eager_ema": torch.equal(shard_eager[2], plain[2]),
-                  "graph_master": torch.equal(shard_graph[1], plain[1]), "graph_ema": torch.equal(shard_graph[2], plain[2]),
-                  "losses": torch.equal(shard_eager[0], plain[0]) and torch.equal(shard_graph[0], plain[0])}
-        out.put(("ok", report))
-        dist.destroy_process_group()
-    except Exception as e:
-        out.put(("err", f"{type(e).__name__}: {e}"))
+def _shard_worker(rank, world):
+    import vit_gan_amd  # noqa: F401
+    from vit_gan_amd.config import Config
+    from vit_gan_amd.engine import GanEngine
+    from vit_gan_amd.generator import SirenGenerator
+    from vit_gan_amd.modules import ViTDiscriminator
+    B = 16
+    res = []
+    for use_graph, shard in ((False, False), (False, True), (True, True)):
+        torch.manual_seed(0)
+        D = ViTDiscriminator(Config(embeddings_dimension=128, classes_count=1, batch_size=B, transformer_blocks_count=3)).cuda().train()
+        G = SirenGenerator(embed=128, layers=2, siren_hidden=256).cuda().train()
+        eng = GanEngine(D, G, batch=B, seed=4, use_graph=use_graph, external_noise=True, ema_decay=0.999, ema_start=2,
+                        exchange_single_rank=shard, shard_mapping_update=shard)
+        assert eng.shard_map == shard and eng.sync.active == shard
+        ls = [eng.step(real, z).clone() for real, z in eu.batches(B, 4, seed=9)]
+        torch.cuda.synchronize()
+        res.append((torch.stack(ls).cpu(), G._flat.flat.detach().cpu().clone(), eng.ema_g.detach().cpu().clone(), eng.graph_active,
+                    eng.graph_fallback_reason))
+        eng.close()
+    plain, shard_eager, shard_graph = res
+    report = {"graph": shard_graph[3] and shard_graph[4] is None,
+              "averaged": not torch.equal(plain[2], plain[1]),
+              "eager_master": torch.equal(shard_eager[1], plain[1]), "eager_ema": torch.equal(shard_eager[2], plain[2]),
+              "graph_master": torch.equal(shard_graph[1], plain[1]), "graph_ema": torch.equal(shard_graph[2], plain[2]),
+              "losses": torch.equal(shard_eager[0], plain[0]) and torch.equal(shard_graph[0], plain[0])}
+    return report
 
 
 @pytest.mark.timeout(300)
@@ -405,18 +351,7 @@ def test_sharded_mapping_update_holds_the_replicated_average():
     """shard_mapping_update on a one-rank RCCL group (the collectives are identities, the call sequence is the sharded one: the fused
     kernel on the two ranges outside the mapping Linear, plain AdamW on the share, vg_ema_update on the gathered layer), eager and
     captured, against the plain engine: master and average bit for bit."""
-    import socket
-    import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    out = ctx.Queue()
-    p = ctx.Process(target=_shard_worker, args=(port, out))
-    p.start()
-    status, val = out.get(timeout=240)
-    p.join(timeout=60)
-    assert status == "ok", val
+    (val,) = eu.run_ranks(_shard_worker, 1, 240, backend="nccl", gpu=True)
     assert all(val.values()), val
 
 

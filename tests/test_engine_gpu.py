@@ -3,26 +3,9 @@ import numpy as np
 import pytest
 import torch
 
+import engine_util as eu
+
 pytestmark = pytest.mark.gpu
-
-
-def _build(B, loss="ns", seed=3, layers=2):
-    import vit_gan_amd  # noqa: F401
-    from vit_gan_amd.config import Config
-    from vit_gan_amd.generator import SirenGenerator
-    from vit_gan_amd.modules import ViTDiscriminator
-    from oracle import gen_oracle as go, step_oracle as so, vit_oracle as vo
-
-    torch.manual_seed(seed)
-    cfg = Config(embeddings_dimension=384, classes_count=1, dropout_rate=0.0, batch_size=B, transformer_blocks_count=layers)
-    D = ViTDiscriminator(cfg)
-    G = SirenGenerator(layers=2, dropout=0.0)
-    ddims = vo.VitDims(layers=layers, classes=1)
-    gdims = go.GenDims(layers=2)
-    d_state = {k: v.detach().clone() for k, v in D.state_dict().items()}
-    g_state = {k: v.detach().clone() for k, v in G.state_dict().items()}
-    oracle = so.GanStepOracle(d_state, g_state, ddims, gdims, loss=loss)
-    return D.cuda(), G.cuda(), oracle
 
 
 @pytest.mark.parametrize("loss", ["ns", "hinge"])
@@ -31,7 +14,7 @@ def test_engine_step_matches_oracle(loss, fuse):
     from vit_gan_amd.engine import GanEngine
 
     B = 8
-    D, G, oracle = _build(B, loss)
+    D, G, oracle = eu.build(B, loss)
     eng = GanEngine(D, G, batch=B, loss=loss, fuse_real_fake=fuse)
     # hinge: not seed 0 - with it every fake logit of step 0 sits below -1, the fake half's gradient is EXACTLY zero, most of D's first
     # AdamW step is lr * sign(rounding noise), and the step-1 generator loss is decided by that noise: 0.017-0.052 off the oracle across
@@ -64,7 +47,7 @@ def test_module_path_matches_engine_path():
     """Drop-in nn.Module usage (the reference loop's calls) gives the same gradients as GanEngine's C calls."""
     import torch.nn.functional as F
     B = 4
-    D, G, oracle = _build(B)
+    D, G, oracle = eu.build(B)
     real = (torch.rand(B, 3, 32, 32, generator=torch.Generator().manual_seed(1)) * 2 - 1).cuda()
     z = torch.randn(B, 1024, generator=torch.Generator().manual_seed(2)).cuda()
     D.zero_grad()
@@ -129,36 +112,6 @@ def test_dropout_path_and_state_dict_roundtrip():
     assert float((yc - y0).abs().max()) < 2.0 ** -5 * float(y0.abs().max()) + 1e-3
 
 
-def _bench_like(B, seed=5, d_layers=2, g_layers=2, **kw):
-    """The configuration bench.py measures - train-mode dropout (D 0.1 / G 0.2), fused real+fake pass, two-stream
-    weight gradients - at a size the CPU model finishes in seconds; the noise comes from the caller (external_noise)."""
-    import vit_gan_amd  # noqa: F401
-    from vit_gan_amd.config import Config
-    from vit_gan_amd.engine import GanEngine
-    from vit_gan_amd.generator import SirenGenerator
-    from vit_gan_amd.modules import ViTDiscriminator
-    torch.manual_seed(seed)
-    cfg = Config(embeddings_dimension=384, classes_count=1, dropout_rate=0.1, batch_size=B, transformer_blocks_count=d_layers)
-    D = ViTDiscriminator(cfg).train()
-    G = SirenGenerator(layers=g_layers, dropout=0.2).train()
-    state = ({k: v.detach().clone() for k, v in D.state_dict().items()}, {k: v.detach().clone() for k, v in G.state_dict().items()})
-    opts = dict(batch=B, seed=77, external_noise=True, fuse_real_fake=True, concurrent_wgrad=False)  # bench.py's defaults
-    opts.update(kw)  # d_dropout / g_dropout = 0.0 switch the fused dropout off
-    eng = GanEngine(D.cuda(), G.cuda(), **opts)
-    return eng, D, G, state
-
-
-def _run_steps(eng, n, B, data_seed=4):
-    g = torch.Generator().manual_seed(data_seed)
-    losses = []
-    for _ in range(n):
-        real = (torch.rand(B, 3, 32, 32, generator=g) * 2 - 1).cuda()
-        z = torch.randn(B, 1024, generator=g).cuda()
-        losses.append(eng.step(real, z).clone())
-    torch.cuda.synchronize()
-    return torch.stack(losses).cpu(), [t.detach().clone().cpu() for t in eng._state_tensors()]
-
-
 def test_engine_graph_replay_equals_eager():
     """hipGraph replay (what bench.py times at N=1) against the eager enqueue of the same steps: every piece of training
     state - both master weight buffers, both bf16 shadows, all four AdamW moment buffers, the step counter - and the
@@ -170,17 +123,14 @@ def test_engine_graph_replay_equals_eager():
     for name, kw in (("eager", dict(use_graph=False)), ("graph", dict(use_graph=True)),
                      ("eager_side_stream", dict(use_graph=False, concurrent_wgrad=True)),
                      ("graph_side_stream", dict(use_graph=True, concurrent_wgrad=True))):
-        eng, D, G, _ = _bench_like(B, **kw)
+        eng, D, G, _ = eu.bench_like(B, **kw)
         assert eng.p_d == 0.1 and eng.p_g == 0.2 and eng.fuse
-        runs[name] = _run_steps(eng, n, B)
+        runs[name] = eu.run_steps(eng, eu.batches(B, n))
         assert eng.steps == n and int(eng.step_t) == n, (name, eng.steps, int(eng.step_t))
-    ref_l, ref_s = runs["eager"]
-    assert torch.isfinite(ref_l).all() and float(ref_s[0].abs().sum()) > 0
+    ref = runs["eager"]
+    assert torch.isfinite(ref.losses).all() and float(ref.state[0].abs().sum()) > 0
     for name in ("graph", "eager_side_stream", "graph_side_stream"):
-        l, s = runs[name]
-        assert torch.equal(l, ref_l), (name, l, ref_l)
-        for i, (a, b) in enumerate(zip(s, ref_s)):
-            assert torch.equal(a, b), f"{name}: state tensor {i} differs from the eager run"
+        eu.assert_same_run(runs[name], ref, f"{name} against the eager run")
 
 
 def _step_masks(u, eng, B, step):
@@ -222,7 +172,7 @@ def test_benchmarked_configuration_matches_the_step_model():
     import gpu_util as u
     from oracle import gen_oracle as go, step_oracle as so, vit_oracle as vo
     B = 8
-    eng, D, G, (d_state, g_state) = _bench_like(B, use_graph=True)
+    eng, D, G, (d_state, g_state) = eu.bench_like(B, use_graph=True)
     model = so.GanStepOracle(d_state, g_state, vo.VitDims(layers=2, classes=1), go.GenDims(layers=2), faithful=True)
     loose = so.GanStepOracle(d_state, g_state, vo.VitDims(layers=2, classes=1), go.GenDims(layers=2))
     g = torch.Generator().manual_seed(9)
@@ -262,98 +212,85 @@ def test_load_state_dict_after_engine_construction_refreshes_the_shadows():
     bit, the step of an engine built after the load."""
     from vit_gan_amd.modules import ViTGAN
     B = 4
-    eng_a, D_a, G_a, _ = _bench_like(B, seed=5, use_graph=False)
-    eng_b, D_b, G_b, (d_other, g_other) = _bench_like(B, seed=6, use_graph=False)   # different weights
+    eng_a, D_a, G_a, _ = eu.bench_like(B, seed=5, use_graph=False)
+    eng_b, D_b, G_b, (d_other, g_other) = eu.bench_like(B, seed=6, use_graph=False)   # different weights
     assert not torch.equal(D_a.vit._flat.flat, D_b.vit._flat.flat)
     D_a.load_state_dict(d_other, strict=True)       # late load: engine A existed already
     G_a.load_state_dict(g_other, strict=True)
-    la, sa = _run_steps(eng_a, 1, B)
-    lb, sb = _run_steps(eng_b, 1, B)
-    assert torch.equal(la, lb)
-    for i, (a, b) in enumerate(zip(sa, sb)):
-        assert torch.equal(a, b), f"state tensor {i}"
+    eu.assert_same_run(eu.run_steps(eng_a, eu.batches(B, 1)), eu.run_steps(eng_b, eu.batches(B, 1)), "late load")
     seed_before = eng_a._noise_seed
     eng_a.sync_from_modules(reset_optimizer=True)
     assert int(eng_a.step_t) == 0 and float(eng_a.m_d.abs().sum()) == 0.0
     assert eng_a._noise_seed != seed_before, "a restarted run would replay the first run's latent sequence (ADVICE r3)"
 
 
-def _dp_worker(rank, world, port, out):
-    import os, sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+def _dp_worker(rank, world):
+    """on gloo, which moves CUDA tensors through the host: lets two ranks share the one GPU of the test box"""
     import torch.distributed as dist
-    dist.init_process_group("gloo", rank=rank, world_size=world)  # gloo moves CUDA tensors through the host:
-    try:                                                          # lets two ranks share the one GPU of the test box
-        import vit_gan_amd  # noqa: F401
-        from vit_gan_amd.config import Config
-        from vit_gan_amd.engine import GanEngine
-        from vit_gan_amd.generator import SirenGenerator
-        from vit_gan_amd.modules import ViTDiscriminator
-        B = 4
+    import vit_gan_amd  # noqa: F401
+    from vit_gan_amd.config import Config
+    from vit_gan_amd.engine import GanEngine
+    from vit_gan_amd.generator import SirenGenerator
+    from vit_gan_amd.modules import ViTDiscriminator
+    B = 4
 
-        def run(dp_chunks, compress, shard=False, ref_master=None):
-            torch.manual_seed(0)  # identical init on every rank (and for every exchange variant)
-            D = ViTDiscriminator(Config(embeddings_dimension=128, classes_count=1, dropout_rate=0.1, batch_size=B,
-                                        transformer_blocks_count=4)).cuda().train()
-            G = SirenGenerator(embed=128, layers=3, siren_hidden=256).cuda().train()
-            eng = GanEngine(D, G, batch=B, seed=100 + rank, compress_mapping_grad=compress, shard_mapping_update=shard)
-            eng.dp_chunks = dp_chunks
-            assert eng.world == world and eng.sync.overlap and eng.shard_map == shard
-            torch.manual_seed(50 + rank)  # different data / noise per rank
-            for _ in range(3):
-                real = torch.rand(B, 3, 32, 32, device="cuda") * 2 - 1
-                losses = eng.step(real)
-            torch.cuda.synchronize()
-            before = G._flat.flat.detach().cpu().clone()
-            if shard:
-                w0, w1 = eng._map_range()
-                a_, b_ = eng.sync.share(w0, w1)
-                own = torch.zeros(w1 - w0, dtype=torch.bool)
-                own[a_ - w0:b_ - w0] = True
-                # the shares this rank does not own are already current - equal to the replicated update's - with no gather_master() call
-                assert torch.equal(before[w0:w1][~own], ref_master[w0:w1][~own]) and torch.equal(before[w0:w1][own], ref_master[w0:w1][own])
-            eng.gather_master()  # a no-op kept for callers: it must change nothing
-            assert torch.equal(before, G._flat.flat.detach().cpu())
-            return (D.vit._flat.flat.detach().cpu(), G._flat.flat.detach().cpu(), D.vit._flat.grad.detach().cpu(), losses.cpu(),
-                    G._flat.grad.detach().cpu(), G._flat.shadow.detach().cpu())
-        # hipGraph replay cannot capture a gloo exchange: the engine must say so and run eager, never silently
-        import warnings
-        with warnings.catch_warnings(record=True) as caught:
-            warnings.simplefilter("always")
-            torch.manual_seed(0)
-            Dg = ViTDiscriminator(Config(embeddings_dimension=128, classes_count=1, batch_size=B, transformer_blocks_count=1)).cuda().train()
-            Gg = SirenGenerator(embed=128, layers=1, siren_hidden=256).cuda().train()
-            eg = GanEngine(Dg, Gg, batch=B, use_graph=True)
-        assert not eg.graph_active and "gloo" in (eg.graph_fallback_reason or ""), eg.graph_fallback_reason
-        assert any("runs EAGER" in str(w_.message) for w_ in caught)
-        assert torch.isfinite(eg.step(torch.rand(B, 3, 32, 32, device="cuda") * 2 - 1)).all()
-        del eg, Dg, Gg
-        w, gw, gsum, losses, ggrad, gsh = run(3, False)    # D and G backward in 3 pieces, exchange overlapped
-        w1, gw1, _, _, ggrad1, _ = run(1, False)           # one all-reduce per network after its whole backward
-        w2, gw2, _, _, ggrad2, _ = run(3, True)            # + mapping-layer gradient exchanged as bf16
-        w3, gw3, _, _, _, gsh3 = run(3, False, shard=True, ref_master=gw)  # mapping layer: reduce-scatter, AdamW on this rank's share, all-gather of the master
-        gather = [None] * world
-        dist.all_gather_object(gather, (w, gw, gsum, losses, gw2, gsh3, gw3))
-        if rank == 0:
-            ok = all(torch.equal(gather[0][0], g[0]) and torch.equal(gather[0][1], g[1]) and torch.equal(gather[0][2], g[2])
-                     and torch.equal(gather[0][4], g[4]) for g in gather[1:])
-            fin = all(torch.isfinite(g[3]).all() for g in gather) and torch.isfinite(w).all()
-            differ = not torch.equal(gather[0][3], gather[1][3])  # different shards -> different local losses
-            staged_equal = torch.equal(w, w1) and torch.equal(gw, gw1) and torch.equal(ggrad, ggrad1)
-            # sharded update: replicas' bf16 shadows bit-identical after 3 steps, the gathered fp32 master bit-identical between the ranks,
-            # and equal to the replicated update's (two ranks: a + b is the same sum in either exchange) - weights of D untouched by it
-            sharded_ok = (all(torch.equal(gather[0][5], g[5]) and torch.equal(gather[0][6], g[6]) for g in gather[1:])
-                          and torch.equal(gw3, gw) and torch.equal(gsh3, gsh) and torch.equal(w3, w))
-            # bf16 exchange of the mapping gradient: same update direction for all but noise-level entries
-            rel = float((ggrad2 - ggrad).abs().max()) / float(ggrad.abs().max())
-            compressed_close = rel < 2.0 ** -7 and float((gw2 - gw).abs().max()) < 3.1e-3 and not torch.equal(ggrad2, ggrad)
-            out.put(("ok", (ok, bool(fin), differ, staged_equal, compressed_close, rel, sharded_ok)))
-    except Exception as e:
-        import traceback
-        out.put(("err", f"rank {rank}: {type(e).__name__}: {e}\n{traceback.format_exc()[-1500:]}"))
-    finally:
-        dist.destroy_process_group()
+    def run(dp_chunks, compress, shard=False, ref_master=None):
+        torch.manual_seed(0)  # identical init on every rank (and for every exchange variant)
+        D = ViTDiscriminator(Config(embeddings_dimension=128, classes_count=1, dropout_rate=0.1, batch_size=B,
+                                    transformer_blocks_count=4)).cuda().train()
+        G = SirenGenerator(embed=128, layers=3, siren_hidden=256).cuda().train()
+        eng = GanEngine(D, G, batch=B, seed=100 + rank, compress_mapping_grad=compress, shard_mapping_update=shard)
+        eng.dp_chunks = dp_chunks
+        assert eng.world == world and eng.sync.overlap and eng.shard_map == shard
+        torch.manual_seed(50 + rank)  # different data / noise per rank
+        for _ in range(3):
+            real = torch.rand(B, 3, 32, 32, device="cuda") * 2 - 1
+            losses = eng.step(real)
+        torch.cuda.synchronize()
+        before = G._flat.flat.detach().cpu().clone()
+        if shard:
+            w0, w1 = eng._map_range()
+            a_, b_ = eng.sync.share(w0, w1)
+            own = torch.zeros(w1 - w0, dtype=torch.bool)
+            own[a_ - w0:b_ - w0] = True
+            # the shares this rank does not own are already current - equal to the replicated update's - with no gather_master() call
+            assert torch.equal(before[w0:w1][~own], ref_master[w0:w1][~own]) and torch.equal(before[w0:w1][own], ref_master[w0:w1][own])
+        eng.gather_master()  # a no-op kept for callers: it must change nothing
+        assert torch.equal(before, G._flat.flat.detach().cpu())
+        return (D.vit._flat.flat.detach().cpu(), G._flat.flat.detach().cpu(), D.vit._flat.grad.detach().cpu(), losses.cpu(),
+                G._flat.grad.detach().cpu(), G._flat.shadow.detach().cpu())
+    # hipGraph replay cannot capture a gloo exchange: the engine must say so and run eager, never silently
+    import warnings
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        torch.manual_seed(0)
+        Dg = ViTDiscriminator(Config(embeddings_dimension=128, classes_count=1, batch_size=B, transformer_blocks_count=1)).cuda().train()
+        Gg = SirenGenerator(embed=128, layers=1, siren_hidden=256).cuda().train()
+        eg = GanEngine(Dg, Gg, batch=B, use_graph=True)
+    assert not eg.graph_active and "gloo" in (eg.graph_fallback_reason or ""), eg.graph_fallback_reason
+    assert any("runs EAGER" in str(w_.message) for w_ in caught)
+    assert torch.isfinite(eg.step(torch.rand(B, 3, 32, 32, device="cuda") * 2 - 1)).all()
+    del eg, Dg, Gg
+    w, gw, gsum, losses, ggrad, gsh = run(3, False)    # D and G backward in 3 pieces, exchange overlapped
+    w1, gw1, _, _, ggrad1, _ = run(1, False)           # one all-reduce per network after its whole backward
+    w2, gw2, _, _, ggrad2, _ = run(3, True)            # + mapping-layer gradient exchanged as bf16
+    w3, gw3, _, _, _, gsh3 = run(3, False, shard=True, ref_master=gw)  # mapping layer: reduce-scatter, AdamW on this rank's share, all-gather of the master
+    gather = [None] * world
+    dist.all_gather_object(gather, (w, gw, gsum, losses, gw2, gsh3, gw3))
+    if rank == 0:
+        ok = all(torch.equal(gather[0][0], g[0]) and torch.equal(gather[0][1], g[1]) and torch.equal(gather[0][2], g[2])
+                 and torch.equal(gather[0][4], g[4]) for g in gather[1:])
+        fin = all(torch.isfinite(g[3]).all() for g in gather) and torch.isfinite(w).all()
+        differ = not torch.equal(gather[0][3], gather[1][3])  # different shards -> different local losses
+        staged_equal = torch.equal(w, w1) and torch.equal(gw, gw1) and torch.equal(ggrad, ggrad1)
+        # sharded update: replicas' bf16 shadows bit-identical after 3 steps, the gathered fp32 master bit-identical between the ranks,
+        # and equal to the replicated update's (two ranks: a + b is the same sum in either exchange) - weights of D untouched by it
+        sharded_ok = (all(torch.equal(gather[0][5], g[5]) and torch.equal(gather[0][6], g[6]) for g in gather[1:])
+                      and torch.equal(gw3, gw) and torch.equal(gsh3, gsh) and torch.equal(w3, w))
+        # bf16 exchange of the mapping gradient: same update direction for all but noise-level entries
+        rel = float((ggrad2 - ggrad).abs().max()) / float(ggrad.abs().max())
+        compressed_close = rel < 2.0 ** -7 and float((gw2 - gw).abs().max()) < 3.1e-3 and not torch.equal(ggrad2, ggrad)
+        return ok, bool(fin), differ, staged_equal, compressed_close, rel, sharded_ok
 
 
 @pytest.mark.timeout(600)
@@ -364,21 +301,7 @@ def test_two_rank_data_parallel_engine_with_current_sharded_master_on_one_gpu():
     2^-7 of the fp32 exchange; the sharded update of the mapping layer (reduce-scatter, AdamW on each rank's share, all-gather of the
     fp32 master) leaves bit-identical replicas and the replicated update's weights, and every rank's master of the
     shares it does not own is already current after the step, with no gather_master() call."""
-    import socket
-    import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    out = ctx.Queue()
-    procs = [ctx.Process(target=_dp_worker, args=(r, 2, port, out)) for r in range(2)]
-    for p in procs:
-        p.start()
-    status, val = out.get(timeout=500)
-    for p in procs:
-        p.join(timeout=120)
-    assert status == "ok", val
-    same, finite, differ, staged_equal, compressed_close, rel, sharded_ok = val
+    same, finite, differ, staged_equal, compressed_close, rel, sharded_ok = eu.run_ranks(_dp_worker, 2, 500, gpu=True)[0]
     assert same, "replicas diverged: weights / reduced gradients differ between ranks"
     assert finite and differ
     assert staged_equal, "staged (overlapped) D / G exchange must equal the single all-reduce bit for bit"
@@ -386,60 +309,50 @@ def test_two_rank_data_parallel_engine_with_current_sharded_master_on_one_gpu():
     assert sharded_ok, "sharded update of the mapping layer: replicas / the replicated update differ"
 
 
-def _dp_coherence_worker(rank, world, port, out):
-    import os, sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+def _dp_coherence_worker(rank, world):
     import torch.distributed as dist
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        import vit_gan_amd  # noqa: F401
-        from vit_gan_amd.config import Config
-        from vit_gan_amd.engine import GanEngine
-        from vit_gan_amd.generator import SirenGenerator
-        from vit_gan_amd.modules import ViTDiscriminator
-        B = 4
-        gen = torch.Generator().manual_seed(60 + rank)  # different data per rank
-        reals = [(torch.rand(B, 3, 32, 32, generator=gen) * 2 - 1).cuda() for _ in range(3)]
-        z = torch.randn(B, 1024, generator=torch.Generator().manual_seed(7)).cuda()
+    import vit_gan_amd  # noqa: F401
+    from vit_gan_amd.config import Config
+    from vit_gan_amd.engine import GanEngine
+    from vit_gan_amd.generator import SirenGenerator
+    from vit_gan_amd.modules import ViTDiscriminator
+    B = 4
+    gen = torch.Generator().manual_seed(60 + rank)  # different data per rank
+    reals = [(torch.rand(B, 3, 32, 32, generator=gen) * 2 - 1).cuda() for _ in range(3)]
+    z = torch.randn(B, 1024, generator=torch.Generator().manual_seed(7)).cuda()
 
-        def run(shard):
-            torch.manual_seed(0)  # identical init on every rank
-            D = ViTDiscriminator(Config(embeddings_dimension=128, classes_count=1, dropout_rate=0.0, batch_size=B,
-                                        transformer_blocks_count=2)).cuda().train()
-            G = SirenGenerator(embed=128, layers=3, siren_hidden=256, dropout=0.0).cuda().train()
-            eng = GanEngine(D, G, batch=B, seed=100 + rank, shard_mapping_update=shard)
-            assert eng.world == world and eng.shard_map == shard
-            eng.step(reals[0])
-            with torch.no_grad():
-                G(z)                    # a module forward (sampling, FID): refresh_shadow() recasts the whole shadow from the master
-            eng.step(reals[1])
-            eng.sync_from_modules()     # the same recast, as after an in-place edit or a load_state_dict
-            eng.step(reals[2])
-            torch.cuda.synchronize()    # no gather_master() anywhere
-            fd, fg = D.vit._flat, G._flat
-            got = tuple(t.detach().cpu().clone() for t in (fd.flat, fd.shadow, fg.flat, fg.shadow))
-            eng.close()
-            return got
+    def run(shard):
+        torch.manual_seed(0)  # identical init on every rank
+        D = ViTDiscriminator(Config(embeddings_dimension=128, classes_count=1, dropout_rate=0.0, batch_size=B,
+                                    transformer_blocks_count=2)).cuda().train()
+        G = SirenGenerator(embed=128, layers=3, siren_hidden=256, dropout=0.0).cuda().train()
+        eng = GanEngine(D, G, batch=B, seed=100 + rank, shard_mapping_update=shard)
+        assert eng.world == world and eng.shard_map == shard
+        eng.step(reals[0])
+        with torch.no_grad():
+            G(z)                    # a module forward (sampling, FID): refresh_shadow() recasts the whole shadow from the master
+        eng.step(reals[1])
+        eng.sync_from_modules()     # the same recast, as after an in-place edit or a load_state_dict
+        eng.step(reals[2])
+        torch.cuda.synchronize()    # no gather_master() anywhere
+        fd, fg = D.vit._flat, G._flat
+        got = tuple(t.detach().cpu().clone() for t in (fd.flat, fd.shadow, fg.flat, fg.shadow))
+        eng.close()
+        return got
 
-        rep, sh = run(False), run(True)
-        gather = [None] * world
-        dist.all_gather_object(gather, (rep, sh))
-        if rank == 0:
-            bits = lambda t: t.view(torch.int16)  # noqa: E731
-            res = {
-                "ranks_equal": all(torch.equal(gather[0][k][i], g[k][i]) for g in gather[1:] for k in (0, 1) for i in range(4)),
-                "shard_equals_replicated": all(torch.equal(g[0][i], g[1][i]) for g in gather for i in range(4)),
-                "shadow_is_rne": all(torch.equal(bits(g[k][i + 1]), bits(g[k][i].to(torch.bfloat16))) for g in gather for k in (0, 1)
-                                     for i in (0, 2)),
-                "finite": all(bool(torch.isfinite(g[k][i]).all()) for g in gather for k in (0, 1) for i in (0, 2)),
-            }
-            out.put(("ok", res))
-    except Exception as e:
-        import traceback
-        out.put(("err", f"rank {rank}: {type(e).__name__}: {e}\n{traceback.format_exc()[-1500:]}"))
-    finally:
-        dist.destroy_process_group()
+    rep, sh = run(False), run(True)
+    gather = [None] * world
+    dist.all_gather_object(gather, (rep, sh))
+    if rank == 0:
+        bits = lambda t: t.view(torch.int16)  # noqa: E731
+        res = {
+            "ranks_equal": all(torch.equal(gather[0][k][i], g[k][i]) for g in gather[1:] for k in (0, 1) for i in range(4)),
+            "shard_equals_replicated": all(torch.equal(g[0][i], g[1][i]) for g in gather for i in range(4)),
+            "shadow_is_rne": all(torch.equal(bits(g[k][i + 1]), bits(g[k][i].to(torch.bfloat16))) for g in gather for k in (0, 1)
+                                 for i in (0, 2)),
+            "finite": all(bool(torch.isfinite(g[k][i]).all()) for g in gather for k in (0, 1) for i in (0, 2)),
+        }
+        return res
 
 
 @pytest.mark.timeout(600)
@@ -448,20 +361,7 @@ def test_two_rank_sharded_mapping_update_keeps_masters_coherent():
     master), step, sync_from_modules(), step.  The replicas' D and G masters and shadows must be bit-identical across the ranks with no
     gather_master() call, bit-equal to the replicated update's, and every shadow the round-to-nearest-even of its master: a rank whose
     master of the mapping shares it does not own were stale would recast stale weights over the gathered ones and diverge."""
-    import socket
-    import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    out = ctx.Queue()
-    procs = [ctx.Process(target=_dp_coherence_worker, args=(r, 2, port, out)) for r in range(2)]
-    for p in procs:
-        p.start()
-    status, val = out.get(timeout=500)
-    for p in procs:
-        p.join(timeout=120)
-    assert status == "ok", val
+    val = eu.run_ranks(_dp_coherence_worker, 2, 500, gpu=True)[0]
     assert val["finite"], val
     assert val["shadow_is_rne"], val
     assert val["ranks_equal"], val
@@ -505,7 +405,7 @@ def test_wasserstein_losses_and_gradient_clipping():
     from oracle import step_oracle as so
 
     B = 8
-    D, G, oracle = _build(B, "wasserstein")
+    D, G, oracle = eu.build(B, "wasserstein")
     oracle.clip_d, oracle.clip_g = 0.05, 0.02
     oracle.diversity_weight = 0.1
     eng = GanEngine(D, G, batch=B, loss="wasserstein", clip_d=0.05, clip_g=0.02, diversity_weight=0.1)
@@ -536,7 +436,7 @@ def test_instance_noise_on_the_discriminator_inputs():
     The engine's noisy copies are handed to the step oracle."""
     from vit_gan_amd.engine import GanEngine
     B = 8
-    D, G, oracle = _build(B, "ns")
+    D, G, oracle = eu.build(B, "ns")
     eng = GanEngine(D, G, batch=B, instance_noise=0.1)
     real = torch.rand(B, 3, 32, 32, generator=torch.Generator().manual_seed(0)) * 2 - 1
     losses = eng.step(real.cuda())
@@ -562,10 +462,10 @@ def test_two_stream_schedule_is_the_unfused_step():
     for name, kw in (("unfused", dict(fuse_real_fake=False, use_graph=False, concurrent_wgrad=False)),
                      ("two_stream", dict(two_stream=True, use_graph=False)),
                      ("two_stream_graph", dict(two_stream=True, use_graph=True))):
-        eng, D, G, _ = _bench_like(B, d_dropout=0.0, g_dropout=0.0, **kw)
-        runs[name] = _run_steps(eng, n, B)
-    (l_u, s_u), (l_t, s_t), (l_g, s_g) = runs["unfused"], runs["two_stream"], runs["two_stream_graph"]
-    assert torch.equal(l_t, l_g) and all(torch.equal(a, b) for a, b in zip(s_t, s_g)), "graph replay != eager (two-stream)"
+        eng, D, G, _ = eu.bench_like(B, d_dropout=0.0, g_dropout=0.0, **kw)
+        runs[name] = eu.run_steps(eng, eu.batches(B, n))
+    (l_u, s_u, _), (l_t, s_t, _) = runs["unfused"], runs["two_stream"]
+    eu.assert_same_run(runs["two_stream"], runs["two_stream_graph"], "graph replay != eager (two-stream)")
     assert torch.equal(l_t[0, :2], l_u[0, :2]), (l_t[0], l_u[0])       # D losses of step 0: identical arithmetic
     # Later losses: the two schedules add the real and the fake pass's weight gradients in a different order (1.5e-8 on gradients
     # of 0.5, checked below); AdamW's first steps are sign-like (m / sqrt(v) = +-1), so an ulp on a noise-level gradient is a
@@ -577,12 +477,12 @@ def test_two_stream_schedule_is_the_unfused_step():
     # the first step's D gradients themselves: the same up to fp32 reassociation of the two passes' sums
     gr = {}
     for name, kw in (("unfused", dict(fuse_real_fake=False, use_graph=False, concurrent_wgrad=False)), ("two_stream", dict(two_stream=True, use_graph=False))):
-        eng, D, G, _ = _bench_like(B, d_dropout=0.0, g_dropout=0.0, **kw)
-        _run_steps(eng, 1, B)
+        eng, D, G, _ = eu.bench_like(B, d_dropout=0.0, g_dropout=0.0, **kw)
+        eu.run_steps(eng, eu.batches(B, 1))
         gr[name] = eng.vit._flat.grad.clone().cpu()
     assert float((gr["unfused"] - gr["two_stream"]).abs().max()) < 1e-6 * float(gr["unfused"].abs().max())
     # with dropout on: the model with the two-stream passes' own masks (pass seeds 0 / 1, half-batch passes 2 / 3)
-    eng, D, G, (d_state, g_state) = _bench_like(B, two_stream=True, use_graph=True)
+    eng, D, G, (d_state, g_state) = eu.bench_like(B, two_stream=True, use_graph=True)
     model = so.GanStepOracle(d_state, g_state, vo.VitDims(layers=2, classes=1), go.GenDims(layers=2), faithful=True)
     g = torch.Generator().manual_seed(9)
     real = torch.rand(B, 3, 32, 32, generator=g) * 2 - 1
@@ -595,60 +495,46 @@ def test_two_stream_schedule_is_the_unfused_step():
         assert abs(x - ref[k]) < 1e-3, (k, got, ref)
 
 
-def _rccl_worker(port, out):
-    import os, sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
+def _rccl_worker(rank, world):
     import torch.distributed as dist
-    try:
-        torch.cuda.set_device(0)
-        dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-        flat = torch.arange(4096, dtype=torch.float32, device="cuda")
-        comm = torch.cuda.Stream()
-        ready = torch.cuda.Event()
-        ready.record(torch.cuda.current_stream())
-        with torch.cuda.stream(comm):            # the exact call pattern of GradSync.reduce_range (overlap path)
-            comm.wait_event(ready)
-            work = dist.all_reduce(flat[1024:3072], op=dist.ReduceOp.SUM, async_op=True)
-            half = flat[:1024].to(torch.bfloat16)
-            dist.all_reduce(half, op=dist.ReduceOp.SUM)
-        work.wait()
-        torch.cuda.current_stream().wait_stream(comm)
+    flat = torch.arange(4096, dtype=torch.float32, device="cuda")
+    comm = torch.cuda.Stream()
+    ready = torch.cuda.Event()
+    ready.record(torch.cuda.current_stream())
+    with torch.cuda.stream(comm):            # the exact call pattern of GradSync.reduce_range (overlap path)
+        comm.wait_event(ready)
+        work = dist.all_reduce(flat[1024:3072], op=dist.ReduceOp.SUM, async_op=True)
+        half = flat[:1024].to(torch.bfloat16)
+        dist.all_reduce(half, op=dist.ReduceOp.SUM)
+    work.wait()
+    torch.cuda.current_stream().wait_stream(comm)
+    torch.cuda.synchronize()
+    ok = torch.equal(flat.cpu(), torch.arange(4096, dtype=torch.float32)) and torch.equal(half.float().cpu(), torch.arange(1024).float().to(torch.bfloat16).float())
+    # the whole step with its (one-rank) RCCL all-reduces captured in a hipGraph: replay == eager, bit for bit, 3 steps
+    import vit_gan_amd  # noqa: F401
+    from vit_gan_amd.config import Config
+    from vit_gan_amd.engine import GanEngine
+    from vit_gan_amd.generator import SirenGenerator
+    from vit_gan_amd.modules import ViTDiscriminator
+    B = 16
+    res = []
+    # (eager, graph) with the bf16 mapping exchange, then (eager, graph) with the sharded update of the mapping layer: on one rank
+    # the reduce-scatter / all-gather are identities, but they are RCCL's calls, on the side stream, inside the capture
+    for use_graph, shard in ((False, False), (True, False), (False, True), (True, True)):
+        torch.manual_seed(0)
+        D = ViTDiscriminator(Config(embeddings_dimension=128, classes_count=1, batch_size=B, transformer_blocks_count=3)).cuda().train()
+        G = SirenGenerator(embed=128, layers=2, siren_hidden=256).cuda().train()
+        eng = GanEngine(D, G, batch=B, seed=4, use_graph=use_graph, external_noise=True, exchange_single_rank=True,
+                        compress_mapping_grad=not shard, shard_mapping_update=shard)
+        assert eng.sync.active and eng.sync.overlap and eng.shard_map == shard
+        ls = [eng.step(real, z).clone() for real, z in eu.batches(B, 3, seed=9)]
         torch.cuda.synchronize()
-        ok = torch.equal(flat.cpu(), torch.arange(4096, dtype=torch.float32)) and torch.equal(half.float().cpu(), torch.arange(1024).float().to(torch.bfloat16).float())
-        # the whole step with its (one-rank) RCCL all-reduces captured in a hipGraph: replay == eager, bit for bit, 3 steps
-        import vit_gan_amd  # noqa: F401
-        from vit_gan_amd.config import Config
-        from vit_gan_amd.engine import GanEngine
-        from vit_gan_amd.generator import SirenGenerator
-        from vit_gan_amd.modules import ViTDiscriminator
-        B = 16
-        res = []
-        # (eager, graph) with the bf16 mapping exchange, then (eager, graph) with the sharded update of the mapping layer: on one rank
-        # the reduce-scatter / all-gather are identities, but they are RCCL's calls, on the side stream, inside the capture
-        for use_graph, shard in ((False, False), (True, False), (False, True), (True, True)):
-            torch.manual_seed(0)
-            D = ViTDiscriminator(Config(embeddings_dimension=128, classes_count=1, batch_size=B, transformer_blocks_count=3)).cuda().train()
-            G = SirenGenerator(embed=128, layers=2, siren_hidden=256).cuda().train()
-            eng = GanEngine(D, G, batch=B, seed=4, use_graph=use_graph, external_noise=True, exchange_single_rank=True,
-                            compress_mapping_grad=not shard, shard_mapping_update=shard)
-            assert eng.sync.active and eng.sync.overlap and eng.shard_map == shard
-            g = torch.Generator().manual_seed(9)
-            ls = []
-            for _ in range(3):
-                real = (torch.rand(B, 3, 32, 32, generator=g) * 2 - 1).cuda()
-                z = torch.randn(B, 1024, generator=g).cuda()
-                ls.append(eng.step(real, z).clone())
-            torch.cuda.synchronize()
-            res.append((torch.stack(ls).cpu(), D.vit._flat.flat.detach().cpu().clone(), G._flat.flat.detach().cpu().clone(),
-                        eng.graph_active, eng.graph_fallback_reason))
-            eng.close()
-        graph_ok = res[1][3] and res[1][4] is None and res[3][3] and res[3][4] is None
-        same = all(torch.equal(a, b) for a, b in zip(res[0][:3], res[1][:3])) and all(torch.equal(a, b) for a, b in zip(res[2][:3], res[3][:3]))
-        out.put(("ok", (ok and graph_ok and same, dist.get_backend(), res[1][4])))
-        dist.destroy_process_group()
-    except Exception as e:
-        out.put(("err", f"{type(e).__name__}: {e}"))
+        res.append((torch.stack(ls).cpu(), D.vit._flat.flat.detach().cpu().clone(), G._flat.flat.detach().cpu().clone(),
+                    eng.graph_active, eng.graph_fallback_reason))
+        eng.close()
+    graph_ok = res[1][3] and res[1][4] is None and res[3][3] and res[3][4] is None
+    same = all(torch.equal(a, b) for a, b in zip(res[0][:3], res[1][:3])) and all(torch.equal(a, b) for a, b in zip(res[2][:3], res[3][:3]))
+    return ok and graph_ok and same, dist.get_backend(), res[1][4]
 
 
 @pytest.mark.timeout(300)
@@ -658,16 +544,5 @@ def test_rccl_backend_executes_the_exchange_calls_on_one_rank():
     all-reduce on the side stream, stream joins - so that path is not first exercised on the 8-GPU node.  It also runs the
     engine's step with those collectives (staged D and G exchange, bf16 mapping gradient) CAPTURED in a hipGraph: three
     replayed steps must equal three eager steps bit for bit (what bench.py does on more than one GPU since round 3)."""
-    import socket
-    import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    out = ctx.Queue()
-    p = ctx.Process(target=_rccl_worker, args=(port, out))
-    p.start()
-    status, val = out.get(timeout=240)
-    p.join(timeout=60)
-    assert status == "ok", val
+    (val,) = eu.run_ranks(_rccl_worker, 1, 240, backend="nccl", gpu=True)
     assert val[0] and val[1] == "nccl", val  # val[2]: the engine's graph fallback reason, if the capture was refused

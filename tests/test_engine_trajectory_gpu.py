@@ -9,6 +9,7 @@ optimizer's wiring."""
 import pytest
 import torch
 
+import engine_util as eu
 from adamw_ref import check_adamw_step
 
 pytestmark = pytest.mark.gpu
@@ -17,22 +18,6 @@ B = 8
 STEPS = 12
 REPLAYS = 200
 CASES = [("ns", {}), ("hinge", {}), ("wasserstein", dict(clip_d=0.05, clip_g=0.02))]
-
-
-def _build(loss):
-    import vit_gan_amd  # noqa: F401
-    from vit_gan_amd.config import Config
-    from vit_gan_amd.generator import SirenGenerator
-    from vit_gan_amd.modules import ViTDiscriminator
-    from oracle import gen_oracle as go, step_oracle as so, vit_oracle as vo
-
-    torch.manual_seed(3)
-    D = ViTDiscriminator(Config(embeddings_dimension=384, classes_count=1, dropout_rate=0.0, batch_size=B, transformer_blocks_count=2))
-    G = SirenGenerator(layers=2, dropout=0.0)
-    oracle = so.GanStepOracle({k: v.detach().clone() for k, v in D.state_dict().items()},
-                              {k: v.detach().clone() for k, v in G.state_dict().items()},
-                              vo.VitDims(layers=2, classes=1), go.GenDims(layers=2), loss=loss, faithful=True)
-    return D.cuda(), G.cuda(), oracle
 
 
 def _slots(module, fp):
@@ -127,7 +112,7 @@ def _compare(module, fp, ref_params, rel, what):
 def test_optimizer_trajectory_matches_fp64_adamw(loss, kw, use_graph):
     from vit_gan_amd.engine import GanEngine
 
-    D, G, oracle = _build(loss)
+    D, G, oracle = eu.build(B, loss, faithful=True)
     eng = GanEngine(D, G, batch=B, loss=loss, use_graph=use_graph, **kw)
     gen = torch.Generator().manual_seed(1)
     reals = [(torch.rand(B, 3, 32, 32, generator=gen) * 2 - 1).cuda() for _ in range(4)]

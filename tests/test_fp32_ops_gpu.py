@@ -10,15 +10,12 @@ import math
 import pytest
 import torch
 
+import gpu_util as u
+
 pytestmark = pytest.mark.gpu
 
 GEMM_REL = 4e-7
 OP_TOL = 1e-5
-
-
-def _u():
-    import gpu_util
-    return gpu_util
 
 
 def _gelu64(z):
@@ -46,7 +43,6 @@ FWD_SHAPES = [(16640, 1152, 384), (33280, 384, 768), (16640, 768, 384), (4160, 5
 @pytest.mark.parametrize("M,N,K", FWD_SHAPES)
 @pytest.mark.parametrize("act", [0, 1, 2])
 def test_linear_f32_fwd(M, N, K, act):
-    u = _u()
     g = torch.Generator().manual_seed(M + 3 * N + 7 * K + act)
     X = torch.randn(M, K, generator=g)
     W = torch.randn(N, K, generator=g) / math.sqrt(K)
@@ -73,7 +69,6 @@ def test_linear_f32_fwd(M, N, K, act):
 
 def test_linear_f32_fwd_dropout_mask_is_the_engines():
     """The dropout epilogue multiplies by exactly the mask vg_dropout_apply produces for (p, seed, site) over the [M, N] output."""
-    u = _u()
     M, N, K, p, seed, site = 1040, 384, 384, 0.1, 1234, 3
     g = torch.Generator().manual_seed(5)
     X, W = torch.randn(M, K, generator=g).cuda(), (torch.randn(N, K, generator=g) / 20).cuda()
@@ -90,7 +85,6 @@ def test_linear_f32_fwd_dropout_mask_is_the_engines():
 @pytest.mark.parametrize("M,N,K", [(16640, 384, 768), (16640, 1152, 384), (33280, 384, 384), (2080, 512, 1024), (1037, 768, 1536), (5, 1, 384)])
 @pytest.mark.parametrize("act", [0, 1, 2])
 def test_linear_f32_dgrad(M, N, K, act):
-    u = _u()
     g = torch.Generator().manual_seed(M + N + K + 11 * act)
     dY = torch.randn(M, N, generator=g)
     W = torch.randn(N, K, generator=g) / math.sqrt(N)
@@ -111,7 +105,6 @@ def test_linear_f32_dgrad(M, N, K, act):
 @pytest.mark.parametrize("M,N,K", [(16640, 1152, 384), (16640, 384, 768), (33280, 384, 384), (33280, 768, 384), (4160, 512, 512), (16384, 768, 48),
                                    (1037, 384, 384), (5, 1, 384)])
 def test_linear_f32_wgrad_accumulates_and_is_repeatable(M, N, K):
-    u = _u()
     lib = u._lib.lib()
     g = torch.Generator().manual_seed(M * 3 + N + K)
     dY, X = torch.randn(M, N, generator=g), torch.randn(M, K, generator=g)
@@ -141,7 +134,6 @@ def test_linear_f32_wgrad_accumulates_and_is_repeatable(M, N, K):
 @pytest.mark.parametrize("M,K", [(64, 64), (130, 130), (16, 200)])
 def test_linear_f32_identity_with_asymmetric_weights(M, K):
     """A = I: every output element is one weight element (a row/column swap in the C/D map would show); B asymmetric."""
-    u = _u()
     N = 96
     X = torch.eye(M, K)
     W = torch.arange(N * K, dtype=torch.float32).reshape(N, K) * 0.001 + torch.arange(N, dtype=torch.float32)[:, None] * 7.0
@@ -169,7 +161,6 @@ def _attn64(qkv, B, H, S, HE, scale):
 
 @pytest.mark.parametrize("B,H,S,HE", [(2, 4, 65, 96), (2, 8, 65, 64), (3, 4, 17, 32), (1, 12, 65, 64), (2, 4, 80, 32), (4, 6, 5, 64)])
 def test_attention_f32(B, H, S, HE):
-    u = _u()
     E = H * HE
     g = torch.Generator().manual_seed(B * 100 + H * 10 + S + HE)
     qkv = torch.randn(B * S, 3 * E, generator=g) * 1.5
@@ -193,7 +184,6 @@ def test_attention_f32(B, H, S, HE):
 @pytest.mark.parametrize("E", [128, 256, 384, 512, 640, 768, 896, 1024])
 @pytest.mark.parametrize("R", [1, 77, 2083])
 def test_layernorm_f32(E, R):
-    u = _u()
     lib = u._lib.lib()
     g = torch.Generator().manual_seed(E + R)
     x = torch.randn(R, E, generator=g) * 3 + 0.5

@@ -10,18 +10,14 @@ import math
 import pytest
 import torch
 
+import gpu_util as u
+
 pytestmark = pytest.mark.gpu
 REPS = 40
 
 
-def _u():
-    import gpu_util
-    return gpu_util
-
-
 @pytest.mark.parametrize("M,N,K", [(1312, 1152, 384), (16640, 384, 384), (8320, 768, 384), (4160, 384, 768), (2600, 384, 1152)])
 def test_forward_and_input_gradient_repeatable(M, N, K):
-    u = _u()
     g = torch.Generator().manual_seed(M + N + K)
     A = u.dev(u.rbf(torch.randn(M, K, generator=g)), u.BF)
     W = u.dev(u.rbf(torch.randn(N, K, generator=g) / math.sqrt(K)), u.BF)
@@ -51,7 +47,6 @@ def test_gelu_and_byte_derivative_epilogues_repeatable(M):
     epilogue, and the epilogues differ per instantiation: the two the step runs beside the plain ones - fc1 + GELU with the
     one-byte derivative as second output (<0, 1, 2>) and the fc2 input gradient times the decoded byte (<1, 8, 0>) - get the same
     screen: many launches, other traffic in flight, every result bit-equal to the first and right against fp32."""
-    u = _u()
     E, H = 384, 768
     g = torch.Generator().manual_seed(M)
     A = u.dev(u.rbf(torch.randn(M, E, generator=g)), u.BF)
@@ -84,7 +79,6 @@ def test_gelu_and_byte_derivative_epilogues_repeatable(M):
                                           (256, 384, 384, 4), (288, 128, 384, 3), (512, 256, 768, 4), (800, 384, 384, 5),
                                           (4160, 512, 1024, 8)])  # last: the 128 x 512-tile variant
 def test_weight_gradient_repeatable(M, N, K, splits):
-    u = _u()
     g = torch.Generator().manual_seed(M + N + K + splits)
     dY = u.dev(u.rbf(torch.randn(M, N, generator=g)), u.BF)
     X = u.dev(u.rbf(torch.randn(M, K, generator=g)), u.BF)

@@ -14,6 +14,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import engine_util as eu
+
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -148,8 +150,7 @@ def test_engine_step_with_gradient_penalty(B, autograd):
     (vg_vit_penalty) - B = 16: 16 x 65 rows are whole units of 16, the fused full-row forms; B = 8: the GEMM + LayerNorm pairs -
     and, gp_autograd=True, as the operator set through autograd."""
     from vit_gan_amd.engine import GanEngine
-    from test_engine_gpu import _build
-    D, G, oracle = _build(B, "wasserstein")
+    D, G, oracle = eu.build(B, "wasserstein")
     oracle.gp_weight = 10.0
     oracle.clip_d = 5.0
     eng = GanEngine(D, G, batch=B, loss="wasserstein", gp_weight=10.0, clip_d=5.0, external_noise=True, gp_autograd=autograd)
@@ -183,14 +184,13 @@ def test_engine_step_with_gradient_penalty_replays_as_a_graph(B, p_drop, autogra
     is torch's); else the C call (B = 8: its unfused forms), also with dropout - its masks are the engine's counter-based ones, a function
     of the step counter."""
     from vit_gan_amd.engine import GanEngine
-    from test_engine_gpu import _build
     g = torch.Generator().manual_seed(0)
     reals = [(torch.rand(B, 3, 32, 32, generator=g) * 2 - 1).cuda() for _ in range(3)]
     zs = [torch.randn(B, 1024, generator=g).cuda() for _ in range(3)]
     eps = torch.rand(B, 1, 1, 1, generator=g).cuda()
     out = []
     for use_graph in (False, True):
-        D, G, _ = _build(B, "wasserstein")
+        D, G, _ = eu.build(B, "wasserstein")
         eng = GanEngine(D, G, batch=B, loss="wasserstein", gp_weight=10.0, clip_d=5.0, external_noise=True, use_graph=use_graph,
                         d_dropout=p_drop, g_dropout=p_drop, gp_autograd=autograd)
         assert eng.gp_c_call == (not autograd)
@@ -212,8 +212,7 @@ def test_deferred_grouped_weight_gradients_equal_autograd(B):
     launch, fold and AccumulateGrad per contribution).  Same products, another K partition and summation order: fp32 round-off apart."""
     from vit_gan_amd import ops2
     from vit_gan_amd.penalty import gradient_penalty
-    from test_engine_gpu import _build
-    D, _, _ = _build(B, "wasserstein")
+    D, _, _ = eu.build(B, "wasserstein")
     fl = D.vit._flat
     g = torch.Generator().manual_seed(B)
     real = (torch.rand(B, 3, 32, 32, generator=g) * 2 - 1).cuda()
@@ -335,8 +334,7 @@ def test_penalty_c_call_with_dropout_is_the_gradient_of_its_own_value(B, layers)
     the same masks.  A mask mismatch between any two passes leaves the value fine and the gradient wrong, so: the directional derivative
     of the call's penalty VALUE along its own gradient, by central differences on the fp32 master weights (same seed and step counter =
     same masks), against |gradient|^2."""
-    from test_engine_gpu import _build
-    D, _, _ = _build(B, "wasserstein", layers=layers)   # (256, 6): the benchmarked configuration
+    D, _, _ = eu.build(B, "wasserstein", layers=layers)   # (256, 6): the benchmarked configuration
     D.train()
     fl = D.vit._flat
     g = torch.Generator().manual_seed(5)

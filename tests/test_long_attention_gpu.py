@@ -5,16 +5,12 @@ import math
 import pytest
 import torch
 
+import gpu_util as u
+
 pytestmark = pytest.mark.gpu
 
 
-def _u():
-    import gpu_util
-    return gpu_util
-
-
 def _case(B, H, S, HE, seed):
-    u = _u()
     E = H * HE
     g = torch.Generator().manual_seed(seed)
     qkv = u.rbf(torch.randn(B * S, 3 * E, generator=g) * 1.5).requires_grad_(True)
@@ -31,7 +27,6 @@ def _ref(qkv, B, H, S, HE, scale):
 
 
 def _run(QKV, DO, B, H, S, HE, scale):
-    u = _u()
     E = H * HE
     O = torch.empty(B * S, E, dtype=u.BF, device="cuda")
     LSE = torch.empty(B, H, S, device="cuda")
@@ -54,7 +49,6 @@ def test_long_attention_generator_scale():
 
 
 def _check(B, H, S, HE, scale):
-    u = _u()
     E = H * HE
     qkv, dO = _case(B, H, S, HE, B + H + S + HE)
     o, lse_ref = _ref(qkv, B, H, S, HE, scale)
@@ -73,7 +67,6 @@ def _check(B, H, S, HE, scale):
 def test_long_attention_full_size():
     """The fused real + fake batch of the ViT-B/16 geometry: B = 512, H = 12, S = 197, HE = 64.  Finite everywhere; sampled heads
     of sampled images against fp32."""
-    u = _u()
     B, H, S, HE = 512, 12, 197, 64
     E, scale = H * HE, 1 / math.sqrt(HE)
     g = torch.Generator().manual_seed(5)
@@ -99,7 +92,6 @@ def test_long_attention_full_size():
 @pytest.mark.parametrize("S,HE", [(197, 64), (256, 96), (145, 32)])
 def test_cls_query_long(S, HE):
     """The CLS-query kernels with 256 keys: against fp32 attention, and against row 0 of the full (long) kernels."""
-    u = _u()
     B, H = 3, 4
     E, scale = H * HE, 1 / math.sqrt(HE)
     g = torch.Generator().manual_seed(S + HE)

@@ -7,7 +7,6 @@ Bound of the controller: the kernel evaluates base f scale in fp64 and rounds ON
 Python float64, so |lr_out - lr_ref| <= 1 ulp32(lr_ref): half an ulp of rounding, and the two fp64 values (they differ only by the
 cosine, ~1e-16 relative) can straddle one rounding boundary and no more.  Where the factor is an explicit branch (1, or ``final``) both
 sides perform the same two IEEE fp64 products, so the result is fp32(lr_ref) bit for bit.  Everything else here is equality."""
-import ctypes as C
 import functools
 import json
 import os
@@ -17,20 +16,17 @@ import numpy as np
 import pytest
 import torch
 
+import engine_util as eu
 import lr_ref
 import step_trace as stt
 from adamw_ref import check_adamw_step, f32, ulp32
+import gpu_util as u
 
 pytestmark = pytest.mark.gpu
 
 BF = torch.bfloat16
 LR_D, LR_G = 5e-4, 2e-4  # two base rates: a rate applied to the wrong network cannot go unseen
 COS = dict(lr_schedule="cosine", lr_warmup=3, lr_total=8, lr_final=0.1)
-
-
-def _u():
-    import gpu_util as u
-    return u
 
 
 def _within_one_ulp(got: float, want: float) -> bool:
@@ -111,20 +107,10 @@ GUARD = 1028  # elements in front of and behind every range: a multiple of 4, no
 
 
 def _state(n, seed):
-    """Per-element edges, like tests/test_optimizer_gpu.py: gradients of exactly 0, ~1e-6, ~1 and ~1e3; moments carried over from
-    earlier steps (some zero); |p| from 1e-4 to 10; an average near and far from p."""
-    gen = torch.Generator().manual_seed(seed)
-    p = torch.sign(torch.randn(n, generator=gen)) * 10.0 ** (torch.rand(n, generator=gen) * 5 - 4)
-    g = torch.randn(n, generator=gen) * torch.tensor([0.0, 1e-6, 1.0, 1e3])[torch.arange(n) % 4]
-    h = torch.tensor([1.0, 1e-6, 1e3, 0.0])[torch.randperm(n, generator=gen) % 4]
-    m = torch.randn(n, generator=gen) * h * 0.3
-    v = (torch.randn(n, generator=gen) * h) ** 2
+    """gpu_util.adamw_state and an average near and far from p"""
+    p, m, v, g, gen = u.adamw_state(n, seed)
     e = p - p * 1e-3 * torch.randn(n, generator=gen)
     return p, m, v, g, e
-
-
-def _off(t, elems):
-    return C.c_void_p(t.data_ptr() + t.element_size() * elems)
 
 
 @pytest.mark.parametrize("n", [4, 4096, 4100])
@@ -132,7 +118,6 @@ def test_device_rate_adamw_is_the_float_form_bit_for_bit(n):
     """n = 4: one thread; 4096: whole workgroups; 4100: a last workgroup with one live thread.  Three counter values, gscale 1 and 0.5,
     both slots of a rate pair that a controller launch has just written on the same stream."""
     from vit_gan_amd import ops
-    u = _u()
     total = n + 2 * GUARD
     b1, b2, eps, wd = 0.9, 0.999, 1e-8, 1e-3
     worst = 0.0
@@ -147,14 +132,14 @@ def test_device_rate_adamw_is_the_float_form_bit_for_bit(n):
                 rates = ops.lr_schedule(step_dev, (LR_D, "cosine", 3, 2000, 0.1), (LR_G, "linear", 0, 1500, 0.0))
                 lr_dev = rates[slot:slot + 1]
                 tail = (b1, b2, eps, wd, 0, u.ptr(step_dev), gscale)
-                u.call("vg_adamw_step_dlr", *(_off(x, GUARD) for x in dl["adam"][:5]), n, u.ptr(lr_dev), *tail, u.stream())
-                u.call("vg_adamw_ema_step_dlr", *(_off(x, GUARD) for x in dl["ema"]), n, u.ptr(lr_dev), *tail, 0.999, 0, u.stream())
+                u.call("vg_adamw_step_dlr", *(u.off(x, GUARD) for x in dl["adam"][:5]), n, u.ptr(lr_dev), *tail, u.stream())
+                u.call("vg_adamw_ema_step_dlr", *(u.off(x, GUARD) for x in dl["ema"]), n, u.ptr(lr_dev), *tail, 0.999, 0, u.stream())
                 lr = float(lr_dev[0])  # (synchronises) the float the kernels read
                 assert lr > 0 and _within_one_ulp(lr, lr_ref.lr_now(LR_G, "linear", t, 0, 1500, 0.0) if slot else lr_ref.lr_now(LR_D, "cosine", t, 3, 2000, 0.1))
                 fl = {name: [u.dev(x.clone()) for x in (p0, g, m0, v0)] + [torch.full((total,), -7.0, dtype=BF, device="cuda"), u.dev(e0.clone())]
                       for name in ("adam", "ema")}
-                u.call("vg_adamw_step", *(_off(x, GUARD) for x in fl["adam"][:5]), n, lr, *tail, u.stream())
-                u.call("vg_adamw_ema_step", *(_off(x, GUARD) for x in fl["ema"]), n, lr, *tail, 0.999, 0, u.stream())
+                u.call("vg_adamw_step", *(u.off(x, GUARD) for x in fl["adam"][:5]), n, lr, *tail, u.stream())
+                u.call("vg_adamw_ema_step", *(u.off(x, GUARD) for x in fl["ema"]), n, lr, *tail, 0.999, 0, u.stream())
                 u.sync()
                 assert int(step_dev[0]) == t and float(lr_dev[0]) == lr, f"{what}: the counter or the rate was written"
                 for name in ("adam", "ema"):
@@ -177,7 +162,6 @@ def test_device_rate_adamw_is_the_float_form_bit_for_bit(n):
 
 
 def test_refused_device_rate_calls_launch_nothing():
-    u = _u()
     from vit_gan_amd import _lib
     n = 4096
     P, G_, M, V, E = (torch.full((n,), 0.25, device="cuda") for _ in range(5))
@@ -199,21 +183,11 @@ def test_refused_device_rate_calls_launch_nothing():
 
 
 # ------------------------------------------------------------------------------------------------------------------------ engine
-def _data(n, skip=0):
-    g = torch.Generator().manual_seed(4)
-    out = []
-    for i in range(skip + n):
-        real, z = torch.rand(stt.B, 3, 32, 32, generator=g) * 2 - 1, torch.randn(stt.B, 1024, generator=g)
-        if i >= skip:
-            out.append((real.cuda(), z.cuda()))
-    return out
-
-
 def _run(eng, n, skip=0, before=None):
     """n steps; ``before(eng, k)`` runs ahead of step k (1-based over the whole run).  Returns the losses and, with a schedule on, the
     rates read back after each step."""
     losses, rates = [], []
-    for k, (real, z) in enumerate(_data(n, skip), start=skip + 1):
+    for k, (real, z) in enumerate(eu.batches(stt.B, n, skip=skip), start=skip + 1):
         if before is not None:
             before(eng, k)
         losses.append(eng.step(real, z).clone())
@@ -377,68 +351,44 @@ def test_graph_replay_follows_the_schedule_and_the_multipliers(name):
     assert r1[8][0] == r1[7][0] and _within_one_ulp(r1[7][0], 0.5 * f32(LR_D) * f32(0.1))
 
 
-def _shard_worker(port, out):
-    import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    import torch.distributed as dist
-    try:
-        torch.cuda.set_device(0)
-        dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-        import vit_gan_amd  # noqa: F401
-        from vit_gan_amd.config import Config
-        from vit_gan_amd.engine import GanEngine
-        from vit_gan_amd.generator import SirenGenerator
-        from vit_gan_amd.modules import ViTDiscriminator
-        B = 16
-        res = []
-        for use_graph, shard in ((False, False), (False, True), (True, True)):
-            torch.manual_seed(0)
-            D = ViTDiscriminator(Config(embeddings_dimension=128, classes_count=1, batch_size=B, transformer_blocks_count=3)).cuda().train()
-            G = SirenGenerator(embed=128, layers=2, siren_hidden=256).cuda().train()
-            eng = GanEngine(D, G, batch=B, seed=4, use_graph=use_graph, external_noise=True, ema_decay=0.999, ema_start=2,
-                            exchange_single_rank=shard, shard_mapping_update=shard, lr_d=5e-4, lr_g=2e-4, lr_schedule="cosine", lr_warmup=2,
-                            lr_total=5, lr_final=0.1)
-            assert eng.shard_map == shard and eng.sync.active == shard
-            g = torch.Generator().manual_seed(9)
-            ls, rates = [], []
-            for _ in range(4):
-                real = (torch.rand(B, 3, 32, 32, generator=g) * 2 - 1).cuda()
-                z = torch.randn(B, 1024, generator=g).cuda()
-                ls.append(eng.step(real, z).clone())
-                rates.append(eng.lr)
-            torch.cuda.synchronize()
-            res.append((torch.stack(ls).cpu(), G._flat.flat.detach().cpu().clone(), eng.ema_g.detach().cpu().clone(), eng.graph_active,
-                        eng.graph_fallback_reason, rates))
-            eng.close()
-        plain, shard_eager, shard_graph = res
-        report = {"graph": shard_graph[3] and shard_graph[4] is None,
-                  "scheduled": len({r[1] for r in plain[5]}) == 4 and plain[5] == shard_eager[5] == shard_graph[5],
-                  "eager_master": torch.equal(shard_eager[1], plain[1]), "eager_ema": torch.equal(shard_eager[2], plain[2]),
-                  "graph_master": torch.equal(shard_graph[1], plain[1]), "graph_ema": torch.equal(shard_graph[2], plain[2]),
-                  "losses": torch.equal(shard_eager[0], plain[0]) and torch.equal(shard_graph[0], plain[0])}
-        out.put(("ok", report))
-        dist.destroy_process_group()
-    except Exception as e:
-        out.put(("err", f"{type(e).__name__}: {e}"))
+def _shard_worker(rank, world):
+    import vit_gan_amd  # noqa: F401
+    from vit_gan_amd.config import Config
+    from vit_gan_amd.engine import GanEngine
+    from vit_gan_amd.generator import SirenGenerator
+    from vit_gan_amd.modules import ViTDiscriminator
+    B = 16
+    res = []
+    for use_graph, shard in ((False, False), (False, True), (True, True)):
+        torch.manual_seed(0)
+        D = ViTDiscriminator(Config(embeddings_dimension=128, classes_count=1, batch_size=B, transformer_blocks_count=3)).cuda().train()
+        G = SirenGenerator(embed=128, layers=2, siren_hidden=256).cuda().train()
+        eng = GanEngine(D, G, batch=B, seed=4, use_graph=use_graph, external_noise=True, ema_decay=0.999, ema_start=2,
+                        exchange_single_rank=shard, shard_mapping_update=shard, lr_d=5e-4, lr_g=2e-4, lr_schedule="cosine", lr_warmup=2,
+                        lr_total=5, lr_final=0.1)
+        assert eng.shard_map == shard and eng.sync.active == shard
+        ls, rates = [], []
+        for real, z in eu.batches(B, 4, seed=9):
+            ls.append(eng.step(real, z).clone())
+            rates.append(eng.lr)
+        torch.cuda.synchronize()
+        res.append((torch.stack(ls).cpu(), G._flat.flat.detach().cpu().clone(), eng.ema_g.detach().cpu().clone(), eng.graph_active,
+                    eng.graph_fallback_reason, rates))
+        eng.close()
+    plain, shard_eager, shard_graph = res
+    report = {"graph": shard_graph[3] and shard_graph[4] is None,
+              "scheduled": len({r[1] for r in plain[5]}) == 4 and plain[5] == shard_eager[5] == shard_graph[5],
+              "eager_master": torch.equal(shard_eager[1], plain[1]), "eager_ema": torch.equal(shard_eager[2], plain[2]),
+              "graph_master": torch.equal(shard_graph[1], plain[1]), "graph_ema": torch.equal(shard_graph[2], plain[2]),
+              "losses": torch.equal(shard_eager[0], plain[0]) and torch.equal(shard_graph[0], plain[0])}
+    return report
 
 
 @pytest.mark.timeout(300)
 def test_sharded_update_follows_the_schedule():
     """shard_mapping_update on a one-rank RCCL group with the schedule on (every piece of the generator's sharded AdamW is a _dlr call
     on slot 1), eager and captured, against the replicated scheduled engine: master and average bit for bit.  A fresh spawned process."""
-    import socket
-    import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    out = ctx.Queue()
-    p = ctx.Process(target=_shard_worker, args=(port, out))
-    p.start()
-    status, val = out.get(timeout=240)
-    p.join(timeout=60)
-    assert status == "ok", val
+    (val,) = eu.run_ranks(_shard_worker, 1, 240, backend="nccl", gpu=True)
     assert all(val.values()), val
 
 

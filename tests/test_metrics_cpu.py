@@ -6,21 +6,16 @@ arguments.  Every test here fails on the parent commit: no ``metrics`` module, n
 (``train_model`` itself needs the GPU, so its ``fid=""`` log line, ``FID: nan``, is asserted in tests/test_metrics_gpu.py; here the
 order of its argument checks is.)"""
 import ctypes as C
-import os
-import socket
-import sys
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
+import engine_util as eu
 import metrics_ref as mr
 import vit_gan_amd  # noqa: F401
 from vit_gan_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(16, 200), (64, 40), (128, 200), (384, 200), (384, 2000)]  # (d, n); n < d: rank-deficient covariances
 
 
@@ -153,48 +148,24 @@ def test_feature_moments_cpu_path_against_the_restatement():
         one.update(x.double())
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
+def _worker(rank, world):
+    import vit_gan_amd  # noqa: F401
+    from vit_gan_amd.metrics import FeatureMoments
 
-
-def _worker(rank, world, port, out):
-    sys.path.insert(0, ROOT)
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        import vit_gan_amd  # noqa: F401
-        from vit_gan_amd.metrics import FeatureMoments
-
-        torch.set_num_threads(2)
-        d, n = 32, 101
-        x = torch.randn(n, d, generator=torch.Generator().manual_seed(9))
-        lo, hi = (0, 37) if rank == 0 else (37, n)  # uneven shards
-        m = FeatureMoments(d).update(x[lo:hi]).all_reduce()
-        whole = FeatureMoments(d).update(x)
-        err = max(float((m.sum - whole.sum).abs().max()), float((m.gram - whole.gram).abs().max()) / float(whole.gram.abs().max()))
-        if rank == 0:
-            out.put(("ok", (m.n, err)))
-    except Exception as e:  # surface the failure in the parent
-        out.put(("err", f"rank {rank}: {type(e).__name__}: {e}"))
-    finally:
-        dist.destroy_process_group()
+    torch.set_num_threads(2)
+    d, n = 32, 101
+    x = torch.randn(n, d, generator=torch.Generator().manual_seed(9))
+    lo, hi = (0, 37) if rank == 0 else (37, n)  # uneven shards
+    m = FeatureMoments(d).update(x[lo:hi]).all_reduce()
+    whole = FeatureMoments(d).update(x)
+    err = max(float((m.sum - whole.sum).abs().max()), float((m.gram - whole.gram).abs().max()) / float(whole.gram.abs().max()))
+    if rank == 0:
+        return m.n, err
 
 
 @pytest.mark.timeout(300)
 def test_two_rank_gloo_all_reduce_of_the_moments():
-    world = 2
-    ctx = mp.get_context("spawn")
-    out = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, out)) for r in range(world)]
-    for p in procs:
-        p.start()
-    status, val = out.get(timeout=240)
-    for p in procs:
-        p.join(timeout=60)
-    assert status == "ok", val
+    val = eu.run_ranks(_worker, 2, 240)[0]
     assert val[0] == 101 and val[1] <= 1e-13, val
 
 

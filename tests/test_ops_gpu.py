@@ -12,22 +12,18 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import gpu_util as u
+
 pytestmark = pytest.mark.gpu
 
 BF_TOL = 2.0 ** -7
 F32_TOL = 3e-5
 
 
-def _u():
-    import gpu_util
-    return gpu_util
-
-
 @pytest.mark.parametrize("M,N,K", [(130, 384, 384), (260, 1152, 384), (77, 96, 768), (256, 384, 48), (64, 768, 96),
                                    (1040, 768, 384)])
 @pytest.mark.parametrize("act", [0, 1, 2, 3])
 def test_linear_fwd(M, N, K, act):
-    u = _u()
     g = torch.Generator().manual_seed(M * 7 + N + K + act)
     A = u.rbf(torch.randn(M, K, generator=g))
     W = u.rbf(torch.randn(N, K, generator=g) / math.sqrt(K))
@@ -59,7 +55,6 @@ WR_SHAPES = [(256, 384), (1312, 1152), (4160, 768), (16640, 1152), (33280, 384),
 @pytest.mark.parametrize("M,N", [(1312, 768), (16640, 768)])
 def test_linear_gelu_fwd_weights_in_registers(M, N):
     """fc1: GELU epilogue with the bf16 pre-activation as second output."""
-    u = _u()
     K = 384
     g = torch.Generator().manual_seed(M + N)
     A = u.rbf(torch.randn(M, K, generator=g))
@@ -86,7 +81,6 @@ def test_linear_gelu_fwd_byte_derivative(M, N, K):
     """fc1 as the engine runs it: bf16 gelu(pre) + gelu'(pre) as ONE BYTE per element, code = round(200 g) + 27 (exact at 0 and 1);
     decoded it is within half a grid step (0.0025) of the fp32 derivative, plus what the accumulation order moves near a rounding
     boundary (one more step)."""
-    u = _u()
     g = torch.Generator().manual_seed(M + N + K)
     A = u.rbf(torch.randn(M, K, generator=g) * 1.5)
     W = u.rbf(torch.randn(N, K, generator=g) / math.sqrt(K))
@@ -114,7 +108,6 @@ def test_linear_gelu_fwd_byte_derivative(M, N, K):
 @pytest.mark.parametrize("M,K,N", [(1312, 768, 384), (33280, 1536, 384), (130, 768, 192), (260, 2048, 512), (100, 96, 768)])
 def test_linear_dgrad_byte_derivative(M, K, N):
     """fc2 input gradient times the decoded one-byte derivative (mul_mode 8), on both kernels."""
-    u = _u()
     g = torch.Generator().manual_seed(M + 5 * K + N)
     dY = u.rbf(torch.randn(M, N, generator=g))
     W = u.rbf(torch.randn(N, K, generator=g) / math.sqrt(N))
@@ -131,7 +124,6 @@ def test_linear_dgrad_byte_derivative(M, K, N):
 @pytest.mark.parametrize("M,N", WR_SHAPES)
 @pytest.mark.parametrize("res", [False, True])
 def test_linear_fwd_weights_in_registers(M, N, res):
-    u = _u()
     K = 384
     g = torch.Generator().manual_seed(M + 3 * N + int(res))
     A = u.rbf(torch.randn(M, K, generator=g))
@@ -153,7 +145,6 @@ def test_linear_fwd_weights_in_registers(M, N, res):
 @pytest.mark.parametrize("mul", [0, 7])
 def test_linear_dgrad_weights_in_registers(M, K, mul):
     """dX[M, K] = dY[M, 384] @ W[384, K] (the out-proj / fc2 input gradients), optionally times a stored derivative."""
-    u = _u()
     N = 384
     g = torch.Generator().manual_seed(M + 5 * K + mul)
     dY = u.rbf(torch.randn(M, N, generator=g))
@@ -174,7 +165,6 @@ def test_linear_dgrad_weights_in_registers(M, K, mul):
 @pytest.mark.parametrize("M,N,K", [(130, 384, 384), (260, 1152, 384), (192, 768, 96), (256, 48, 384), (100, 96, 768)])
 @pytest.mark.parametrize("mul", [0, 4, 5])
 def test_linear_dgrad(M, N, K, mul):
-    u = _u()
     g = torch.Generator().manual_seed(M + N * 3 + K + mul)
     dY = u.rbf(torch.randn(M, N, generator=g))
     W = u.rbf(torch.randn(N, K, generator=g) / math.sqrt(N))
@@ -203,7 +193,6 @@ def test_linear_dgrad(M, N, K, mul):
                                           (33280, 1152, 384, 10),
                                           (2080, 1536, 512, 4), (1040, 512, 1024, 8), (64, 128, 512, 1)])  # 128 x 512 tiles (E = 512)
 def test_linear_wgrad(M, N, K, splits):
-    u = _u()
     g = torch.Generator().manual_seed(M + N + K)
     dY = u.rbf(torch.randn(M, N, generator=g))
     X = u.rbf(torch.randn(M, K, generator=g))
@@ -226,7 +215,6 @@ def test_linear_wgrad(M, N, K, splits):
 
 @pytest.mark.parametrize("R,E", [(130, 384), (65, 128), (33, 512), (7, 768)])
 def test_layernorm(R, E):
-    u = _u()
     g = torch.Generator().manual_seed(R + E)
     x = u.rbf(torch.randn(R, E, generator=g) * 2 + 0.5).requires_grad_(True)
     gam = (1 + 0.1 * torch.randn(E, generator=g)).requires_grad_(True)
@@ -260,7 +248,6 @@ def test_layernorm(R, E):
 
 @pytest.mark.parametrize("B,T,E,bcast", [(3, 32, 384, True), (3, 32, 384, False), (2, 17, 128, False)])
 def test_sln(B, T, E, bcast):
-    u = _u()
     g = torch.Generator().manual_seed(B + T + E + int(bcast))
     R = B * T
     h = u.rbf(torch.randn(T if bcast else R, E, generator=g)).requires_grad_(True)
@@ -310,7 +297,6 @@ def test_sln(B, T, E, bcast):
 @pytest.mark.parametrize("B,H,S,HE,scale", [(3, 4, 65, 96, None), (2, 4, 32, 96, 1 / math.sqrt(384)), (2, 8, 65, 64, None),
                                             (2, 4, 65, 32, None), (2, 2, 17, 64, None), (1, 4, 80, 96, None), (2, 4, 1, 32, None)])
 def test_attention(B, H, S, HE, scale):
-    u = _u()
     E = H * HE
     scale = scale or 1 / math.sqrt(HE)
     g = torch.Generator().manual_seed(B + H + S + HE)
@@ -341,7 +327,6 @@ def test_attention(B, H, S, HE, scale):
 def test_attention_cls_query(B, H, S, HE):
     """The top block's attention as the classifier sees it (one query per image, row 0): against fp32 attention, and against the
     full kernels at that row - the forward's row 0, and the backward fed a d_out that is zero on every other row."""
-    u = _u()
     E, scale = H * HE, 1 / math.sqrt(HE)
     g = torch.Generator().manual_seed(B + H + S + HE)
     qkv = u.rbf(torch.randn(B * S, 3 * E, generator=g) * 1.5).requires_grad_(True)
@@ -383,7 +368,6 @@ def test_attention_cls_query(B, H, S, HE):
 @pytest.mark.parametrize("kind", [0, 1])
 @pytest.mark.parametrize("role", [0, 1, 2])
 def test_gan_loss(kind, role):
-    u = _u()
     from oracle import step_oracle as so
     x = (torch.randn(300, generator=torch.Generator().manual_seed(role + 3 * kind)) * 2).requires_grad_(True)
     name = "ns" if kind == 0 else "hinge"
@@ -401,7 +385,6 @@ def test_gan_loss(kind, role):
 @pytest.mark.parametrize("kind", [0, 1, 2])
 def test_gan_loss_pair_is_two_single_calls(kind):
     """The fused real + fake pass evaluates both halves' losses in one launch: bit-equal to the two single launches."""
-    u = _u()
     g = torch.Generator().manual_seed(kind)
     n0, n1 = 256, 256
     x = u.dev(torch.randn(n0 + n1, generator=g) * 2)
@@ -417,7 +400,6 @@ def test_gan_loss_pair_is_two_single_calls(kind):
 def test_step_begin_kernels():
     """vg_zero_tick: zero_grad + device step counter in one launch; vg_step_inputs: bf16 cast of the real batch (torch's rounding) and the
     latent batch ~ N(0, 1), counter-based on (seed, step): reproducible, fresh per step and per seed, moments of a normal sample."""
-    u = _u()
     g = torch.full((4096 + 4,), 3.0, device="cuda")
     step = torch.tensor([7], dtype=torch.int32, device="cuda")
     u.call("vg_zero_tick", u.ptr(g), 4096, u.ptr(step), u.stream())
@@ -454,7 +436,6 @@ def test_step_begin_kernels():
 
 
 def test_adamw_matches_torch():
-    u = _u()
     n = 4096 + 64
     g = torch.Generator().manual_seed(5)
     p0 = torch.randn(n, generator=g)
@@ -475,7 +456,6 @@ def test_adamw_matches_torch():
 
 
 def test_grad_clip_matches_torch():
-    import gpu_util as u
     g = torch.Generator().manual_seed(3)
     for n, max_norm, gscale in ((4096, 0.5, 1.0), (1 << 20, 5.0, 0.25), (1000 * 4, 100.0, 1.0)):
         x = torch.randn(n, generator=g) * 0.01
@@ -491,7 +471,6 @@ def test_grad_clip_matches_torch():
 
 
 def test_wasserstein_loss_kind():
-    import gpu_util as u
     x = torch.randn(37, generator=torch.Generator().manual_seed(1))
     for role, want, dw in ((0, -x.mean(), -1.0), (1, x.mean(), 1.0), (2, -x.mean(), -1.0)):
         xd, dl, lo = u.dev(x), torch.empty(37, device="cuda"), torch.empty(1, device="cuda")
@@ -505,7 +484,6 @@ def test_wasserstein_loss_kind():
 def test_diversity_loss_matches_torch(B, D):
     """vg_diversity_loss vs torch.cdist(p=1) (src/v2/utils.py:147-152): loss within 1e-4 relative; gradient (added onto an
     existing bf16 gradient) within 2^-7 of max|ref|."""
-    import gpu_util as u
     g = torch.Generator().manual_seed(B + D)
     x = torch.randn(B, D, generator=g).to(torch.bfloat16)
     d0 = (torch.randn(B, D, generator=g) * 1e-3).to(torch.bfloat16)
@@ -525,7 +503,6 @@ def test_diversity_loss_matches_torch(B, D):
 def test_linear_wgrad_rejects_undersized_slab_without_launching():
     """Round-1 fault (gpurun_out/splits.log: 'Write access to a read-only page'): K slices written past a slab carved for
     fewer slices.  The public entry point now takes the slab size and refuses; nothing is launched (dW untouched)."""
-    u = _u()
     M, N, K = 512, 128, 128
     a = torch.zeros(M, N, dtype=u.BF, device="cuda"); b = torch.zeros(M, K, dtype=u.BF, device="cuda")
     dW = torch.full((N, K), 7.0, device="cuda")
@@ -551,7 +528,6 @@ def test_attention_fp8(B, H, S, HE):
     the operands quantised where the kernel quantises them (e4m3 Q, K for the scores in forward AND backward recompute;
     e4m3 of 256 p and of V for P.V; every gradient-carrying product in bf16) - tight, it pins layout and scaling;
     (b) plain fp32 attention - loose: what e4m3's 3 mantissa bits cost."""
-    u = _u()
     E, scale = H * HE, 1 / math.sqrt(HE)
     f8 = torch.float8_e4m3fn
     g = torch.Generator().manual_seed(B + H + S + HE)

@@ -1,13 +1,13 @@
 """The optimizer kernels on the engine's path: vg_adamw_step with the device step counter (what GanEngine passes) and without it,
 against the float64 AdamW of tests/adamw_ref.py, and vg_cast_f32_bf16 (the only writer of the bf16 shadow every GEMM reads)
 against torch's round-to-nearest-even."""
-import ctypes as C
 
 import numpy as np
 import pytest
 import torch
 
 from adamw_ref import check_adamw_step
+import gpu_util as u
 
 pytestmark = pytest.mark.gpu
 
@@ -15,39 +15,17 @@ BF = torch.bfloat16
 LR, EPS = 5e-4, 1e-8
 
 
-def _u():
-    import gpu_util as u
-    return u
-
-
-def _off(t, elems):
-    return C.c_void_p(t.data_ptr() + t.element_size() * elems)
-
-
-def _state(n, seed):
-    """Per-element edges: gradients of exactly 0 (eps dominates), ~1e-6, ~1 and ~1e3; moments carried over from earlier steps
-    (some zero); |p| from 1e-4 to 10."""
-    gen = torch.Generator().manual_seed(seed)
-    p = torch.sign(torch.randn(n, generator=gen)) * 10.0 ** (torch.rand(n, generator=gen) * 5 - 4)
-    g = torch.randn(n, generator=gen) * torch.tensor([0.0, 1e-6, 1.0, 1e3])[torch.arange(n) % 4]
-    h = torch.tensor([1.0, 1e-6, 1e3, 0.0])[torch.randperm(n, generator=gen) % 4]
-    m = torch.randn(n, generator=gen) * h * 0.3
-    v = (torch.randn(n, generator=gen) * h) ** 2
-    return p, m, v, g
-
-
 def _run(t, betas, device_counter, n=8196, lo=0, total=None, seed=None, lr=LR, wds=(0.0, 1e-3)):
     """All (gscale, wd) combinations at step t on n elements starting at element lo of buffers of `total` elements."""
-    u = _u()
     total = n if total is None else total
-    p0, m0, v0, g = _state(total, seed if seed is not None else 7 * t + int(100 * betas[0]))
+    p0, m0, v0, g, _ = u.adamw_state(total, seed if seed is not None else 7 * t + int(100 * betas[0]))
     worst = (0.0, 0.0)
     for gscale in (1.0, 0.5, 0.125):
         for wd in wds:
             P, M, V, G_ = (u.dev(x.clone()) for x in (p0, m0, v0, g))
             SH = torch.full((total,), -7.0, dtype=BF, device="cuda")
             step_dev = torch.tensor([t], dtype=torch.int32, device="cuda") if device_counter else None
-            u.call("vg_adamw_step", _off(P, lo), _off(G_, lo), _off(M, lo), _off(V, lo), _off(SH, lo), n, lr, betas[0], betas[1], EPS, wd,
+            u.call("vg_adamw_step", u.off(P, lo), u.off(G_, lo), u.off(M, lo), u.off(V, lo), u.off(SH, lo), n, lr, betas[0], betas[1], EPS, wd,
                    0 if device_counter else t, u.ptr(step_dev), gscale, u.stream())
             u.sync()
             if device_counter:
@@ -100,7 +78,6 @@ def test_adamw_decays_before_the_moment_step(t):
 
 
 def test_adamw_rejects_a_length_not_divisible_by_4():
-    u = _u()
     from vit_gan_amd import _lib
     n = 4098
     P, G_, M, V = (torch.full((n,), 0.25, device="cuda") for _ in range(4))
@@ -138,13 +115,12 @@ NAN_WORDS = [0x7FC00000, 0xFFC00000, 0x7F800001, 0xFF800001, 0x7FFFFFFF, 0xFFFFF
 
 
 def _cast(x, lo=0, total=None):
-    u = _u()
     n = x.numel()
     total = n if total is None else total
     src = torch.zeros(total, dtype=torch.float32, device="cuda")
     src[lo:lo + n] = x.cuda()
     dst = torch.full((total,), 3.0, dtype=BF, device="cuda")
-    u.call("vg_cast_f32_bf16", _off(src, lo), _off(dst, lo), n, u.stream())
+    u.call("vg_cast_f32_bf16", u.off(src, lo), u.off(dst, lo), n, u.stream())
     u.sync()
     d = dst.cpu()
     out = torch.ones(total, dtype=torch.bool)
@@ -182,7 +158,6 @@ def test_cast_random_data_is_rne(n):
 
 
 def test_cast_rejects_a_length_not_divisible_by_4():
-    u = _u()
     from vit_gan_amd import _lib
     src = torch.ones(6, device="cuda")
     dst = torch.zeros(6, dtype=BF, device="cuda")

@@ -8,6 +8,8 @@ import os
 import pytest
 import torch
 
+import engine_util as eu
+
 pytestmark = pytest.mark.gpu
 
 
@@ -192,9 +194,8 @@ def test_r1_c_call_with_dropout_is_the_gradient_of_its_own_value():
     """The five passes must draw the same masks: a mismatch leaves the value fine and the gradient wrong.  The directional derivative of
     the call's VALUE along its own gradient, central differences on the fp32 master (same seed and step counter = same masks), against
     |gradient|^2 - the gradient penalty's test on vg_vit_r1, in the project's band (0.8, 1.25)."""
-    from test_engine_gpu import _build
     B = 16
-    D, _, _ = _build(B, "ns", layers=2)
+    D, _, _ = eu.build(B, "ns", layers=2)
     D.train()
     fl = D.vit._flat
     x = (torch.rand(B, 3, 32, 32, generator=torch.Generator().manual_seed(5)) * 2 - 1).cuda()
@@ -220,11 +221,6 @@ def test_r1_c_call_with_dropout_is_the_gradient_of_its_own_value():
     assert 0.8 < fd / gn2 < 1.25
 
 
-def _data(B, n, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return [((torch.rand(B, 3, 32, 32, generator=g) * 2 - 1).cuda(), torch.randn(B, 1024, generator=g).cuda()) for _ in range(n)]
-
-
 def test_engine_step_adds_the_r1_gradient():
     """One eager step of two engines on identical modules and inputs, R1 on (gamma 10) and off.  D's own pass of the first step does
     not see the penalty: the discriminator's two losses are bit-equal.  (The generator's loss is taken through the UPDATED D, training.py:
@@ -241,12 +237,11 @@ def test_engine_step_adds_the_r1_gradient():
     rows or slices of the same batch are gradients of the same kind; they are given no more room than the totals),
         |(on - off) - r| <= (2 k - 1) 2^-24 S <= 67 * 2^-24 * S ~ 4.0e-6 S.   The difference itself is taken in float64."""
     from vit_gan_amd.engine import GanEngine
-    from test_engine_gpu import _build
     B = 16
-    (real, z), = _data(B, 1)
+    (real, z), = eu.batches(B, 1, seed=0)
     res = {}
     for gamma in (10.0, 0.0):
-        D, G, _ = _build(B, "ns")
+        D, G, _ = eu.build(B, "ns")
         eng = GanEngine(D, G, batch=B, loss="ns", external_noise=True, d_dropout=0.0, g_dropout=0.0, r1_gamma=gamma, seed=2)
         w_before = D.vit._flat.flat.detach().clone()
         losses = eng.step(real, z).clone()
@@ -320,12 +315,11 @@ def test_lazy_schedule_in_the_call_trace():
 
 def test_r1_loss_changes_on_due_steps_only():
     from vit_gan_amd.engine import GanEngine
-    from test_engine_gpu import _build
     B = 8
-    D, G, _ = _build(B, "ns")
+    D, G, _ = eu.build(B, "ns")
     eng = GanEngine(D, G, batch=B, external_noise=True, r1_gamma=10.0, r1_interval=4)
     seen = [eng.r1_loss.clone()]
-    for real, z in _data(B, 6):
+    for real, z in eu.batches(B, 6, seed=0):
         eng.step(real, z)
         seen.append(eng.r1_loss.clone())
     torch.cuda.synchronize()
@@ -337,8 +331,7 @@ def test_r1_loss_changes_on_due_steps_only():
 def _run(B, n, use_graph, p_drop=0.1, first=None, **kw):
     """n steps (after loading ``first`` = (engine state, D weights, G weights, steps done)) -> (losses, D master, G master, r1_loss, engine)"""
     from vit_gan_amd.engine import GanEngine
-    from test_engine_gpu import _build
-    D, G, _ = _build(B, "ns")
+    D, G, _ = eu.build(B, "ns")
     eng = GanEngine(D, G, batch=B, external_noise=True, use_graph=use_graph, d_dropout=p_drop, g_dropout=p_drop, seed=1, **kw)
     skip = 0
     if first is not None:
@@ -346,7 +339,7 @@ def _run(B, n, use_graph, p_drop=0.1, first=None, **kw):
         D.load_state_dict(d_sd)
         G.load_state_dict(g_sd)
         eng.load_state_dict(state)
-    ls = [eng.step(real, z).clone() for real, z in _data(B, skip + n)[skip:]]
+    ls = [eng.step(real, z).clone() for real, z in eu.batches(B, n, skip=skip, seed=0)]
     torch.cuda.synchronize()
     return torch.stack(ls).cpu(), D.vit._flat.flat.detach().cpu().clone(), G._flat.flat.detach().cpu().clone(), eng.r1_loss.cpu().clone(), eng, D, G
 

@@ -19,6 +19,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import gpu_util as u
+
 pytestmark = pytest.mark.gpu
 
 BF_TOL = 2.0 ** -7
@@ -34,11 +36,6 @@ def width(request):
     E = request.param
     yield
     E = 384
-
-
-def _u():
-    import gpu_util
-    return gpu_util
 
 
 def _rcall(u, name, *args):
@@ -70,7 +67,6 @@ SHAPES = [(16, 384), (48, 768), (1040, 384), (2080, 1152), (2096, 768), (4160, 7
 @pytest.mark.parametrize("M,K", SHAPES)
 @pytest.mark.parametrize("drop", [0.0, 0.1])
 def test_linear_ln_fwd(M, K, drop):
-    u = _u()
     g = torch.Generator().manual_seed(M + K)
     A = u.rbf(torch.randn(M, K, generator=g))
     W = u.rbf(torch.randn(E, K, generator=g) / math.sqrt(K))
@@ -117,7 +113,6 @@ def test_linear_ln_fwd(M, K, drop):
 @pytest.mark.parametrize("M,K", SHAPES)
 @pytest.mark.parametrize("drop", [0.0, 0.1])
 def test_linear_dgrad_ln_bwd(M, K, drop):
-    u = _u()
     g = torch.Generator().manual_seed(M * 3 + K)
     dY = u.rbf(torch.randn(M, K, generator=g))
     W = u.rbf(torch.randn(K, E, generator=g) / math.sqrt(K))  # nn.Linear(E, K).weight: the Linear the LayerNorm feeds
@@ -168,7 +163,6 @@ def test_linear_dgrad_ln_bwd(M, K, drop):
 
 
 def test_row_kernel_rejects_unsupported_shapes():
-    u = _u()
     L = u._lib.lib()
     if E != 384:
         assert L.vg_row_pack_elems_e(E, 48) == -2 and L.vg_row_pack_elems_e(768, 768) == -2 and L.vg_row_pack_elems_e(E, 1024) == E * 1024
@@ -191,7 +185,6 @@ def test_row_kernel_rejects_unsupported_shapes():
 def test_row_kernel_race_screen(M, K):
     """The ring protocol (counted vmcnt per wave, one barrier per stage, fragments a stage ahead) under repetition: 40 launches of
     the same problem must be bit-identical (an early fragment read or a late DMA shows as a rare differing tile)."""
-    u = _u()
     g = torch.Generator().manual_seed(5)
     A = u.dev(torch.randn(M, K, generator=g), u.BF)
     W = torch.randn(E, K, generator=g) / math.sqrt(K)
@@ -212,7 +205,6 @@ def test_rows_do_not_depend_on_the_tile_they_land_in(K):
     """A row's result must be BIT-identical whatever the batch around it: the same 2 080 rows are run as a problem of their own
     (tiles of 2 m-tiles), as the head of 16 640 rows (4-5 m-tiles) and of 33 280 rows (8-9 m-tiles).  The epilogue is
     instantiated per tile height; this is what catches a multiply-add contracted in one instantiation and not in another."""
-    u = _u()
     g = torch.Generator().manual_seed(11)
     Mbig, Ms = 33280, 2080
     A = u.dev(torch.randn(Mbig, K, generator=g), u.BF)
@@ -248,7 +240,6 @@ def test_fused_forward_is_bit_identical_to_the_unfused_pair(M, K):
     normalised rows agree BIT for bit (same k order in the MFMA chains, one rounding of the sum, the statistics written with
     the arithmetic forms norm.hip compiles to).  This is what lets batches that take the fused path (rows in whole units of 16)
     and batches that do not (tests/test_fullsize_gpu.py: 8 images) produce identical logits."""
-    u = _u()
     g = torch.Generator().manual_seed(M + K)
     A = u.dev(torch.randn(M, K, generator=g), u.BF)
     W = u.dev(torch.randn(E, K, generator=g) / math.sqrt(K), u.BF)
@@ -274,7 +265,6 @@ SLN_SHAPES = [(64, 384), (96, 768), (1024, 384), (2048, 1152), (8192, 384), (819
 @pytest.mark.parametrize("M,K", SLN_SHAPES)
 @pytest.mark.parametrize("table", [False, True])
 def test_linear_sln_fwd(M, K, table):
-    u = _u()
     T = 32
     g = torch.Generator().manual_seed(M + K + int(table))
     A = u.rbf(torch.randn(M, K, generator=g))
@@ -308,7 +298,6 @@ def test_linear_sln_fwd(M, K, table):
 @pytest.mark.parametrize("M,K", SLN_SHAPES)
 @pytest.mark.parametrize("bcast,acc", [(0, 0), (32, 1)])
 def test_linear_dgrad_sln_bwd(M, K, bcast, acc):
-    u = _u()
     g = torch.Generator().manual_seed(M * 3 + K + bcast)
     dY = u.rbf(torch.randn(M, K, generator=g))
     W = u.rbf(torch.randn(K, E, generator=g) / math.sqrt(K))

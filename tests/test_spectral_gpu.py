@@ -6,9 +6,13 @@ exported checkpoint and the module-forward path.
 Every test prints the worst observed fraction of its bounds with pytest -s.  These tests had not run on an MI355X when they were
 written ("Spectral normalisation", says so): no device figures are recorded yet.
 """
+import contextlib
+
 import pytest
 import torch
 
+import engine_util as eu
+import gpu_util
 import spectral_ref as sr
 
 pytestmark = pytest.mark.gpu
@@ -121,43 +125,15 @@ def test_single_matrix_ops():
 
 # ------------------------------------------------------------------------------------------------------------- the engine
 def _engine(B, which, layers=2, full=False, seed=5, **kw):
-    from vit_gan_amd.config import Config
-    from vit_gan_amd.engine import GanEngine
-    from vit_gan_amd.generator import SirenGenerator
-    from vit_gan_amd.modules import ViTDiscriminator
-    torch.manual_seed(seed)
-    if full:  # the C2 shape: the full-size discriminator and generator bench.py measures
-        D = ViTDiscriminator(Config(embeddings_dimension=384, classes_count=1, batch_size=B)).cuda().train()
-        G = SirenGenerator().cuda().train()
-    else:
-        D = ViTDiscriminator(Config(embeddings_dimension=384, classes_count=1, dropout_rate=0.1, batch_size=B, transformer_blocks_count=layers)).cuda().train()
-        G = SirenGenerator(layers=2, dropout=0.2).cuda().train()
-    opts = dict(batch=B, seed=77, external_noise=True)
+    opts = dict(external_noise=True)
     opts.update(kw)
     if which is not None:
         opts["spectral_norm"] = which
-    return GanEngine(D, G, **opts), D, G
+    return eu.train_engine(B, seed, d_layers=layers, full=full, **opts)[:3]
 
 
-def _steps(eng, n, B, data_seed=4, each=None):
-    g = torch.Generator().manual_seed(data_seed)
-    losses = []
-    for i in range(n):
-        real = (torch.rand(B, 3, 32, 32, generator=g) * 2 - 1).cuda()
-        z = torch.randn(B, 1024, generator=g).cuda()
-        losses.append(eng.step(real, z).clone())
-        if each is not None:
-            torch.cuda.synchronize()
-            each(i)
-    torch.cuda.synchronize()
-    return torch.stack(losses).cpu(), [t.detach().clone().cpu() for t in eng._state_tensors()]
-
-
-def _same(a, b, what=""):
-    assert torch.equal(a[0], b[0]), (what, a[0], b[0])
-    assert len(a[1]) == len(b[1])
-    for i, (x, y) in enumerate(zip(a[1], b[1])):
-        assert torch.equal(x, y), f"{what}: state tensor {i} differs"
+def _steps(eng, n, B, each=None):
+    return eu.run_steps(eng, eu.batches(B, n), each=each)
 
 
 def test_option_off_is_the_plain_step():
@@ -165,7 +141,7 @@ def test_option_off_is_the_plain_step():
     a, _, _ = _engine(B, None)
     b, _, _ = _engine(B, "")
     assert b.spec is None and b.vit._flat.spectral is None and "spectral_state" not in b.state_dict()
-    _same(_steps(a, n, B), _steps(b, n, B), "spectral_norm=''")
+    eu.assert_same_run(_steps(a, n, B), _steps(b, n, B), "spectral_norm=''")
 
 
 @pytest.mark.parametrize("which,B,full", [("all", 16, False), ("qkv", 16, False), ("all", 256, True), ("qkv", 256, True)])
@@ -208,82 +184,57 @@ def test_engine_keeps_the_normalised_weights_inside_the_operator_bounds(which, B
             assert dev <= bound, (step, sp.names[i], dev, dev_ref, bound)
             worst["dev_kernel"], worst["dev_ref"] = max(worst["dev_kernel"], dev), max(worst["dev_ref"], dev_ref)
 
-    losses, _ = _steps(eng, 3 if full else 4, B, each=each)
-    assert torch.isfinite(losses).all()
+    assert torch.isfinite(_steps(eng, 3 if full else 4, B, each=each).losses).all()
     print(f"\n{which} B={B} full={full}: worst fraction of the sigma / shadow bound {worst['sigma']:.3f} / {worst['shadow']:.3f}; "
           f"|sigma_max(shadow) / sigma0 - 1| kernel {worst['dev_kernel']:.3e}, restatement {worst['dev_ref']:.3e}")
     eng.close()
     assert fd.spectral is None
 
 
-def _reference_step(oracle, real, z, sp_entries, keys, state, gp_epsilon=None):
-    """The normalised step from the step oracle's public pieces.  oracle.d holds the RAW weights; D is evaluated on the effective ones
-    (raw scaled in place around each pass), the restatement projects the accumulated gradients, AdamW acts on the raw weights, one
-    restated power iteration follows, and the generator's pass sees the new effective weights."""
-    from oracle import step_oracle as so
-    from oracle.vit_oracle import vit_forward
-    B = real.shape[0]
+class _Normalised:
+    """StepHooks.weights of the normalised step.  oracle.d holds the RAW weights; D is evaluated on the effective ones (raw scaled in place
+    around each pass), the restatement projects the accumulated gradients, AdamW acts on the raw weights, one restated power iteration
+    follows, and the generator's pass sees the new effective weights.  ``s``: the scale in force, per key."""
 
-    def scaled(factors):
-        class _Ctx:
-            def __enter__(self_):
-                with torch.no_grad():
-                    for k, s in factors.items():
-                        oracle.d[k].mul_(s)
+    def __init__(self, keys, state):
+        self.keys, self.state = keys, state
+        self.s = {k: state[k]["sigma0"] / state[k]["sigma"] for k in keys}
+        assert all(s == 1.0 for s in self.s.values())  # the first step: the effective weights ARE the raw ones, no rescaling error in the reference
 
-            def __exit__(self_, *a):
-                with torch.no_grad():
-                    for k, s in factors.items():
-                        oracle.d[k].div_(s)
-        return _Ctx()
+    @contextlib.contextmanager
+    def scaled(self, d):
+        with torch.no_grad():
+            for k, s in self.s.items():
+                d[k].mul_(s)
+        try:
+            yield
+        finally:
+            with torch.no_grad():
+                for k, s in self.s.items():
+                    d[k].div_(s)
 
-    s_now = {k: state[k]["sigma0"] / state[k]["sigma"] for k in keys}
-    assert all(s == 1.0 for s in s_now.values())  # the first step: the effective weights ARE the raw ones, no rescaling error in the reference
-    for p in oracle.d.values():
-        p.grad = None
-    fake = oracle.G(z)
-    loss_real = so.d_loss_real(oracle.D(real), oracle.loss)
-    loss_real.backward()
-    loss_fake = so.d_loss_fake(oracle.D(fake.detach()), oracle.loss)
-    loss_fake.backward()
-    gp = None
-    if oracle.gp_weight:
-        gp = so.gradient_penalty(lambda t: vit_forward(oracle.d, t, oracle.ddims), real, fake.detach(), gp_epsilon)
-        (oracle.gp_weight * gp).backward()
-    with torch.no_grad():
-        for k in keys:  # dL/dW_eff -> dL/dW
-            p, stt = oracle.d[k], state[k]
-            N = p.shape[0]
-            g2 = sr.project(p.grad.reshape(N, -1), p.detach().reshape(N, -1), stt["u"], stt["v"], stt["sigma"], stt["sigma0"])
-            p.grad.copy_(g2.reshape(p.shape).to(p.dtype))
-    if oracle.clip_d is not None:
-        torch.nn.utils.clip_grad_norm_(list(oracle.d.values()), max_norm=oracle.clip_d)
-    oracle.opt_d.step()
-    s_new = {}
-    for k in keys:
-        p = oracle.d[k].detach()
-        _, sigma, _ = sr.power_step(p.reshape(p.shape[0], -1), state[k]["u"])
-        s_new[k] = state[k]["sigma0"] / sigma
-    for p in oracle.g.values():
-        p.grad = None
-    with scaled(s_new):
-        loss_g = so.g_loss(oracle.D(fake), oracle.loss)
-        loss_g.backward()
-    if oracle.clip_g is not None:
-        torch.nn.utils.clip_grad_norm_(list(oracle.g.values()), max_norm=oracle.clip_g)
-    oracle.opt_g.step()
-    return {"d_real": float(loss_real.detach()), "d_fake": float(loss_fake.detach()), "g": float(loss_g.detach()),
-            "gp": None if gp is None else float(gp.detach()), "s_new": s_new}
+    def project(self, d):
+        with torch.no_grad():
+            for k in self.keys:  # dL/dW_eff -> dL/dW
+                p, stt = d[k], self.state[k]
+                N = p.shape[0]
+                g2 = sr.project(p.grad.reshape(N, -1), p.detach().reshape(N, -1), stt["u"], stt["v"], stt["sigma"], stt["sigma0"])
+                p.grad.copy_(g2.reshape(p.shape).to(p.dtype))
+
+    def remeasure(self, d):
+        for k in self.keys:
+            p = d[k].detach()
+            _, sigma, _ = sr.power_step(p.reshape(p.shape[0], -1), self.state[k]["u"])
+            self.s[k] = self.state[k]["sigma0"] / sigma
 
 
 @pytest.mark.parametrize("gp", [False, True])
 def test_normalised_engine_step_matches_the_reference_step(gp):
     """losses and the first AdamW update at the tolerances of test_wasserstein_losses_and_gradient_clipping (its configuration plus the
     normalisation); with gp_weight = 10 and a fixed epsilon at those of test_engine_step_with_gradient_penalty (its configuration)"""
-    from test_engine_gpu import _build
     from vit_gan_amd.engine import GanEngine
     B = 8
-    D, G, oracle = _build(B, "wasserstein")
+    D, G, oracle = eu.build(B, "wasserstein")
     if gp:
         oracle.gp_weight, oracle.clip_d = 10.0, 5.0
         eng = GanEngine(D, G, batch=B, loss="wasserstein", gp_weight=10.0, clip_d=5.0, external_noise=True, d_dropout=0.0, g_dropout=0.0,
@@ -305,17 +256,17 @@ def test_normalised_engine_step_matches_the_reference_step(gp):
     w0 = {k: v.detach().cpu().clone() for k, v in D.state_dict().items()}
     losses = eng.step(real.cuda(), z.cuda())
     torch.cuda.synchronize()
-    ref = _reference_step(oracle, real.to(BF).float(), z, sp.entries, keys, state, eps if gp else None)
+    from oracle.step_oracle import StepHooks
+    weights = _Normalised(keys, state)
+    ref = oracle.step(real.to(BF).float(), z, gp_epsilon=eps if gp else None, hooks=StepHooks(weights=weights))
     got = losses.cpu().tolist()
-    print(f"normalised step (gp {gp}): engine {got} gp {float(eng.gp_loss):.5f}; reference { {k: v for k, v in ref.items() if k != 's_new'} }")
-    for v, k in zip(got, ("d_real", "d_fake", "g")):
-        assert abs(v - ref[k]) < 2e-2, (k, got, ref)
+    print(f"normalised step (gp {gp}): engine {got} gp {float(eng.gp_loss):.5f}; reference {ref} gp {oracle.last_gp}")
+    eu.assert_losses_match(got, ref, 2e-2)
     if gp:
-        assert abs(float(eng.gp_loss) - ref["gp"]) < 0.03 * abs(ref["gp"]) + 1e-3
+        eu.assert_penalty_matches(float(eng.gp_loss), oracle.last_gp, 0.03, 1e-3)
     for k in ("vit.encoder.1.fc2.weight", "vit.encoder.0.attention.queries.weight"):
-        upd, ref_upd = D.state_dict()[k].detach().cpu() - w0[k], oracle.d[k].detach() - w0[k]
-        assert float((upd - ref_upd).abs().max()) < 1.1e-3 and float(((upd - ref_upd).abs() < 1e-4).float().mean()) > 0.9, k
-    print("scale the generator's pass saw, engine - reference, worst:", max(abs(float(sp.scale(i)) - ref["s_new"][k]) for i, k in enumerate(keys)))
+        eu.assert_first_update_matches(D, w0, oracle, k, 1.1e-3, 1e-4, 0.9)
+    print("scale the generator's pass saw, engine - reference, worst:", max(abs(float(sp.scale(i)) - weights.s[k]) for i, k in enumerate(keys)))
 
 
 def test_graph_replay_equals_eager_and_does_not_depend_on_host_synchronisation():
@@ -323,19 +274,17 @@ def test_graph_replay_equals_eager_and_does_not_depend_on_host_synchronisation()
     that its call left no memset node in the captured step: many replays with a host sync after every step against none at all give
     bit-identical weights - a memset or memcpy node in the graph is what broke that."""
     B, n = 4, 3
-    runs = {}
-    for name, use_graph in (("eager", False), ("graph", True)):
-        eng, D, G = _engine(B, "all", use_graph=use_graph, loss="wasserstein", clip_d=5.0, gp_weight=10.0)
+
+    def make(use_graph, which="all"):
+        eng = _engine(B, which, use_graph=use_graph, loss="wasserstein", clip_d=5.0, gp_weight=10.0)[0]
         # a fixed epsilon: torch.rand's stream is not the same in a captured step (the graph-safe generator) as in an eager one
         eng.gp_epsilon = torch.rand(B, 1, 1, 1, generator=torch.Generator().manual_seed(2)).cuda()
-        runs[name] = _steps(eng, n, B)
-        assert eng.graph_active == use_graph and eng.graph_fallback_reason is None and int(eng.step_t) == n
+        return eng
+    runs, engines = eu.graph_against_eager(make, eu.batches(B, n))
+    for eng in engines.values():
         assert any(t is eng.spec.state for t in eng._state_tensors())
         eng.close()
-    _same(runs["graph"], runs["eager"], "graph replay")
-    plain, _, _ = _engine(B, None, loss="wasserstein", clip_d=5.0, gp_weight=10.0)
-    plain.gp_epsilon = torch.rand(B, 1, 1, 1, generator=torch.Generator().manual_seed(2)).cuda()
-    assert not torch.equal(_steps(plain, n, B)[1][0], runs["eager"][1][0])  # the normalisation is really in the step
+    assert not torch.equal(_steps(make(False, None), n, B).state[0], runs["eager"].state[0])  # the normalisation is really in the step
     out = []
     B = 64
     for sync_every_step in (False, True):
@@ -359,27 +308,9 @@ def test_graph_replay_equals_eager_and_does_not_depend_on_host_synchronisation()
 def test_resume_equals_the_uninterrupted_run(use_graph):
     B = 4
     kw = dict(use_graph=use_graph, loss="wasserstein", clip_d=5.0, ema_decay=0.999, diffaug="color,translation")
-    eng, D, G = _engine(B, "all", **kw)
-    g = torch.Generator().manual_seed(4)
-    data = [((torch.rand(B, 3, 32, 32, generator=g) * 2 - 1).cuda(), torch.randn(B, 1024, generator=g).cuda()) for _ in range(6)]
-    whole = [eng.step(*d).clone() for d in data]
-    torch.cuda.synchronize()
-    want = [t.detach().clone() for t in eng._state_tensors()]
-    eng.close()
-    a, D1, G1 = _engine(B, "all", **kw)
-    first = [a.step(*d).clone() for d in data[:3]]
-    torch.cuda.synchronize()
-    nets, st = (D1.state_dict(), G1.state_dict()), a.state_dict()
+    _, _, _, st, made = eu.resume_against_whole(lambda **net: _engine(B, "all", **net, **kw), eu.batches(B, 6), 3)
+    a, b = made[1][0], made[2][0]
     assert st["spectral_norm"] == "all" and st["spectral_state"].numel() == a.spec.state_floats
-    a.close()
-    b, D2, G2 = _engine(B, "all", seed=99, **kw)  # other initial weights: everything must come from the saved state
-    D2.load_state_dict(nets[0]), G2.load_state_dict(nets[1])
-    b.load_state_dict(st)
-    second = [b.step(*d).clone() for d in data[3:]]
-    torch.cuda.synchronize()
-    assert torch.equal(torch.stack(first + second), torch.stack(whole))
-    for i, (x, y) in enumerate(zip(b._state_tensors(), want)):
-        assert torch.equal(x, y), f"state tensor {i}"
     # a state without the normalisation's: strict raises, non-strict measures again from the current weights
     bare = {k: v for k, v in st.items() if not k.startswith("spectral")}
     with pytest.raises(ValueError, match="spectral_state"):
@@ -420,9 +351,7 @@ def test_exported_checkpoint_and_module_forward():
     ws = torch.empty(_lib.lib().vg_vit_ws_bytes(C.byref(eng.vit._dims), B), dtype=torch.uint8, device="cuda")
     net = _lib.VgVitNet(eng.vit._dims, fd.flat.data_ptr(), fd.shadow.data_ptr(), fd.grad.data_ptr(), 0.0, 0, None, None, 0, 0)
     logits = torch.empty(B, 1, dtype=torch.float32, device="cuda")
-    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-    _lib.check(_lib.lib().vg_vit_forward(C.byref(net), B, p(imgs), 0, p(ws), p(logits), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-               "vg_vit_forward")
+    gpu_util.call("vg_vit_forward", C.byref(net), B, gpu_util.ptr(imgs), 0, gpu_util.ptr(ws), gpu_util.ptr(logits), gpu_util.stream())
     sd = eng.effective_state_dict()
     assert set(sd) == set(D.state_dict())
     plain = ViTDiscriminator(Config(embeddings_dimension=384, classes_count=1, dropout_rate=0.1, batch_size=B, transformer_blocks_count=2)).cuda().eval()
@@ -438,45 +367,24 @@ def test_exported_checkpoint_and_module_forward():
     assert torch.equal(fd.shadow.view(torch.int16), fd.flat.to(BF).view(torch.int16))
 
 
-def _rccl_worker(port, out):
-    import os, sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    sys.path[:0] = [os.path.dirname(here), here]
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    import torch.distributed as dist
-    try:
-        torch.cuda.set_device(0)
-        dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
-        import vit_gan_amd  # noqa: F401
-        B, res = 16, []
-        for use_graph, group in ((False, False), (False, True), (True, True)):
-            kw = dict(exchange_single_rank=True) if group else {}
-            eng, D, G = _engine(B, "all", use_graph=use_graph, loss="wasserstein", clip_d=5.0, **kw)
-            assert eng.sync.active == group
-            res.append(_steps(eng, 3, B) + (eng.graph_active, eng.graph_fallback_reason))
-            eng.close()
-        ok = all(torch.equal(res[0][0], r[0]) and all(torch.equal(a, b) for a, b in zip(res[0][1], r[1])) for r in res[1:])
-        out.put(("ok", (ok, res[2][2], res[2][3])))
-        dist.destroy_process_group()
-    except Exception as e:
-        import traceback
-        out.put(("err", f"{type(e).__name__}: {e}\n{traceback.format_exc()[-1500:]}"))
+def _rccl_worker(rank, world):
+    import vit_gan_amd  # noqa: F401
+    B, res, ran = 16, [], []
+    for use_graph, group in ((False, False), (False, True), (True, True)):
+        kw = dict(exchange_single_rank=True) if group else {}
+        eng, D, G = _engine(B, "all", use_graph=use_graph, loss="wasserstein", clip_d=5.0, **kw)
+        assert eng.sync.active == group
+        res.append(_steps(eng, 3, B))
+        ran.append((eng.graph_active, eng.graph_fallback_reason))
+        eng.close()
+    for r in res[1:]:
+        eu.assert_same_run(res[0], r, "one-rank group against no group")
+    return ran[2]
 
 
 @pytest.mark.timeout(300)
 def test_one_rank_rccl_group_equals_the_single_process_engine():
     """exchange_single_rank=True (the staged backward and its all-reduces on a one-rank RCCL group), eager and captured, against the
     engine without a process group: bit-equal losses and state, the normalisation's included."""
-    import socket
-    import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    out = ctx.Queue()
-    p = ctx.Process(target=_rccl_worker, args=(port, out))
-    p.start()
-    status, val = out.get(timeout=240)
-    p.join(timeout=60)
-    assert status == "ok", val
-    assert val[0] and val[1] and val[2] is None, val
+    (val,) = eu.run_ranks(_rccl_worker, 1, 240, backend="nccl", gpu=True)
+    assert val[0] and val[1] is None, val
